@@ -20,6 +20,7 @@ At N = 1 the line also carries `other_configs`: the same pass loop, about a seco
 BASELINE.json -- configs[3] (--bins 2,7.95,0.05, 122 epochs), configs[2] on one GPU (1000 replicates) and configs[4]
 (100 pairs x 20 replicates) -- each with its value, kernel time and roofline.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (also fine)
+    python bench.py ... --dump-outputs DIR      (also writes the results of the last timed step: DIR/{rates,iterations,loglik,flags}.npy)
 
 Rank 0 prints ONE JSON line.  `roofline` prices the EM kernel against HBM as SURVEY.md section 8(d) prescribes
 (algorithmic bytes per replicate-iteration = 2*A*8 counts + A*8 grid + 3*E*8 epochs/rates) and names what
@@ -52,12 +53,13 @@ OTHER_CONFIG_S = 1.0  # timed region of each entry of `other_configs`
 BINS = "3,7,0.2"
 B_PER_GPU = 100
 CPU_SAMPLE = 64  # replicates timed on the host (about 10 s on one core at 23 epochs)
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: bound on the files written
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps, each of --passes-per-step passes of the hot path")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--replicates", type=int, default=B_PER_GPU, help="bootstrap replicates per GPU (weak scaling)")
     ap.add_argument("--total-replicates", type=int, default=0,
@@ -73,7 +75,24 @@ def parse_args():
     ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive (host-pointer ABI) timing")
     ap.add_argument("--no-cxx-rccl-check", action="store_true",
                     help="skip the run of `Colate --ranks N` (C++ host + RCCL all-gather) after the measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller (rates, iterations, loglik, flags of every row) "
+                         "as DIR/<name>.npy in float64, at most %d MB in all (a seeded sample of rows beyond that)" % (DUMP_MAX_BYTES >> 20))
     return ap.parse_args()
+
+
+def dump_outputs(d, rates, iters, ll, flags):
+    """The results of the timed path's last step as float64 .npy files (iterations and status flags are integers, exact in
+    float64).  Past DUMP_MAX_BYTES a fixed, seeded sample of rows is written, its row numbers in rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    B = rates.shape[0]
+    per_row = 8 * (rates.shape[1] + 3)
+    rows = np.arange(B)
+    if B * per_row > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, (DUMP_MAX_BYTES - 4096) // (per_row + 8), replace=False))
+        np.save(os.path.join(d, "rows.npy"), rows.astype(np.float64))
+    for name, a in (("rates", rates), ("iterations", iters), ("loglik", ll), ("flags", flags)):
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a[rows], dtype=np.float64))
 
 
 # --------------------------------------------------------------------------------------------- launcher
@@ -577,6 +596,8 @@ def run_rank(args):
         dist.all_gather_into_tensor(allr, mine)
         per_rank = allr.cpu().view(world, 2).tolist()
     rates_all, iters_all, ll_all, flags_all = w.layout.unpack(run.h_all)  # every rank has every row's results
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, rates_all, iters_all, ll_all, flags_all)
 
     # launches enqueued back to back without the per-step copy and synchronisation (N = 1 only; not `value`)
     device_only = None

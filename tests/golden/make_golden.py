@@ -7,6 +7,7 @@ shim; Colate_ref = its `Colate` CLI) and this script records inputs + outputs:
 
   l1_estep.json     coal_EM::EM_shared / EM_notshared (coal_EM.cpp:153-468) on grids of
                     (epochs, rates, age): logl, num[E], denom[E] as hex floats (bit-exact)
+  l1_random.npz     the same two calls on random rates and ages over three epoch grids (float64 arrays)
   l2_em_*.json      count tables -> `Colate_ref --mode mut` through its .colate_mat hook
                     (coal.cpp:3169-3170, 3471-3499): .coal text and "Total iterations" per replicate
   l3_pairs/         four samples over one set of .mut files, the reference CLI run once per (target, reference) pair
@@ -96,6 +97,36 @@ def make_l1():
     json.dump({"generator": "tests/golden/make_golden.py (oracle/_ref/libref_em.so)", "cases": cases},
               open(os.path.join(HERE, "l1_estep.json"), "w"))
     print("l1_estep.json:", len(cases), "cases")
+
+
+def make_l1_random():
+    """coal_EM::EM_shared / EM_notshared on random rates (two of them zero) and 25 random grid ages per rate vector, for three
+    epoch grids; per grid g: rates_g[6, E], ages_g[6, 25] and the outputs logl_g[6, 25, 2], num_g / denom_g[6, 25, 2, E]
+    (last axis but one: kind 0 = shared, 1 = not shared)."""
+    assert ol.REF is not None, "oracle/_ref/libref_em.so missing: make -C oracle ref"
+    rng = np.random.default_rng(99)
+    grid = ol.age_grid()
+    bins_list = ("3,7,0.2", "2,7.95,0.05", "3,6,0.5")
+    out = {"bins": np.array(bins_list)}
+    for g, bins in enumerate(bins_list):
+        ep, _ = ol.epochs_from_bins(bins)
+        E = ep.size
+        R, A = 6, 25
+        rates_g, ages_g = np.zeros((R, E)), np.zeros((R, A))
+        ll_g, num_g, den_g = np.zeros((R, A, 2)), np.zeros((R, A, 2, E)), np.zeros((R, A, 2, E))
+        for i in range(R):
+            rates = np.exp(rng.uniform(np.log(5e-9), np.log(1e-2), E))
+            rates[rng.integers(0, E, 2)] = 0.0
+            if rates[-1] <= 0:
+                rates[-1] = 1e-5
+            rates_g[i] = rates
+            ages_g[i] = rng.choice(grid, A)
+            for j, a in enumerate(ages_g[i]):
+                for kind in (0, 1):
+                    ll_g[i, j, kind], num_g[i, j, kind], den_g[i, j, kind] = ol.ref_em_call(kind, ep, rates, a)
+        out.update({f"rates_{g}": rates_g, f"ages_{g}": ages_g, f"logl_{g}": ll_g, f"num_{g}": num_g, f"denom_{g}": den_g})
+    np.savez_compressed(os.path.join(HERE, "l1_random.npz"), **out)
+    print("l1_random.npz:", sum(out[f"logl_{g}"].size for g in range(len(bins_list))), "cases")
 
 
 def make_l2():
@@ -319,6 +350,7 @@ def make_l4():
 if __name__ == "__main__":
     assert os.path.exists(REF_BIN), "oracle/_ref/Colate_ref missing: make -C oracle ref (needs /root/reference)"
     make_l1()
+    make_l1_random()
     make_l2()
     make_l3()
     make_l3_pairs()

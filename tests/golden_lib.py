@@ -29,6 +29,21 @@ def l1_cases():
                    logl=float.fromhex(c["logl"]), num=unhex(c["num"]), denom=unhex(c["denom"]))
 
 
+def l1_random_cases():
+    """The reference's E-step on random rates and ages (l1_random.npz): one dict per (grid, rate vector, age, kind)."""
+    import oracle_lib as ol
+
+    z = np.load(os.path.join(HERE, "l1_random.npz"))
+    for g, bins in enumerate(z["bins"]):
+        ep = ol.epochs_from_bins(str(bins))[0]
+        rates, ages, logl, num, den = (z[f"{k}_{g}"] for k in ("rates", "ages", "logl", "num", "denom"))
+        for i in range(rates.shape[0]):
+            for j in range(ages.shape[1]):
+                for kind in (0, 1):
+                    yield dict(epochs=ep, kind=kind, age=float(ages[i, j]), rates=rates[i], logl=float(logl[i, j, kind]),
+                               num=num[i, j, kind], denom=den[i, j, kind])
+
+
 def l2_names():
     return sorted(f[len("l2_em_"):-5] for f in os.listdir(HERE) if f.startswith("l2_em_"))
 

@@ -49,6 +49,23 @@ def test_dry_run_one_rank_needs_no_launcher():
     assert d["n_gpus"] == 1 and d["config"]["replicates_total"] == 3
 
 
+def _load_dump(d):
+    import numpy as np
+
+    out = {n: np.load(os.path.join(d, n + ".npy")) for n in ("rates", "iterations", "loglik", "flags")}
+    assert all(a.dtype == np.float64 for a in out.values())
+    return out
+
+
+def test_dry_run_dump_outputs_two_ranks_gloo(tmp_path):
+    """--dump-outputs: rank 0 writes every row's results of the last timed step (both ranks' rows, after the all-gather)."""
+    d = _run(["--gpus", "2", "--steps", "2", "--warmup", "0", "--pairs", "3", "--replicates", "5", "--dump-outputs", str(tmp_path)],
+             COLATE_BENCH_DRY="1")
+    got = _load_dump(str(tmp_path))
+    assert got["rates"].shape == (15, d["config"]["epochs"]) and got["iterations"].shape == (15,)
+    assert (got["iterations"] == 1001).all() and got["loglik"].shape == got["flags"].shape == (15,)
+
+
 def test_refuses_more_ranks_than_gpus_unless_rehearsing():
     """Without a GPU (here) or with fewer GPUs than ranks the nccl path must fail loudly, not fall back."""
     e = dict(os.environ)
@@ -90,6 +107,31 @@ def test_pairs_shape_and_other_configs_on_the_gpu():
     two = _run(common + ["--gpus", "2", "--pairs", "6", "--replicates", "4", "--no-other-configs"], COLATE_BENCH_BACKEND="gloo")
     assert two["n_gpus"] == 2 and two["config"]["replicates_total"] == 24 and two["config"]["em_iterations_mean"] >= 1001
     assert two["config"]["status_flags_nonzero"] == 0
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """Two runs with the same arguments dump the same results (same seeded inputs, the same kernel), and those are what the
+    host-pointer entry point returns for the benchmark's replicates."""
+    import numpy as np
+
+    import colate_amd
+    from colate_amd import workloads
+
+    common = ["--steps", "2", "--warmup", "1", "--passes-per-step", "1", "--replicates", "8", "--no-other-configs", "--no-cpu-baseline",
+              "--no-host-path", "--no-cxx-rccl-check"]
+    runs = []
+    for k in range(2):
+        _run(common + ["--dump-outputs", str(tmp_path / str(k))])
+        runs.append(_load_dump(str(tmp_path / str(k))))
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
+    grid = colate_amd.age_grid()
+    epochs, _ = colate_amd.epochs_from_bins("3,7,0.2")
+    csh, cns = workloads.bootstrap_tables(grid, 8, nb=115, scale=11.0, seed=12345)
+    rates, iters, ll, flags = colate_amd.em_batch(grid, csh, cns, epochs)
+    assert np.array_equal(runs[0]["rates"], rates) and np.array_equal(runs[0]["iterations"], iters)
+    assert np.array_equal(runs[0]["loglik"], ll) and np.array_equal(runs[0]["flags"], flags)
 
 
 @pytest.mark.gpu

@@ -1,6 +1,6 @@
 """The oracle (oracle/colate_oracle.c) pinned against the reference: the committed golden vectors
 (generated from the reference build by tests/golden/make_golden.py) and, when oracle/_ref is
-present, the reference itself.  CPU only."""
+present, the reference itself as well.  CPU only."""
 import numpy as np
 import pytest
 
@@ -30,23 +30,19 @@ def test_l2_em_text_and_iterations(name):
     assert gl.coal_text(ep, rates) == c["coal"]
 
 
-@pytest.mark.skipif(ol.REF is None, reason="oracle/_ref/libref_em.so not built (needs /root/reference)")
 def test_oracle_equals_reference_on_random_inputs():
-    rng = np.random.default_rng(99)
-    grid = ol.age_grid()
-    for bins in ("3,7,0.2", "2,7.95,0.05", "3,6,0.5"):
-        ep, _ = ol.epochs_from_bins(bins)
-        for _ in range(6):
-            rates = np.exp(rng.uniform(np.log(5e-9), np.log(1e-2), ep.size))
-            rates[rng.integers(0, ep.size, 2)] = 0.0
-            if rates[-1] <= 0:
-                rates[-1] = 1e-5
-            for a in rng.choice(grid, 25):
-                for kind in (0, 1):
-                    l0, n0, d0 = ol.ref_em_call(kind, ep, rates, a)
-                    l1, n1, d1 = ol.em_call(kind, ep, rates, a)
-                    assert l0 == l1 or (np.isnan(l0) and np.isnan(l1))
-                    assert np.array_equal(n0, n1, equal_nan=True) and np.array_equal(d0, d1, equal_nan=True)
+    """Random rates (two of them zero) and ages over three epoch grids: the reference's outputs as recorded in
+    golden/l1_random.npz and, when oracle/_ref is present, as the reference computes them now."""
+    n = 0
+    for c in gl.l1_random_cases():
+        ep, rates, a, kind = c["epochs"], c["rates"], c["age"], c["kind"]
+        l1, n1, d1 = ol.em_call(kind, ep, rates, a)
+        refs = [(c["logl"], c["num"], c["denom"])] + ([ol.ref_em_call(kind, ep, rates, a)] if ol.REF is not None else [])
+        for l0, n0, d0 in refs:
+            assert l0 == l1 or (np.isnan(l0) and np.isnan(l1))
+            assert np.array_equal(n0, n1, equal_nan=True) and np.array_equal(d0, d1, equal_nan=True)
+        n += 1
+    assert n == 900
 
 
 def test_logsumexp_special_values():

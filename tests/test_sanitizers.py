@@ -6,6 +6,7 @@ that come out.  A sanitizer report makes the binary exit non-zero (-fno-sanitize
 import gzip
 import json
 import os
+import platform
 import shutil
 import subprocess
 
@@ -18,6 +19,10 @@ ASAN_CLI = os.path.join(ROOT, "colate_amd", "bin", "Colate_asan")
 TSAN_CLI = os.path.join(ROOT, "colate_amd", "bin", "Colate_tsan")
 ASAN_ORACLE = os.path.join(ROOT, "oracle", "oracle_asan")
 ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=97", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+# ThreadSanitizer's shadow layout expects the default placement of mappings: under a kernel with more mmap randomisation bits
+# (vm.mmap_rnd_bits > 28) the runtime stops at start-up with "unexpected memory mapping".  The TSan binary therefore runs with
+# address randomisation turned off for that one process (personality flag, no system setting).
+TSAN_PREFIX = ["setarch", platform.machine(), "-R"] if shutil.which("setarch") else []
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -27,7 +32,7 @@ def _build():
 
 
 def _run(exe, args, cwd, **env):
-    r = subprocess.run([exe] + args, cwd=cwd, capture_output=True, env=dict(ENV, **env))
+    r = subprocess.run((TSAN_PREFIX if exe == TSAN_CLI else []) + [exe] + args, cwd=cwd, capture_output=True, env=dict(ENV, **env))
     err = r.stderr.decode()
     assert "ERROR: AddressSanitizer" not in err and "runtime error:" not in err and "LeakSanitizer" not in err, err[-3000:]
     assert "ThreadSanitizer" not in err, err[-3000:]

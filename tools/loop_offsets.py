@@ -17,6 +17,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "colate_amd", "csrc")
@@ -30,7 +31,11 @@ def target(a, args):
 
 
 def loops_of(unit, flags):
-    elf = f"/tmp/loop_offsets_{unit}.elf"
+    with tempfile.TemporaryDirectory(prefix="loop_offsets_") as d:
+        return _loops_of(unit, flags, os.path.join(d, unit + ".elf"))
+
+
+def _loops_of(unit, flags, elf):
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-I{ROOT}/include", "--offload-arch=gfx950",
                            "-mllvm", "-force-precise-rotation-cost=true", *flags, "--cuda-device-only", "-c", "--no-gpu-bundle-output",
                            os.path.join(CSRC, unit), "-o", elf], stderr=subprocess.DEVNULL)
