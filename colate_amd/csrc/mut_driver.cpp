@@ -18,14 +18,9 @@
 #include <signal.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cerrno>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
-#include <deque>
-#include <memory>
-#include <mutex>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -317,90 +312,12 @@ bool read_mut_file(const std::string& filename, std::vector<MutRow>& rows) {
   return for_each_mut_row(filename, [&rows](const MutRow& r) { rows.push_back(r); });
 }
 
-// Reader thread: inflates and tokenises the .mut files in order, at most two chromosomes ahead of the table fill.  The
-// fill itself has to stay sequential -- every sampled age is a draw from the run's one std::mt19937 (coal.cpp:2262, 2282),
-// so the order of the draws is part of the result -- but nothing of the parsing depends on it.
-class MutPrefetcher {
- public:
-  explicit MutPrefetcher(std::vector<std::string> files) : files_(std::move(files)), slots_(files_.size()) {
-    const unsigned hc = std::thread::hardware_concurrency();
-    int nthreads = (hc >= 6 && files_.size() > 1) ? (hc >= 12 ? 4 : 2) : 1;
-    // COLATE_THREADS=n: at most n threads of this process work on the inputs at a time, the caller's included --
-    // n <= 1: no thread is started at all (files are parsed by next() itself); n >= 2: up to min(4, n - 1) readers here,
-    // the rest of the n - 1 go to the age sampling (sample_threads(): readers and samplers overlap only while the
-    // fill waits for a file)
-    if (const char* e = std::getenv("COLATE_THREADS")) nthreads = std::atoi(e) <= 1 ? 0 : std::min(nthreads, std::atoi(e) - 1);
-    for (int t = 0; t < nthreads; t++)
-      workers_.emplace_back([this] {
-        for (;;) {
-          size_t i;
-          {
-            std::unique_lock<std::mutex> lk(m_);
-            // at most kAhead files parsed beyond the one the fill is at (memory: ~56 MB per million rows)
-            cv_.wait(lk, [this] { return stop_ || next_ >= files_.size() || next_ < consumed_ + kAhead; });
-            if (stop_ || next_ >= files_.size()) return;
-            i = next_++;
-          }
-          std::vector<MutRow> rows;
-          const double t0 = StageTimes::now();
-          read_mut_file(files_[i], rows);
-          const double dt = StageTimes::now() - t0;
-          std::lock_guard<std::mutex> lk(m_);
-          parse_seconds_ += dt;
-          slots_[i].rows = std::move(rows);
-          slots_[i].ready = true;
-          cv_.notify_all();
-        }
-      });
-  }
-  ~MutPrefetcher() {
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (std::thread& t : workers_)
-      if (t.joinable()) t.join();
-  }
-  void next(std::vector<MutRow>& rows) {  // the next file's rows, in the order given
-    const double t0 = StageTimes::now();
-    if (workers_.empty()) {  // COLATE_THREADS <= 1: on the calling thread
-      read_mut_file(files_[consumed_++], rows);
-      g_times.parse_mut += StageTimes::now() - t0;
-      return;
-    }
-    std::unique_lock<std::mutex> lk(m_);
-    const size_t i = consumed_;
-    cv_.wait(lk, [&] { return slots_[i].ready; });
-    rows = std::move(slots_[i].rows);
-    consumed_++;
-    g_times.wait_for_parser += StageTimes::now() - t0;
-    g_times.parse_mut = parse_seconds_;
-    cv_.notify_all();
-  }
-
- private:
-  static constexpr size_t kAhead = 5;
-  struct Slot {
-    std::vector<MutRow> rows;
-    bool ready = false;
-  };
-  std::vector<std::string> files_;
-  std::vector<Slot> slots_;
-  std::vector<std::thread> workers_;
-  std::mutex m_;
-  std::condition_variable cv_;
-  size_t next_ = 0, consumed_ = 0;
-  double parse_seconds_ = 0;
-  bool stop_ = false;
-};
-
-// data.cpp:213-235: sequence = upper-cased lines after the header, concatenated
+// data.cpp:213-235: sequence = upper-cased lines after the header, concatenated (also read on the engine's pool threads)
 void read_fasta_mask(const std::string& filename, std::string& seq) {
   GzText is;
   if (!is.open(filename) && !is.open(filename + ".gz")) {
     std::cerr << "Error while opening file " << filename << "." << std::endl;
-    std::exit(1);
+    reader_exit();  // (data.cpp: exit(1))
   }
   std::string line;
   is.getline(line);
@@ -464,268 +381,12 @@ struct TmpStream {
 
 
 
-// ---- sampling of the mutation ages, off the main thread ---------------------------------------------------------------
-// Every used SNP spreads its weight over 100 ages drawn uniformly between age_begin and age_end (coal.cpp:2260-2295), each
-// draw one std::uniform_real_distribution<double>(0,1) call on the run's single std::mt19937: the ORDER of the draws is part
-// of the result, their evaluation is not.  The main thread therefore walks the SNPs (filters, stream merges: sequential by
-// nature), draws the uniforms in the reference's order into a buffer per genome block, and hands the block to a worker, which
-// does the log / round / accumulate per draw (two thirds of the time of the whole table fill).  A genome block's tables are
-// touched by one job only and the SNPs of a job are taken in order, so every table cell sums the same terms in the same
-// order as the reference: bit-identical.  One case breaks the fixed "100 draws per SNP": the reference REdraws a sample whose
-// age bin lies beyond the grid (coal.cpp:2286-2287, ages above 9e6 generations); a worker that meets one raises `redo` and
-// the whole fill is repeated on the sequential path.
-struct UsedSnp {
-  double age_begin, age_end, w_sh, w_ns;
-  bool emp;  // age_begin <= sample age: the F path (coal.cpp:2245-2275), not-shared weight only, no redraws
-};
-struct SampleJob {
-  std::vector<UsedSnp> snps;
-  std::vector<double> u;  // 100 uniforms per SNP, in draw order
-  double *sh = nullptr, *ns = nullptr;  // the block's two tables (buffers of tab.sh[blk], tab.ns[blk]: stable while blocks are added)
-};
-class SamplePool {
- public:
-  SamplePool(int nthreads, double C, int A, double age) : C_(C), A_(A), age_(age) {
-    for (int i = 0; i < nthreads; i++) workers_.emplace_back([this] { run(); });
-  }
-  ~SamplePool() { finish(); }
-  double waited_ = 0;  // seconds submit() waited for room
-  void submit(SampleJob&& j) {
-    const double t0 = StageTimes::now();
-    std::unique_lock<std::mutex> lk(m_);
-    // bounds the uniforms held in memory: a job is a whole genome block (800 bytes of uniforms per used SNP, 80 MB for a
-    // dense 100k-SNP block), so the queue is limited by its bytes -- kQueueBytes, or one job whatever its size -- as
-    // well as by its length
-    const size_t bytes = j.u.size() * sizeof(double);
-    cv_room_.wait(lk, [&] { return q_.empty() || (q_.size() < 2 * workers_.size() + 2 && queued_bytes_ + bytes <= kQueueBytes); });
-    waited_ += StageTimes::now() - t0;
-    queued_bytes_ += bytes;
-    q_.push_back(std::move(j));
-    cv_work_.notify_one();
-  }
-  void finish() {  // waits for all jobs
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      done_ = true;
-    }
-    cv_work_.notify_all();
-    for (std::thread& t : workers_)
-      if (t.joinable()) t.join();
-    workers_.clear();
-  }
-  bool redo() const { return redo_.load(); }
-
- private:
-  void run() {
-    for (;;) {
-      SampleJob j;
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_work_.wait(lk, [this] { return !q_.empty() || done_; });
-        if (q_.empty()) return;
-        j = std::move(q_.front());
-        q_.pop_front();
-        queued_bytes_ -= j.u.size() * sizeof(double);
-        cv_room_.notify_one();
-      }
-      if (redo_.load()) continue;
-      double *sh = j.sh, *ns = j.ns;
-      const double* u = j.u.data();
-      for (const UsedSnp& s : j.snps) {
-        const double span = s.age_end - s.age_begin;
-        if (s.emp) {
-          for (int k = 0; k < 100; k++) {
-            double sampled_age = u[k] * span + s.age_begin;
-            if (sampled_age < age_) sampled_age = age_;
-            const int bin = age_bin_index(sampled_age, C_);
-            if (bin < A_) ns[bin] += s.w_ns;
-          }
-        } else {
-          for (int k = 0; k < 100; k++) {
-            const double sampled_age = u[k] * span + s.age_begin;
-            const int bin = age_bin_index(sampled_age, C_);
-            if (sampled_age < age_ || bin >= A_) {  // the reference would draw again: the stream no longer lines up
-              redo_.store(true);
-              break;
-            }
-            sh[bin] += s.w_sh;
-            ns[bin] += s.w_ns;
-          }
-          if (redo_.load()) break;
-        }
-        u += 100;
-      }
-    }
-  }
-  const double C_;
-  const int A_;
-  const double age_;
-  std::vector<std::thread> workers_;
-  std::mutex m_;
-  std::condition_variable cv_work_, cv_room_;
-  std::deque<SampleJob> q_;
-  static constexpr size_t kQueueBytes = size_t(256) << 20;
-  size_t queued_bytes_ = 0;
-  bool done_ = false;
-  std::atomic<bool> redo_{false};
-};
-// std::uniform_real_distribution<double>(0, 1) on std::mt19937 is std::generate_canonical<double, 53>: two 32-bit draws,
-// (r1 + r2 * 2^32) / 2^64 in double, capped below 1 (libstdc++ bits/random.tcc).  The same arithmetic spelled out costs a
-// third (the library version goes through long double); it is used only after a self-check against the library's own
-// distribution on this machine's libstdc++ (the sequence is part of the result), else the library call is.
-inline double canonical_fast(std::mt19937& g) {
-  const double r1 = (double)g();
-  const double r2 = (double)g();
-  double ret = (r1 + r2 * 4294967296.0) * 0x1p-64;
-  if (ret >= 1.0) ret = std::nextafter(1.0, 0.0);
-  return ret;
-}
-inline bool canonical_fast_ok() {
-  static const bool ok = [] {
-    for (unsigned seed : {1u, 12345u, 4294967295u}) {
-      std::mt19937 a(seed), b(seed);
-      std::uniform_real_distribution<double> d(0, 1);
-      for (int i = 0; i < 4096; i++)
-        if (d(a) != canonical_fast(b)) return false;
-      if (a != b) return false;
-    }
-    return true;
-  }();
-  return ok;
-}
-
-
-// The uniforms themselves, on a thread of their own: the stream does not depend on the data, only HOW MANY of its values the
-// fill takes does.  The thread runs ahead on a copy of the run's generator, filling chunks of kChunk doubles, and keeps the
-// generator state at the start of every chunk; when the fill is over, the run's generator is set to the state at the start of
-// the last chunk touched and advanced by the few draws taken from it -- exactly where the sequential code would have left it.
-class UniformStream {
- public:
-  static constexpr size_t kChunk = 1u << 18;  // doubles per chunk (2 MB)
-  UniformStream(const std::mt19937& start, bool fast) : gen_(start), first_(start) {
-    // the bulk generator only if it reproduces this machine's library on the run's own state
-    bulk_ok_ = fast && bulk_.load(start);
-    if (bulk_ok_) {
-      BulkMt19937 probe = bulk_;
-      std::mt19937 lib = start;
-      std::uniform_real_distribution<double> d(0, 1);
-      uint32_t w[2 * 1300];
-      probe.generate(w, 2 * 1300);  // (across two regenerations of the state)
-      for (int i = 0; i < 1300 && bulk_ok_; i++) bulk_ok_ = (d(lib) == canonical_from(w[2 * i], w[2 * i + 1]));
-      std::mt19937 back;
-      bulk_ok_ = bulk_ok_ && probe.store(back) && back == lib;
-    }
-    fast_ = fast;
-    worker_ = std::thread([this] { run(); });
-  }
-  ~UniformStream() { stop(); }
-  void take(double* out, size_t n) {  // the next n uniforms of the stream
-    while (n) {
-      if (!cur_ || pos_ == kChunk) next_chunk();
-      const size_t k = std::min(n, kChunk - pos_);
-      std::memcpy(out, cur_->u.data() + pos_, k * sizeof(double));
-      out += k, n -= k, pos_ += k;
-    }
-  }
-  // the generator as the sequential code would hold it now (after every uniform handed out so far)
-  std::mt19937 state_after_taken() {
-    stop();
-    if (!cur_) return first_;
-    if (bulk_ok_) {
-      BulkMt19937 b = cur_->bulk_at_start;
-      b.discard(2 * (unsigned long long)pos_);  // two 32-bit draws per uniform (generate_canonical<double, 53>)
-      std::mt19937 g;
-      if (b.store(g)) return g;
-    }
-    std::mt19937 g = cur_->at_start;
-    g.discard(2 * (unsigned long long)pos_);
-    return g;
-  }
-
- private:
-  static double canonical_from(uint32_t r1, uint32_t r2) {
-    double ret = ((double)r1 + (double)r2 * 4294967296.0) * 0x1p-64;
-    if (ret >= 1.0) ret = std::nextafter(1.0, 0.0);
-    return ret;
-  }
-  struct Chunk {
-    std::mt19937 at_start;
-    BulkMt19937 bulk_at_start;
-    std::vector<double> u;
-  };
-  void run() {
-    std::uniform_real_distribution<double> d(0, 1);
-    std::vector<uint32_t> words(bulk_ok_ ? 2 * kChunk : 0);
-    for (;;) {
-      std::unique_ptr<Chunk> c(new Chunk);
-      c->u.resize(kChunk);
-      if (bulk_ok_) {
-        c->bulk_at_start = bulk_;
-        bulk_.generate(words.data(), 2 * kChunk);
-        for (size_t i = 0; i < kChunk; i++) c->u[i] = canonical_from(words[2 * i], words[2 * i + 1]);
-      } else {
-        c->at_start = gen_;
-        if (fast_)
-          for (size_t i = 0; i < kChunk; i++) c->u[i] = canonical_fast(gen_);
-        else
-          for (size_t i = 0; i < kChunk; i++) c->u[i] = d(gen_);
-      }
-      std::unique_lock<std::mutex> lk(m_);
-      cv_room_.wait(lk, [this] { return ready_.size() < 8 || stop_; });
-      if (stop_) return;
-      ready_.push_back(std::move(c));
-      cv_ready_.notify_one();
-    }
-  }
-  void next_chunk() {
-    const double t0 = StageTimes::now();
-    std::unique_lock<std::mutex> lk(m_);
-    cv_ready_.wait(lk, [this] { return !ready_.empty(); });
-    waited_ += StageTimes::now() - t0;
-    cur_ = std::move(ready_.front());
-    ready_.pop_front();
-    pos_ = 0;
-    cv_room_.notify_one();
-  }
-  void stop() {
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      stop_ = true;
-    }
-    cv_room_.notify_all();
-    if (worker_.joinable()) worker_.join();
-  }
- public:
-  double waited_ = 0;  // seconds the fill waited for uniforms
-  bool bulk() const { return bulk_ok_; }
-
- private:
-  std::mt19937 gen_;
-  const std::mt19937 first_;
-  BulkMt19937 bulk_;
-  bool bulk_ok_ = false, fast_ = false;
-  std::thread worker_;
-  std::mutex m_;
-  std::condition_variable cv_ready_, cv_room_;
-  std::deque<std::unique_ptr<Chunk>> ready_;
-  std::unique_ptr<Chunk> cur_;
-  size_t pos_ = 0;
-  bool stop_ = false;
-};
-
-inline int sample_threads() {
-  if (const char* e = std::getenv("COLATE_THREADS")) return std::max(0, std::atoi(e) - 1);
-  const unsigned hc = std::thread::hardware_concurrency();
-  return hc >= 4 ? (int)std::min(hc - 2, 12u) : 0;  // 0: sample on the main thread (the sequential path)
-}
-
-// coal.cpp:2071-2321.  Returns the number of blocks.
-int fill_tables_impl(const std::vector<std::string>& chr_names,
-                     const std::vector<std::string>& mut_files, const std::string& target_file,
-                     const std::string& ref_file, const std::vector<std::string>& target_masks,
-                     const std::vector<std::string>& ref_masks, double C, std::mt19937& rng,
-                     int num_bases_per_block, int A, BlockTables& tab,
-                     std::map<std::string, std::vector<MutRow>>* mut_cache, SamplePool* pool) {
+// coal.cpp:2071-2321, on the calling thread.  Returns the number of blocks.
+int fill_tables_from_tmp(const std::vector<std::string>& chr_names,
+                         const std::vector<std::string>& mut_files, const std::string& target_file,
+                         const std::string& ref_file, const std::vector<std::string>& target_masks,
+                         const std::vector<std::string>& ref_masks, double C, std::mt19937& rng,
+                         int num_bases_per_block, int A, PairTables& tab) {
   const double age = 0, ref_age = 0;  // forced, coal.cpp:2074-2075
   std::uniform_real_distribution<double> dist_unif(0, 1);
   const float num_samples = 100;
@@ -736,52 +397,24 @@ int fill_tables_impl(const std::vector<std::string>& chr_names,
   if (!ref.fp) std::cerr << "Failed to open " << ref_file << std::endl;
   const bool has_tar_mask = !target_masks.empty(), has_ref_mask = !ref_masks.empty();
 
+  // [nb][A] tables, one block of A zeros per genome block (the block being filled is the last)
   int num_blocks = 0;
   size_t blk = 0;
-  tab.add_block(A);
-  SampleJob job;  // (pool) the used SNPs of the current block and their uniforms
-  auto flush_job = [&]() {
-    if (pool && !job.snps.empty()) {
-      job.sh = tab.sh[blk].data();
-      job.ns = tab.ns[blk].data();
-      pool->submit(std::move(job));
-      job = SampleJob();
-    }
-  };
-  std::unique_ptr<UniformStream> stream;  // (pool) the run's uniforms, generated ahead on their own thread
-  if (pool) stream.reset(new UniformStream(rng, canonical_fast_ok()));
-  auto draw100 = [&]() {  // the SNP's 100 uniforms, in the reference's draw order
-    const size_t at = job.u.size();
-    job.u.resize(at + 100);
-    stream->take(job.u.data() + at, 100);
-  };
+  for (std::vector<double>* t : {&tab.sh, &tab.ns, &tab.she, &tab.nse}) t->assign((size_t)A, 0.0);
   auto advance_block = [&]() {
-    flush_job();
     blk++;
     num_blocks++;
-    if (blk >= tab.sh.size()) tab.add_block(A);
+    for (std::vector<double>* t : {&tab.sh, &tab.ns, &tab.she, &tab.nse}) t->resize((blk + 1) * A, 0.0);
   };
 
-  std::vector<MutRow> rows_local;
+  std::vector<MutRow> rows;
   std::string tar_mask, ref_mask;
-  std::unique_ptr<MutPrefetcher> prefetch;
-  if (!mut_cache) prefetch.reset(new MutPrefetcher(mut_files));
   for (size_t chr = 0; chr < mut_files.size(); chr++) {
     std::cerr << "parsing CHR: " << chr + 1 << " / " << mut_files.size() << std::endl;
-    // --pairs: every (target, reference) pair walks the same .mut rows; parse each file once
-    const std::vector<MutRow>* rows_p = &rows_local;
-    if (mut_cache) {
-      auto it = mut_cache->find(mut_files[chr]);
-      if (it == mut_cache->end()) {
-        read_mut_file(mut_files[chr], (*mut_cache)[mut_files[chr]]);
-        it = mut_cache->find(mut_files[chr]);
-      }
-      rows_p = &it->second;
-    } else {
-      prefetch->next(rows_local);
-    }
-    const std::vector<MutRow>& rows = *rows_p;
+    const double t_parse0 = StageTimes::now();
+    read_mut_file(mut_files[chr], rows);
     const double t_fill0 = StageTimes::now();
+    g_times.parse_mut += t_fill0 - t_parse0;
     if (has_tar_mask) read_fasta_mask(target_masks[chr], tar_mask);
     if (has_ref_mask) read_fasta_mask(ref_masks[chr], ref_mask);
     int current_block_base = 0;
@@ -848,31 +481,22 @@ int fill_tables_impl(const std::vector<std::string>& chr_names,
       f_DAF_target = std::round(f_DAF_target);
       f_AAF_target = std::round(f_AAF_target);
 
-      std::vector<double>& sh = tab.sh[blk];
-      std::vector<double>& ns = tab.ns[blk];
+      double* const sh = tab.sh.data() + blk * A;
+      double* const ns = tab.ns.data() + blk * A;
       const int DAF_ref = ref.DAF;
       if (age_begin <= age) {  // coal.cpp:2245-2275
         const int bin2 = age_bin_index(m.age_end, C);
         if (bin2 < A) {  // row 0 of the A*A table; larger indices land in rows nobody reads
-          tab.sh_emp[blk][bin2] += f_DAF_target * DAF_ref / ((double)N_ref);
-          tab.ns_emp[blk][bin2] += f_AAF_target * DAF_ref / ((double)N_ref);
+          tab.she[blk * A + bin2] += f_DAF_target * DAF_ref / ((double)N_ref);
+          tab.nse[blk * A + bin2] += f_AAF_target * DAF_ref / ((double)N_ref);
         }
-        if (pool) {  // the draws now, in the reference's order; their evaluation on a worker
-          job.snps.push_back(UsedSnp{age_begin, (double)m.age_end, 0.0, f_AAF_target * DAF_ref / ((double)N_ref * num_samples), true});
-          draw100();
-        } else {
-          for (int j = 0; j < num_samples; j++) {
-            double sampled_age = dist_unif(rng) * (m.age_end - age_begin) + age_begin;
-            if (sampled_age < age) sampled_age = age;
-            const int bin = age_bin_index(sampled_age, C);
-            if (bin < A) ns[bin] += f_AAF_target * DAF_ref / ((double)N_ref * num_samples);
-          }
+        for (int j = 0; j < num_samples; j++) {
+          double sampled_age = dist_unif(rng) * (m.age_end - age_begin) + age_begin;
+          if (sampled_age < age) sampled_age = age;
+          const int bin = age_bin_index(sampled_age, C);
+          if (bin < A) ns[bin] += f_AAF_target * DAF_ref / ((double)N_ref * num_samples);
         }
-      } else if (pool) {  // coal.cpp:2277-2297
-        job.snps.push_back(UsedSnp{age_begin, (double)m.age_end, f_DAF_target * DAF_ref / ((double)N_ref * num_samples),
-                                   f_AAF_target * DAF_ref / ((double)N_ref * num_samples), false});
-        draw100();
-      } else {
+      } else {  // coal.cpp:2277-2297
         int j = 0;
         while (j < num_samples) {
           const double sampled_age = dist_unif(rng) * (m.age_end - age_begin) + age_begin;
@@ -886,57 +510,17 @@ int fill_tables_impl(const std::vector<std::string>& chr_names,
           }
         }
       }
-      if (pool && pool->redo()) break;  // (a redraw was needed somewhere: this pass is void)
     }
     advance_block();  // chromosome end, coal.cpp:2306-2310
     g_times.table_fill += StageTimes::now() - t_fill0;
-    if (pool && pool->redo()) break;  // (this pass is void: do not parse the rest for nothing)
   }
   if (tgt.fp) std::fclose(tgt.fp);
   if (ref.fp) std::fclose(ref.fp);
-  if (pool) {
-    const double t0 = StageTimes::now();
-    pool->finish();  // (before the tables are trimmed)
-    rng = stream->state_after_taken();
-    if (g_times.on)
-      std::cerr << "Timing: table fill waited " << stream->waited_ << " s for uniforms (bulk generator " << (stream->bulk() ? "on" : "off")
-                << "), " << pool->waited_ << " s for room in the sampling queue, " << StageTimes::now() - t0 << " s for the last jobs" << std::endl;
-  }
-  tab.sh.resize(num_blocks);
-  tab.ns.resize(num_blocks);
-  tab.sh_emp.resize(num_blocks);
-  tab.ns_emp.resize(num_blocks);
+  for (std::vector<double>* t : {&tab.sh, &tab.ns, &tab.she, &tab.nse}) t->resize((size_t)num_blocks * A);
+  tab.nb = num_blocks;
   return num_blocks;
 }
 
-// coal.cpp:2071-2321 with the sampling on worker threads where the machine has them.  COLATE_THREADS=n: 1 = everything on the
-// calling thread, no thread is started (MutPrefetcher parses inline, the sequential path samples); n >= 2: n - 1 sampling
-// workers + the uniform-stream thread next to the caller, and up to min(4, n - 1) .mut readers that run ahead of the fill.
-// Returns the number of blocks.
-int fill_tables_from_tmp(const std::vector<std::string>& chr_names,
-                         const std::vector<std::string>& mut_files, const std::string& target_file,
-                         const std::string& ref_file, const std::vector<std::string>& target_masks,
-                         const std::vector<std::string>& ref_masks, double C, std::mt19937& rng,
-                         int num_bases_per_block, int A, BlockTables& tab,
-                         std::map<std::string, std::vector<MutRow>>* mut_cache) {
-  const int nt = sample_threads();
-  if (nt > 0) {
-    const std::mt19937 rng0 = rng;
-    BlockTables t2;
-    SamplePool pool(nt, C, A, /*age=*/0.0);
-    const int nb = fill_tables_impl(chr_names, mut_files, target_file, ref_file, target_masks, ref_masks, C, rng,
-                                    num_bases_per_block, A, t2, mut_cache, &pool);
-    pool.finish();
-    if (!pool.redo()) {
-      tab = std::move(t2);
-      return nb;
-    }
-    rng = rng0;  // a sample beyond the age grid had to be redrawn: once more, on the sequential path
-    if (g_times.on) std::cerr << "Timing: a sample beyond the age grid was redrawn; the table fill is repeated sequentially" << std::endl;
-  }
-  return fill_tables_impl(chr_names, mut_files, target_file, ref_file, target_masks, ref_masks, C, rng, num_bases_per_block, A,
-                          tab, mut_cache, nullptr);
-}
 
 // OUT.colate_mat (coal.cpp:3471-3499): 185 grid values, then per replicate 185 shared
 // and 185 not-shared counts, read with operator>> (a failed extraction leaves zeros).
@@ -996,9 +580,11 @@ void print_usage_footer() {  // coal.cpp:3852-3861
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
 }
 
-// coal.cpp:3295-3313: with --chr one .mut per listed chromosome (<mut>_chr<name>.mut), else the --mut path verbatim and
-// the chromosome name ""
-void chromosome_files(const Options& opt, std::vector<std::string>& names, std::vector<std::string>& mut_files) {
+// coal.cpp:3295-3313: with --chr one .mut (<mut>_chr<name>.mut) and one fasta per mask (<mask>_chr<name>.fa) per listed
+// chromosome, else the paths verbatim and the chromosome name ""
+void chromosome_files(const Options& opt, std::vector<std::string>& names, std::vector<std::string>& mut_files,
+                      std::vector<std::string>* target_masks, std::vector<std::string>* ref_masks) {
+  const bool tmask = target_masks && opt.has("target_mask"), rmask = ref_masks && opt.has("reference_mask");
   if (opt.has("chr")) {
     GzText is_chr;
     if (!is_chr.open(opt.get("chr"))) std::cerr << "Error while opening file " << opt.get("chr") << std::endl;
@@ -1006,10 +592,14 @@ void chromosome_files(const Options& opt, std::vector<std::string>& names, std::
     while (is_chr.getline(line)) {
       names.push_back(line);
       mut_files.push_back(opt.get("mut") + "_chr" + line + ".mut");
+      if (tmask) target_masks->push_back(opt.get("target_mask") + "_chr" + line + ".fa");
+      if (rmask) ref_masks->push_back(opt.get("reference_mask") + "_chr" + line + ".fa");
     }
   } else {
     names.push_back("");
     mut_files.push_back(opt.get("mut"));
+    if (tmask) target_masks->push_back(opt.get("target_mask"));
+    if (rmask) ref_masks->push_back(opt.get("reference_mask"));
   }
 }
 
@@ -1081,7 +671,8 @@ int run_mut(const Options& opt) {
   }
   const std::string out = opt.get("output");
 
-  std::vector<double> csh, cns, fsh, fns, fshe, fnse, weights;
+  std::vector<double> csh, cns, weights;
+  PairTables tab;  // (block bootstrap + F redistribution, coal.cpp:3326-3451, on its flat [nb][A] tables)
   int num_blocks = 0;
   bool gpu_bootstrap = false;
   const std::string mat = out + ".colate_mat";
@@ -1089,48 +680,23 @@ int run_mut(const Options& opt) {
     std::cerr << "Loading precomputed file " << mat << std::endl;
     load_colate_mat(mat, B, A, age_grid, csh, cns);
   } else if (opt.has("target_tmp") && opt.has("reference_tmp")) {
-    std::vector<std::string> mut_files, tmask, rmask, names;
-    if (opt.has("chr")) {  // coal.cpp:3295-3310
-      GzText is_chr;
-      if (!is_chr.open(opt.get("chr")))
-        std::cerr << "Error while opening file " << opt.get("chr") << std::endl;
-      std::string line;
-      while (is_chr.getline(line)) {
-        names.push_back(line);
-        mut_files.push_back(opt.get("mut") + "_chr" + line + ".mut");
-        if (opt.has("target_mask")) tmask.push_back(opt.get("target_mask") + "_chr" + line + ".fa");
-        if (opt.has("reference_mask")) rmask.push_back(opt.get("reference_mask") + "_chr" + line + ".fa");
-      }
-    } else {
-      names.push_back("");
-      mut_files.push_back(opt.get("mut"));
-      if (opt.has("target_mask")) tmask.push_back(opt.get("target_mask"));
-      if (opt.has("reference_mask")) rmask.push_back(opt.get("reference_mask"));
-    }
-    // Without masks the pair goes through the engine of the batched front end (mut_pairs.cpp) as a list of one: every .mut file
-    // parsed in parallel, the .colate.in files mapped, the SNP walk on one thread and the age sampling of the genome blocks on
-    // all the others, exact table-driven age bins -- the same tables bit for bit (22 x 1M rows: 3.3 -> 0.x s of table fill,
-    // profiles/r04/bench/e2e_large.txt).  With masks (and with COLATE_THREADS=1 or COLATE_SINGLE_FEEDER=1) the single-pair
-    // feeder below, which is also what the engine falls back to.
-    int nb = -1;
+    std::vector<std::string> names, mut_files, tmask, rmask;
+    chromosome_files(opt, names, mut_files, &tmask, &rmask);
+    // The pair goes through the engine of the batched front end (mut_pairs.cpp) as a list of one: every .mut file parsed in
+    // parallel, the .colate.in files mapped, the SNP walk on one thread and the age sampling of the genome blocks on all the
+    // others (or on the GPU), exact table-driven age bins -- the same tables bit for bit (22 x 1M rows: 3.3 -> 0.x s of table
+    // fill, profiles/r04/bench/e2e_large.txt).  COLATE_THREADS=1: the sequential feeder, which is also what the engine falls
+    // back to.
+    const std::string& tgt_file = opt.get("target_tmp");
+    const std::string& ref_file = opt.get("reference_tmp");
     const char* thr_env = std::getenv("COLATE_THREADS");
-    if (tmask.empty() && rmask.empty() && !std::getenv("COLATE_SINGLE_FEEDER") && !(thr_env && std::atoi(thr_env) <= 1)) {
+    int nb;
+    if (thr_env && std::atoi(thr_env) <= 1) {
+      nb = fill_tables_from_tmp(names, mut_files, tgt_file, ref_file, tmask, rmask, C, rng, num_bases_per_block, A, tab);
+    } else {
       for (size_t chr = 0; chr < mut_files.size(); chr++) std::cerr << "parsing CHR: " << chr + 1 << " / " << mut_files.size() << std::endl;
-      nb = fill_single_pair(opt, opt.get("target_tmp"), opt.get("reference_tmp"), seed, A, fsh, fns, fshe, fnse, rng);
-    }
-    if (nb < 0) {
-      BlockTables tab;
-      nb = fill_tables_from_tmp(names, mut_files, opt.get("target_tmp"), opt.get("reference_tmp"), tmask, rmask, C, rng,
-                                num_bases_per_block, A, tab);
-      // block bootstrap + F redistribution (coal.cpp:3326-3451) on flat [nb][A] tables
-      const int nbp = nb > 0 ? nb : 0;
-      fsh.resize((size_t)nbp * A), fns.resize((size_t)nbp * A), fshe.resize((size_t)nbp * A), fnse.resize((size_t)nbp * A);
-      for (int j = 0; j < nbp; j++) {
-        std::copy(tab.sh[j].begin(), tab.sh[j].end(), fsh.begin() + (size_t)j * A);
-        std::copy(tab.ns[j].begin(), tab.ns[j].end(), fns.begin() + (size_t)j * A);
-        std::copy(tab.sh_emp[j].begin(), tab.sh_emp[j].end(), fshe.begin() + (size_t)j * A);
-        std::copy(tab.ns_emp[j].begin(), tab.ns_emp[j].end(), fnse.begin() + (size_t)j * A);
-      }
+      nb = fill_single_pair(opt, tgt_file, ref_file, tmask, rmask, seed, A, tab);
+      rng = tab.rng;
     }
     std::cerr << "Number of blocks: " << nb << std::endl;
     if (nb < 1) {
@@ -1151,8 +717,8 @@ int run_mut(const Options& opt) {
         std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
         return 1;
       }
-    } else if (int rc = colate_bootstrap_counts(&rng, B, nb, A, age_grid.data(), age, fsh.data(), fns.data(),
-                                                fshe.data(), fnse.data(), csh.data(), cns.data())) {
+    } else if (int rc = colate_bootstrap_counts(&rng, B, nb, A, age_grid.data(), age, tab.sh.data(), tab.ns.data(),
+                                                tab.she.data(), tab.nse.data(), csh.data(), cns.data())) {
       std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
       return 1;
     }
@@ -1191,8 +757,7 @@ int run_mut(const Options& opt) {
   }
   auto report_times = [&]() {
     if (g_times.on)
-      std::cerr << "Timing: parse_mut " << g_times.parse_mut << " s (on the reader thread when pipelined), table_fill "
-                << g_times.table_fill << " s, waited_for_parser " << g_times.wait_for_parser << " s, bootstrap_em "
+      std::cerr << "Timing: parse_mut " << g_times.parse_mut << " s, table_fill " << g_times.table_fill << " s, bootstrap_em "
                 << g_times.bootstrap_em << " s" << std::endl;
   };
   if (opt.has("counts_only")) {
@@ -1263,8 +828,8 @@ int run_mut(const Options& opt) {
     if (!rc) rc = colate_comm_create(id, g_rank.nranks, g_rank.rank, &comm);
     if (!rc) {
       if (gpu_bootstrap)
-        rc = colate_bootstrap_em_batch_allgather(comm, B, num_blocks, E, A, age_grid.data(), age, weights.data(), fsh.data(),
-                                                 fns.data(), fshe.data(), fnse.data(), epochs.data(), init_rates.data(),
+        rc = colate_bootstrap_em_batch_allgather(comm, B, num_blocks, E, A, age_grid.data(), age, weights.data(), tab.sh.data(),
+                                                 tab.ns.data(), tab.she.data(), tab.nse.data(), epochs.data(), init_rates.data(),
                                                  COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER, COLATE_DEFAULT_REL_TOL,
                                                  COLATE_DEFAULT_RATE_FLOOR, rates.data(), iters.data(), ll.data(), flags.data());
       else
@@ -1293,8 +858,8 @@ int run_mut(const Options& opt) {
                                  COLATE_DEFAULT_MIN_ITER, COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR,
                                  rates.data(), iters.data(), ll.data(), flags.data());
   } else if (gpu_bootstrap) {
-    rc = colate_bootstrap_em_batch(B, num_blocks, E, A, age_grid.data(), age, weights.data(), fsh.data(), fns.data(),
-                                   fshe.data(), fnse.data(), epochs.data(), init_rates.data(), COLATE_DEFAULT_MAX_ITER,
+    rc = colate_bootstrap_em_batch(B, num_blocks, E, A, age_grid.data(), age, weights.data(), tab.sh.data(), tab.ns.data(),
+                                   tab.she.data(), tab.nse.data(), epochs.data(), init_rates.data(), COLATE_DEFAULT_MAX_ITER,
                                    COLATE_DEFAULT_MIN_ITER, COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR,
                                    rates.data(), iters.data(), ll.data(), flags.data(), csh.data(), cns.data());
     if (rc == 0 && opt.has("counts_out")) write_counts();

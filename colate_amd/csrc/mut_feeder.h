@@ -1,6 +1,7 @@
 // colate_amd/csrc/mut_feeder.h -- what the two host-side translation units of the `Colate --mode mut` driver share:
-// mut_driver.cpp (command line, readers, the single-pair feeder of include/coal/coal.cpp:2071-2321, mut() driver, --ranks launcher)
-// and mut_pairs.cpp (the batched all-pairs front end, SURVEY.md section 8 f2 / BASELINE configs[4]).
+// mut_driver.cpp (command line, readers, the sequential feeder of include/coal/coal.cpp:2071-2321, mut() driver, --ranks launcher)
+// and mut_pairs.cpp (the batched front end, SURVEY.md section 8 f2 / BASELINE configs[4], whose engine fills every table of a
+// `--pairs` run and of a single pair, and hands a pair it cannot fill exactly to the sequential feeder).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -21,7 +22,7 @@ struct Options {
 
 // stage timing (COLATE_TIMING=1: one stderr line at the end)
 struct StageTimes {
-  double parse_mut = 0, table_fill = 0, wait_for_parser = 0, bootstrap_em = 0;
+  double parse_mut = 0, table_fill = 0, bootstrap_em = 0;
   bool on = std::getenv("COLATE_TIMING") != nullptr;
   static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 };
@@ -40,15 +41,13 @@ struct MutRow {
 bool read_mut_file(const std::string& filename, std::vector<MutRow>& rows);
 // the same, row by row (nothing is kept)
 bool for_each_mut_row(const std::string& filename, const std::function<void(const MutRow&)>& sink);
+// the upper-cased sequence of a fasta mask (data.cpp:213-235); exits like the reference when the file cannot be opened
+void read_fasta_mask(const std::string& filename, std::string& seq);
 
-struct BlockTables {  // one entry per genome block; emp = row 0 of the reference's A*A tables
-  std::vector<std::vector<double>> sh, ns, sh_emp, ns_emp;
-  void add_block(int A) {
-    sh.emplace_back(A, 0.0);
-    ns.emplace_back(A, 0.0);
-    sh_emp.emplace_back(A, 0.0);
-    ns_emp.emplace_back(A, 0.0);
-  }
+struct PairTables {  // flat [nb][A] tables of one pair, as the bootstrap takes them; she / nse = row 0 of the reference's A*A tables
+  int nb = 0;
+  std::vector<double> sh, ns, she, nse;
+  std::mt19937 rng;  // the run's generator after the table fill
 };
 
 inline int age_bin_index(double x, double C) {  // coal.cpp:2265, 2284
@@ -59,7 +58,7 @@ inline int age_bin_index(double x, double C) {  // coal.cpp:2265, 2284
 
 // std::mt19937's recurrence with the state regenerated 624 words at a time in loops the compiler vectorises (the library's
 // operator() does the same work word by word: 7.5 ns per word on the build container, against ~2 here).  Same sequence by
-// construction; UniformStream checks it against the library's generator before it trusts it.  State goes in and out of a
+// construction; bulk_stream_ok (mut_pairs.cpp) checks it against the library's generator before it is trusted.  State goes in and out of a
 // std::mt19937 through its textual form (the 624 words and the position, [rand.eng.mers]).
 class BulkMt19937 {
  public:
@@ -136,18 +135,20 @@ bool read_all(int fd, void* buf, size_t n);
 struct PairSpec {
   std::string target, reference, output;
   double target_age = 0, ref_age = 0;
+  std::vector<std::string> target_masks, ref_masks;  // one fasta per chromosome, or none
 };
 
-// coal.cpp:2071-2321 for one (target, reference) pair from the files themselves: the single-pair feeder (sampling on worker
-// threads where the machine has them).  Returns the number of genome blocks.
+// coal.cpp:2071-2321 for one (target, reference) pair, on the calling thread in the reference's order: the sequential feeder.
+// Fills tab.sh, ns, she, nse and tab.nb (not tab.rng: the draws come from `rng`).  Returns the number of genome blocks.
 int fill_tables_from_tmp(const std::vector<std::string>& chr_names, const std::vector<std::string>& mut_files,
                          const std::string& target_file, const std::string& ref_file,
                          const std::vector<std::string>& target_masks, const std::vector<std::string>& ref_masks, double C,
-                         std::mt19937& rng, int num_bases_per_block, int A, BlockTables& tab,
-                         std::map<std::string, std::vector<MutRow>>* mut_cache = nullptr);
+                         std::mt19937& rng, int num_bases_per_block, int A, PairTables& tab);
 
-// the chromosome list of --chr (coal.cpp:3295-3310): names and <mut>_chr<name>.mut paths; without --chr one unnamed chromosome
-void chromosome_files(const Options& opt, std::vector<std::string>& names, std::vector<std::string>& mut_files);
+// the chromosome list of --chr (coal.cpp:3295-3310): names, <mut>_chr<name>.mut paths and, where asked for and given,
+// <mask>_chr<name>.fa paths of --target_mask / --reference_mask; without --chr one unnamed chromosome and the paths verbatim
+void chromosome_files(const Options& opt, std::vector<std::string>& names, std::vector<std::string>& mut_files,
+                      std::vector<std::string>* target_masks = nullptr, std::vector<std::string>* ref_masks = nullptr);
 
 void write_counts_file(const std::string& path, int B, int A, const std::vector<double>& grid, const double* csh,
                        const double* cns);
@@ -155,10 +156,10 @@ void print_usage_footer();  // "CPU Time spent: ...; Max Memory usage: ..." (coa
 
 // mut_pairs.cpp
 int run_mut_pairs(const Options& opt);
-// One pair through the engine of the batched front end: the flat [nb][A] tables and the generator as the fill leaves it.
-// Returns the number of genome blocks, or -1 if the engine cannot be used here (the caller then runs fill_tables_from_tmp).
-int fill_single_pair(const Options& opt, const std::string& target, const std::string& reference, int seed, int A,
-                     std::vector<double>& sh, std::vector<double>& ns, std::vector<double>& she, std::vector<double>& nse,
-                     std::mt19937& rng);
+// One pair (masks per chromosome, or none) through the engine of the batched front end: the tables and the generator as
+// the fill leaves it.  Returns the number of genome blocks.
+int fill_single_pair(const Options& opt, const std::string& target, const std::string& reference,
+                     const std::vector<std::string>& target_masks, const std::vector<std::string>& ref_masks, int seed, int A,
+                     PairTables& out);
 
 }  // namespace colate_drv

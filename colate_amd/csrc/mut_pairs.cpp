@@ -173,8 +173,8 @@ class Pool {
 
 // ------------------------------------------------------------------ .mut rows, reduced to what a pair's walk needs
 // A row that fails the row-level conditions of coal.cpp:2150 (flipped, one branch, age_begin < age_end) or whose alleles are
-// not single bases (coal.cpp:2160-2176) touches neither stream nor generator in the reference's loop (without masks, which
-// --pairs refuses): such rows are dropped when the file is parsed.
+// not single bases (coal.cpp:2160-2176) touches neither stream nor generator in the reference's loop: such rows are dropped when
+// the file is parsed.  (So does a row a mask removes, coal.cpp:2169-2174: PairFill::skip.)
 struct CompactRow {
   int pos;
   float age_begin, age_end;
@@ -498,7 +498,7 @@ void build_walk_index(TmpFile& f, const WalkRows& w) {
 
 // ------------------------------------------------------------------ the uniform stream of the seed, generated once
 // std::uniform_real_distribution<double>(0, 1) on std::mt19937 = generate_canonical<double, 53>: two 32-bit draws per value
-// (mut_driver.cpp, canonical_fast).  One producer thread fills a ring of chunks; readers address the stream by offset.
+// (libstdc++ bits/random.tcc).  One producer thread fills a ring of chunks; readers address the stream by offset.
 inline double canonical_from_words(uint32_t r1, uint32_t r2) {
   double ret = ((double)r1 + (double)r2 * 4294967296.0) * 0x1p-64;
   if (ret >= 1.0) ret = std::nextafter(1.0, 0.0);
@@ -858,6 +858,8 @@ struct PairFill {
   // inputs
   size_t index = 0;
   const TmpFile *tgt_file = nullptr, *ref_file = nullptr;
+  // per chromosome, per CompactRow: a mask removes the row (coal.cpp:2169-2174); empty without masks
+  std::vector<std::vector<char>> skip;
   // walk state (coal.cpp:2071-2321)
   Cursor tgt, ref;
   size_t chr = 0, row = 0;
@@ -1075,7 +1077,8 @@ struct Engine {
     if (pf.blocks.empty()) pf.blocks.emplace_back(new Block(A));
     while (pf.chr < rows.size()) {
       if (pf.redo.load(std::memory_order_relaxed)) break;
-      const bool indexed = use_index && pf.ref_file->indexable && pf.tgt_file->indexable;
+      // (a pair with masks walks with the cursors: the indices assume a search at every row)
+      const bool indexed = use_index && pf.skip.empty() && pf.ref_file->indexable && pf.tgt_file->indexable;
       if (!pf.chr_open) {
         pf.current_block_base = 0;
         if (!indexed) {
@@ -1116,6 +1119,7 @@ struct Engine {
           flush(pf);
           return;
         }
+        if (!pf.skip.empty() && pf.skip[pf.chr][pf.row]) continue;  // (neither cursor is touched for it)
         const CompactRow& m = rr[pf.row];
         const int bp_mut = m.pos;
         bool use = true;
@@ -1177,12 +1181,6 @@ bool read_pair_list(const std::string& path, std::vector<PairSpec>& pairs) {
   return true;
 }
 
-struct PairTables {  // flat [nb][A] tables of one pair, as the bootstrap takes them
-  int nb = 0;
-  std::vector<double> sh, ns, she, nse;
-  std::mt19937 rng;  // the run's generator after the table fill
-};
-
 // The tables of the pairs listed in `todo` (indices into `pairs`); false after an error message.
 bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A,
                 std::vector<PairTables>& out) {
@@ -1198,21 +1196,10 @@ bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const st
   // the sequential feeder (one pair after the other, files re-read): when the bulk generator does not reproduce this
   // machine's std::mt19937 stream, and for a pair in which a sample beyond the age grid had to be redrawn
   auto fill_sequentially = [&](size_t p) {
-    std::mt19937 rng;
-    rng.seed(seed);
-    BlockTables tab;
-    const int nb = fill_tables_from_tmp(names, mut_files, pairs[p].target, pairs[p].reference, {}, {}, C, rng,
-                                        num_bases_per_block, A, tab);
     PairTables& pt = out[p];
-    pt.nb = nb;
-    pt.sh.resize((size_t)std::max(nb, 0) * A), pt.ns.resize(pt.sh.size()), pt.she.resize(pt.sh.size()), pt.nse.resize(pt.sh.size());
-    for (int j = 0; j < nb; j++) {
-      std::copy(tab.sh[j].begin(), tab.sh[j].end(), pt.sh.begin() + (size_t)j * A);
-      std::copy(tab.ns[j].begin(), tab.ns[j].end(), pt.ns.begin() + (size_t)j * A);
-      std::copy(tab.sh_emp[j].begin(), tab.sh_emp[j].end(), pt.she.begin() + (size_t)j * A);
-      std::copy(tab.ns_emp[j].begin(), tab.ns_emp[j].end(), pt.nse.begin() + (size_t)j * A);
-    }
-    pt.rng = rng;
+    pt.rng.seed(seed);
+    fill_tables_from_tmp(names, mut_files, pairs[p].target, pairs[p].reference, pairs[p].target_masks, pairs[p].ref_masks, C,
+                         pt.rng, num_bases_per_block, A, pt);
   };
   if (!bulk_stream_ok((unsigned)seed)) {
     std::cerr << "Note: the bulk generator does not reproduce this machine's std::mt19937 stream; filling the pairs one by one." << std::endl;
@@ -1311,6 +1298,38 @@ bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const st
   pool.wait_idle();
   for (auto& kv : tmp_files)
     if (!kv.second->ok) std::cerr << "Failed to open " << kv.first << std::endl;  // (the reference goes on and reads nothing)
+  std::vector<std::unique_ptr<PairFill>> fills;
+  for (size_t p : todo) {
+    fills.emplace_back(new PairFill);
+    PairFill& pf = *fills.back();
+    pf.index = p;
+    pf.slot = fills.size() - 1;
+    pf.tgt_file = tmp_files[pairs[p].target].get(), pf.ref_file = tmp_files[pairs[p].reference].get();
+    pf.tgt.open(*pf.tgt_file), pf.ref.open(*pf.ref_file);
+  }
+  // ---- the rows each pair's masks remove (coal.cpp:2169-2174), one task per (pair, chromosome), one mask string alive per task
+  for (auto& pfp : fills) {
+    const PairSpec& ps = pairs[pfp->index];
+    if (ps.target_masks.empty() && ps.ref_masks.empty()) continue;
+    pfp->skip.resize(rows.size());
+    for (size_t c = 0; c < rows.size(); c++) {
+      PairFill* pf = pfp.get();
+      pool.submit([&ps, &rows, pf, c] {
+        const HugeVector<CompactRow>& rr = rows[c];
+        std::vector<char>& skip = pf->skip[c];
+        skip.assign(rr.size(), 0);
+        std::string mask;
+        for (const std::vector<std::string>* files : {&ps.target_masks, &ps.ref_masks}) {
+          if (files->empty()) continue;
+          read_fasta_mask((*files)[c], mask);
+          for (size_t i = 0; i < rr.size(); i++) {
+            const int bp = rr[i].pos;
+            if ((size_t)bp < mask.size() && mask[bp - 1] != 'P') skip[i] = 1;
+          }
+        }
+      });
+    }
+  }
   // ---- what the walks find in each file, once per file (build_walk_index)
   const char* e_idx = std::getenv("COLATE_INDEXED_WALK");
   const bool use_index = !(e_idx && std::atoi(e_idx) == 0);
@@ -1319,18 +1338,19 @@ bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const st
     WalkRows wr{&names, &rows, true};
     for (const HugeVector<CompactRow>& r : rows)
       for (size_t i = 1; i < r.size() && wr.rows_ascend; i++) wr.rows_ascend = r[i].pos >= r[i - 1].pos && r[i - 1].pos >= 0;
-    for (size_t p : todo) tmp_files[pairs[p].target]->want_tgt = true, tmp_files[pairs[p].reference]->want_ref = true;
+    for (auto& pf : fills)
+      if (pf->skip.empty()) tmp_files[pairs[pf->index].target]->want_tgt = true, tmp_files[pairs[pf->index].reference]->want_ref = true;
     for (auto& kv : tmp_files) {
       TmpFile* f = kv.second.get();
-      if (f->ok) pool.submit([f, wr] {
+      if (f->ok && (f->want_ref || f->want_tgt)) pool.submit([f, wr] {
         const double t0 = now_s();
         build_walk_index(*f, wr);
         WorkSeconds::add(g_work.index, now_s() - t0);
       });
     }
-    pool.wait_idle();
-    for (auto& kv : tmp_files) n_indexed += kv.second->indexable ? 1 : 0;
   }
+  pool.wait_idle();  // (the indices and the masks' rows)
+  for (auto& kv : tmp_files) n_indexed += kv.second->indexable ? 1 : 0;
   const double t1 = now_s();
   size_t n_rows = 0, n_kept = 0, n_rec = 0;
   for (size_t c = 0; c < rows.size(); c++) n_rows += rows_total[c], n_kept += rows[c].size();
@@ -1361,15 +1381,6 @@ bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const st
   }
   Engine eng{names, rows, A, C, num_bases_per_block, stream, fastbin, pool, fastbin.ok() ? pick_bin_snp() : nullptr, fastbin.ok() ? pick_add_snp() : nullptr,
              dev_pending ? &devq : nullptr, use_index};
-  std::vector<std::unique_ptr<PairFill>> fills;
-  for (size_t p : todo) {
-    fills.emplace_back(new PairFill);
-    PairFill& pf = *fills.back();
-    pf.index = p;
-    pf.slot = fills.size() - 1;
-    pf.tgt_file = tmp_files[pairs[p].target].get(), pf.ref_file = tmp_files[pairs[p].reference].get();
-    pf.tgt.open(*pf.tgt_file), pf.ref.open(*pf.ref_file);
-  }
   int windows = 0;
   uint64_t dev_next_chunk = 0;
   size_t dev_jobs = 0, dev_recs = 0, dev_launches = 0;
@@ -1537,18 +1548,16 @@ bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const st
 
 }  // namespace
 
-int fill_single_pair(const Options& opt, const std::string& target, const std::string& reference, int seed, int A,
-                     std::vector<double>& sh, std::vector<double>& ns, std::vector<double>& she, std::vector<double>& nse,
-                     std::mt19937& rng) {
-  if (!bulk_stream_ok((unsigned)seed)) return -1;  // (fill_pairs would run the single-pair feeder itself: let the caller do it)
+int fill_single_pair(const Options& opt, const std::string& target, const std::string& reference,
+                     const std::vector<std::string>& target_masks, const std::vector<std::string>& ref_masks, int seed, int A,
+                     PairTables& out) {
   std::vector<PairSpec> one(1);
   one[0].target = target, one[0].reference = reference;
+  one[0].target_masks = target_masks, one[0].ref_masks = ref_masks;
   std::vector<PairTables> tabs;
-  if (!fill_pairs(opt, one, {0}, seed, A, tabs)) return -1;
-  PairTables& pt = tabs[0];
-  sh = std::move(pt.sh), ns = std::move(pt.ns), she = std::move(pt.she), nse = std::move(pt.nse);
-  rng = pt.rng;
-  return pt.nb;
+  fill_pairs(opt, one, {0}, seed, A, tabs);
+  out = std::move(tabs[0]);
+  return out.nb;
 }
 
 int run_mut_pairs(const Options& opt) {

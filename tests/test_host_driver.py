@@ -208,10 +208,10 @@ def test_pairs_mode_counts_equal_separate_runs(tmp_path):
     # every input file is read once, whatever number of pairs it takes part in (here: both files in both pairs)
     assert "3 .mut files" in r.stderr.decode() and "2 .colate.in files" in r.stderr.decode(), r.stderr.decode()[-800:]
     for tgt, ref, out, ta, ra in specs:
-        # (COLATE_SINGLE_FEEDER=1: the pair alone through the single-pair feeder, not through the engine of the batched front end)
+        # (COLATE_THREADS=1: the pair alone through the sequential feeder, not through the engine of the batched front end)
         r = _run_cli(common + ["--target_tmp", tgt, "--reference_tmp", ref, "--target_age", ta, "--reference_age", ra,
                                "-o", out + "_single", "--counts_out", out + "_single.counts", "--counts_only"], str(tmp_path),
-                     env=dict(os.environ, COLATE_SINGLE_FEEDER="1"))
+                     env=dict(os.environ, COLATE_THREADS="1"))
         assert r.returncode == 0, r.stderr.decode()[-800:]
         assert (tmp_path / (out + ".counts")).read_text() == (tmp_path / (out + "_single.counts")).read_text()
 
@@ -219,7 +219,7 @@ def test_pairs_mode_counts_equal_separate_runs(tmp_path):
 def test_pairs_with_a_file_that_ends_inside_a_record(tmp_path):
     """A .colate.in that ends in the middle of a record: the reference's fread calls leave the fields they do not reach as they were
     (coal.cpp:2126-2133).  The batched front end decodes every file once into fixed records -- but not such a file, whose last record
-    depends on what the walk's variables held: its walks go through the byte cursor, and the tables are those of the single-pair feeder."""
+    depends on what the walk's variables held: its walks go through the byte cursor, and the tables are those of the sequential feeder."""
     case = gl.l3_stage("l3_modern", str(tmp_path))
     for name, cut in (("T.colate.in", 7), ("R.colate.in", 3)):
         raw = (tmp_path / name).read_bytes()
@@ -231,7 +231,7 @@ def test_pairs_with_a_file_that_ends_inside_a_record(tmp_path):
     assert r.returncode == 0, r.stderr.decode()[-800:]
     for tgt, ref, out in specs:
         r = _run_cli(common + ["--target_tmp", tgt, "--reference_tmp", ref, "-o", out + "_single", "--counts_out", out + "_single.counts",
-                               "--counts_only"], str(tmp_path), env=dict(os.environ, COLATE_SINGLE_FEEDER="1"))
+                               "--counts_only"], str(tmp_path), env=dict(os.environ, COLATE_THREADS="1"))
         assert r.returncode == 0, r.stderr.decode()[-800:]
         assert (tmp_path / (out + ".counts")).read_text() == (tmp_path / (out + "_single.counts")).read_text()
 
@@ -517,60 +517,92 @@ def test_ranks_refused_once_the_process_has_used_the_device(ca, tmp_path):
     assert r.returncode == 1 and "must run before this process first uses a GPU" in r.stderr, (r.returncode, r.stderr)
 
 
-def _counts(tmp_path, threads, extra=(), single_feeder=False):
-    """single_feeder: the pair through the single-pair feeder of mut_driver.cpp (reader threads, uniform-stream thread, sampling
-    workers) instead of the engine of the batched front end (mut_pairs.cpp), which is what a pair without masks takes by default."""
+def _counts(tmp_path, threads, extra=()):
+    """COLATE_THREADS=1: the pair through the sequential feeder of mut_driver.cpp; more: the engine of the batched front end
+    (mut_pairs.cpp) with a list of one pair."""
     env = dict(os.environ, COLATE_THREADS=str(threads), COLATE_TIMING="1")
-    if single_feeder:
-        env["COLATE_SINGLE_FEEDER"] = "1"
-    out = f"c{threads}{'s' if single_feeder else ''}"
+    out = f"c{threads}"
     r = subprocess.run([CLI, "--mode", "mut", "--mut", "P", "--target_tmp", "T.colate.in", "--reference_tmp", "R.colate.in", "--chr",
                         "chr.txt", "--bins", "3,7,0.2", "--seed", "11", "--num_bootstraps", "7", "--counts_only", "--counts_out",
                         out + ".counts", "-o", out] + list(extra), cwd=str(tmp_path), capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stderr[-500:]
     assert "Timing: parse_mut" in r.stderr
-    _counts.redone = "repeated sequentially" in r.stderr or "1 pair(s) redone sequentially" in r.stderr
+    _counts.engine = "pairs front end on" in r.stderr
+    _counts.redone = "1 pair(s) redone sequentially" in r.stderr
+    assert _counts.engine == (threads > 1), r.stderr[-500:]
     return (tmp_path / (out + ".counts")).read_text()
 
 
+def _push_beyond_the_age_grid(path, n):
+    """Rewrites `n` used-looking rows of a .mut.gz so that most of their sampled ages lie beyond the last grid point (8.9e6
+    generations): the reference draws such a sample again (coal.cpp:2286-2287)."""
+    import gzip
+
+    lines = gzip.open(path, "rt").read().split("\n")
+    n_changed = 0
+    for i in range(1, len(lines)):
+        f = lines[i].split(";")
+        if len(f) > 10 and f[7] == "0" and f[5] == "7" and float(f[8]) > 1e4 and n_changed < n:
+            f[8], f[9] = "5e+06", "4e+07"
+            lines[i] = ";".join(f)
+            n_changed += 1
+    assert n_changed == n
+    with gzip.open(path, "wt") as g:
+        g.write("\n".join(lines))
+
+
 def test_threaded_table_fill_is_bit_identical_to_sequential(tmp_path):
-    """The reader threads, the uniform-stream thread and the sampling workers (mut_driver.cpp) leave the count tables -- and
-    the std::mt19937 state the bootstrap weights are drawn from afterwards -- exactly as the sequential code does."""
+    """The engine of the batched front end with a list of one pair (worker threads, shared uniform stream) leaves the count tables
+    -- and the std::mt19937 state the bootstrap weights are drawn from afterwards -- exactly as the sequential feeder does."""
     import synth_files
 
     synth_files.write_inputs(str(tmp_path), chroms=("1", "2", "3"), snps_per_chr=4000, seed=3, gz=True)
-    threaded = _counts(tmp_path, 8, single_feeder=True)
+    threaded = _counts(tmp_path, 8)
     assert not _counts.redone
     assert threaded == _counts(tmp_path, 1)
-    assert threaded == _counts(tmp_path, 8)  # ... and so does the engine of the batched front end with a list of one pair
-    assert not _counts.redone
 
 
 def test_threaded_table_fill_redoes_sequentially_when_a_sample_is_redrawn(tmp_path):
     """A mutation older than the age grid makes the reference draw again (coal.cpp:2286-2287), which breaks the fixed 100
-    draws per SNP the threaded fill relies on: it must notice and repeat the fill sequentially, with the same result."""
-    import gzip
-
+    draws per SNP the engine relies on: it must notice and hand the pair to the sequential feeder, with the same result."""
     import synth_files
 
     synth_files.write_inputs(str(tmp_path), chroms=("1", "2"), snps_per_chr=2500, seed=5, gz=True)
-    p = tmp_path / "P_chr2.mut.gz"
-    lines = gzip.open(p, "rt").read().split("\n")
-    n_changed = 0
-    for i in range(1, len(lines)):
-        f = lines[i].split(";")
-        if len(f) > 10 and f[7] == "0" and f[5] == "7" and float(f[8]) > 1e4 and n_changed < 40:
-            f[8], f[9] = "5e+06", "4e+07"  # most sampled ages lie beyond the last grid point (8.9e6 generations)
-            lines[i] = ";".join(f)
-            n_changed += 1
-    assert n_changed == 40
-    with gzip.open(p, "wt") as g:
-        g.write("\n".join(lines))
-    threaded = _counts(tmp_path, 8, single_feeder=True)
-    assert _counts.redone  # (the threaded pass gave up ...)
+    _push_beyond_the_age_grid(tmp_path / "P_chr2.mut.gz", 40)
+    threaded = _counts(tmp_path, 8)
+    assert _counts.redone  # (the engine gave the pair up ...)
     assert threaded == _counts(tmp_path, 1)  # (... and the repeat is the sequential result)
-    assert threaded == _counts(tmp_path, 8)  # (the engine of the batched front end notices too and hands the pair to the feeder)
-    assert _counts.redone
+
+
+def _masked_counts(tmp_path, case, threads):
+    args = list(case["args"])
+    args[args.index("-o") + 1] = f"m{threads}"
+    r = _run_cli(args + ["--counts_out", f"m{threads}.counts", "--counts_only"], str(tmp_path),
+                 env=dict(os.environ, COLATE_THREADS=str(threads), COLATE_TIMING="1"))
+    assert r.returncode == 0, r.stderr.decode()[-800:]
+    return r.stderr.decode(), (tmp_path / f"m{threads}.counts").read_text()
+
+
+def test_engine_fills_masked_pair_like_the_sequential_feeder(tmp_path):
+    """A single pair with --target_mask and --reference_mask goes through the engine (the masks remove rows before either cursor
+    moves, coal.cpp:2169-2174): the same tables as the sequential feeder."""
+    case = gl.l3_stage("l3_masks", str(tmp_path))
+    err, engine = _masked_counts(tmp_path, case, 8)
+    assert "pairs front end on" in err and "0 pair(s) redone" in err, err[-800:]
+    err1, sequential = _masked_counts(tmp_path, case, 1)
+    assert "pairs front end on" not in err1
+    assert engine == sequential
+
+
+def test_engine_hands_masked_pair_to_the_sequential_feeder_with_its_masks(tmp_path):
+    """The masked pair with samples beyond the age grid: the engine gives it up, and the sequential feeder it falls back to
+    applies the masks too (the tables equal COLATE_THREADS=1, which would differ without them)."""
+    case = gl.l3_stage("l3_masks", str(tmp_path))
+    _push_beyond_the_age_grid(tmp_path / "P_chr1.mut.gz", 10)
+    err, engine = _masked_counts(tmp_path, case, 8)
+    assert "1 pair(s) redone" in err, err[-800:]
+    _, sequential = _masked_counts(tmp_path, case, 1)
+    assert engine == sequential
 
 
 def test_malformed_mut_line_is_reported_from_the_reader_thread(tmp_path):

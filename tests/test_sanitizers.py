@@ -107,7 +107,7 @@ def test_pairs_front_end_clean_and_equal_to_single_runs(tmp_path):
     """The batched all-pairs front end (mut_pairs.cpp: thread pool, shared uniform stream in windows, mapped .colate.in
     files, per-block sampling jobs) under ASan/UBSan and under ThreadSanitizer, on inputs large enough for several stream
     windows (COLATE_UNIFORM_WINDOW_MB=4: about 5 000 used SNPs per window), with 1, 3 and 8 workers: no report, and every
-    pair's tables equal to those of the pair run alone through the single-pair feeder of the regular build."""
+    pair's tables equal to those of the pair run alone through the sequential feeder of the regular build."""
     import synth_files
 
     synth_files.write_inputs(str(tmp_path), chroms=("1", "2"), snps_per_chr=16000, seed=5, gz=True, extra_targets=1, extra_refs=1)
@@ -121,7 +121,7 @@ def test_pairs_front_end_clean_and_equal_to_single_runs(tmp_path):
     for tgt, ref, out, ta, ra in specs[:4]:
         subprocess.check_call([cli] + common + ["--target_tmp", tgt, "--reference_tmp", ref, "--target_age", ta, "--reference_age", ra,
                                                  "-o", out + "_single", "--counts_out", out + "_single.counts", "--counts_only"],
-                              cwd=str(tmp_path), stderr=subprocess.DEVNULL, env=dict(os.environ, COLATE_SINGLE_FEEDER="1"))
+                              cwd=str(tmp_path), stderr=subprocess.DEVNULL, env=dict(os.environ, COLATE_THREADS="1"))
         expected[out] = (tmp_path / (out + "_single.counts")).read_text()
     for exe, threads in ((ASAN_CLI, "3"), (TSAN_CLI, "1"), (TSAN_CLI, "3"), (TSAN_CLI, "8")):
         r, err = _run(exe, common + ["--pairs", "pairs.txt", "--counts_only"], str(tmp_path), COLATE_THREADS=threads,
@@ -144,5 +144,5 @@ def test_pairs_front_end_clean_and_equal_to_single_runs(tmp_path):
     assert r.returncode == 0, err[-800:]
     subprocess.check_call([cli] + common + ["--target_tmp", "trunc.colate.in", "--reference_tmp", "R.colate.in", "-o", "p5_single",
                                              "--counts_out", "p5_single.counts", "--counts_only"], cwd=str(tmp_path), stderr=subprocess.DEVNULL,
-                          env=dict(os.environ, COLATE_SINGLE_FEEDER="1"))
+                          env=dict(os.environ, COLATE_THREADS="1"))
     assert (tmp_path / "p5.counts").read_text() == (tmp_path / "p5_single.counts").read_text()
