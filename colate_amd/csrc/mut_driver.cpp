@@ -128,9 +128,12 @@ void print_help() {
             << "      --device arg           Optional (colate_amd): GPU ordinal, default 0.\n"
             << "      --devices arg          Optional (colate_amd): shard the bootstrap replicates over GPUs 0..N-1 (one process).\n"
             << "      --ranks arg            Optional (colate_amd): the same as N processes, one per GPU, one RCCL all-gather.\n"
-            << "      --pairs arg            Optional (colate_amd): file of `target_tmp reference_tmp output [target_age reference_age]`\n"
+            << "      --pairs arg            Optional (colate_amd): file of `target_tmp reference_tmp output [target_age [reference_age]]`\n"
             << "                             lines; all pairs share --mut/--chr/--bins/--num_bootstraps/--seed, each .mut is parsed\n"
-            << "                             once and all replicates of all pairs run in one GPU launch.\n"
+            << "                             once and all replicates of all pairs run in one GPU launch.  After the three names a\n"
+            << "                             line may carry, in any order and mixed with the ages, target_mask=PREFIX,\n"
+            << "                             reference_mask=PREFIX (expanded as --target_mask / --reference_mask are) and\n"
+            << "                             coal=FILE (the pair's --coal warm start; --bins is then not needed for that line).\n"
             << "      --counts_out arg       Optional (colate_amd): write the bootstrap count tables (.colate_mat layout).\n"
             << "      --counts_only          Optional (colate_amd): stop after --counts_out (no GPU needed).\n"
             << "      --write_colate_mat     Optional (colate_amd): write <output>.colate_mat as the reference does for BCF/BAM inputs.\n"
@@ -313,12 +316,21 @@ bool read_mut_file(const std::string& filename, std::vector<MutRow>& rows) {
 }
 
 // data.cpp:213-235: sequence = upper-cased lines after the header, concatenated (also read on the engine's pool threads)
-void read_fasta_mask(const std::string& filename, std::string& seq) {
-  GzText is;
+static void open_fasta_mask(GzText& is, const std::string& filename) {
   if (!is.open(filename) && !is.open(filename + ".gz")) {
     std::cerr << "Error while opening file " << filename << "." << std::endl;
     reader_exit();  // (data.cpp: exit(1))
   }
+}
+
+void check_fasta_mask(const std::string& filename) {
+  GzText is;
+  open_fasta_mask(is, filename);
+}
+
+void read_fasta_mask(const std::string& filename, std::string& seq) {
+  GzText is;
+  open_fasta_mask(is, filename);
   std::string line;
   is.getline(line);
   seq.clear();
@@ -584,7 +596,6 @@ void print_usage_footer() {  // coal.cpp:3852-3861
 // chromosome, else the paths verbatim and the chromosome name ""
 void chromosome_files(const Options& opt, std::vector<std::string>& names, std::vector<std::string>& mut_files,
                       std::vector<std::string>* target_masks, std::vector<std::string>* ref_masks) {
-  const bool tmask = target_masks && opt.has("target_mask"), rmask = ref_masks && opt.has("reference_mask");
   if (opt.has("chr")) {
     GzText is_chr;
     if (!is_chr.open(opt.get("chr"))) std::cerr << "Error while opening file " << opt.get("chr") << std::endl;
@@ -592,15 +603,20 @@ void chromosome_files(const Options& opt, std::vector<std::string>& names, std::
     while (is_chr.getline(line)) {
       names.push_back(line);
       mut_files.push_back(opt.get("mut") + "_chr" + line + ".mut");
-      if (tmask) target_masks->push_back(opt.get("target_mask") + "_chr" + line + ".fa");
-      if (rmask) ref_masks->push_back(opt.get("reference_mask") + "_chr" + line + ".fa");
     }
   } else {
     names.push_back("");
     mut_files.push_back(opt.get("mut"));
-    if (tmask) target_masks->push_back(opt.get("target_mask"));
-    if (rmask) ref_masks->push_back(opt.get("reference_mask"));
   }
+  if (target_masks && opt.has("target_mask")) *target_masks = mask_files(opt, names, opt.get("target_mask"));
+  if (ref_masks && opt.has("reference_mask")) *ref_masks = mask_files(opt, names, opt.get("reference_mask"));
+}
+
+std::vector<std::string> mask_files(const Options& opt, const std::vector<std::string>& names, const std::string& prefix) {
+  if (!opt.has("chr")) return {prefix};
+  std::vector<std::string> files;
+  for (const std::string& n : names) files.push_back(prefix + "_chr" + n + ".fa");
+  return files;
 }
 
 int run_mut(const Options& opt) {
@@ -695,7 +711,7 @@ int run_mut(const Options& opt) {
       nb = fill_tables_from_tmp(names, mut_files, tgt_file, ref_file, tmask, rmask, C, rng, num_bases_per_block, A, tab);
     } else {
       for (size_t chr = 0; chr < mut_files.size(); chr++) std::cerr << "parsing CHR: " << chr + 1 << " / " << mut_files.size() << std::endl;
-      nb = fill_single_pair(opt, tgt_file, ref_file, tmask, rmask, seed, A, tab);
+      nb = fill_single_pair(opt, names, mut_files, tgt_file, ref_file, tmask, rmask, seed, A, tab);
       rng = tab.rng;
     }
     std::cerr << "Number of blocks: " << nb << std::endl;

@@ -43,6 +43,8 @@ bool read_mut_file(const std::string& filename, std::vector<MutRow>& rows);
 bool for_each_mut_row(const std::string& filename, const std::function<void(const MutRow&)>& sink);
 // the upper-cased sequence of a fasta mask (data.cpp:213-235); exits like the reference when the file cannot be opened
 void read_fasta_mask(const std::string& filename, std::string& seq);
+// ... only the opening (and its exit)
+void check_fasta_mask(const std::string& filename);
 
 struct PairTables {  // flat [nb][A] tables of one pair, as the bootstrap takes them; she / nse = row 0 of the reference's A*A tables
   int nb = 0;
@@ -136,6 +138,7 @@ struct PairSpec {
   std::string target, reference, output;
   double target_age = 0, ref_age = 0;
   std::vector<std::string> target_masks, ref_masks;  // one fasta per chromosome, or none
+  std::string coal;                                   // --pairs `coal=FILE`: the pair's epochs and starting rates ("": --bins)
 };
 
 // coal.cpp:2071-2321 for one (target, reference) pair, on the calling thread in the reference's order: the sequential feeder.
@@ -149,6 +152,8 @@ int fill_tables_from_tmp(const std::vector<std::string>& chr_names, const std::v
 // <mask>_chr<name>.fa paths of --target_mask / --reference_mask; without --chr one unnamed chromosome and the paths verbatim
 void chromosome_files(const Options& opt, std::vector<std::string>& names, std::vector<std::string>& mut_files,
                       std::vector<std::string>* target_masks = nullptr, std::vector<std::string>* ref_masks = nullptr);
+// the fasta files of one mask PREFIX over those chromosomes: PREFIX_chr<name>.fa each with --chr, else PREFIX itself
+std::vector<std::string> mask_files(const Options& opt, const std::vector<std::string>& names, const std::string& prefix);
 
 void write_counts_file(const std::string& path, int B, int A, const std::vector<double>& grid, const double* csh,
                        const double* cns);
@@ -158,7 +163,8 @@ void print_usage_footer();  // "CPU Time spent: ...; Max Memory usage: ..." (coa
 int run_mut_pairs(const Options& opt);
 // One pair (masks per chromosome, or none) through the engine of the batched front end: the tables and the generator as
 // the fill leaves it.  Returns the number of genome blocks.
-int fill_single_pair(const Options& opt, const std::string& target, const std::string& reference,
+int fill_single_pair(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                     const std::string& target, const std::string& reference,
                      const std::vector<std::string>& target_masks, const std::vector<std::string>& ref_masks, int seed, int A,
                      PairTables& out);
 

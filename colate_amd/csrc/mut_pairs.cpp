@@ -41,6 +41,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <set>
 #include <thread>
 
 #include "colate_amd.h"
@@ -55,7 +56,7 @@ double now_s() { return StageTimes::now(); }
 
 // thread-seconds per kind of work (COLATE_TIMING=1 prints them)
 struct WorkSeconds {
-  std::atomic<double> parse_mut{0}, load_tmp{0}, index{0}, walk{0}, sample{0};
+  std::atomic<double> parse_mut{0}, load_tmp{0}, index{0}, walk{0}, sample{0}, mask{0};
   static void add(std::atomic<double>& a, double dt) {
     double v = a.load();
     while (!a.compare_exchange_weak(v, v + dt)) {}
@@ -174,7 +175,7 @@ class Pool {
 // ------------------------------------------------------------------ .mut rows, reduced to what a pair's walk needs
 // A row that fails the row-level conditions of coal.cpp:2150 (flipped, one branch, age_begin < age_end) or whose alleles are
 // not single bases (coal.cpp:2160-2176) touches neither stream nor generator in the reference's loop: such rows are dropped when
-// the file is parsed.  (So does a row a mask removes, coal.cpp:2169-2174: PairFill::skip.)
+// the file is parsed.  (So does a row a mask removes, coal.cpp:2169-2174: MaskBits.)
 struct CompactRow {
   int pos;
   float age_begin, age_end;
@@ -228,8 +229,10 @@ struct TmpFile {
     uint16_t DAF, AAF;  // the record's counts where position and alleles match (coal.cpp:2201-2219), else 0, 0
   };
   std::vector<HugeVector<RefIdx>> ref_idx;  // [chromosome][row]
-  std::vector<HugeVector<TgtIdx>> tgt_idx;
-  bool indexable = false, want_ref = false, want_tgt = false;
+  std::vector<HugeVector<TgtIdx>> tgt_idx;  // (also what a masked pair's walk reads for its reference sample, see MaskBits)
+  bool want_ref = false, want_tgt = false;
+  bool ref_ok = false, tgt_ok = false;  // the index of that role was built
+  bool indexable = false;               // ... every index wanted of the file was
   TmpFile() = default;
   TmpFile(const TmpFile&) = delete;
   TmpFile& operator=(const TmpFile&) = delete;
@@ -398,6 +401,17 @@ struct Cursor {
 // So a pair's walk is one pass over two 8-byte arrays instead of two cursor merges over 16-byte records with a name to track:
 // 100 pairs x 1 GB of streaming became 100 x 0.3 GB, and a few instructions per row.  Anything else (a chromosome missing in a file,
 // runs out of order, a position below the one in front of it, a file that was not decoded, an empty chromosome name) keeps the cursors.
+//
+// A pair with masks does not search the rows its masks remove (coal.cpp:2169-2174): neither cursor moves there, so prev_pass, which
+// assumes a search at every row, does not hold for it.  But both cursors obey one rule that needs no history beyond the pair's own:
+// with rows and records in non-descending order, a cursor before a search sits on the first record at or behind the position of
+// its previous search (the lower bound; the chromosome's first record before any), so it moves in row i's search iff the record in
+// front of row i's lower bound exists and lies at or behind that position -- TgtIdx::prev_bp, a property of the file alone.  A
+// masked pair therefore reads TgtIdx for BOTH samples and keeps two positions of its own (PairFill::last_searched: the latest row
+// that passed both masks, where the reference cursor searched; last_ref_pass: the latest that passed as reference, where the
+// target cursor searched).  Equal row positions: the second search finds the cursor on the lower bound already, whose record in
+// front lies below the position (no move, DAF = 0).  A search that runs off the chromosome's end leaves every later row of it
+// without a match, and the lower bound of every later row is that end too (DAF = AAF = 0 there).
 struct WalkRows {
   const std::vector<std::string>* names;
   const std::vector<HugeVector<CompactRow>>* rows;
@@ -439,61 +453,76 @@ bool find_runs(const TmpFile& f, const std::vector<std::string>& names, std::vec
   return true;
 }
 
-void build_walk_index(TmpFile& f, const WalkRows& w) {
-  f.indexable = false;
-  std::vector<std::pair<size_t, size_t>> runs;
-  if (!w.rows_ascend || !find_runs(f, *w.names, runs)) return;
+// The indices of one role, built where the file is well-formed for it (false: the pairs that need it keep the cursors).
+bool build_ref_index(TmpFile& f, const WalkRows& w, const std::vector<std::pair<size_t, size_t>>& runs) {
   const size_t C = w.names->size();
-  if (f.want_ref) f.ref_idx.assign(C, HugeVector<TmpFile::RefIdx>());
-  if (f.want_tgt) f.tgt_idx.assign(C, HugeVector<TmpFile::TgtIdx>());
+  const DecRec* const R = f.recs.data();
+  f.ref_idx.assign(C, HugeVector<TmpFile::RefIdx>());
   for (size_t c = 0; c < C; c++) {
     const HugeVector<CompactRow>& rr = (*w.rows)[c];
-    const DecRec* const R = f.recs.data();
     const size_t b = runs[c].first, e = runs[c].second;
-    if (f.want_ref) {
-      HugeVector<TmpFile::RefIdx>& out = f.ref_idx[c];
-      out.resize(rr.size());
-      size_t k = b;  // the record the cursor is on: the chromosome's first, read by the skip loop (or by the overrun of the chromosome before)
-      int32_t prev_pass = -1;
-      bool off_end = false;
-      for (size_t i = 0; i < rr.size(); i++) {
-        TmpFile::RefIdx x{prev_pass, 0, 0};
-        if (!off_end) {
-          size_t k2 = k;
-          while (k2 < e && R[k2].bp < rr[i].pos) k2++;
-          if (k2 == e) {
-            off_end = true;  // the cursor has left the chromosome: no match for this row nor any later one
-          } else {
-            if (k2 > k && R[k2].bp == rr[i].pos && R[k2].anc == rr[i].anc && R[k2].der == rr[i].der && R[k2].DAF != 0) {
-              const long long N = (long long)R[k2].DAF + R[k2].AAF;
-              if (R[k2].DAF < 0 || R[k2].DAF > 65535 || N <= 0 || N > 65535) return;  // (counts beyond the index's fields: cursors)
-              x.DAF = (uint16_t)R[k2].DAF, x.N = (uint16_t)N;
-              prev_pass = rr[i].pos;
-            }
-            k = k2;
+    HugeVector<TmpFile::RefIdx>& out = f.ref_idx[c];
+    out.resize(rr.size());
+    size_t k = b;  // the record the cursor is on: the chromosome's first, read by the skip loop (or by the overrun of the chromosome before)
+    int32_t prev_pass = -1;
+    bool off_end = false;
+    for (size_t i = 0; i < rr.size(); i++) {
+      TmpFile::RefIdx x{prev_pass, 0, 0};
+      if (!off_end) {
+        size_t k2 = k;
+        while (k2 < e && R[k2].bp < rr[i].pos) k2++;
+        if (k2 == e) {
+          off_end = true;  // the cursor has left the chromosome: no match for this row nor any later one
+        } else {
+          if (k2 > k && R[k2].bp == rr[i].pos && R[k2].anc == rr[i].anc && R[k2].der == rr[i].der && R[k2].DAF != 0) {
+            const long long N = (long long)R[k2].DAF + R[k2].AAF;
+            if (R[k2].DAF < 0 || R[k2].DAF > 65535 || N <= 0 || N > 65535) return false;  // (counts beyond the index's fields: cursors)
+            x.DAF = (uint16_t)R[k2].DAF, x.N = (uint16_t)N;
+            prev_pass = rr[i].pos;
           }
+          k = k2;
         }
-        out[i] = x;
       }
-    }
-    if (f.want_tgt) {
-      HugeVector<TmpFile::TgtIdx>& out = f.tgt_idx[c];
-      out.resize(rr.size());
-      size_t k = b;
-      for (size_t i = 0; i < rr.size(); i++) {
-        while (k < e && R[k].bp < rr[i].pos) k++;
-        TmpFile::TgtIdx x{-2, 0, 0};
-        if (k < e && k > b) x.prev_bp = R[k - 1].bp;
-        if (k < e && R[k].bp == rr[i].pos && R[k].anc == rr[i].anc && R[k].der == rr[i].der) {
-          if (R[k].DAF < 0 || R[k].DAF > 65535 || R[k].AAF < 0 || R[k].AAF > 65535) return;
-          x.DAF = (uint16_t)R[k].DAF, x.AAF = (uint16_t)R[k].AAF;
-        }
-        if (x.prev_bp < -2) return;  // (negative positions: cursors)
-        out[i] = x;
-      }
+      out[i] = x;
     }
   }
-  f.indexable = true;
+  return true;
+}
+
+bool build_tgt_index(TmpFile& f, const WalkRows& w, const std::vector<std::pair<size_t, size_t>>& runs) {
+  const size_t C = w.names->size();
+  const DecRec* const R = f.recs.data();
+  f.tgt_idx.assign(C, HugeVector<TmpFile::TgtIdx>());
+  for (size_t c = 0; c < C; c++) {
+    const HugeVector<CompactRow>& rr = (*w.rows)[c];
+    const size_t b = runs[c].first, e = runs[c].second;
+    HugeVector<TmpFile::TgtIdx>& out = f.tgt_idx[c];
+    out.resize(rr.size());
+    size_t k = b;
+    for (size_t i = 0; i < rr.size(); i++) {
+      while (k < e && R[k].bp < rr[i].pos) k++;
+      TmpFile::TgtIdx x{-2, 0, 0};
+      if (k < e && k > b) {
+        if (R[k - 1].bp < -1) return false;  // (-2 means "no record in front"; negative positions: cursors)
+        x.prev_bp = R[k - 1].bp;
+      }
+      if (k < e && R[k].bp == rr[i].pos && R[k].anc == rr[i].anc && R[k].der == rr[i].der) {
+        if (R[k].DAF < 0 || R[k].DAF > 65535 || R[k].AAF < 0 || R[k].AAF > 65535) return false;
+        x.DAF = (uint16_t)R[k].DAF, x.AAF = (uint16_t)R[k].AAF;
+      }
+      out[i] = x;
+    }
+  }
+  return true;
+}
+
+void build_walk_index(TmpFile& f, const WalkRows& w) {
+  f.indexable = f.ref_ok = f.tgt_ok = false;
+  std::vector<std::pair<size_t, size_t>> runs;
+  if (!w.rows_ascend || !find_runs(f, *w.names, runs)) return;
+  if (f.want_ref && !(f.ref_ok = build_ref_index(f, w, runs))) f.ref_idx.clear();
+  if (f.want_tgt && !(f.tgt_ok = build_tgt_index(f, w, runs))) f.tgt_idx.clear();
+  f.indexable = (!f.want_ref || f.ref_ok) && (!f.want_tgt || f.tgt_ok);
 }
 
 // ------------------------------------------------------------------ the uniform stream of the seed, generated once
@@ -854,16 +883,26 @@ struct Block {
   explicit Block(int A) : t((size_t)4 * A, 0.0) {}
 };
 
+// One sample's mask (a FASTA per chromosome), decoded once for every pair that names it: one bit per CompactRow, set where the row
+// passes (coal.cpp:2169-2174: `bp < length && seq[bp - 1] != 'P'` removes it; beyond the end of the mask it passes).  rows / 8 bytes.
+struct MaskBits {
+  std::vector<std::vector<uint64_t>> pass;  // [chromosome][row / 64]
+  bool passes(size_t c, size_t i) const { return (pass[c][i >> 6] >> (i & 63)) & 1; }
+};
+
 struct PairFill {
   // inputs
   size_t index = 0;
   const TmpFile *tgt_file = nullptr, *ref_file = nullptr;
-  // per chromosome, per CompactRow: a mask removes the row (coal.cpp:2169-2174); empty without masks
-  std::vector<std::vector<char>> skip;
+  const MaskBits *tmask = nullptr, *rmask = nullptr;  // the samples' masks (null: none)
+  bool masked() const { return tmask || rmask; }
+  bool passes(size_t c, size_t i) const { return (!tmask || tmask->passes(c, i)) && (!rmask || rmask->passes(c, i)); }
+  bool indexed = false;  // walks through the files' indices (build_walk_index)
   // walk state (coal.cpp:2071-2321)
   Cursor tgt, ref;
   size_t chr = 0, row = 0;
   bool chr_open = false;
+  int32_t last_searched = -1, last_ref_pass = -1;  // a masked pair's indexed walk: positions of the latest searches of this chromosome
   int current_block_base = 0;
   size_t blk = 0;
   int num_blocks = 0;
@@ -1075,12 +1114,12 @@ struct Engine {
     Cursor& tgt = pf.tgt;
     Cursor& ref = pf.ref;
     if (pf.blocks.empty()) pf.blocks.emplace_back(new Block(A));
+    const bool indexed = pf.indexed;
     while (pf.chr < rows.size()) {
       if (pf.redo.load(std::memory_order_relaxed)) break;
-      // (a pair with masks walks with the cursors: the indices assume a search at every row)
-      const bool indexed = use_index && pf.skip.empty() && pf.ref_file->indexable && pf.tgt_file->indexable;
       if (!pf.chr_open) {
         pf.current_block_base = 0;
+        pf.last_searched = pf.last_ref_pass = -1;
         if (!indexed) {
           ref.set_name(chr_names[pf.chr].c_str());
           tgt.set_name(chr_names[pf.chr].c_str());
@@ -1095,6 +1134,31 @@ struct Engine {
         pf.chr_open = true;
       }
       const HugeVector<CompactRow>& rr = rows[pf.chr];
+      if (indexed && pf.masked()) {  // the same from the lower bounds of both files and the pair's own searches (WalkRows)
+        const TmpFile::TgtIdx* const RL = pf.ref_file->tgt_idx[pf.chr].data();
+        const TmpFile::TgtIdx* const TI = pf.tgt_file->tgt_idx[pf.chr].data();
+        for (; pf.row < rr.size(); pf.row++) {
+          if (pf.off >= limit) {
+            flush(pf);
+            return;
+          }
+          if (!pf.passes(pf.chr, pf.row)) continue;  // (neither cursor is touched for it)
+          const int32_t pos = rr[pf.row].pos;
+          const TmpFile::TgtIdx r = RL[pf.row];
+          const int32_t ref_from = pf.last_searched;
+          pf.last_searched = pos;
+          if (r.DAF == 0 || r.prev_bp < ref_from) continue;  // no record of these alleles carrying the derived one -- or the cursor did not move
+          const TmpFile::TgtIdx t = TI[pf.row];
+          const int32_t tgt_from = pf.last_ref_pass;
+          pf.last_ref_pass = pos;
+          if ((t.DAF | t.AAF) == 0 || t.prev_bp < tgt_from) continue;
+          use_snp(pf, rr[pf.row], t.DAF, t.AAF, r.DAF, (int)r.DAF + (int)r.AAF);
+        }
+        advance_block(pf);
+        pf.chr++;
+        pf.chr_open = false;
+        continue;
+      }
       if (indexed) {  // what the two cursors would find, from the two files' indices (build_walk_index)
         const TmpFile::RefIdx* const RI = pf.ref_file->ref_idx[pf.chr].data();
         const TmpFile::TgtIdx* const TI = pf.tgt_file->tgt_idx[pf.chr].data();
@@ -1119,7 +1183,7 @@ struct Engine {
           flush(pf);
           return;
         }
-        if (!pf.skip.empty() && pf.skip[pf.chr][pf.row]) continue;  // (neither cursor is touched for it)
+        if (pf.masked() && !pf.passes(pf.chr, pf.row)) continue;  // (neither cursor is touched for it)
         const CompactRow& m = rr[pf.row];
         const int bp_mut = m.pos;
         bool use = true;
@@ -1157,21 +1221,53 @@ struct Engine {
   }
 };
 
-// "target reference output [target_age reference_age]" per line
-bool read_pair_list(const std::string& path, std::vector<PairSpec>& pairs) {
+// "target reference output [target_age [reference_age]]" per line; after the three names, `key=value` tokens in any order and
+// mixed with the ages: target_mask=PREFIX, reference_mask=PREFIX (expanded as the single-pair CLI expands --target_mask /
+// --reference_mask: with --chr PREFIX_chr<name>.fa per chromosome, else PREFIX itself) and coal=FILE (the pair's warm start).
+// A token with '=' is a key, any other the next age.  An unknown, repeated or empty key, a third age or an age that is no
+// number is an error naming the file and the line.  A line of fewer than three tokens is skipped.
+bool read_pair_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names, std::vector<PairSpec>& pairs) {
   std::ifstream is(path);
   if (!is) {
     std::cerr << "Error while opening file " << path << std::endl;
     return false;
   }
   std::string line;
-  while (std::getline(is, line)) {
+  for (size_t line_no = 1; std::getline(is, line); line_no++) {
     std::istringstream ss(line);
     PairSpec ps;
     if (!(ss >> ps.target >> ps.reference >> ps.output)) continue;
-    std::string a1, a2;
-    if (ss >> a1) ps.target_age = std::stof(a1);
-    if (ss >> a2) ps.ref_age = std::stof(a2);
+    auto fail = [&](const std::string& what) {
+      std::cerr << "Error: " << path << ", line " << line_no << ": " << what << std::endl;
+      return false;
+    };
+    int n_ages = 0;
+    bool seen_tm = false, seen_rm = false, seen_coal = false;
+    for (std::string tok; ss >> tok;) {
+      const size_t eq = tok.find('=');
+      if (eq == std::string::npos) {
+        if (n_ages == 2) return fail("more than two ages ('" + tok + "')");
+        float v = 0;
+        size_t used = 0;
+        try {
+          v = std::stof(tok, &used);
+        } catch (...) {
+          used = 0;
+        }
+        if (used == 0 || used != tok.size()) return fail("the age '" + tok + "' is not a number");
+        (n_ages++ == 0 ? ps.target_age : ps.ref_age) = v;
+        continue;
+      }
+      const std::string key = tok.substr(0, eq), value = tok.substr(eq + 1);
+      bool* seen = key == "target_mask" ? &seen_tm : key == "reference_mask" ? &seen_rm : key == "coal" ? &seen_coal : nullptr;
+      if (!seen) return fail("unknown key '" + key + "' (known: target_mask, reference_mask, coal)");
+      if (*seen) return fail("the key '" + key + "' is given twice");
+      if (value.empty()) return fail("the key '" + key + "' has no value");
+      *seen = true;
+      if (key == "target_mask") ps.target_masks = mask_files(opt, chr_names, value);
+      else if (key == "reference_mask") ps.ref_masks = mask_files(opt, chr_names, value);
+      else ps.coal = value;
+    }
     pairs.push_back(ps);
   }
   if (pairs.empty()) {
@@ -1182,12 +1278,11 @@ bool read_pair_list(const std::string& path, std::vector<PairSpec>& pairs) {
 }
 
 // The tables of the pairs listed in `todo` (indices into `pairs`); false after an error message.
-bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A,
-                std::vector<PairTables>& out) {
+// `names` / `mut_files`: the chromosomes (chromosome_files).
+bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& out) {
   const double C = 10;
   const int num_bases_per_block = 30e6;
-  std::vector<std::string> names, mut_files;
-  chromosome_files(opt, names, mut_files);
   const int T = pairs_threads();
   const double t0 = now_s();
   out.assign(pairs.size(), PairTables());
@@ -1307,27 +1402,49 @@ bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const st
     pf.tgt_file = tmp_files[pairs[p].target].get(), pf.ref_file = tmp_files[pairs[p].reference].get();
     pf.tgt.open(*pf.tgt_file), pf.ref.open(*pf.ref_file);
   }
-  // ---- the rows each pair's masks remove (coal.cpp:2169-2174), one task per (pair, chromosome), one mask string alive per task
+  // ---- the masks (coal.cpp:2169-2174): every distinct mask once, one task per (mask, chromosome) with one FASTA string alive in it
+  std::map<std::vector<std::string>, std::unique_ptr<MaskBits>> masks;  // (key: the mask's file per chromosome)
+  std::atomic<size_t> mask_reads{0};
+  // a missing file ends the run here, on this thread, in the order the sequential feeder opens them (chromosome by chromosome,
+  // pair by pair, target before reference): the first missing one is named, whatever the pool's timing
+  {
+    std::set<std::string> checked;
+    for (size_t c = 0; c < rows.size(); c++)
+      for (auto& pfp : fills)
+        for (const std::vector<std::string>* files : {&pairs[pfp->index].target_masks, &pairs[pfp->index].ref_masks})
+          if (c < files->size() && checked.insert((*files)[c]).second) check_fasta_mask((*files)[c]);
+  }
   for (auto& pfp : fills) {
     const PairSpec& ps = pairs[pfp->index];
-    if (ps.target_masks.empty() && ps.ref_masks.empty()) continue;
-    pfp->skip.resize(rows.size());
-    for (size_t c = 0; c < rows.size(); c++) {
-      PairFill* pf = pfp.get();
-      pool.submit([&ps, &rows, pf, c] {
-        const HugeVector<CompactRow>& rr = rows[c];
-        std::vector<char>& skip = pf->skip[c];
-        skip.assign(rr.size(), 0);
-        std::string mask;
-        for (const std::vector<std::string>* files : {&ps.target_masks, &ps.ref_masks}) {
-          if (files->empty()) continue;
-          read_fasta_mask((*files)[c], mask);
-          for (size_t i = 0; i < rr.size(); i++) {
-            const int bp = rr[i].pos;
-            if ((size_t)bp < mask.size() && mask[bp - 1] != 'P') skip[i] = 1;
-          }
+    for (const std::vector<std::string>* files : {&ps.target_masks, &ps.ref_masks}) {
+      if (files->empty()) continue;
+      std::unique_ptr<MaskBits>& m = masks[*files];
+      if (!m) {
+        m.reset(new MaskBits);
+        m->pass.resize(rows.size());
+        for (size_t c = 0; c < rows.size(); c++) {
+          MaskBits* mb = m.get();
+          const std::string* path = c < files->size() ? &(*files)[c] : nullptr;  // (none: every row passes)
+          pool.submit([&rows, &mask_reads, mb, path, c] {
+            const double t0 = now_s();
+            const HugeVector<CompactRow>& rr = rows[c];
+            std::vector<uint64_t>& bits = mb->pass[c];
+            bits.assign((rr.size() + 63) / 64, 0);
+            std::string seq;
+            if (path) {
+              read_fasta_mask(*path, seq);  // (a missing file: the reference's message, exit 1)
+              mask_reads++;
+            }
+            for (size_t i = 0; i < rr.size(); i++) {
+              const int bp = rr[i].pos;
+              const bool removed = bp >= 1 && (size_t)bp < seq.size() && seq[(size_t)bp - 1] != 'P';
+              if (!removed) bits[i >> 6] |= uint64_t(1) << (i & 63);
+            }
+            WorkSeconds::add(g_work.mask, now_s() - t0);
+          });
         }
-      });
+      }
+      (files == &ps.target_masks ? pfp->tmask : pfp->rmask) = m.get();
     }
   }
   // ---- what the walks find in each file, once per file (build_walk_index)
@@ -1338,8 +1455,12 @@ bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const st
     WalkRows wr{&names, &rows, true};
     for (const HugeVector<CompactRow>& r : rows)
       for (size_t i = 1; i < r.size() && wr.rows_ascend; i++) wr.rows_ascend = r[i].pos >= r[i - 1].pos && r[i - 1].pos >= 0;
-    for (auto& pf : fills)
-      if (pf->skip.empty()) tmp_files[pairs[pf->index].target]->want_tgt = true, tmp_files[pairs[pf->index].reference]->want_ref = true;
+    for (auto& pf : fills) {  // (a masked pair reads the lower bounds, TgtIdx, of its reference sample too)
+      TmpFile& t = *tmp_files[pairs[pf->index].target];
+      TmpFile& r = *tmp_files[pairs[pf->index].reference];
+      t.want_tgt = true;
+      (pf->masked() ? r.want_tgt : r.want_ref) = true;
+    }
     for (auto& kv : tmp_files) {
       TmpFile* f = kv.second.get();
       if (f->ok && (f->want_ref || f->want_tgt)) pool.submit([f, wr] {
@@ -1351,6 +1472,12 @@ bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const st
   }
   pool.wait_idle();  // (the indices and the masks' rows)
   for (auto& kv : tmp_files) n_indexed += kv.second->indexable ? 1 : 0;
+  size_t n_pairs_indexed = 0, n_masked = 0;
+  for (auto& pf : fills) {
+    pf->indexed = use_index && pf->tgt_file->tgt_ok && (pf->masked() ? pf->ref_file->tgt_ok : pf->ref_file->ref_ok);
+    n_pairs_indexed += pf->indexed ? 1 : 0;
+    n_masked += pf->masked() ? 1 : 0;
+  }
   const double t1 = now_s();
   size_t n_rows = 0, n_kept = 0, n_rec = 0;
   for (size_t c = 0; c < rows.size(); c++) n_rows += rows_total[c], n_kept += rows[c].size();
@@ -1534,7 +1661,9 @@ bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const st
               << stream.convert_seconds() << " s), " << redone
               << " pair(s) redone sequentially in " << now_s() - t2 << " s); thread-seconds: .mut parse " << g_work.parse_mut.load()
               << ", .colate.in decode " << g_work.load_tmp.load() << ", walk indices " << g_work.index.load() << " (" << n_indexed << " of "
-              << tmp_files.size() << " files)" << ", SNP walks " << g_work.walk.load() << ", age sampling "
+              << tmp_files.size() << " files)" << ", " << n_pairs_indexed << " of " << fills.size() << " pairs walked through indices ("
+              << n_masked << " masked), masks " << g_work.mask.load() << " (" << masks.size() << " masks decoded once: " << mask_reads.load()
+              << " FASTA reads)" << ", SNP walks " << g_work.walk.load() << ", age sampling "
               << g_work.sample.load()
               << (dev ? "; age sampling on the GPU: " + std::to_string(dev_jobs) + " (pair, block) jobs, " + std::to_string(dev_recs) + " SNPs in " + std::to_string(dev_launches) + " launches, " +
                             std::to_string(dev->gpu_seconds()) + " s of copies and kernels, " + std::to_string(dev_upload_s) + " s uploading the uniform stream, " + std::to_string(dev_make_s) + " s setting up, " + std::to_string(dev_staging_s) + " s page-locking the record buffers beside the first windows, " +
@@ -1548,30 +1677,38 @@ bool fill_pairs(const Options& opt, const std::vector<PairSpec>& pairs, const st
 
 }  // namespace
 
-int fill_single_pair(const Options& opt, const std::string& target, const std::string& reference,
-                     const std::vector<std::string>& target_masks, const std::vector<std::string>& ref_masks, int seed, int A,
-                     PairTables& out) {
+int fill_single_pair(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                     const std::string& target, const std::string& reference, const std::vector<std::string>& target_masks,
+                     const std::vector<std::string>& ref_masks, int seed, int A, PairTables& out) {
   std::vector<PairSpec> one(1);
   one[0].target = target, one[0].reference = reference;
   one[0].target_masks = target_masks, one[0].ref_masks = ref_masks;
   std::vector<PairTables> tabs;
-  fill_pairs(opt, one, {0}, seed, A, tabs);
+  fill_pairs(opt, names, mut_files, one, {0}, seed, A, tabs);
   out = std::move(tabs[0]);
   return out.nb;
 }
 
 int run_mut_pairs(const Options& opt) {
-  if (!opt.has("mut") || !opt.has("bins")) {
-    std::cerr << "Error: --pairs needs --mut and --bins (and optionally --chr, --num_bootstraps, --seed)." << std::endl;
+  if (!opt.has("mut")) {
+    std::cerr << "Error: --pairs needs --mut (and optionally --chr, --bins, --num_bootstraps, --seed)." << std::endl;
     return 1;
   }
   for (const char* o : {"target_mask", "reference_mask", "coal"})
-    if (opt.has(o)) {  // per-sample masks / one warm start cannot apply to a whole list of pairs: refuse, do not ignore
-      std::cerr << "Error: --" << o << " cannot be combined with --pairs (run such pairs one by one)." << std::endl;
+    if (opt.has(o)) {  // one mask / one warm start cannot mean the same for a whole list of pairs: refuse, do not ignore
+      std::cerr << "Error: --" << o << " cannot be combined with --pairs (give it per line: " << o << "=...)." << std::endl;
       return 1;
     }
+  std::vector<std::string> chr_names, mut_files;
+  chromosome_files(opt, chr_names, mut_files);  // (once: the list's mask prefixes expand with these names, and the fill reads these files)
   std::vector<PairSpec> pairs;
-  if (!read_pair_list(opt.get("pairs"), pairs)) return 1;
+  if (!read_pair_list(opt.get("pairs"), opt, chr_names, pairs)) return 1;
+  if (!opt.has("bins"))
+    for (size_t p = 0; p < pairs.size(); p++)
+      if (pairs[p].coal.empty()) {  // (a line with coal= takes its epochs from that file)
+        std::cerr << "Error: --pairs needs --bins for pair " << p + 1 << " (it names no coal= file)." << std::endl;
+        return 1;
+      }
   const bool talk = g_rank.rank == 0;
   if (talk) {
     std::cerr << "---------------------------------------------------------" << std::endl;
@@ -1611,19 +1748,32 @@ int run_mut_pairs(const Options& opt) {
     warm.t = std::thread([warm_dev] { (void)colate_warm_up(warm_dev); });
   }
 
-  // ---- epochs per pair (coal.cpp:3551-3632): they depend on the ages only, so the launches are known before any file is read
-  std::vector<std::vector<double>> epochs(P);
+  // ---- epochs per pair (coal.cpp:3501-3632): from the ages and --bins, or from the pair's coal= file (which also gives its
+  // starting rates, coal.cpp:3638-3646): the launches are known before any file is read
+  std::vector<std::vector<double>> epochs(P), init(P);
   std::vector<int> ep_null(P, 0);
   std::vector<double> age(P);
   for (size_t p = 0; p < P; p++) {
     age[p] = std::max(pairs[p].target_age, pairs[p].ref_age) / years_per_gen;
     epochs[p].resize(COLATE_MAX_EPOCHS);
-    const int E = colate_epochs_from_bins(opt.get("bins").c_str(), age[p], years_per_gen, epochs[p].data(), COLATE_MAX_EPOCHS, &ep_null[p]);
+    init[p].assign(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
+    int E;
+    if (!pairs[p].coal.empty()) {
+      E = colate_epochs_from_coal(pairs[p].coal.c_str(), age[p], epochs[p].data(), init[p].data(), COLATE_MAX_EPOCHS);
+      if (E > 0 && talk) {  // (as the single-pair CLI prints them, after the pair's number)
+        std::cerr << "Pair " << p + 1 << ": ";
+        for (int e = 0; e < E; e++) std::cerr << init[p][e] << " ";
+        std::cerr << std::endl;
+      }
+    } else {
+      E = colate_epochs_from_bins(opt.get("bins").c_str(), age[p], years_per_gen, epochs[p].data(), COLATE_MAX_EPOCHS, &ep_null[p]);
+    }
     if (E <= 0) {
-      std::cerr << colate_last_error() << std::endl;
+      std::cerr << "Error: pair " << p + 1 << ": " << colate_last_error() << std::endl;
       return 1;
     }
     epochs[p].resize(E);
+    init[p].resize(E);
   }
   // classes of pairs with the same number of epochs, in order of first appearance: one launch each
   std::vector<std::vector<size_t>> classes;
@@ -1650,7 +1800,7 @@ int run_mut_pairs(const Options& opt) {
   std::sort(todo.begin(), todo.end());
 
   std::vector<PairTables> tabs;
-  if (!fill_pairs(opt, pairs, todo, seed, A, tabs)) return 1;
+  if (!fill_pairs(opt, chr_names, mut_files, pairs, todo, seed, A, tabs)) return 1;
   for (size_t p : todo) {
     if (talk) std::cerr << "Pair " << p + 1 << " / " << P << ": " << pairs[p].target << " x " << pairs[p].reference << ": Number of blocks: " << tabs[p].nb << std::endl;
     if (tabs[p].nb < 1) {
@@ -1732,7 +1882,7 @@ int run_mut_pairs(const Options& opt) {
     const int g0 = first_group[c], gn = group_count[c];
     // this process's groups of the class, concatenated
     std::vector<int> nb(gn);
-    std::vector<double> g_age(gn), g_w, g_sh, g_ns, g_she, g_nse, g_ep((size_t)gn * E), g_init((size_t)gn * E, COLATE_DEFAULT_INIT_RATE);
+    std::vector<double> g_age(gn), g_w, g_sh, g_ns, g_she, g_nse, g_ep((size_t)gn * E), g_init((size_t)gn * E);
     for (int g = 0; g < gn; g++) {
       const size_t p = cls[(size_t)(g0 + g)];
       const PairTables& pt = tabs[p];
@@ -1743,6 +1893,7 @@ int run_mut_pairs(const Options& opt) {
       g_she.insert(g_she.end(), pt.she.begin(), pt.she.end());
       g_nse.insert(g_nse.end(), pt.nse.begin(), pt.nse.end());
       std::copy(epochs[p].begin(), epochs[p].end(), g_ep.begin() + (size_t)g * E);
+      std::copy(init[p].begin(), init[p].end(), g_init.begin() + (size_t)g * E);
     }
     std::vector<double> rates(R * E), ll(R), csh, cns;
     std::vector<int> iters(R), flags(R);
@@ -1761,8 +1912,11 @@ int run_mut_pairs(const Options& opt) {
         rc = colate_bootstrap_counts_from_weights(B, nb[g], A, age_grid.data(), g_age[g], g_w.data() + wo, g_sh.data() + (size_t)bo * A,
                                                   g_ns.data() + (size_t)bo * A, g_she.data() + (size_t)bo * A, g_nse.data() + (size_t)bo * A,
                                                   csh.data() + (size_t)g * B * A, cns.data() + (size_t)g * B * A);
-      std::vector<double> r_ep(R * E), r_init(R * E, COLATE_DEFAULT_INIT_RATE);
-      for (size_t r = 0; r < R; r++) std::copy(g_ep.begin() + (r / B) * E, g_ep.begin() + (r / B + 1) * E, r_ep.begin() + r * E);
+      std::vector<double> r_ep(R * E), r_init(R * E);
+      for (size_t r = 0; r < R; r++) {
+        std::copy(g_ep.begin() + (r / B) * E, g_ep.begin() + (r / B + 1) * E, r_ep.begin() + r * E);
+        std::copy(g_init.begin() + (r / B) * E, g_init.begin() + (r / B + 1) * E, r_init.begin() + r * E);
+      }
       if (!rc)
         rc = colate_em_batch_rows_sharded((int)dev_list.size(), dev_list.data(), (int)R, E, A, age_grid.data(), csh.data(), cns.data(),
                                           r_ep.data(), r_init.data(), COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER,
