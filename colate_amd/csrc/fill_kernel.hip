@@ -175,7 +175,7 @@ DeviceFill* DeviceFill::create(int device, int A, const double* guard_lo, const 
     return nullptr;
   }
   if (A < 1 || A > kSlots * kWave) {
-    why = "more than 256 age bins";
+    why = "age bins outside 1 .. 256";
     return nullptr;
   }
   DeviceFill* d = new DeviceFill;
@@ -228,9 +228,12 @@ DeviceFill* DeviceFill::create(int device, int A, const double* guard_lo, const 
 
 DeviceFill::~DeviceFill() {
   (void)hipSetDevice(device_);
-  for (void* p : pinned_) (void)hipHostUnregister(p);
+  // every stream first (errors ignored): after a failed submit copies out of the pinned uniform ring may still be in flight
+  if (copy_stream_) (void)hipStreamSynchronize((hipStream_t)copy_stream_);
   for (int b = 0; b < kDev; b++)
     if (stream_[b]) (void)hipStreamSynchronize((hipStream_t)stream_[b]);
+  (void)hipGetLastError();
+  for (void* p : pinned_) (void)hipHostUnregister(p);
   for (int b = 0; b < 2; b++) {
     if (stage_[b]) (void)hipHostFree(stage_[b]);
     if (h_jobs_[b]) (void)hipHostFree(h_jobs_[b]);
@@ -243,7 +246,6 @@ DeviceFill::~DeviceFill() {
       if (ev_[b][k]) (void)hipEventDestroy((hipEvent_t)ev_[b][k]);
     if (stream_[b]) (void)hipStreamDestroy((hipStream_t)stream_[b]);
   }
-  if (copy_stream_) (void)hipStreamSynchronize((hipStream_t)copy_stream_);
   if (upload_ev_) (void)hipEventDestroy((hipEvent_t)upload_ev_);
   if (copy_stream_) (void)hipStreamDestroy((hipStream_t)copy_stream_);
   for (void* p : {(void*)d_u_, (void*)d_lo_, (void*)d_hi_, (void*)d_tables_, (void*)d_flags_})

@@ -1040,6 +1040,9 @@ struct Engine {
   }
   void advance_block(PairFill& pf) const {
     flush(pf);
+    // the device holds kMaxBlocks tables per pair: from block kMaxBlocks on -- with used SNPs or without (every --chr entry closes
+    // a block) -- the pair is filled on the host, or the read-back would take a table that is not this pair's
+    if (devq && pf.blk >= DevQueue::kMaxBlocks) pf.redo.store(true);
     if (devq && !pf.dev_cur.empty()) {
       const size_t had = pf.dev_cur.size();
       if (pf.blk >= DevQueue::kMaxBlocks || pf.dev_cur.size() > 0xffffffffull) {
@@ -1621,6 +1624,10 @@ bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const
       for (auto& pfp : fills) {
         PairFill& pf = *pfp;
         if (pf.redo.load()) continue;
+        if (pf.num_blocks > (int)DevQueue::kMaxBlocks) {  // (advance_block has marked it already: its tables do not fit its slot)
+          pf.redo.store(true);
+          continue;
+        }
         for (int j = 0; j < pf.num_blocks && !pf.redo.load(); j++) {
           const size_t t = pf.slot * DevQueue::kMaxBlocks + (size_t)j;
           if (dflags[t]) pf.redo.store(true);

@@ -97,6 +97,52 @@ def write_inputs(outdir, chroms=("1", "2"), snps_per_chr=1500, seed=7, span=95_0
     return outdir
 
 
+def read_records(path):
+    """The records of a .colate.in written by write_inputs: (chrom, bp, anc, der, aaf, daf) each."""
+    data = open(path, "rb").read()
+    out, i = [], 0
+    while i < len(data):
+        (n,) = struct.unpack_from("<i", data, i)
+        chrom = data[i + 4:i + 4 + n].decode()
+        i += 4 + n
+        (bp,) = struct.unpack_from("<i", data, i)
+        anc, der = chr(data[i + 4]), chr(data[i + 5])
+        aaf, daf = struct.unpack_from("<ii", data, i + 6)
+        i += 14
+        out.append((chrom, bp, anc, der, aaf, daf))
+    return out
+
+
+def keep_records(path, keep):
+    """Rewrites a .colate.in with only the records for which keep(chrom, bp) holds; returns how many were dropped."""
+    recs = read_records(path)
+    kept = [r for r in recs if keep(r[0], r[1])]
+    with open(path, "wb") as f:
+        for chrom, bp, anc, der, aaf, daf in kept:
+            c = chrom.encode()
+            f.write(struct.pack("<i", len(c)) + c + struct.pack("<i", bp) + anc.encode() + der.encode() + struct.pack("<ii", aaf, daf))
+    return len(recs) - len(kept)
+
+
+def push_beyond_the_age_grid(path, n):
+    """Rewrites the first `n` used-looking rows (not flipped, one branch, one SNP, age_begin > 1e4) of a plain or gzipped .mut so
+    that most of their sampled ages lie beyond the last grid point (8.9e6 generations), where the reference draws again
+    (coal.cpp:2286-2287); returns their positions."""
+    opener = gzip.open if path.endswith(".gz") else open
+    lines = opener(path, "rt").read().split("\n")
+    pos = []
+    for i in range(1, len(lines)):
+        f = lines[i].split(";")
+        if len(f) > 10 and f[7] == "0" and f[5] == "7" and len(f[10]) == 3 and float(f[8]) > 1e4 and len(pos) < n:
+            f[8], f[9] = "5e+06", "4e+07"
+            lines[i] = ";".join(f)
+            pos.append(int(f[1]))
+    assert len(pos) == n, (path, len(pos))
+    with opener(path, "wt") as g:
+        g.write("\n".join(lines))
+    return pos
+
+
 if __name__ == "__main__":
     import sys
 

@@ -574,6 +574,18 @@ def test_threaded_table_fill_redoes_sequentially_when_a_sample_is_redrawn(tmp_pa
     assert threaded == _counts(tmp_path, 1)  # (... and the repeat is the sequential result)
 
 
+def test_engine_fills_a_pair_of_more_than_512_blocks_like_the_sequential_feeder(tmp_path):
+    """520 small contigs in --chr (every entry closes a block): the engine's per-pair block tables grow past the 512 a pair has
+    on the device, and the tables stay the sequential feeder's."""
+    import synth_files
+
+    synth_files.write_inputs(str(tmp_path), chroms=tuple(f"c{i}" for i in range(520)), snps_per_chr=8, seed=23, span=20_000)
+    engine = _counts(tmp_path, 8)
+    assert _counts.engine
+    sequential = _counts(tmp_path, 1)
+    assert engine == sequential
+
+
 def _masked_counts(tmp_path, case, threads):
     args = list(case["args"])
     args[args.index("-o") + 1] = f"m{threads}"
