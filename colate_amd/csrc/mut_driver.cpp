@@ -4,7 +4,8 @@
 // feeder that turns two .colate.in streams and the .mut files into per-block
 // age-bin tables (include/coal/coal.cpp:2071-2321 with include/src/mutations.cpp:56-283
 // and include/src/data.cpp:213-235), and the mut() driver (include/coal/coal.cpp:3071-3863)
-// around the GPU EM (colate_em_batch).
+// around the GPU EM (colate_em_batch), for one pair (run_mut) and for a `--pairs` list
+// (run_mut_pairs; the tables of both come from the engine of mut_pairs.cpp).
 //
 // Everything here runs once per invocation on the host; the per-replicate EM,
 // which is where the reference spends its time, is the HIP kernel.
@@ -619,6 +620,209 @@ std::vector<std::string> mask_files(const Options& opt, const std::vector<std::s
   return files;
 }
 
+// ------------------------------------------------------------------ what the single-pair and the --pairs drivers share
+namespace {
+
+// a failed C-ABI call: "Error: <the library's message> (<rc>)"; returns the exit code
+int api_error(int rc) {
+  std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
+  return 1;
+}
+
+// The settings every pair of a run shares: --years_per_gen, the age grid of the A bins, then (read_replicates) the seed of
+// the run's generator and the number of bootstrap replicates B.  Two steps: the single-pair driver prints its sample age
+// and the number of bins in between.
+struct RunSetup {
+  double years_per_gen = 28.0;
+  std::vector<double> age_grid;
+  int A = 0, seed = 0, B = 1;
+  explicit RunSetup(const Options& opt) : age_grid(256) {
+    if (opt.has("years_per_gen")) years_per_gen = std::stof(opt.get("years_per_gen"));
+    A = colate_age_grid(age_grid.data(), 256);
+    age_grid.resize(A);
+  }
+  bool read_replicates(const Options& opt) {  // false after the error message
+    seed = std::time(0) + getpid();  // coal.cpp:3158
+    if (opt.has("seed")) seed = std::stoi(opt.get("seed"));
+    if (opt.has("num_bootstraps")) B = std::stoi(opt.get("num_bootstraps"));
+    if (B < 1) {
+      std::cerr << "Error: --num_bootstraps must be at least 1." << std::endl;
+      return false;
+    }
+    return true;
+  }
+};
+
+// One process, one GPU: create the HIP context on a second thread while this one reads the inputs (a fresh process pays a
+// few hundred ms for it; end to end 0.63 -> see profiles/r02/bench/e2e.txt); joined when the guard goes.  Not with --ranks
+// (every rank picks its own device after the fork) or --devices (several contexts), not when no device is needed.
+struct DeviceWarmUp {
+  std::thread t;
+  explicit DeviceWarmUp(const Options& opt) {
+    if (g_rank.ranked || opt.has("devices") || opt.has("counts_only")) return;
+    int dev = 0;  // the device the run will use (--device N)
+    try {
+      if (opt.has("device")) dev = std::stoi(opt.get("device"));
+    } catch (...) {
+      dev = 0;  // (reported where the option is used)
+    }
+    t = std::thread([dev] { (void)colate_warm_up(dev); });
+  }
+  ~DeviceWarmUp() {
+    if (t.joinable()) t.join();
+  }
+};
+
+// A pair's epochs and starting rates (coal.cpp:3501-3646): from the .coal file `coal` (which gives the rates too; ep_null 0)
+// or, without one, from --bins and the pair's age.  Returns E, the two vectors sized to it, or <= 0 (colate_last_error()).
+int pair_epochs(const Options& opt, const std::string* coal, double age, double years_per_gen, std::vector<double>& epochs,
+                std::vector<double>& init, int& ep_null) {
+  epochs.assign(COLATE_MAX_EPOCHS, 0.0);
+  init.assign(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
+  ep_null = 0;
+  const int E = coal ? colate_epochs_from_coal(coal->c_str(), age, epochs.data(), init.data(), COLATE_MAX_EPOCHS)
+                     : colate_epochs_from_bins(opt.get("bins").c_str(), age, years_per_gen, epochs.data(), COLATE_MAX_EPOCHS, &ep_null);
+  if (E > 0) epochs.resize(E), init.resize(E);
+  return E;
+}
+
+// --device N: this process's GPU (a rank picks its own, RankComm); --devices N: `devs` = 0..N-1 to shard the rows over
+// (left empty without it).  False after the error message.
+bool bind_devices(const Options& opt, std::vector<int>& devs) {
+  if (opt.has("device") && !g_rank.ranked) {
+    if (int rc = colate_set_device(std::stoi(opt.get("device")))) {
+      api_error(rc);
+      return false;
+    }
+  }
+  if (opt.has("devices")) {
+    const int nd = std::stoi(opt.get("devices"));
+    if (nd < 1) {
+      std::cerr << "Error: --devices must be at least 1." << std::endl;
+      return false;
+    }
+    for (int d = 0; d < nd; d++) devs.push_back(d);
+  }
+  return true;
+}
+
+// `--ranks`: this rank's GPU, (--device + rank) % the node's devices, and the RCCL communicator of all ranks, whose id rank 0
+// creates and the launcher relays (run_ranked).  The communicator is destroyed with the object.
+struct RankComm {
+  void* comm = nullptr;
+  RankComm() = default;
+  RankComm(const RankComm&) = delete;
+  RankComm& operator=(const RankComm&) = delete;
+  ~RankComm() { colate_comm_destroy(comm); }
+
+  bool open(const Options& opt) {  // false after the error message
+#ifdef COLATE_TEST_HOOKS  // (only in lib/testhooks/libcolate_amd.so, which the tests of the launcher load: never in the product library)
+    if (const char* h = std::getenv("COLATE_TEST_HANG_RANK")) {  // a rank stuck as if inside a collective
+      if (std::atoi(h) == g_rank.rank)
+        for (;;) ::pause();
+    }
+#endif
+    const int ndev = colate_device_count();
+    if (ndev < 1) {
+      std::cerr << "Error: " << colate_last_error() << std::endl;
+      return false;
+    }
+    const int dev0 = opt.has("device") ? std::stoi(opt.get("device")) : 0;
+    unsigned char id[COLATE_COMM_ID_BYTES];
+    int rc = colate_set_device((dev0 + g_rank.rank) % ndev);
+    if (!rc) {
+      if (g_rank.rank == 0) {
+        rc = colate_comm_unique_id(id);
+        if (!write_all(g_rank.fd_id_out, id, rc ? 0 : sizeof(id)) && !rc) rc = COLATE_EIO;
+        ::close(g_rank.fd_id_out);  // (on failure the launcher sees end-of-file and tells the others)
+      } else if (!read_all(g_rank.fd_id_in, id, sizeof(id))) {
+        std::cerr << "Error: rank " << g_rank.rank << " did not receive the communicator id." << std::endl;
+        return false;
+      }
+    }
+    if (!rc) rc = colate_comm_create(id, g_rank.nranks, g_rank.rank, &comm);
+    if (rc) api_error(rc);
+    return !rc;
+  }
+};
+
+// The lines of one pair's B replicates.  `pair`: the pair's number in a --pairs list, which then leads each line; 0 for the
+// single pair.
+void report_replicates(int pair, int B, int E, const int* iters, const int* flags) {
+  const std::string p = std::to_string(pair);
+  int unresolved_max = 0;
+  for (int i = 0; i < B; i++) {
+    std::cerr << (pair ? "Pair " + p + " " : "") << "Bootstrap " << i + 1 << ": Total iterations " << iters[i] << std::endl;
+    if (flags[i] & (COLATE_FLAG_NAN | COLATE_FLAG_NEG))
+      std::cerr << "Warning: " << (pair ? "pair " + p + " " : "") << "bootstrap " << i + 1
+                << " produced NaN or negative sufficient statistics (the reference aborts here)." << std::endl;
+    unresolved_max = std::max(unresolved_max, COLATE_UNRESOLVED_EPOCHS(flags[i]));
+  }
+  if (unresolved_max > 0)  // (include/colate_amd.h, COLATE_FLAG_UNRESOLVED)
+    std::cerr << "Note: " << (pair ? "pair " + p + ": " : "") << "the last " << unresolved_max << " of " << E
+              << " epochs are older than the data resolve: "
+              << "their printed rates depend on rounding residue (in the reference build too) and are not reproducible."
+              << std::endl;
+}
+
+// "target reference output [target_age [reference_age]]" per line; after the three names, `key=value` tokens in any order and
+// mixed with the ages: target_mask=PREFIX, reference_mask=PREFIX (expanded as the single-pair CLI expands --target_mask /
+// --reference_mask: with --chr PREFIX_chr<name>.fa per chromosome, else PREFIX itself) and coal=FILE (the pair's warm start).
+// A token with '=' is a key, any other the next age.  An unknown, repeated or empty key, a third age or an age that is no
+// number is an error naming the file and the line.  A line of fewer than three tokens is skipped.
+bool read_pair_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names, std::vector<PairSpec>& pairs) {
+  std::ifstream is(path);
+  if (!is) {
+    std::cerr << "Error while opening file " << path << std::endl;
+    return false;
+  }
+  std::string line;
+  for (size_t line_no = 1; std::getline(is, line); line_no++) {
+    std::istringstream ss(line);
+    PairSpec ps;
+    if (!(ss >> ps.target >> ps.reference >> ps.output)) continue;
+    auto fail = [&](const std::string& what) {
+      std::cerr << "Error: " << path << ", line " << line_no << ": " << what << std::endl;
+      return false;
+    };
+    int n_ages = 0;
+    bool seen_tm = false, seen_rm = false, seen_coal = false;
+    for (std::string tok; ss >> tok;) {
+      const size_t eq = tok.find('=');
+      if (eq == std::string::npos) {
+        if (n_ages == 2) return fail("more than two ages ('" + tok + "')");
+        float v = 0;
+        size_t used = 0;
+        try {
+          v = std::stof(tok, &used);
+        } catch (...) {
+          used = 0;
+        }
+        if (used == 0 || used != tok.size()) return fail("the age '" + tok + "' is not a number");
+        (n_ages++ == 0 ? ps.target_age : ps.ref_age) = v;
+        continue;
+      }
+      const std::string key = tok.substr(0, eq), value = tok.substr(eq + 1);
+      bool* seen = key == "target_mask" ? &seen_tm : key == "reference_mask" ? &seen_rm : key == "coal" ? &seen_coal : nullptr;
+      if (!seen) return fail("unknown key '" + key + "' (known: target_mask, reference_mask, coal)");
+      if (*seen) return fail("the key '" + key + "' is given twice");
+      if (value.empty()) return fail("the key '" + key + "' has no value");
+      *seen = true;
+      if (key == "target_mask") ps.target_masks = mask_files(opt, chr_names, value);
+      else if (key == "reference_mask") ps.ref_masks = mask_files(opt, chr_names, value);
+      else ps.coal = value;
+    }
+    pairs.push_back(ps);
+  }
+  if (pairs.empty()) {
+    std::cerr << "Error: no pairs in " << path << std::endl;
+    return false;
+  }
+  return true;
+}
+
+}  // namespace
+
 int run_mut(const Options& opt) {
   if (!opt.has("mut") || !opt.has("output")) {  // coal.cpp:3077-3087
     std::cout << "Not enough arguments supplied." << std::endl;
@@ -630,25 +834,7 @@ int run_mut(const Options& opt) {
   }
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating coalescence rates for (ancient) samples.." << std::endl;
-
-  // One process, one GPU: create the HIP context on a second thread while this one parses the input files (a fresh
-  // process pays a few hundred ms for it; end to end 0.63 -> see profiles/r02/bench/e2e.txt).  Not with --ranks (every
-  // rank picks its own device after the fork) or --devices (several contexts), not when no device is needed.
-  struct Warm {
-    std::thread t;
-    ~Warm() {
-      if (t.joinable()) t.join();
-    }
-  } warm;
-  if (!g_rank.ranked && !opt.has("devices") && !opt.has("counts_only")) {
-    int warm_dev = 0;  // the device the run will use (--device N)
-    try {
-      if (opt.has("device")) warm_dev = std::stoi(opt.get("device"));
-    } catch (...) {
-      warm_dev = 0;  // (reported where the option is used)
-    }
-    warm.t = std::thread([warm_dev] { (void)colate_warm_up(warm_dev); });
-  }
+  const DeviceWarmUp warm(opt);
 
   double target_age = 0, ref_age = 0;
   try {
@@ -662,29 +848,18 @@ int run_mut(const Options& opt) {
     std::cerr << "Error: sample ages must be non-negative." << std::endl;
     return 1;
   }
-  double years_per_gen = 28.0;
-  if (opt.has("years_per_gen")) years_per_gen = std::stof(opt.get("years_per_gen"));
-  const double age = std::max(target_age, ref_age) / years_per_gen;
+  RunSetup run(opt);
+  const double age = std::max(target_age, ref_age) / run.years_per_gen;
   std::cerr << age << std::endl;
   const bool is_ancient = age > 0.0;
 
   const double C = 10;
-  std::vector<double> age_grid(256);
-  const int A = colate_age_grid(age_grid.data(), 256);
-  age_grid.resize(A);
+  const int A = run.A;
+  std::vector<double>& age_grid = run.age_grid;
   std::cerr << "num_bins: " << A << std::endl;
-
-  const int num_bases_per_block = 30e6;
-  std::mt19937 rng;
-  int seed = std::time(0) + getpid();  // coal.cpp:3158
-  if (opt.has("seed")) seed = std::stoi(opt.get("seed"));
-  rng.seed(seed);
-  int B = 1;
-  if (opt.has("num_bootstraps")) B = std::stoi(opt.get("num_bootstraps"));
-  if (B < 1) {
-    std::cerr << "Error: --num_bootstraps must be at least 1." << std::endl;
-    return 1;
-  }
+  if (!run.read_replicates(opt)) return 1;
+  const int num_bases_per_block = 30e6, seed = run.seed, B = run.B;
+  std::mt19937 rng(seed);
   const std::string out = opt.get("output");
 
   std::vector<double> csh, cns, weights;
@@ -696,24 +871,28 @@ int run_mut(const Options& opt) {
     std::cerr << "Loading precomputed file " << mat << std::endl;
     load_colate_mat(mat, B, A, age_grid, csh, cns);
   } else if (opt.has("target_tmp") && opt.has("reference_tmp")) {
-    std::vector<std::string> names, mut_files, tmask, rmask;
-    chromosome_files(opt, names, mut_files, &tmask, &rmask);
+    std::vector<std::string> names, mut_files;
+    std::vector<PairSpec> one(1);
+    PairSpec& pair = one[0];
+    pair.target = opt.get("target_tmp"), pair.reference = opt.get("reference_tmp");
+    chromosome_files(opt, names, mut_files, &pair.target_masks, &pair.ref_masks);
     // The pair goes through the engine of the batched front end (mut_pairs.cpp) as a list of one: every .mut file parsed in
     // parallel, the .colate.in files mapped, the SNP walk on one thread and the age sampling of the genome blocks on all the
     // others (or on the GPU), exact table-driven age bins -- the same tables bit for bit (22 x 1M rows: 3.3 -> 0.x s of table
     // fill, profiles/r04/bench/e2e_large.txt).  COLATE_THREADS=1: the sequential feeder, which is also what the engine falls
     // back to.
-    const std::string& tgt_file = opt.get("target_tmp");
-    const std::string& ref_file = opt.get("reference_tmp");
     const char* thr_env = std::getenv("COLATE_THREADS");
-    int nb;
     if (thr_env && std::atoi(thr_env) <= 1) {
-      nb = fill_tables_from_tmp(names, mut_files, tgt_file, ref_file, tmask, rmask, C, rng, num_bases_per_block, A, tab);
+      fill_tables_from_tmp(names, mut_files, pair.target, pair.reference, pair.target_masks, pair.ref_masks, C, rng,
+                           num_bases_per_block, A, tab);
     } else {
       for (size_t chr = 0; chr < mut_files.size(); chr++) std::cerr << "parsing CHR: " << chr + 1 << " / " << mut_files.size() << std::endl;
-      nb = fill_single_pair(opt, names, mut_files, tgt_file, ref_file, tmask, rmask, seed, A, tab);
+      std::vector<PairTables> tabs;
+      fill_pairs(opt, names, mut_files, one, {0}, seed, A, tabs);
+      tab = std::move(tabs[0]);
       rng = tab.rng;
     }
+    const int nb = tab.nb;
     std::cerr << "Number of blocks: " << nb << std::endl;
     if (nb < 1) {
       std::cerr << "Error: no genome blocks were read." << std::endl;
@@ -729,14 +908,10 @@ int run_mut(const Options& opt) {
                     !opt.has("write_colate_mat");
     if (gpu_bootstrap) {
       weights.resize((size_t)B * nb);
-      if (int rc = colate_bootstrap_weights(&rng, B, nb, weights.data())) {
-        std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-        return 1;
-      }
+      if (int rc = colate_bootstrap_weights(&rng, B, nb, weights.data())) return api_error(rc);
     } else if (int rc = colate_bootstrap_counts(&rng, B, nb, A, age_grid.data(), age, tab.sh.data(), tab.ns.data(),
                                                 tab.she.data(), tab.nse.data(), csh.data(), cns.data())) {
-      std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-      return 1;
+      return api_error(rc);
     }
   } else {
     std::cerr << "Error: colate_amd reads --target_tmp/--reference_tmp (.colate.in) inputs or an "
@@ -782,94 +957,47 @@ int run_mut(const Options& opt) {
   }
 
   // ---- epochs (coal.cpp:3501-3646)
-  std::vector<double> epochs(COLATE_MAX_EPOCHS), init_rates(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
-  int E = 0, ep_null = 0;
-  if (opt.has("coal")) {
-    E = colate_epochs_from_coal(opt.get("coal").c_str(), age, epochs.data(), init_rates.data(), COLATE_MAX_EPOCHS);
-    if (E > 0) {
-      for (int e = 0; e < E; e++) std::cerr << init_rates[e] << " ";
-      std::cerr << std::endl;
-    }
-  } else if (opt.has("bins")) {
-    E = colate_epochs_from_bins(opt.get("bins").c_str(), age, years_per_gen, epochs.data(), COLATE_MAX_EPOCHS, &ep_null);
-  } else {
+  if (!opt.has("coal") && !opt.has("bins")) {
     std::cerr << "Error: need --bins or --coal." << std::endl;
     return 1;
   }
+  std::vector<double> epochs, init_rates;
+  int ep_null = 0;
+  const int E = pair_epochs(opt, opt.has("coal") ? &opt.get("coal") : nullptr, age, run.years_per_gen, epochs, init_rates, ep_null);
   if (E <= 0) {
     std::cerr << colate_last_error() << std::endl;
     return 1;
   }
-  epochs.resize(E);
-  init_rates.resize(E);
+  if (opt.has("coal")) {
+    for (double r : init_rates) std::cerr << r << " ";
+    std::cerr << std::endl;
+  }
 
   std::cerr << "Maximising likelihood using EM.. " << std::endl;
-  if (opt.has("device") && !g_rank.ranked) {
-    if (int rc = colate_set_device(std::stoi(opt.get("device")))) {
-      std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-      return 1;
-    }
-  }
+  std::vector<int> devs;
+  if (!bind_devices(opt, devs)) return 1;
   std::vector<double> rates((size_t)B * E), ll(B);
   std::vector<int> iters(B), flags(B);
   int rc;
   const double t_em0 = StageTimes::now();
   if (g_rank.ranked) {
     // one process per GPU: this rank's contiguous replicate range on its own device, then ONE RCCL all-gather
-#ifdef COLATE_TEST_HOOKS  // (only in lib/testhooks/libcolate_amd.so, which the tests of the launcher load: never in the product library)
-    if (const char* h = std::getenv("COLATE_TEST_HANG_RANK")) {  // a rank stuck as if inside a collective
-      if (std::atoi(h) == g_rank.rank)
-        for (;;) ::pause();
-    }
-#endif
-    const int ndev = colate_device_count();
-    if (ndev < 1) {
-      std::cerr << "Error: " << colate_last_error() << std::endl;
-      return 1;
-    }
-    const int dev0 = opt.has("device") ? std::stoi(opt.get("device")) : 0;
-    unsigned char id[COLATE_COMM_ID_BYTES];
-    void* comm = nullptr;
-    rc = colate_set_device((dev0 + g_rank.rank) % ndev);
-    if (!rc) {
-      if (g_rank.rank == 0) {
-        rc = colate_comm_unique_id(id);
-        if (!write_all(g_rank.fd_id_out, id, rc ? 0 : sizeof(id)) && !rc) rc = COLATE_EIO;
-        ::close(g_rank.fd_id_out);  // (on failure the launcher sees end-of-file and tells the others)
-      } else if (!read_all(g_rank.fd_id_in, id, sizeof(id))) {
-        std::cerr << "Error: rank " << g_rank.rank << " did not receive the communicator id." << std::endl;
-        return 1;
-      }
-    }
-    if (!rc) rc = colate_comm_create(id, g_rank.nranks, g_rank.rank, &comm);
-    if (!rc) {
-      if (gpu_bootstrap)
-        rc = colate_bootstrap_em_batch_allgather(comm, B, num_blocks, E, A, age_grid.data(), age, weights.data(), tab.sh.data(),
-                                                 tab.ns.data(), tab.she.data(), tab.nse.data(), epochs.data(), init_rates.data(),
-                                                 COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER, COLATE_DEFAULT_REL_TOL,
-                                                 COLATE_DEFAULT_RATE_FLOOR, rates.data(), iters.data(), ll.data(), flags.data());
-      else
-        rc = colate_em_batch_allgather(comm, B, E, A, age_grid.data(), csh.data(), cns.data(), epochs.data(),
-                                       init_rates.data(), COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER,
-                                       COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, rates.data(), iters.data(),
-                                       ll.data(), flags.data());
-    }
-    std::string msg = rc ? colate_last_error() : "";
-    colate_comm_destroy(comm);
-    if (rc) {
-      std::cerr << "Error: " << msg << " (" << rc << ")" << std::endl;
-      return 1;
-    }
+    RankComm comm;
+    if (!comm.open(opt)) return 1;
+    if (gpu_bootstrap)
+      rc = colate_bootstrap_em_batch_allgather(comm.comm, B, num_blocks, E, A, age_grid.data(), age, weights.data(), tab.sh.data(),
+                                               tab.ns.data(), tab.she.data(), tab.nse.data(), epochs.data(), init_rates.data(),
+                                               COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER, COLATE_DEFAULT_REL_TOL,
+                                               COLATE_DEFAULT_RATE_FLOOR, rates.data(), iters.data(), ll.data(), flags.data());
+    else
+      rc = colate_em_batch_allgather(comm.comm, B, E, A, age_grid.data(), csh.data(), cns.data(), epochs.data(),
+                                     init_rates.data(), COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER,
+                                     COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, rates.data(), iters.data(),
+                                     ll.data(), flags.data());
+    if (rc) return api_error(rc);
     if (g_rank.rank != 0) return 0;  // every rank holds all results; rank 0 reports and writes them
-  } else if (opt.has("devices")) {
-    const int nd = std::stoi(opt.get("devices"));
-    if (nd < 1) {
-      std::cerr << "Error: --devices must be at least 1." << std::endl;
-      return 1;
-    }
-    std::vector<int> devs(nd);
-    for (int d = 0; d < nd; d++) devs[d] = d;
-    rc = colate_em_batch_sharded(nd, devs.data(), B, E, A, age_grid.data(), csh.data(), cns.data(),
+  } else if (!devs.empty()) {
+    rc = colate_em_batch_sharded((int)devs.size(), devs.data(), B, E, A, age_grid.data(), csh.data(), cns.data(),
                                  epochs.data(), init_rates.data(), COLATE_DEFAULT_MAX_ITER,
                                  COLATE_DEFAULT_MIN_ITER, COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR,
                                  rates.data(), iters.data(), ll.data(), flags.data());
@@ -887,23 +1015,8 @@ int run_mut(const Options& opt) {
   }
   g_times.bootstrap_em = StageTimes::now() - t_em0;
   report_times();
-  if (rc) {
-    std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-    return 1;
-  }
-  int unresolved_max = 0;
-  for (int i = 0; i < B; i++) {
-    std::cerr << "Bootstrap " << i + 1 << ": Total iterations " << iters[i] << std::endl;
-    if (flags[i] & (COLATE_FLAG_NAN | COLATE_FLAG_NEG))
-      std::cerr << "Warning: bootstrap " << i + 1
-                << " produced NaN or negative sufficient statistics (the reference aborts here)."
-                << std::endl;
-    unresolved_max = std::max(unresolved_max, COLATE_UNRESOLVED_EPOCHS(flags[i]));
-  }
-  if (unresolved_max > 0)  // (include/colate_amd.h, COLATE_FLAG_UNRESOLVED)
-    std::cerr << "Note: the last " << unresolved_max << " of " << E << " epochs are older than the data resolve: "
-              << "their printed rates depend on rounding residue (in the reference build too) and are not reproducible."
-              << std::endl;
+  if (rc) return api_error(rc);
+  report_replicates(0, B, E, iters.data(), flags.data());
   if (colate_write_coal((out + ".coal").c_str(), B, E, epochs.data(), rates.data(), is_ancient ? 1 : 0, ep_null)) {
     std::cerr << "Error: " << colate_last_error() << std::endl;
     return 1;
@@ -913,6 +1026,196 @@ int run_mut(const Options& opt) {
   return 0;
 }
 
+int run_mut_pairs(const Options& opt) {
+  if (!opt.has("mut")) {
+    std::cerr << "Error: --pairs needs --mut (and optionally --chr, --bins, --num_bootstraps, --seed)." << std::endl;
+    return 1;
+  }
+  for (const char* o : {"target_mask", "reference_mask", "coal"})
+    if (opt.has(o)) {  // one mask / one warm start cannot mean the same for a whole list of pairs: refuse, do not ignore
+      std::cerr << "Error: --" << o << " cannot be combined with --pairs (give it per line: " << o << "=...)." << std::endl;
+      return 1;
+    }
+  std::vector<std::string> chr_names, mut_files;
+  chromosome_files(opt, chr_names, mut_files);  // (once: the list's mask prefixes expand with these names, and the fill reads these files)
+  std::vector<PairSpec> pairs;
+  if (!read_pair_list(opt.get("pairs"), opt, chr_names, pairs)) return 1;
+  if (!opt.has("bins"))
+    for (size_t p = 0; p < pairs.size(); p++)
+      if (pairs[p].coal.empty()) {  // (a line with coal= takes its epochs from that file)
+        std::cerr << "Error: --pairs needs --bins for pair " << p + 1 << " (it names no coal= file)." << std::endl;
+        return 1;
+      }
+  const bool talk = g_rank.rank == 0;
+  if (talk) {
+    std::cerr << "---------------------------------------------------------" << std::endl;
+    std::cerr << "Calculating coalescence rates for " << pairs.size() << " pairs of (ancient) samples.." << std::endl;
+  }
+  RunSetup run(opt);
+  if (!run.read_replicates(opt)) return 1;
+  const int A = run.A, B = run.B;
+  const std::vector<double>& age_grid = run.age_grid;
+  const size_t P = pairs.size();
+  const bool counts_only = opt.has("counts_only");
+  const bool want_counts = counts_only || opt.has("counts_out");
+  const DeviceWarmUp warm(opt);
+
+  // ---- epochs per pair (coal.cpp:3501-3632): from the ages and --bins, or from the pair's coal= file (which also gives its
+  // starting rates, coal.cpp:3638-3646): the launches are known before any file is read
+  std::vector<std::vector<double>> epochs(P), init(P);
+  std::vector<int> ep_null(P, 0);
+  std::vector<double> age(P);
+  for (size_t p = 0; p < P; p++) {
+    age[p] = std::max(pairs[p].target_age, pairs[p].ref_age) / run.years_per_gen;
+    const std::string* coal = pairs[p].coal.empty() ? nullptr : &pairs[p].coal;
+    if (pair_epochs(opt, coal, age[p], run.years_per_gen, epochs[p], init[p], ep_null[p]) <= 0) {
+      std::cerr << "Error: pair " << p + 1 << ": " << colate_last_error() << std::endl;
+      return 1;
+    }
+    if (coal && talk) {  // (as the single-pair CLI prints them, after the pair's number)
+      std::cerr << "Pair " << p + 1 << ": ";
+      for (double r : init[p]) std::cerr << r << " ";
+      std::cerr << std::endl;
+    }
+  }
+  // classes of pairs with the same number of epochs, in order of first appearance: one launch each
+  std::vector<std::vector<size_t>> classes;
+  for (size_t p = 0; p < P; p++) {
+    size_t c = 0;
+    while (c < classes.size() && epochs[classes[c][0]].size() != epochs[p].size()) c++;
+    if (c == classes.size()) classes.emplace_back();
+    classes[c].push_back(p);
+  }
+  // --ranks N: this rank's rows [lo, hi) of every class (row = position in the class * B + replicate) and the pairs they belong to
+  std::vector<size_t> todo;
+  std::vector<int> first_group(classes.size(), 0), group_count(classes.size(), 0);
+  for (size_t c = 0; c < classes.size(); c++) {
+    const int R = (int)(classes[c].size() * (size_t)B);
+    int lo = 0, hi = R;
+    if (g_rank.ranked) colate_shard_bounds(R, g_rank.nranks, g_rank.rank, &lo, &hi);
+    if (counts_only && g_rank.ranked && g_rank.rank != 0) lo = hi = 0;
+    if (hi > lo) {
+      first_group[c] = lo / B;
+      group_count[c] = (hi - 1) / B - lo / B + 1;
+      for (int g = 0; g < group_count[c]; g++) todo.push_back(classes[c][(size_t)(first_group[c] + g)]);
+    }
+  }
+  std::sort(todo.begin(), todo.end());
+
+  std::vector<PairTables> tabs;
+  if (!fill_pairs(opt, chr_names, mut_files, pairs, todo, run.seed, A, tabs)) return 1;
+  for (size_t p : todo) {
+    if (talk) std::cerr << "Pair " << p + 1 << " / " << P << ": " << pairs[p].target << " x " << pairs[p].reference << ": Number of blocks: " << tabs[p].nb << std::endl;
+    if (tabs[p].nb < 1) {
+      std::cerr << "Error: no genome blocks were read for pair " << p + 1 << "." << std::endl;
+      return 1;
+    }
+  }
+  // ---- bootstrap weights from each pair's own generator (coal.cpp:3350-3357)
+  std::vector<std::vector<double>> weights(P);
+  for (size_t p : todo) {
+    weights[p].resize((size_t)B * tabs[p].nb);
+    if (int rc = colate_bootstrap_weights(&tabs[p].rng, B, tabs[p].nb, weights[p].data())) return api_error(rc);
+  }
+  if (counts_only) {  // no device: the weighted sums and the F redistribution on the host (coal.cpp:3358-3451)
+    for (size_t p : todo) {
+      std::vector<double> csh((size_t)B * A), cns((size_t)B * A);
+      PairTables& pt = tabs[p];
+      if (int rc = colate_bootstrap_counts_from_weights(B, pt.nb, A, age_grid.data(), age[p], weights[p].data(), pt.sh.data(),
+                                                        pt.ns.data(), pt.she.data(), pt.nse.data(), csh.data(), cns.data()))
+        return api_error(rc);
+      write_counts_file(pairs[p].output + ".counts", B, A, age_grid, csh.data(), cns.data());
+    }
+    return 0;
+  }
+
+  if (talk) std::cerr << "Maximising likelihood using EM.. " << std::endl;
+  std::vector<int> dev_list;
+  if (!bind_devices(opt, dev_list)) return 1;
+  RankComm comm;
+  if (g_rank.ranked && !comm.open(opt)) return 1;
+  const double t_em0 = StageTimes::now();
+  int status = 0;
+  for (size_t c = 0; c < classes.size() && status == 0; c++) {
+    const std::vector<size_t>& cls = classes[c];
+    const int G = (int)cls.size(), E = (int)epochs[cls[0]].size();
+    const size_t R = (size_t)G * B;
+    const int g0 = first_group[c], gn = group_count[c];
+    // this process's groups of the class, concatenated
+    std::vector<int> nb(gn);
+    std::vector<double> g_age(gn), g_w, g_sh, g_ns, g_she, g_nse, g_ep((size_t)gn * E), g_init((size_t)gn * E);
+    for (int g = 0; g < gn; g++) {
+      const size_t p = cls[(size_t)(g0 + g)];
+      const PairTables& pt = tabs[p];
+      nb[g] = pt.nb, g_age[g] = age[p];
+      g_w.insert(g_w.end(), weights[p].begin(), weights[p].end());
+      g_sh.insert(g_sh.end(), pt.sh.begin(), pt.sh.end());
+      g_ns.insert(g_ns.end(), pt.ns.begin(), pt.ns.end());
+      g_she.insert(g_she.end(), pt.she.begin(), pt.she.end());
+      g_nse.insert(g_nse.end(), pt.nse.begin(), pt.nse.end());
+      std::copy(epochs[p].begin(), epochs[p].end(), g_ep.begin() + (size_t)g * E);
+      std::copy(init[p].begin(), init[p].end(), g_init.begin() + (size_t)g * E);
+    }
+    std::vector<double> rates(R * E), ll(R), csh, cns;
+    std::vector<int> iters(R), flags(R);
+    if (want_counts) csh.resize(R * A), cns.resize(R * A);
+    int rc;
+    if (g_rank.ranked) {
+      rc = colate_bootstrap_em_batch_groups_allgather(comm.comm, G, B, g0, gn, E, A, age_grid.data(), nb.data(), g_age.data(), g_w.data(),
+                                                      g_sh.data(), g_ns.data(), g_she.data(), g_nse.data(), g_ep.data(), g_init.data(),
+                                                      COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER, COLATE_DEFAULT_REL_TOL,
+                                                      COLATE_DEFAULT_RATE_FLOOR, rates.data(), iters.data(), ll.data(), flags.data());
+    } else if (!dev_list.empty()) {
+      // --devices N (one process, several GPUs): counts on the host, the rows sharded over GPUs 0..N-1
+      csh.resize(R * A), cns.resize(R * A);
+      rc = 0;
+      for (int g = 0, wo = 0, bo = 0; g < G && !rc; wo += B * nb[g], bo += nb[g], g++)
+        rc = colate_bootstrap_counts_from_weights(B, nb[g], A, age_grid.data(), g_age[g], g_w.data() + wo, g_sh.data() + (size_t)bo * A,
+                                                  g_ns.data() + (size_t)bo * A, g_she.data() + (size_t)bo * A, g_nse.data() + (size_t)bo * A,
+                                                  csh.data() + (size_t)g * B * A, cns.data() + (size_t)g * B * A);
+      std::vector<double> r_ep(R * E), r_init(R * E);
+      for (size_t r = 0; r < R; r++) {
+        std::copy(g_ep.begin() + (r / B) * E, g_ep.begin() + (r / B + 1) * E, r_ep.begin() + r * E);
+        std::copy(g_init.begin() + (r / B) * E, g_init.begin() + (r / B + 1) * E, r_init.begin() + r * E);
+      }
+      if (!rc)
+        rc = colate_em_batch_rows_sharded((int)dev_list.size(), dev_list.data(), (int)R, E, A, age_grid.data(), csh.data(), cns.data(),
+                                          r_ep.data(), r_init.data(), COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER,
+                                          COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, rates.data(), iters.data(), ll.data(),
+                                          flags.data());
+    } else {
+      rc = colate_bootstrap_em_batch_groups(G, B, E, A, age_grid.data(), nb.data(), g_age.data(), g_w.data(), g_sh.data(), g_ns.data(),
+                                            g_she.data(), g_nse.data(), g_ep.data(), g_init.data(), COLATE_DEFAULT_MAX_ITER,
+                                            COLATE_DEFAULT_MIN_ITER, COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, rates.data(),
+                                            iters.data(), ll.data(), flags.data(), want_counts ? csh.data() : nullptr,
+                                            want_counts ? cns.data() : nullptr);
+    }
+    if (rc) {
+      status = api_error(rc);
+      break;
+    }
+    if (!talk) continue;
+    for (int g = 0; g < G; g++) {
+      const size_t p = cls[(size_t)g];
+      report_replicates((int)p + 1, B, E, iters.data() + (size_t)g * B, flags.data() + (size_t)g * B);
+      if (want_counts && !csh.empty())
+        write_counts_file(pairs[p].output + ".counts", B, A, age_grid, csh.data() + (size_t)g * B * A, cns.data() + (size_t)g * B * A);
+      if (colate_write_coal((pairs[p].output + ".coal").c_str(), B, E, epochs[p].data(), rates.data() + (size_t)g * B * E,
+                            age[p] > 0.0 ? 1 : 0, ep_null[p])) {
+        std::cerr << "Error: " << colate_last_error() << std::endl;
+        status = 1;
+        break;
+      }
+    }
+  }
+  g_times.bootstrap_em = StageTimes::now() - t_em0;
+  if (g_times.on)
+    std::cerr << "Timing: inputs " << g_times.parse_mut << " s, pairs' table fill " << g_times.table_fill << " s, bootstrap_em "
+              << g_times.bootstrap_em << " s" << std::endl;
+  if (status || !talk) return status;
+  print_usage_footer();
+  return 0;
+}
 
 void write_counts_file(const std::string& path, int B, int A, const std::vector<double>& grid,
                        const double* csh, const double* cns) {
@@ -1086,6 +1389,12 @@ int run_ranked(const Options& opt, int nranks) {
   }
   if (opt.has("devices")) {
     std::cerr << "Error: --ranks cannot be combined with --devices." << std::endl;
+    return 1;
+  }
+  if (opt.has("pairs") && opt.has("counts_out") && !opt.has("counts_only")) {
+    // (the ranks all-gather the rates, not the counts; --counts_only computes every pair's counts on rank 0)
+    std::cerr << "Error: --ranks cannot write the .counts files of a --pairs list (--counts_out) unless --counts_only is given."
+              << std::endl;
     return 1;
   }
   // where the ranks other than 0 keep their progress lines: next to the output (with --pairs: next to the list of pairs)

@@ -1,7 +1,8 @@
 // colate_amd/csrc/mut_feeder.h -- what the two host-side translation units of the `Colate --mode mut` driver share:
-// mut_driver.cpp (command line, readers, the sequential feeder of include/coal/coal.cpp:2071-2321, mut() driver, --ranks launcher)
-// and mut_pairs.cpp (the batched front end, SURVEY.md section 8 f2 / BASELINE configs[4], whose engine fills every table of a
-// `--pairs` run and of a single pair, and hands a pair it cannot fill exactly to the sequential feeder).
+// mut_driver.cpp (command line, readers, the sequential feeder of include/coal/coal.cpp:2071-2321, the single-pair and the
+// --pairs drivers around mut(), --ranks launcher) and mut_pairs.cpp (the table-fill engine of the batched front end, SURVEY.md
+// section 8 f2 / BASELINE configs[4], which fills every table of a `--pairs` run and of a single pair, and hands a pair it cannot
+// fill exactly to the sequential feeder).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -159,13 +160,10 @@ void write_counts_file(const std::string& path, int B, int A, const std::vector<
                        const double* cns);
 void print_usage_footer();  // "CPU Time spent: ...; Max Memory usage: ..." (coal.cpp:3852-3861)
 
-// mut_pairs.cpp
-int run_mut_pairs(const Options& opt);
-// One pair (masks per chromosome, or none) through the engine of the batched front end: the tables and the generator as
-// the fill leaves it.  Returns the number of genome blocks.
-int fill_single_pair(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
-                     const std::string& target, const std::string& reference,
-                     const std::vector<std::string>& target_masks, const std::vector<std::string>& ref_masks, int seed, int A,
-                     PairTables& out);
+// mut_pairs.cpp: the engine.  The tables of the pairs listed in `todo` (indices into `pairs`; the others stay empty) and
+// each pair's generator as the fill leaves it; `names` / `mut_files`: the chromosomes (chromosome_files).  False after an
+// error message.
+bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& out);
 
 }  // namespace colate_drv

@@ -1,5 +1,7 @@
-// colate_amd/csrc/mut_pairs.cpp -- `Colate --mode mut --pairs FILE`: the batched all-pairs front end
-// (BASELINE configs[4]: 10 target x 10 reference .colate.in, 20 replicates each).
+// colate_amd/csrc/mut_pairs.cpp -- the table-fill engine of `Colate --mode mut --pairs FILE`, the batched all-pairs front end
+// (BASELINE configs[4]: 10 target x 10 reference .colate.in, 20 replicates each), which also fills the
+// tables of a single pair.  The drivers around it (the pair list, epochs, devices, the EM launches, the reports) are in
+// mut_driver.cpp.
 //
 // The reference has no such mode: it is run once per (target, reference) pair and every run re-reads the .mut files,
 // walks both .colate.in streams (include/coal/coal.cpp:2071-2321) and draws 100 ages per used SNP from the run's own
@@ -34,7 +36,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <fstream>
 #include <functional>
 #include <iostream>
 #include <limits>
@@ -1224,64 +1225,9 @@ struct Engine {
   }
 };
 
-// "target reference output [target_age [reference_age]]" per line; after the three names, `key=value` tokens in any order and
-// mixed with the ages: target_mask=PREFIX, reference_mask=PREFIX (expanded as the single-pair CLI expands --target_mask /
-// --reference_mask: with --chr PREFIX_chr<name>.fa per chromosome, else PREFIX itself) and coal=FILE (the pair's warm start).
-// A token with '=' is a key, any other the next age.  An unknown, repeated or empty key, a third age or an age that is no
-// number is an error naming the file and the line.  A line of fewer than three tokens is skipped.
-bool read_pair_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names, std::vector<PairSpec>& pairs) {
-  std::ifstream is(path);
-  if (!is) {
-    std::cerr << "Error while opening file " << path << std::endl;
-    return false;
-  }
-  std::string line;
-  for (size_t line_no = 1; std::getline(is, line); line_no++) {
-    std::istringstream ss(line);
-    PairSpec ps;
-    if (!(ss >> ps.target >> ps.reference >> ps.output)) continue;
-    auto fail = [&](const std::string& what) {
-      std::cerr << "Error: " << path << ", line " << line_no << ": " << what << std::endl;
-      return false;
-    };
-    int n_ages = 0;
-    bool seen_tm = false, seen_rm = false, seen_coal = false;
-    for (std::string tok; ss >> tok;) {
-      const size_t eq = tok.find('=');
-      if (eq == std::string::npos) {
-        if (n_ages == 2) return fail("more than two ages ('" + tok + "')");
-        float v = 0;
-        size_t used = 0;
-        try {
-          v = std::stof(tok, &used);
-        } catch (...) {
-          used = 0;
-        }
-        if (used == 0 || used != tok.size()) return fail("the age '" + tok + "' is not a number");
-        (n_ages++ == 0 ? ps.target_age : ps.ref_age) = v;
-        continue;
-      }
-      const std::string key = tok.substr(0, eq), value = tok.substr(eq + 1);
-      bool* seen = key == "target_mask" ? &seen_tm : key == "reference_mask" ? &seen_rm : key == "coal" ? &seen_coal : nullptr;
-      if (!seen) return fail("unknown key '" + key + "' (known: target_mask, reference_mask, coal)");
-      if (*seen) return fail("the key '" + key + "' is given twice");
-      if (value.empty()) return fail("the key '" + key + "' has no value");
-      *seen = true;
-      if (key == "target_mask") ps.target_masks = mask_files(opt, chr_names, value);
-      else if (key == "reference_mask") ps.ref_masks = mask_files(opt, chr_names, value);
-      else ps.coal = value;
-    }
-    pairs.push_back(ps);
-  }
-  if (pairs.empty()) {
-    std::cerr << "Error: no pairs in " << path << std::endl;
-    return false;
-  }
-  return true;
-}
+}  // namespace
 
-// The tables of the pairs listed in `todo` (indices into `pairs`); false after an error message.
-// `names` / `mut_files`: the chromosomes (chromosome_files).
+// (mut_feeder.h)
 bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
                 const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& out) {
   const double C = 10;
@@ -1680,300 +1626,6 @@ bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const
   g_times.parse_mut = t1 - t0;
   g_times.table_fill = now_s() - t1;
   return true;
-}
-
-}  // namespace
-
-int fill_single_pair(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
-                     const std::string& target, const std::string& reference, const std::vector<std::string>& target_masks,
-                     const std::vector<std::string>& ref_masks, int seed, int A, PairTables& out) {
-  std::vector<PairSpec> one(1);
-  one[0].target = target, one[0].reference = reference;
-  one[0].target_masks = target_masks, one[0].ref_masks = ref_masks;
-  std::vector<PairTables> tabs;
-  fill_pairs(opt, names, mut_files, one, {0}, seed, A, tabs);
-  out = std::move(tabs[0]);
-  return out.nb;
-}
-
-int run_mut_pairs(const Options& opt) {
-  if (!opt.has("mut")) {
-    std::cerr << "Error: --pairs needs --mut (and optionally --chr, --bins, --num_bootstraps, --seed)." << std::endl;
-    return 1;
-  }
-  for (const char* o : {"target_mask", "reference_mask", "coal"})
-    if (opt.has(o)) {  // one mask / one warm start cannot mean the same for a whole list of pairs: refuse, do not ignore
-      std::cerr << "Error: --" << o << " cannot be combined with --pairs (give it per line: " << o << "=...)." << std::endl;
-      return 1;
-    }
-  std::vector<std::string> chr_names, mut_files;
-  chromosome_files(opt, chr_names, mut_files);  // (once: the list's mask prefixes expand with these names, and the fill reads these files)
-  std::vector<PairSpec> pairs;
-  if (!read_pair_list(opt.get("pairs"), opt, chr_names, pairs)) return 1;
-  if (!opt.has("bins"))
-    for (size_t p = 0; p < pairs.size(); p++)
-      if (pairs[p].coal.empty()) {  // (a line with coal= takes its epochs from that file)
-        std::cerr << "Error: --pairs needs --bins for pair " << p + 1 << " (it names no coal= file)." << std::endl;
-        return 1;
-      }
-  const bool talk = g_rank.rank == 0;
-  if (talk) {
-    std::cerr << "---------------------------------------------------------" << std::endl;
-    std::cerr << "Calculating coalescence rates for " << pairs.size() << " pairs of (ancient) samples.." << std::endl;
-  }
-  double years_per_gen = 28.0;
-  if (opt.has("years_per_gen")) years_per_gen = std::stof(opt.get("years_per_gen"));
-  std::vector<double> age_grid(256);
-  const int A = colate_age_grid(age_grid.data(), 256);
-  age_grid.resize(A);
-  int seed = std::time(0) + getpid();
-  if (opt.has("seed")) seed = std::stoi(opt.get("seed"));
-  int B = 1;
-  if (opt.has("num_bootstraps")) B = std::stoi(opt.get("num_bootstraps"));
-  if (B < 1) {
-    std::cerr << "Error: --num_bootstraps must be at least 1." << std::endl;
-    return 1;
-  }
-  const size_t P = pairs.size();
-  const bool counts_only = opt.has("counts_only");
-  const bool want_counts = counts_only || opt.has("counts_out");
-
-  // One process, one GPU: create the HIP context on a second thread while the inputs are read (as run_mut does)
-  struct Warm {
-    std::thread t;
-    ~Warm() {
-      if (t.joinable()) t.join();
-    }
-  } warm;
-  if (!g_rank.ranked && !opt.has("devices") && !counts_only) {
-    int warm_dev = 0;
-    try {
-      if (opt.has("device")) warm_dev = std::stoi(opt.get("device"));
-    } catch (...) {
-      warm_dev = 0;
-    }
-    warm.t = std::thread([warm_dev] { (void)colate_warm_up(warm_dev); });
-  }
-
-  // ---- epochs per pair (coal.cpp:3501-3632): from the ages and --bins, or from the pair's coal= file (which also gives its
-  // starting rates, coal.cpp:3638-3646): the launches are known before any file is read
-  std::vector<std::vector<double>> epochs(P), init(P);
-  std::vector<int> ep_null(P, 0);
-  std::vector<double> age(P);
-  for (size_t p = 0; p < P; p++) {
-    age[p] = std::max(pairs[p].target_age, pairs[p].ref_age) / years_per_gen;
-    epochs[p].resize(COLATE_MAX_EPOCHS);
-    init[p].assign(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
-    int E;
-    if (!pairs[p].coal.empty()) {
-      E = colate_epochs_from_coal(pairs[p].coal.c_str(), age[p], epochs[p].data(), init[p].data(), COLATE_MAX_EPOCHS);
-      if (E > 0 && talk) {  // (as the single-pair CLI prints them, after the pair's number)
-        std::cerr << "Pair " << p + 1 << ": ";
-        for (int e = 0; e < E; e++) std::cerr << init[p][e] << " ";
-        std::cerr << std::endl;
-      }
-    } else {
-      E = colate_epochs_from_bins(opt.get("bins").c_str(), age[p], years_per_gen, epochs[p].data(), COLATE_MAX_EPOCHS, &ep_null[p]);
-    }
-    if (E <= 0) {
-      std::cerr << "Error: pair " << p + 1 << ": " << colate_last_error() << std::endl;
-      return 1;
-    }
-    epochs[p].resize(E);
-    init[p].resize(E);
-  }
-  // classes of pairs with the same number of epochs, in order of first appearance: one launch each
-  std::vector<std::vector<size_t>> classes;
-  for (size_t p = 0; p < P; p++) {
-    size_t c = 0;
-    while (c < classes.size() && epochs[classes[c][0]].size() != epochs[p].size()) c++;
-    if (c == classes.size()) classes.emplace_back();
-    classes[c].push_back(p);
-  }
-  // --ranks N: this rank's rows [lo, hi) of every class (row = position in the class * B + replicate) and the pairs they belong to
-  std::vector<size_t> todo;
-  std::vector<int> first_group(classes.size(), 0), group_count(classes.size(), 0);
-  for (size_t c = 0; c < classes.size(); c++) {
-    const int R = (int)(classes[c].size() * (size_t)B);
-    int lo = 0, hi = R;
-    if (g_rank.ranked) colate_shard_bounds(R, g_rank.nranks, g_rank.rank, &lo, &hi);
-    if (counts_only && g_rank.ranked && g_rank.rank != 0) lo = hi = 0;
-    if (hi > lo) {
-      first_group[c] = lo / B;
-      group_count[c] = (hi - 1) / B - lo / B + 1;
-      for (int g = 0; g < group_count[c]; g++) todo.push_back(classes[c][(size_t)(first_group[c] + g)]);
-    }
-  }
-  std::sort(todo.begin(), todo.end());
-
-  std::vector<PairTables> tabs;
-  if (!fill_pairs(opt, chr_names, mut_files, pairs, todo, seed, A, tabs)) return 1;
-  for (size_t p : todo) {
-    if (talk) std::cerr << "Pair " << p + 1 << " / " << P << ": " << pairs[p].target << " x " << pairs[p].reference << ": Number of blocks: " << tabs[p].nb << std::endl;
-    if (tabs[p].nb < 1) {
-      std::cerr << "Error: no genome blocks were read for pair " << p + 1 << "." << std::endl;
-      return 1;
-    }
-  }
-  // ---- bootstrap weights from each pair's own generator (coal.cpp:3350-3357)
-  std::vector<std::vector<double>> weights(P);
-  for (size_t p : todo) {
-    weights[p].resize((size_t)B * tabs[p].nb);
-    if (int rc = colate_bootstrap_weights(&tabs[p].rng, B, tabs[p].nb, weights[p].data())) {
-      std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-      return 1;
-    }
-  }
-  if (counts_only) {  // no device: the weighted sums and the F redistribution on the host (coal.cpp:3358-3451)
-    for (size_t p : todo) {
-      std::vector<double> csh((size_t)B * A), cns((size_t)B * A);
-      PairTables& pt = tabs[p];
-      if (int rc = colate_bootstrap_counts_from_weights(B, pt.nb, A, age_grid.data(), age[p], weights[p].data(), pt.sh.data(),
-                                                        pt.ns.data(), pt.she.data(), pt.nse.data(), csh.data(), cns.data())) {
-        std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-        return 1;
-      }
-      write_counts_file(pairs[p].output + ".counts", B, A, age_grid, csh.data(), cns.data());
-    }
-    return 0;
-  }
-
-  if (talk) std::cerr << "Maximising likelihood using EM.. " << std::endl;
-  if (opt.has("device") && !g_rank.ranked) {
-    if (int rc = colate_set_device(std::stoi(opt.get("device")))) {
-      std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-      return 1;
-    }
-  }
-  std::vector<int> dev_list;
-  if (opt.has("devices")) {
-    const int nd = std::stoi(opt.get("devices"));
-    if (nd < 1) {
-      std::cerr << "Error: --devices must be at least 1." << std::endl;
-      return 1;
-    }
-    for (int d = 0; d < nd; d++) dev_list.push_back(d);
-  }
-  void* comm = nullptr;
-  if (g_rank.ranked) {
-    const int ndev = colate_device_count();
-    if (ndev < 1) {
-      std::cerr << "Error: " << colate_last_error() << std::endl;
-      return 1;
-    }
-    const int dev0 = opt.has("device") ? std::stoi(opt.get("device")) : 0;
-    unsigned char id[COLATE_COMM_ID_BYTES];
-    int rc = colate_set_device((dev0 + g_rank.rank) % ndev);
-    if (!rc) {
-      if (g_rank.rank == 0) {
-        rc = colate_comm_unique_id(id);
-        if (!write_all(g_rank.fd_id_out, id, rc ? 0 : sizeof(id)) && !rc) rc = COLATE_EIO;
-        ::close(g_rank.fd_id_out);
-      } else if (!read_all(g_rank.fd_id_in, id, sizeof(id))) {
-        std::cerr << "Error: rank " << g_rank.rank << " did not receive the communicator id." << std::endl;
-        return 1;
-      }
-    }
-    if (!rc) rc = colate_comm_create(id, g_rank.nranks, g_rank.rank, &comm);
-    if (rc) {
-      std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-      return 1;
-    }
-  }
-  const double t_em0 = now_s();
-  int status = 0;
-  for (size_t c = 0; c < classes.size() && status == 0; c++) {
-    const std::vector<size_t>& cls = classes[c];
-    const int G = (int)cls.size(), E = (int)epochs[cls[0]].size();
-    const size_t R = (size_t)G * B;
-    const int g0 = first_group[c], gn = group_count[c];
-    // this process's groups of the class, concatenated
-    std::vector<int> nb(gn);
-    std::vector<double> g_age(gn), g_w, g_sh, g_ns, g_she, g_nse, g_ep((size_t)gn * E), g_init((size_t)gn * E);
-    for (int g = 0; g < gn; g++) {
-      const size_t p = cls[(size_t)(g0 + g)];
-      const PairTables& pt = tabs[p];
-      nb[g] = pt.nb, g_age[g] = age[p];
-      g_w.insert(g_w.end(), weights[p].begin(), weights[p].end());
-      g_sh.insert(g_sh.end(), pt.sh.begin(), pt.sh.end());
-      g_ns.insert(g_ns.end(), pt.ns.begin(), pt.ns.end());
-      g_she.insert(g_she.end(), pt.she.begin(), pt.she.end());
-      g_nse.insert(g_nse.end(), pt.nse.begin(), pt.nse.end());
-      std::copy(epochs[p].begin(), epochs[p].end(), g_ep.begin() + (size_t)g * E);
-      std::copy(init[p].begin(), init[p].end(), g_init.begin() + (size_t)g * E);
-    }
-    std::vector<double> rates(R * E), ll(R), csh, cns;
-    std::vector<int> iters(R), flags(R);
-    if (want_counts) csh.resize(R * A), cns.resize(R * A);
-    int rc;
-    if (g_rank.ranked) {
-      rc = colate_bootstrap_em_batch_groups_allgather(comm, G, B, g0, gn, E, A, age_grid.data(), nb.data(), g_age.data(), g_w.data(),
-                                                      g_sh.data(), g_ns.data(), g_she.data(), g_nse.data(), g_ep.data(), g_init.data(),
-                                                      COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER, COLATE_DEFAULT_REL_TOL,
-                                                      COLATE_DEFAULT_RATE_FLOOR, rates.data(), iters.data(), ll.data(), flags.data());
-    } else if (!dev_list.empty()) {
-      // --devices N (one process, several GPUs): counts on the host, the rows sharded over GPUs 0..N-1
-      csh.resize(R * A), cns.resize(R * A);
-      rc = 0;
-      for (int g = 0, wo = 0, bo = 0; g < G && !rc; wo += B * nb[g], bo += nb[g], g++)
-        rc = colate_bootstrap_counts_from_weights(B, nb[g], A, age_grid.data(), g_age[g], g_w.data() + wo, g_sh.data() + (size_t)bo * A,
-                                                  g_ns.data() + (size_t)bo * A, g_she.data() + (size_t)bo * A, g_nse.data() + (size_t)bo * A,
-                                                  csh.data() + (size_t)g * B * A, cns.data() + (size_t)g * B * A);
-      std::vector<double> r_ep(R * E), r_init(R * E);
-      for (size_t r = 0; r < R; r++) {
-        std::copy(g_ep.begin() + (r / B) * E, g_ep.begin() + (r / B + 1) * E, r_ep.begin() + r * E);
-        std::copy(g_init.begin() + (r / B) * E, g_init.begin() + (r / B + 1) * E, r_init.begin() + r * E);
-      }
-      if (!rc)
-        rc = colate_em_batch_rows_sharded((int)dev_list.size(), dev_list.data(), (int)R, E, A, age_grid.data(), csh.data(), cns.data(),
-                                          r_ep.data(), r_init.data(), COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER,
-                                          COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, rates.data(), iters.data(), ll.data(),
-                                          flags.data());
-    } else {
-      rc = colate_bootstrap_em_batch_groups(G, B, E, A, age_grid.data(), nb.data(), g_age.data(), g_w.data(), g_sh.data(), g_ns.data(),
-                                            g_she.data(), g_nse.data(), g_ep.data(), g_init.data(), COLATE_DEFAULT_MAX_ITER,
-                                            COLATE_DEFAULT_MIN_ITER, COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, rates.data(),
-                                            iters.data(), ll.data(), flags.data(), want_counts ? csh.data() : nullptr,
-                                            want_counts ? cns.data() : nullptr);
-    }
-    if (rc) {
-      std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-      status = 1;
-      break;
-    }
-    if (!talk) continue;
-    for (int g = 0; g < G; g++) {
-      const size_t p = cls[(size_t)g];
-      int unresolved_max = 0;
-      for (int i = 0; i < B; i++) {
-        const size_t r = (size_t)g * B + i;
-        std::cerr << "Pair " << p + 1 << " Bootstrap " << i + 1 << ": Total iterations " << iters[r] << std::endl;
-        if (flags[r] & (COLATE_FLAG_NAN | COLATE_FLAG_NEG))
-          std::cerr << "Warning: pair " << p + 1 << " bootstrap " << i + 1
-                    << " produced NaN or negative sufficient statistics (the reference aborts here)." << std::endl;
-        unresolved_max = std::max(unresolved_max, COLATE_UNRESOLVED_EPOCHS(flags[r]));
-      }
-      if (unresolved_max > 0)
-        std::cerr << "Note: pair " << p + 1 << ": the last " << unresolved_max << " of " << E
-                  << " epochs are older than the data resolve (include/colate_amd.h, COLATE_FLAG_UNRESOLVED)." << std::endl;
-      if (want_counts && !csh.empty())
-        write_counts_file(pairs[p].output + ".counts", B, A, age_grid, csh.data() + (size_t)g * B * A, cns.data() + (size_t)g * B * A);
-      if (colate_write_coal((pairs[p].output + ".coal").c_str(), B, E, epochs[p].data(), rates.data() + (size_t)g * B * E,
-                            age[p] > 0.0 ? 1 : 0, ep_null[p])) {
-        std::cerr << "Error: " << colate_last_error() << std::endl;
-        status = 1;
-        break;
-      }
-    }
-  }
-  colate_comm_destroy(comm);
-  g_times.bootstrap_em = now_s() - t_em0;
-  if (g_times.on)
-    std::cerr << "Timing: inputs " << g_times.parse_mut << " s, pairs' table fill " << g_times.table_fill << " s, bootstrap_em "
-              << g_times.bootstrap_em << " s" << std::endl;
-  if (status || !talk) return status;
-  print_usage_footer();
-  return 0;
 }
 
 }  // namespace colate_drv

@@ -339,6 +339,11 @@ def test_pairs_refuses_masks_and_coal(tmp_path):
     for extra in (["--target_mask", "TM"], ["--reference_mask", "RM"], ["--coal", "x.coal"]):
         r = _run_cli(base + extra, str(tmp_path))
         assert r.returncode != 0 and b"--pairs" in r.stderr, r.stderr.decode()[-300:]
+    # the ranks all-gather rates, not counts: --ranks refuses --counts_out for a list unless --counts_only is given, before it
+    # forks (no device needed), and writes no .counts
+    r = _run_cli(base[:-1] + ["--ranks", "1", "--counts_out", "x"], str(tmp_path))
+    assert r.returncode != 0 and b"--counts_out" in r.stderr and b"--pairs" in r.stderr, r.stderr.decode()[-300:]
+    assert not list(tmp_path.glob("*.counts")) and not (tmp_path / "x").exists()
 
 
 @pytest.mark.parametrize("name", ["wg_e23", "wg_e122"])
