@@ -219,21 +219,14 @@ struct TmpFile {
   HugeVector<DecRec> recs;
   std::vector<std::string> names{std::string()};
   bool decoded = false;  // false: more than 65535 distinct names -- the walks decode the bytes themselves
-  // What a walk finds in this file, row by row of the .mut files, as far as it does not depend on the other sample of the pair
-  // (build_walk_index below): as the reference sample of a pair / as its target.
-  struct RefIdx {
-    int32_t prev_pass;  // position of the latest earlier row of the chromosome that passes as reference (-1: none)
-    uint16_t DAF, N;    // the record's DAF and DAF + AAF where the row passes the tests of coal.cpp:2181-2199, else 0, 0
+  // What a walk finds in this file, row by row of the .mut files, whatever the other sample of the pair (build_walk_index below):
+  // the row's lower bound, the first record of its chromosome at or behind its position.
+  struct RowIdx {
+    int32_t prev_bp;    // position of the record in front of the lower bound (-2: the lower bound is the chromosome's first, or there is none)
+    uint16_t DAF, AAF;  // the lower bound's counts where position and alleles match (coal.cpp:2181-2219), else 0, 0
   };
-  struct TgtIdx {
-    int32_t prev_bp;    // position of the record in front of the row's (-2: the row's record is the chromosome's first, or there is none)
-    uint16_t DAF, AAF;  // the record's counts where position and alleles match (coal.cpp:2201-2219), else 0, 0
-  };
-  std::vector<HugeVector<RefIdx>> ref_idx;  // [chromosome][row]
-  std::vector<HugeVector<TgtIdx>> tgt_idx;  // (also what a masked pair's walk reads for its reference sample, see MaskBits)
-  bool want_ref = false, want_tgt = false;
-  bool ref_ok = false, tgt_ok = false;  // the index of that role was built
-  bool indexable = false;               // ... every index wanted of the file was
+  std::vector<HugeVector<RowIdx>> idx;  // [chromosome][row]
+  bool indexed = false;                 // the index was built
   TmpFile() = default;
   TmpFile(const TmpFile&) = delete;
   TmpFile& operator=(const TmpFile&) = delete;
@@ -388,31 +381,22 @@ struct Cursor {
 };
 
 // ------------------------------------------------------------------ what a pair's walk finds in one file, computed once per file
-// The walk of coal.cpp:2125-2243 steps two cursors through the two samples' records, row by row of the .mut file.  What it finds is
-// almost a property of each file alone.  For files in which every chromosome of the list is one run of records, the runs in the list's
-// order, positions not descending -- and .mut rows whose positions do not descend --:
-//   * the REFERENCE cursor is advanced at every row, whatever the target: the row passes iff the cursor had to move in this row's
-//     search (its DAF / AAF are reset in front of every search, coal.cpp:2182-2183, and only a record read now sets them again:
-//     a record reached while an earlier row was searched, or the chromosome's first, which the skip loop reads, gives DAF = 0),
-//     stops on a record of the row's position and alleles, and that record's DAF is not 0;
-//   * the TARGET cursor is advanced only at rows that passed as reference.  Its record for a row is the first at or behind the
-//     row's position; it counts iff position and alleles match and the cursor moved in this row's search, i.e. iff the record in
-//     front of it lies at or behind the latest earlier row that passed as reference (which that search had started from) -- a
-//     number of the target file (prev_bp) against a number of the reference file (prev_pass).
+// The walk of coal.cpp:2125-2243 steps two cursors through the two samples' records, row by row of the .mut file: the REFERENCE
+// cursor searches at every row the masks let through, the TARGET cursor only at rows that passed as reference.  A search counts iff
+// the cursor moved in it (DAF / AAF are reset in front of every search, coal.cpp:2182-2183, and only a record read now sets them
+// again) and stopped on a record of the row's position and alleles (as reference: with a DAF that is not 0).  For files in which every
+// chromosome of the list is one run of records, the runs in the list's order, positions not descending -- and .mut rows whose
+// positions do not descend -- one rule says all of it: a cursor before a search sits on the lower bound of its previous search's
+// position (the chromosome's first record before any), so it moves in row i's search iff the record in front of row i's lower bound
+// exists and lies at or behind that position.  The lower bound, the record in front of it (RowIdx::prev_bp) and the counts are a
+// property of the file alone; the positions of the two latest searches are the pair's own (the rows where they were, kept by the walk).
+// Without masks every row is searched, and the rule reads "the reference cursor moves iff prev_bp >= the previous row's position; the
+// target cursor iff prev_bp >= the latest earlier row that passed as reference".  Equal row positions: the second search finds the
+// cursor on the lower bound already, whose record in front lies below the position (no move, DAF = 0).  A search that runs off the
+// chromosome's end leaves every later row of it without a match, and the lower bound of every later row is that end too (DAF = AAF = 0).
 // So a pair's walk is one pass over two 8-byte arrays instead of two cursor merges over 16-byte records with a name to track:
 // 100 pairs x 1 GB of streaming became 100 x 0.3 GB, and a few instructions per row.  Anything else (a chromosome missing in a file,
 // runs out of order, a position below the one in front of it, a file that was not decoded, an empty chromosome name) keeps the cursors.
-//
-// A pair with masks does not search the rows its masks remove (coal.cpp:2169-2174): neither cursor moves there, so prev_pass, which
-// assumes a search at every row, does not hold for it.  But both cursors obey one rule that needs no history beyond the pair's own:
-// with rows and records in non-descending order, a cursor before a search sits on the first record at or behind the position of
-// its previous search (the lower bound; the chromosome's first record before any), so it moves in row i's search iff the record in
-// front of row i's lower bound exists and lies at or behind that position -- TgtIdx::prev_bp, a property of the file alone.  A
-// masked pair therefore reads TgtIdx for BOTH samples and keeps two positions of its own (PairFill::last_searched: the latest row
-// that passed both masks, where the reference cursor searched; last_ref_pass: the latest that passed as reference, where the
-// target cursor searched).  Equal row positions: the second search finds the cursor on the lower bound already, whose record in
-// front lies below the position (no move, DAF = 0).  A search that runs off the chromosome's end leaves every later row of it
-// without a match, and the lower bound of every later row is that end too (DAF = AAF = 0 there).
 struct WalkRows {
   const std::vector<std::string>* names;
   const std::vector<HugeVector<CompactRow>>* rows;
@@ -454,61 +438,25 @@ bool find_runs(const TmpFile& f, const std::vector<std::string>& names, std::vec
   return true;
 }
 
-// The indices of one role, built where the file is well-formed for it (false: the pairs that need it keep the cursors).
-bool build_ref_index(TmpFile& f, const WalkRows& w, const std::vector<std::pair<size_t, size_t>>& runs) {
+bool build_row_index(TmpFile& f, const WalkRows& w, const std::vector<std::pair<size_t, size_t>>& runs) {
   const size_t C = w.names->size();
   const DecRec* const R = f.recs.data();
-  f.ref_idx.assign(C, HugeVector<TmpFile::RefIdx>());
+  f.idx.assign(C, HugeVector<TmpFile::RowIdx>());
   for (size_t c = 0; c < C; c++) {
     const HugeVector<CompactRow>& rr = (*w.rows)[c];
     const size_t b = runs[c].first, e = runs[c].second;
-    HugeVector<TmpFile::RefIdx>& out = f.ref_idx[c];
-    out.resize(rr.size());
-    size_t k = b;  // the record the cursor is on: the chromosome's first, read by the skip loop (or by the overrun of the chromosome before)
-    int32_t prev_pass = -1;
-    bool off_end = false;
-    for (size_t i = 0; i < rr.size(); i++) {
-      TmpFile::RefIdx x{prev_pass, 0, 0};
-      if (!off_end) {
-        size_t k2 = k;
-        while (k2 < e && R[k2].bp < rr[i].pos) k2++;
-        if (k2 == e) {
-          off_end = true;  // the cursor has left the chromosome: no match for this row nor any later one
-        } else {
-          if (k2 > k && R[k2].bp == rr[i].pos && R[k2].anc == rr[i].anc && R[k2].der == rr[i].der && R[k2].DAF != 0) {
-            const long long N = (long long)R[k2].DAF + R[k2].AAF;
-            if (R[k2].DAF < 0 || R[k2].DAF > 65535 || N <= 0 || N > 65535) return false;  // (counts beyond the index's fields: cursors)
-            x.DAF = (uint16_t)R[k2].DAF, x.N = (uint16_t)N;
-            prev_pass = rr[i].pos;
-          }
-          k = k2;
-        }
-      }
-      out[i] = x;
-    }
-  }
-  return true;
-}
-
-bool build_tgt_index(TmpFile& f, const WalkRows& w, const std::vector<std::pair<size_t, size_t>>& runs) {
-  const size_t C = w.names->size();
-  const DecRec* const R = f.recs.data();
-  f.tgt_idx.assign(C, HugeVector<TmpFile::TgtIdx>());
-  for (size_t c = 0; c < C; c++) {
-    const HugeVector<CompactRow>& rr = (*w.rows)[c];
-    const size_t b = runs[c].first, e = runs[c].second;
-    HugeVector<TmpFile::TgtIdx>& out = f.tgt_idx[c];
+    HugeVector<TmpFile::RowIdx>& out = f.idx[c];
     out.resize(rr.size());
     size_t k = b;
     for (size_t i = 0; i < rr.size(); i++) {
       while (k < e && R[k].bp < rr[i].pos) k++;
-      TmpFile::TgtIdx x{-2, 0, 0};
+      TmpFile::RowIdx x{-2, 0, 0};
       if (k < e && k > b) {
         if (R[k - 1].bp < -1) return false;  // (-2 means "no record in front"; negative positions: cursors)
         x.prev_bp = R[k - 1].bp;
       }
       if (k < e && R[k].bp == rr[i].pos && R[k].anc == rr[i].anc && R[k].der == rr[i].der) {
-        if (R[k].DAF < 0 || R[k].DAF > 65535 || R[k].AAF < 0 || R[k].AAF > 65535) return false;
+        if (R[k].DAF < 0 || R[k].DAF > 65535 || R[k].AAF < 0 || R[k].AAF > 65535) return false;  // (counts beyond the index's fields: cursors)
         x.DAF = (uint16_t)R[k].DAF, x.AAF = (uint16_t)R[k].AAF;
       }
       out[i] = x;
@@ -517,13 +465,11 @@ bool build_tgt_index(TmpFile& f, const WalkRows& w, const std::vector<std::pair<
   return true;
 }
 
+// The index, built where the file is well-formed for it (else the pairs that walk the file keep the cursors).
 void build_walk_index(TmpFile& f, const WalkRows& w) {
-  f.indexable = f.ref_ok = f.tgt_ok = false;
   std::vector<std::pair<size_t, size_t>> runs;
-  if (!w.rows_ascend || !find_runs(f, *w.names, runs)) return;
-  if (f.want_ref && !(f.ref_ok = build_ref_index(f, w, runs))) f.ref_idx.clear();
-  if (f.want_tgt && !(f.tgt_ok = build_tgt_index(f, w, runs))) f.tgt_idx.clear();
-  f.indexable = (!f.want_ref || f.ref_ok) && (!f.want_tgt || f.tgt_ok);
+  f.indexed = w.rows_ascend && find_runs(f, *w.names, runs) && build_row_index(f, w, runs);
+  if (!f.indexed) f.idx.clear();
 }
 
 // ------------------------------------------------------------------ the uniform stream of the seed, generated once
@@ -875,10 +821,6 @@ AddSnpFn pick_add_snp() {
 }
 
 // ------------------------------------------------------------------ one pair's tables and its walk through the SNPs
-struct UsedSnp {
-  double age_begin, age_end, w_sh, w_ns;
-  bool emp;  // age_begin <= sample age: the F path (coal.cpp:2245-2275), not-shared weight only, no redraws
-};
 struct Block {
   std::vector<double> t;  // sh | ns | sh_emp | ns_emp, A values each (emp = row 0 of the reference's A*A tables)
   explicit Block(int A) : t((size_t)4 * A, 0.0) {}
@@ -903,17 +845,14 @@ struct PairFill {
   Cursor tgt, ref;
   size_t chr = 0, row = 0;
   bool chr_open = false;
-  int32_t last_searched = -1, last_ref_pass = -1;  // a masked pair's indexed walk: positions of the latest searches of this chromosome
+  int64_t last_searched = -1, last_ref_pass = -1;  // the indexed walk: rows of the two cursors' latest searches in this chromosome (-1: none)
   int current_block_base = 0;
   size_t blk = 0;
   int num_blocks = 0;
   uint64_t off = 0;  // uniforms taken so far
-  std::vector<UsedSnp> pending;
-  uint64_t pending_off = 0;
-  // sampling on the device: the records of the block being walked (handed over when the block is complete) and this pair's tables there
-  std::vector<FillRec> dev_cur;
-  uint64_t dev_cur_off = 0;
-  size_t slot = 0;
+  std::vector<FillRec> recs;  // the used SNPs of the current block not yet handed to the sampling, and the stream offset of the first
+  uint64_t recs_off = 0;
+  size_t slot = 0;  // position in the list of pairs being filled (its tables on the device: DeviceSampler)
   bool walked = false;
   double inline_sample_s = 0;  // seconds this pair's walker spent sampling itself (pool full)
   // results
@@ -923,19 +862,238 @@ struct PairFill {
   size_t used_snps = 0;
 };
 
-// (pair, block) jobs whose block is complete, waiting for the next hand-over to the device (fill_pairs, at the end of a window)
-struct DevQueue {
+using Fills = std::vector<std::unique_ptr<PairFill>>;
+
+// ------------------------------------------------------------------ the age sampling on the device (fill_device.h)
+// Everything the fill does with the GPU: the choice of device, the set-up, a job per (pair, block) as the walkers complete blocks,
+// the uniform stream uploaded window by window, the hand-overs, and the tables read back.  Any failure sends the pairs to the host.
+class DeviceSampler {
+ public:
   static constexpr uint32_t kMaxBlocks = 512;  // tables per pair on the device (a pair with more goes back to the host)
-  std::mutex m;
-  struct Item {
+
+  // Meant for the device: COLATE_DEVICE_FILL is not 0, the age-bin table passed its self-check and there is a HIP device (else
+  // the timing line says which not).  The device: --device, plus the rank under --ranks.  A batch: COLATE_DEVICE_FILL_BATCH records (24 bytes each,
+  // two pinned buffers; 64 M by default) -- or all there can be: a pair uses a row at most once, and a row of a .mut file is more
+  // than four bytes even compressed.
+  DeviceSampler(const Options& opt, const std::vector<std::string>& mut_files, size_t npairs, const FastBin& fastbin,
+                SharedUniforms& stream, Pool& pool)
+      : fastbin_(fastbin), stream_(stream), pool_(pool) {
+    const char* e = std::getenv("COLATE_DEVICE_FILL");
+    if (e && std::atoi(e) == 0) {
+      note_ = "COLATE_DEVICE_FILL=0";
+      return;
+    }
+    if (!fastbin.ok()) {
+      note_ = "no age-bin table";
+      return;
+    }
+    colate::mark_device_touched();  // (the HIP runtime comes up here: no --ranks fork from this process afterwards)
+    if (!DeviceFill::available()) {
+      note_ = "no HIP device";
+      return;
+    }
+    try {
+      if (opt.has("device")) device_ = std::stoi(opt.get("device"));
+    } catch (...) {
+      device_ = 0;
+    }
+    if (g_rank.ranked) device_ += g_rank.rank;
+    uint64_t rows_bound = 0;
+    for (const std::string& f : mut_files) {
+      struct stat st;
+      if (::stat(f.c_str(), &st) == 0) rows_bound += (uint64_t)st.st_size / 4 + 1;
+      else if (::stat((f + ".gz").c_str(), &st) == 0) rows_bound += (uint64_t)st.st_size / 4 + 1;
+    }
+    batch_ = (size_t)64 << 20;
+    if (const char* b = std::getenv("COLATE_DEVICE_FILL_BATCH")) batch_ = (size_t)std::max(1024, std::atoi(b));
+    batch_ = std::min<uint64_t>(batch_, std::max<uint64_t>(1024, rows_bound * npairs));
+  }
+  ~DeviceSampler() {
+    if (staging_.joinable()) staging_.join();
+  }
+
+  // The set-up, once the inputs are read (n_kept rows: a pair uses at most every one; W chunks of uniforms per window).  false: the
+  // sampling runs on the host.
+  bool start(int A, size_t npairs, uint64_t n_kept, uint64_t W) {
+    if (!note_.empty()) return false;
+    const double t0 = now_s();
+    A_ = A, W_ = W;
+    const uint64_t max_uniforms = (n_kept * 100 / SharedUniforms::kChunk + W + 3) * SharedUniforms::kChunk;
+    dev_.reset(DeviceFill::create(device_, A, fastbin_.guard_lo(), fastbin_.guard_hi(), npairs * kMaxBlocks,
+                                  std::min<uint64_t>(batch_, std::max<uint64_t>(1024, n_kept * npairs)), note_));
+    if (!dev_ || !dev_->alloc_uniforms(max_uniforms)) {
+      std::cerr << "Note: age sampling on the GPU could not be set up (" << (dev_ ? dev_->error() : note_) << "); sampling on the host." << std::endl;
+      if (dev_) note_ = dev_->error();
+      dev_.reset();
+      return false;
+    }
+    stream_.for_each_buffer([&](double* p, size_t bytes) { dev_->pin(p, bytes); });
+    make_s_ = now_s() - t0;
+    // (the record buffers -- gigabytes to page-lock -- beside the first windows: the first hand-over waits for them)
+    staging_ = std::thread([this] {
+      const double t1 = now_s();
+      staging_ok_ = dev_->alloc_staging();
+      staging_s_ = now_s() - t1;
+    });
+    return true;
+  }
+
+  // A walker has completed the pair's block: its records become a job of the next hand-over.  From block kMaxBlocks on -- with used
+  // SNPs or without (every --chr entry closes a block) -- the pair is filled on the host, or the read-back would take a table that is
+  // not this pair's.
+  void complete_block(PairFill& pf) {
+    const size_t had = pf.recs.size();
+    if (pf.blk >= kMaxBlocks || had > 0xffffffffull) {
+      pf.redo.store(true);
+    } else if (had > 0) {
+      Item it{FillJob{0, pf.recs_off, (uint32_t)had, (uint32_t)(pf.slot * kMaxBlocks + pf.blk)}, std::move(pf.recs)};
+      std::lock_guard<std::mutex> lk(m_);
+      backlog_.push_back(std::move(it));
+      backlog_recs_ += had;
+      pf.recs = std::vector<FillRec>();
+      if (!spare_.empty()) {
+        pf.recs = std::move(spare_.back());
+        spare_.pop_back();
+      }
+    }
+    pf.recs.clear();
+    if (pf.recs.capacity() == 0) pf.recs.reserve(had + had / 8);  // (the next block is about as long: no doubling copies on the way)
+  }
+
+  // The walks of window w are done.  The uniforms its jobs read (a pair's last SNP of the window may reach 100 into the next chunk)
+  // are uploaded, the copies running beside the next window's walks; the ring's chunks are handed back to the producer one window
+  // late, when the copies out of them have completed.  Then the blocks completed so far go to the device, as far as they make a batch.
+  void end_window(uint64_t w, const Fills& fills) {
+    if (!failed_) {
+      const double t0 = now_s();
+      if (!dev_->sync_uploads()) failed_ = true;
+      stream_.release_before(next_chunk_ > 0 ? next_chunk_ - 1 : 0);  // (the overlap chunk is uploaded twice: kept)
+      while (next_chunk_ <= (w + 1) * W_) {  // (runs of chunks that are consecutive in the ring's memory: one copy each)
+        const uint64_t first = next_chunk_;
+        uint64_t n = 0;
+        const double* p0 = stream_.chunk(first);
+        while (first + n <= (w + 1) * W_ && (first + n) % stream_.ring_chunks() == first % stream_.ring_chunks() + n) {
+          (void)stream_.chunk(first + n);  // (waits until it has been generated)
+          n++;
+        }
+        if (!dev_->upload_uniforms(first * SharedUniforms::kChunk, p0, n * SharedUniforms::kChunk)) failed_ = true;
+        next_chunk_ += n;
+      }
+      upload_s_ += now_s() - t0;
+      hand_over(false, fills);
+    }
+    if (failed_)  // (the device is out: every pair goes through the host's sequential feeder; no walk waits for the stream)
+      for (auto& pf : fills) pf->redo.store(true);
+  }
+
+  // The tables of every (pair, block) back from the device; a pair with a flagged block is filled again on the host.
+  void finish(const Fills& fills) {
+    const double t0 = now_s();
+    hand_over(true, fills);
+    std::vector<double> tab;
+    std::vector<int> flags;
+    if (failed_ || !dev_->finish(tab, flags)) {
+      std::cerr << "Note: age sampling on the GPU failed (" << dev_->error() << "); filling the pairs on the host." << std::endl;
+      for (auto& pf : fills) pf->redo.store(true);
+    } else {
+      for (auto& pfp : fills) {
+        PairFill& pf = *pfp;
+        if (pf.redo.load()) continue;
+        if (pf.num_blocks > (int)kMaxBlocks) {  // (complete_block has marked it already: its tables do not fit its slot)
+          pf.redo.store(true);
+          continue;
+        }
+        for (int j = 0; j < pf.num_blocks && !pf.redo.load(); j++) {
+          const size_t t = pf.slot * kMaxBlocks + (size_t)j;
+          if (flags[t]) pf.redo.store(true);
+          else std::copy(tab.begin() + t * 2 * A_, tab.begin() + (t + 1) * 2 * A_, pf.blocks[(size_t)j]->t.begin());
+        }
+      }
+    }
+    finish_s_ = now_s() - t0;
+  }
+
+  // the end of the timing line
+  std::string timing() const {
+    if (!dev_) return "; age sampling on the host (" + note_ + ")";
+    return "; age sampling on the GPU: " + std::to_string(jobs_) + " (pair, block) jobs, " + std::to_string(recs_) + " SNPs in " +
+           std::to_string(launches_) + " launches, " + std::to_string(dev_->gpu_seconds()) + " s of copies and kernels, " +
+           std::to_string(upload_s_) + " s uploading the uniform stream, " + std::to_string(make_s_) + " s setting up, " +
+           std::to_string(staging_s_) + " s page-locking the record buffers beside the first windows, " + std::to_string(finish_s_) +
+           " s for the last launch and the tables";
+  }
+
+ private:
+  struct Item {  // a (pair, block) job whose block is complete, and its records
     FillJob job;
     std::vector<FillRec> recs;
   };
-  std::vector<Item> ready;
+  // Hand-over to the device.  A job is a chain of dependent additions, SNP after SNP, on one wave: what makes the GPU fast is the
+  // number of chains in flight.  A window completes ~2 blocks per pair -- 180 jobs for 1024 SIMDs, 145 ms per launch however few
+  // they are --, so the completed blocks are kept until half a staging buffer of records has come together (some 2000 jobs at
+  // BASELINE configs[4]) and go in one launch: their records side by side into the pinned buffer (the pool copies).  (Between two
+  // windows: no walker runs.)
+  void hand_over(bool all, const Fills& fills) {
+    while (!failed_ && !backlog_.empty() && (all || backlog_recs_ >= dev_->staging_capacity() / 2)) {
+      if (staging_.joinable()) {
+        staging_.join();
+        if (!staging_ok_) {
+          failed_ = true;
+          break;
+        }
+      }
+      std::vector<FillJob> jobs;
+      size_t nrecs = 0, taken = 0;
+      for (; taken < backlog_.size() && jobs.size() < 60000; taken++) {
+        Item& it = backlog_[taken];
+        if (it.recs.size() > dev_->staging_capacity()) {  // (a block larger than a batch: the host takes the pair)
+          fills[it.job.table / kMaxBlocks]->redo.store(true);
+          backlog_recs_ -= it.recs.size();
+          it.recs.clear();
+          continue;
+        }
+        if (nrecs + it.recs.size() > dev_->staging_capacity()) break;
+        it.job.rec_off = nrecs;
+        nrecs += it.recs.size();
+        if (!it.recs.empty()) jobs.push_back(it.job);
+      }
+      FillRec* const dst = dev_->staging();
+      for (size_t i = 0; i < taken; i++)
+        if (!backlog_[i].recs.empty()) {
+          Item* itp = &backlog_[i];
+          pool_.submit([dst, itp] { std::memcpy(dst + itp->job.rec_off, itp->recs.data(), itp->recs.size() * sizeof(FillRec)); });
+        }
+      pool_.wait_idle();
+      jobs_ += jobs.size(), recs_ += nrecs, launches_ += jobs.empty() ? 0 : 1;
+      if (!dev_->submit(jobs, nrecs)) failed_ = true;
+      backlog_recs_ -= nrecs;
+      for (size_t i = 0; i < taken; i++)
+        if (backlog_[i].recs.capacity() > 0) {
+          backlog_[i].recs.clear();
+          spare_.push_back(std::move(backlog_[i].recs));
+        }
+      backlog_.erase(backlog_.begin(), backlog_.begin() + (long)taken);
+    }
+  }
+
+  const FastBin& fastbin_;
+  SharedUniforms& stream_;
+  Pool& pool_;
+  std::string note_;  // why the sampling runs on the host (empty: it is meant for the device)
+  int device_ = 0, A_ = 0;
+  size_t batch_ = 0;
+  uint64_t W_ = 0, next_chunk_ = 0;
+  std::unique_ptr<DeviceFill> dev_;
+  std::thread staging_;
+  bool staging_ok_ = false, failed_ = false;
+  std::mutex m_;                // (the walkers': backlog_ and spare_)
+  std::vector<Item> backlog_;  // completed blocks not handed over yet
   // record vectors whose job has been handed over, for the next blocks: a fresh vector per block is a fresh mapping of a megabyte --
   // 13 GB of page faults over BASELINE configs[4], whose price (0.3 .. 2 us each, 16 threads on one address space) was the
   // difference between walks of 28 and of 68 thread-seconds from one run to the next
-  std::vector<std::vector<FillRec>> spare;
+  std::vector<std::vector<FillRec>> spare_;
+  size_t backlog_recs_ = 0, jobs_ = 0, recs_ = 0, launches_ = 0;
+  double make_s_ = 0, staging_s_ = 0, upload_s_ = 0, finish_s_ = 0;
 };
 
 struct Engine {
@@ -949,11 +1107,10 @@ struct Engine {
   Pool& pool;
   BinSnpFn bin_snp = nullptr;  // the vector form of the 100 bins of a SNP where the CPU has one (and the table passed its self-check)
   AddSnpFn add_snp = nullptr;  // ... and of the additions
-  DevQueue* devq = nullptr;    // not null: the sampling runs on the device (fill_device.h)
-  bool use_index = true;       // walk through the per-file indices where both files of a pair have one (build_walk_index)
+  DeviceSampler* dev = nullptr;  // not null: the sampling runs on the device
 
   // the 100 draws of every SNP of one genome-block segment, in order (coal.cpp:2260-2273, 2279-2295)
-  void sample(PairFill& pf, Block& b, const std::vector<UsedSnp>& snps, uint64_t off) const {
+  void sample(PairFill& pf, Block& b, const std::vector<FillRec>& snps, uint64_t off) const {
     struct Timer {
       double t0 = now_s();
       ~Timer() { WorkSeconds::add(g_work.sample, now_s() - t0); }
@@ -964,15 +1121,16 @@ struct Engine {
     double tmp[104];
     const double* const g_lo = fastbin.guard_lo();
     const double* const g_hi = fastbin.guard_hi();
-    for (const UsedSnp& s : snps) {
+    for (const FillRec& s : snps) {
       if (pf.redo.load(std::memory_order_relaxed)) return;
       const double* u = stream.get100(off, tmp);
       const bool last_of_chunk = (off % SharedUniforms::kChunk) + 104 > SharedUniforms::kChunk;  // (the vector code reads 104 values)
       off += 100;
-      const double span = s.age_end - s.age_begin;
-      if (bin_snp && !s.emp) {
+      const bool emp = s.begin <= 0;  // the F path (coal.cpp:2245-2275): not-shared weight only, no redraws
+      const double begin = s.begin, span = (double)s.end - begin;
+      if (bin_snp && !emp) {
         // the bins the samples can fall into: from that of age_begin to that of the largest possible sample (u < 1)
-        const int b_lo = fastbin(s.age_begin), b_hi = fastbin(std::nextafter(span + s.age_begin, std::numeric_limits<double>::infinity()));
+        const int b_lo = fastbin(begin), b_hi = fastbin(std::nextafter(span + begin, std::numeric_limits<double>::infinity()));
         const int K = b_hi + 1 - b_lo;
         if (b_lo >= 1 && K >= 1 && K <= 16 && b_hi + 1 < A) {
           if (last_of_chunk && u != tmp) {  // (never read past the chunk: copy the hundred, pad)
@@ -981,7 +1139,7 @@ struct Engine {
           }
           if (u == tmp) tmp[100] = tmp[101] = tmp[102] = tmp[103] = 0.0;
           int bins[104];
-          if (bin_snp(u, span, s.age_begin, g_lo, g_hi, b_lo, K, bins)) {
+          if (bin_snp(u, span, begin, g_lo, g_hi, b_lo, K, bins)) {
             // per bin: as many additions of the SNP's weight as samples fell into it, one after the other -- the same sums as the
             // sample-by-sample loop below (additions to different bins commute; those to one bin are all of the same addend)
             int cnt[18] = {0};
@@ -1002,16 +1160,16 @@ struct Engine {
           }
         }
       }
-      if (s.emp) {
+      if (emp) {
         for (int k = 0; k < 100; k++) {
-          double sampled_age = u[k] * span + s.age_begin;
+          double sampled_age = u[k] * span + begin;
           if (sampled_age < age) sampled_age = age;
           const int bin = fastbin(sampled_age);
           if (bin < A) ns[bin] += s.w_ns;
         }
       } else {
         for (int k = 0; k < 100; k++) {
-          const double sampled_age = u[k] * span + s.age_begin;
+          const double sampled_age = u[k] * span + begin;
           const int bin = fastbin(sampled_age);
           if (sampled_age < age || bin >= A) {  // the reference would draw again: the stream no longer lines up
             pf.redo.store(true);
@@ -1024,13 +1182,14 @@ struct Engine {
     }
   }
 
-  void flush(PairFill& pf) const {  // hand the current block's pending SNPs to the pool (or run them here when it is full)
-    if (devq) return;  // (on the device a block is one job: its records wait in dev_cur until advance_block)
-    if (pf.pending.empty()) return;
-    auto snps = std::make_shared<std::vector<UsedSnp>>(std::move(pf.pending));
-    pf.pending = std::vector<UsedSnp>();
+  // The end of a window or of a block: on the host the records so far go to the pool (or are sampled here when it is full); on the
+  // device a block's records wait for the end of the block (DeviceSampler::complete_block).
+  void flush(PairFill& pf) const {
+    if (dev || pf.recs.empty()) return;
+    auto snps = std::make_shared<std::vector<FillRec>>(std::move(pf.recs));
+    pf.recs = std::vector<FillRec>();
     Block* b = pf.blocks[pf.blk].get();
-    const uint64_t off = pf.pending_off;
+    const uint64_t off = pf.recs_off;
     PairFill* p = &pf;
     if (pool.queued() > (size_t)(4 * pool.size() + 8)) {
       const double t0 = now_s();
@@ -1040,29 +1199,8 @@ struct Engine {
       pool.submit([this, p, b, snps, off] { sample(*p, *b, *snps, off); });
   }
   void advance_block(PairFill& pf) const {
-    flush(pf);
-    // the device holds kMaxBlocks tables per pair: from block kMaxBlocks on -- with used SNPs or without (every --chr entry closes
-    // a block) -- the pair is filled on the host, or the read-back would take a table that is not this pair's
-    if (devq && pf.blk >= DevQueue::kMaxBlocks) pf.redo.store(true);
-    if (devq && !pf.dev_cur.empty()) {
-      const size_t had = pf.dev_cur.size();
-      if (pf.blk >= DevQueue::kMaxBlocks || pf.dev_cur.size() > 0xffffffffull) {
-        pf.redo.store(true);
-      } else {
-        DevQueue::Item it;
-        it.job = FillJob{0, pf.dev_cur_off, (uint32_t)pf.dev_cur.size(), (uint32_t)(pf.slot * DevQueue::kMaxBlocks + pf.blk)};
-        it.recs = std::move(pf.dev_cur);
-        std::lock_guard<std::mutex> lk(devq->m);
-        devq->ready.push_back(std::move(it));
-        pf.dev_cur = std::vector<FillRec>();
-        if (!devq->spare.empty()) {
-          pf.dev_cur = std::move(devq->spare.back());
-          devq->spare.pop_back();
-        }
-      }
-      pf.dev_cur.clear();
-      if (pf.dev_cur.capacity() == 0) pf.dev_cur.reserve(had + had / 8);  // (the next block is about as long: no doubling copies on the way)
-    }
+    if (dev) dev->complete_block(pf);
+    else flush(pf);
     pf.blk++;
     pf.num_blocks++;
     if (pf.blk >= pf.blocks.size()) pf.blocks.emplace_back(new Block(A));
@@ -1086,8 +1224,8 @@ struct Engine {
     f_AAF_target /= N_target / 2.0;
     f_DAF_target = std::round(f_DAF_target);
     f_AAF_target = std::round(f_AAF_target);
-    if (pf.pending.empty()) pf.pending_off = pf.off;
-    if (devq && pf.dev_cur.empty()) pf.dev_cur_off = pf.off;
+    if (pf.recs.empty()) pf.recs_off = pf.off;
+    double w_sh = 0.0;
     if (age_begin <= age) {  // coal.cpp:2245-2275
       const int bin2 = age_bin_index(m.age_end, C);
       if (bin2 < A) {  // row 0 of the A*A table; larger indices land in rows nobody reads
@@ -1095,14 +1233,11 @@ struct Engine {
         t[2 * A + bin2] += f_DAF_target * DAF_ref / ((double)N_ref);
         t[3 * A + bin2] += f_AAF_target * DAF_ref / ((double)N_ref);
       }
-      const double w_ns = f_AAF_target * DAF_ref / ((double)N_ref * num_samples);
-      if (devq) pf.dev_cur.push_back(FillRec{(float)age_begin, m.age_end, 0.0, w_ns});  // (age_begin: a float, or the sample age 0)
-      else pf.pending.push_back(UsedSnp{age_begin, (double)m.age_end, 0.0, w_ns, true});
     } else {  // coal.cpp:2277-2297
-      const double w_sh = f_DAF_target * DAF_ref / ((double)N_ref * num_samples), w_ns = f_AAF_target * DAF_ref / ((double)N_ref * num_samples);
-      if (devq) pf.dev_cur.push_back(FillRec{(float)age_begin, m.age_end, w_sh, w_ns});
-      else pf.pending.push_back(UsedSnp{age_begin, (double)m.age_end, w_sh, w_ns, false});
+      w_sh = f_DAF_target * DAF_ref / ((double)N_ref * num_samples);
     }
+    const double w_ns = f_AAF_target * DAF_ref / ((double)N_ref * num_samples);
+    pf.recs.push_back(FillRec{(float)age_begin, m.age_end, w_sh, w_ns});  // (age_begin: a float, or the sample age 0)
     pf.off += 100;
     pf.used_snps++;
   }
@@ -1115,104 +1250,29 @@ struct Engine {
     WorkSeconds::add(g_work.walk, now_s() - t_walk0 - (pf.inline_sample_s - sample0));
   }
   void walk_impl(PairFill& pf, uint64_t limit) const {
-    Cursor& tgt = pf.tgt;
-    Cursor& ref = pf.ref;
     if (pf.blocks.empty()) pf.blocks.emplace_back(new Block(A));
-    const bool indexed = pf.indexed;
     while (pf.chr < rows.size()) {
       if (pf.redo.load(std::memory_order_relaxed)) break;
       if (!pf.chr_open) {
         pf.current_block_base = 0;
         pf.last_searched = pf.last_ref_pass = -1;
-        if (!indexed) {
-          ref.set_name(chr_names[pf.chr].c_str());
-          tgt.set_name(chr_names[pf.chr].c_str());
-          while (!ref.match) {  // skip to this chromosome, coal.cpp:2125-2134
-            if (!ref.next()) break;
+        if (!pf.indexed) {
+          pf.ref.set_name(chr_names[pf.chr].c_str());
+          pf.tgt.set_name(chr_names[pf.chr].c_str());
+          while (!pf.ref.match) {  // skip to this chromosome, coal.cpp:2125-2134
+            if (!pf.ref.next()) break;
           }
-          while (!tgt.match) {
-            if (!tgt.next()) break;
+          while (!pf.tgt.match) {
+            if (!pf.tgt.next()) break;
           }
         }
         pf.row = 0;
         pf.chr_open = true;
       }
-      const HugeVector<CompactRow>& rr = rows[pf.chr];
-      if (indexed && pf.masked()) {  // the same from the lower bounds of both files and the pair's own searches (WalkRows)
-        const TmpFile::TgtIdx* const RL = pf.ref_file->tgt_idx[pf.chr].data();
-        const TmpFile::TgtIdx* const TI = pf.tgt_file->tgt_idx[pf.chr].data();
-        for (; pf.row < rr.size(); pf.row++) {
-          if (pf.off >= limit) {
-            flush(pf);
-            return;
-          }
-          if (!pf.passes(pf.chr, pf.row)) continue;  // (neither cursor is touched for it)
-          const int32_t pos = rr[pf.row].pos;
-          const TmpFile::TgtIdx r = RL[pf.row];
-          const int32_t ref_from = pf.last_searched;
-          pf.last_searched = pos;
-          if (r.DAF == 0 || r.prev_bp < ref_from) continue;  // no record of these alleles carrying the derived one -- or the cursor did not move
-          const TmpFile::TgtIdx t = TI[pf.row];
-          const int32_t tgt_from = pf.last_ref_pass;
-          pf.last_ref_pass = pos;
-          if ((t.DAF | t.AAF) == 0 || t.prev_bp < tgt_from) continue;
-          use_snp(pf, rr[pf.row], t.DAF, t.AAF, r.DAF, (int)r.DAF + (int)r.AAF);
-        }
-        advance_block(pf);
-        pf.chr++;
-        pf.chr_open = false;
-        continue;
-      }
-      if (indexed) {  // what the two cursors would find, from the two files' indices (build_walk_index)
-        const TmpFile::RefIdx* const RI = pf.ref_file->ref_idx[pf.chr].data();
-        const TmpFile::TgtIdx* const TI = pf.tgt_file->tgt_idx[pf.chr].data();
-        for (; pf.row < rr.size(); pf.row++) {
-          if (pf.off >= limit) {
-            flush(pf);
-            return;
-          }
-          const TmpFile::RefIdx r = RI[pf.row];
-          if (r.N == 0) continue;  // the reference sample does not carry the derived allele here (or its record was read too early)
-          const TmpFile::TgtIdx t = TI[pf.row];
-          if ((t.DAF | t.AAF) == 0 || r.prev_pass > t.prev_bp) continue;  // no target record here -- or one that an earlier search had reached
-          use_snp(pf, rr[pf.row], t.DAF, t.AAF, r.DAF, r.N);
-        }
-        advance_block(pf);
-        pf.chr++;
-        pf.chr_open = false;
-        continue;
-      }
-      for (; pf.row < rr.size(); pf.row++) {
-        if (pf.off >= limit) {
-          flush(pf);
-          return;
-        }
-        if (pf.masked() && !pf.passes(pf.chr, pf.row)) continue;  // (neither cursor is touched for it)
-        const CompactRow& m = rr[pf.row];
-        const int bp_mut = m.pos;
-        bool use = true;
-        // the reference sample must carry the derived allele, coal.cpp:2181-2199
-        ref.DAF = 0;
-        ref.AAF = 0;
-        while (ref.match && ref.bp < bp_mut) {
-          if (!ref.next()) break;
-        }
-        if (!ref.match || ref.bp != bp_mut || ref.anc != m.anc || ref.der != m.der) use = false;
-        if (ref.DAF == 0) use = false;
-        const int N_ref = ref.DAF + ref.AAF;
-        if (use) {  // coal.cpp:2201-2219
-          tgt.DAF = 0;
-          tgt.AAF = 0;
-          while (tgt.match && tgt.bp < bp_mut) {
-            if (!tgt.next()) break;
-          }
-          if (!tgt.match || tgt.bp != bp_mut || tgt.anc != m.anc || tgt.der != m.der) use = false;
-        }
-        const int N_target = tgt.DAF + tgt.AAF;
-        if (N_target == 0) use = false;
-        if (!use) continue;
-
-        use_snp(pf, m, tgt.DAF, tgt.AAF, ref.DAF, N_ref);
+      const bool done = !pf.indexed ? walk_cursors(pf, limit) : pf.masked() ? walk_indexed<true>(pf, limit) : walk_indexed<false>(pf, limit);
+      if (!done) {
+        flush(pf);
+        return;
       }
       advance_block(pf);  // chromosome end, coal.cpp:2306-2310
       pf.chr++;
@@ -1223,7 +1283,210 @@ struct Engine {
     pf.blocks.resize((size_t)pf.num_blocks);
     if (!stream.state_at(pf.off, pf.rng_end)) pf.redo.store(true);
   }
+
+  // The rows of the pair's chromosome from pf.row on, through the two files' indices (WalkRows); false: stopped at `limit`.  The
+  // mask test is compiled in only for the pairs that have masks.
+  template <bool Masked>
+  bool walk_indexed(PairFill& pf, uint64_t limit) const {
+    const HugeVector<CompactRow>& rr = rows[pf.chr];
+    const TmpFile::RowIdx* const RI = pf.ref_file->idx[pf.chr].data();
+    const TmpFile::RowIdx* const TI = pf.tgt_file->idx[pf.chr].data();
+    auto pos = [&rr](int64_t i) { return i < 0 ? -1 : rr[(size_t)i].pos; };
+    int64_t searched = pf.last_searched, ref_pass = pf.last_ref_pass;
+    size_t i = pf.row;
+    for (; i < rr.size() && pf.off < limit; i++) {
+      if (Masked && !pf.passes(pf.chr, i)) continue;  // (neither cursor is touched for it)
+      const TmpFile::RowIdx r = RI[i];
+      const int64_t ref_from = searched;
+      searched = (int64_t)i;
+      if (r.DAF == 0 || r.prev_bp < pos(ref_from)) continue;  // no record of these alleles carrying the derived one -- or the cursor did not move
+      const TmpFile::RowIdx t = TI[i];
+      const int64_t tgt_from = ref_pass;
+      ref_pass = (int64_t)i;
+      if ((t.DAF | t.AAF) == 0 || t.prev_bp < pos(tgt_from)) continue;
+      use_snp(pf, rr[i], t.DAF, t.AAF, r.DAF, (int)r.DAF + (int)r.AAF);
+    }
+    pf.row = i, pf.last_searched = searched, pf.last_ref_pass = ref_pass;
+    return i == rr.size();
+  }
+
+  // the same through the two cursors of coal.cpp:2125-2243
+  bool walk_cursors(PairFill& pf, uint64_t limit) const {
+    const HugeVector<CompactRow>& rr = rows[pf.chr];
+    Cursor& tgt = pf.tgt;
+    Cursor& ref = pf.ref;
+    for (; pf.row < rr.size(); pf.row++) {
+      if (pf.off >= limit) return false;
+      if (pf.masked() && !pf.passes(pf.chr, pf.row)) continue;  // (neither cursor is touched for it)
+      const CompactRow& m = rr[pf.row];
+      const int bp_mut = m.pos;
+      bool use = true;
+      // the reference sample must carry the derived allele, coal.cpp:2181-2199
+      ref.DAF = 0;
+      ref.AAF = 0;
+      while (ref.match && ref.bp < bp_mut) {
+        if (!ref.next()) break;
+      }
+      if (!ref.match || ref.bp != bp_mut || ref.anc != m.anc || ref.der != m.der) use = false;
+      if (ref.DAF == 0) use = false;
+      const int N_ref = ref.DAF + ref.AAF;
+      if (use) {  // coal.cpp:2201-2219
+        tgt.DAF = 0;
+        tgt.AAF = 0;
+        while (tgt.match && tgt.bp < bp_mut) {
+          if (!tgt.next()) break;
+        }
+        if (!tgt.match || tgt.bp != bp_mut || tgt.anc != m.anc || tgt.der != m.der) use = false;
+      }
+      const int N_target = tgt.DAF + tgt.AAF;
+      if (N_target == 0) use = false;
+      if (!use) continue;
+
+      use_snp(pf, m, tgt.DAF, tgt.AAF, ref.DAF, N_ref);
+    }
+    return true;
+  }
 };
+
+// ------------------------------------------------------------------ every input file once
+struct Inputs {
+  std::vector<HugeVector<CompactRow>> rows;  // [chromosome]: the .mut rows a walk looks at
+  size_t n_rows = 0, n_kept = 0;             // rows read, rows kept
+  std::map<std::string, std::unique_ptr<TmpFile>> tmp_files;
+  size_t tmp_bytes = 0;
+  std::map<std::vector<std::string>, std::unique_ptr<MaskBits>> masks;  // (key: the mask's file per chromosome)
+  size_t mask_reads = 0;
+  size_t n_indexed = 0;  // files with a walk index
+};
+
+// The .mut files (all chromosomes in parallel), every .colate.in file of the pairs, every distinct mask -- one task per (mask,
+// chromosome) with one FASTA string alive in it (coal.cpp:2169-2174) -- and, unless use_index is false, every file's walk index.
+Inputs load_inputs(Pool& pool, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                   const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, bool use_index) {
+  Inputs in;
+  in.rows.resize(mut_files.size());
+  std::vector<size_t> rows_total(mut_files.size(), 0);
+  for (size_t c = 0; c < mut_files.size(); c++)
+    pool.submit([&, c] {
+      const double t0 = now_s();
+      HugeVector<CompactRow>& r = in.rows[c];
+      size_t n = 0;
+      CompactRow cr;
+      for_each_mut_row(mut_files[c], [&](const MutRow& m) {
+        n++;
+        if (compact_row(m, cr)) r.push_back(cr);
+      });
+      rows_total[c] = n;
+      WorkSeconds::add(g_work.parse_mut, now_s() - t0);
+    });
+  for (size_t p : todo)
+    for (const std::string* path : {&pairs[p].target, &pairs[p].reference})
+      if (!in.tmp_files.count(*path)) {
+        TmpFile* f = new TmpFile;
+        f->path = *path;
+        in.tmp_files[*path].reset(f);
+        pool.submit([f] {
+          const double t0 = now_s();
+          if (load_tmp_file(*f)) {
+            decode_tmp_file(*f);
+            if (f->decoded && f->data && f->size) {  // (the bytes are no longer needed)
+              ::munmap(const_cast<char*>(f->data), f->size);
+              f->data = nullptr;
+            }
+          }
+          WorkSeconds::add(g_work.load_tmp, now_s() - t0);
+        });
+      }
+  pool.wait_idle();
+  for (size_t c = 0; c < in.rows.size(); c++) in.n_rows += rows_total[c], in.n_kept += in.rows[c].size();
+  for (auto& kv : in.tmp_files) {
+    in.tmp_bytes += kv.second->size;
+    if (!kv.second->ok) std::cerr << "Failed to open " << kv.first << std::endl;  // (the reference goes on and reads nothing)
+  }
+  // a missing mask ends the run here, on this thread, in the order the sequential feeder opens them (chromosome by chromosome,
+  // pair by pair, target before reference): the first missing one is named, whatever the pool's timing
+  std::set<std::string> checked;
+  for (size_t c = 0; c < in.rows.size(); c++)
+    for (size_t p : todo)
+      for (const std::vector<std::string>* files : {&pairs[p].target_masks, &pairs[p].ref_masks})
+        if (c < files->size() && checked.insert((*files)[c]).second) check_fasta_mask((*files)[c]);
+  std::atomic<size_t> mask_reads{0};
+  for (size_t p : todo)
+    for (const std::vector<std::string>* files : {&pairs[p].target_masks, &pairs[p].ref_masks}) {
+      if (files->empty() || in.masks.count(*files)) continue;
+      std::unique_ptr<MaskBits>& m = in.masks[*files];
+      m.reset(new MaskBits);
+      m->pass.resize(in.rows.size());
+      for (size_t c = 0; c < in.rows.size(); c++) {
+        MaskBits* mb = m.get();
+        const std::string* path = c < files->size() ? &(*files)[c] : nullptr;  // (none: every row passes)
+        pool.submit([&in, &mask_reads, mb, path, c] {
+          const double t0 = now_s();
+          const HugeVector<CompactRow>& rr = in.rows[c];
+          std::vector<uint64_t>& bits = mb->pass[c];
+          bits.assign((rr.size() + 63) / 64, 0);
+          std::string seq;
+          if (path) {
+            read_fasta_mask(*path, seq);  // (a missing file: the reference's message, exit 1)
+            mask_reads++;
+          }
+          for (size_t i = 0; i < rr.size(); i++) {
+            const int bp = rr[i].pos;
+            const bool removed = bp >= 1 && (size_t)bp < seq.size() && seq[(size_t)bp - 1] != 'P';
+            if (!removed) bits[i >> 6] |= uint64_t(1) << (i & 63);
+          }
+          WorkSeconds::add(g_work.mask, now_s() - t0);
+        });
+      }
+    }
+  if (use_index) {
+    WalkRows wr{&names, &in.rows, true};
+    for (const HugeVector<CompactRow>& r : in.rows)
+      for (size_t i = 1; i < r.size() && wr.rows_ascend; i++) wr.rows_ascend = r[i].pos >= r[i - 1].pos && r[i - 1].pos >= 0;
+    for (auto& kv : in.tmp_files) {
+      TmpFile* f = kv.second.get();
+      if (f->ok) pool.submit([f, wr] {
+        const double t0 = now_s();
+        build_walk_index(*f, wr);
+        WorkSeconds::add(g_work.index, now_s() - t0);
+      });
+    }
+  }
+  pool.wait_idle();
+  in.mask_reads = mask_reads.load();
+  for (auto& kv : in.tmp_files) in.n_indexed += kv.second->indexed ? 1 : 0;
+  return in;
+}
+
+// a PairFill per pair to fill, with its files, masks and cursors
+Fills open_pairs(const Inputs& in, const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo) {
+  Fills fills;
+  for (size_t p : todo) {
+    fills.emplace_back(new PairFill);
+    PairFill& pf = *fills.back();
+    pf.index = p;
+    pf.slot = fills.size() - 1;
+    pf.tgt_file = in.tmp_files.at(pairs[p].target).get(), pf.ref_file = in.tmp_files.at(pairs[p].reference).get();
+    pf.tgt.open(*pf.tgt_file), pf.ref.open(*pf.ref_file);
+    if (!pairs[p].target_masks.empty()) pf.tmask = in.masks.at(pairs[p].target_masks).get();
+    if (!pairs[p].ref_masks.empty()) pf.rmask = in.masks.at(pairs[p].ref_masks).get();
+    pf.indexed = pf.tgt_file->indexed && pf.ref_file->indexed;
+  }
+  return fills;
+}
+
+// the pair's tables as the drivers take them (false: the pair has to be filled again, sequentially)
+bool collect(const PairFill& pf, int A, PairTables& pt) {
+  if (pf.redo.load()) return false;
+  pt.nb = pf.num_blocks;
+  std::vector<double>* const tab[4] = {&pt.sh, &pt.ns, &pt.she, &pt.nse};  // (the order of Block::t)
+  for (int k = 0; k < 4; k++) {
+    tab[k]->resize((size_t)pt.nb * A);
+    for (int j = 0; j < pt.nb; j++) std::copy_n(pf.blocks[(size_t)j]->t.data() + k * A, A, tab[k]->begin() + (size_t)j * A);
+  }
+  pt.rng = pf.rng_end;
+  return true;
+}
 
 }  // namespace
 
@@ -1252,267 +1515,28 @@ bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const
   }
 
   // ---- the shared uniform stream (its producer starts now), the age-bin table, and -- where there is a GPU -- the sampling on the
-  // device (fill_device.h).  The host code is what runs otherwise, and for any pair the device hands back.
+  // device.  The host code is what runs otherwise, and for any pair the device hands back.
   size_t window_mb = 64;
   if (const char* e = std::getenv("COLATE_UNIFORM_WINDOW_MB")) window_mb = (size_t)std::max(4, std::atoi(e));
   const uint64_t W = std::max<uint64_t>(2, window_mb * (1u << 20) / (SharedUniforms::kChunk * sizeof(double)));  // chunks per window
   SharedUniforms stream((unsigned)seed, (size_t)(2 * W + 2));
   FastBin fastbin(A, C);
   if (!fastbin.ok()) std::cerr << "Note: the age-bin table failed its self-check; sampling through log()." << std::endl;
-  std::unique_ptr<DeviceFill> dev;
-  DevQueue devq;
-  std::string dev_note;
-  std::thread dev_maker;
-  bool dev_pending = false, dev_staging_ok = false;
-  int dev_device = 0;
-  size_t dev_batch = 0;
-  double dev_make_s = 0, dev_staging_s = 0;
-  {
-    const char* e = std::getenv("COLATE_DEVICE_FILL");
-    const bool want = !(e && std::atoi(e) == 0);
-    if (!want) dev_note = "COLATE_DEVICE_FILL=0";
-    else if (!fastbin.ok()) dev_note = "no age-bin table";
-    else if (!DeviceFill::available()) dev_note = "no HIP device";
-    else {
-      int device = 0;
-      try {
-        if (opt.has("device")) device = std::stoi(opt.get("device"));
-      } catch (...) {
-        device = 0;
-      }
-      if (g_rank.ranked) device += g_rank.rank;
-      // a batch: COLATE_DEVICE_FILL_BATCH records (24 bytes each, two pinned buffers; 64 M by default) -- or all there can be: a pair
-      // uses a row at most once, and a row of a .mut file is more than four bytes even compressed
-      uint64_t rows_bound = 0;
-      for (const std::string& f : mut_files) {
-        struct stat st;
-        if (::stat(f.c_str(), &st) == 0) rows_bound += (uint64_t)st.st_size / 4 + 1;
-        else if (::stat((f + ".gz").c_str(), &st) == 0) rows_bound += (uint64_t)st.st_size / 4 + 1;
-      }
-      size_t batch = (size_t)64 << 20;
-      if (const char* b = std::getenv("COLATE_DEVICE_FILL_BATCH")) batch = (size_t)std::max(1024, std::atoi(b));
-      batch = std::min<uint64_t>(batch, std::max<uint64_t>(1024, rows_bound * todo.size()));
-      dev_pending = true;
-      dev_device = device, dev_batch = batch;
-    }
-  }
-  struct JoinMaker {
-    std::thread& t;
-    ~JoinMaker() {
-      if (t.joinable()) t.join();
-    }
-  } join_maker{dev_maker};
-
   Pool pool(T);
-  // ---- every input file once
-  std::vector<HugeVector<CompactRow>> rows(mut_files.size());
-  std::vector<size_t> rows_total(mut_files.size(), 0);
-  for (size_t c = 0; c < mut_files.size(); c++)
-    pool.submit([&, c] {
-      const double t0 = now_s();
-      HugeVector<CompactRow>& r = rows[c];
-      size_t n = 0;
-      CompactRow cr;
-      for_each_mut_row(mut_files[c], [&](const MutRow& m) {
-        n++;
-        if (compact_row(m, cr)) r.push_back(cr);
-      });
-      rows_total[c] = n;
-      WorkSeconds::add(g_work.parse_mut, now_s() - t0);
-    });
-  std::map<std::string, std::unique_ptr<TmpFile>> tmp_files;
-  for (size_t p : todo)
-    for (const std::string* path : {&pairs[p].target, &pairs[p].reference})
-      if (!tmp_files.count(*path)) {
-        TmpFile* f = new TmpFile;
-        f->path = *path;
-        tmp_files[*path].reset(f);
-        pool.submit([f] {
-          const double t0 = now_s();
-          if (load_tmp_file(*f)) {
-            decode_tmp_file(*f);
-            if (f->decoded && f->data && f->size) {  // (the bytes are no longer needed)
-              ::munmap(const_cast<char*>(f->data), f->size);
-              f->data = nullptr;
-            }
-          }
-          WorkSeconds::add(g_work.load_tmp, now_s() - t0);
-        });
-      }
-  pool.wait_idle();
-  for (auto& kv : tmp_files)
-    if (!kv.second->ok) std::cerr << "Failed to open " << kv.first << std::endl;  // (the reference goes on and reads nothing)
-  std::vector<std::unique_ptr<PairFill>> fills;
-  for (size_t p : todo) {
-    fills.emplace_back(new PairFill);
-    PairFill& pf = *fills.back();
-    pf.index = p;
-    pf.slot = fills.size() - 1;
-    pf.tgt_file = tmp_files[pairs[p].target].get(), pf.ref_file = tmp_files[pairs[p].reference].get();
-    pf.tgt.open(*pf.tgt_file), pf.ref.open(*pf.ref_file);
-  }
-  // ---- the masks (coal.cpp:2169-2174): every distinct mask once, one task per (mask, chromosome) with one FASTA string alive in it
-  std::map<std::vector<std::string>, std::unique_ptr<MaskBits>> masks;  // (key: the mask's file per chromosome)
-  std::atomic<size_t> mask_reads{0};
-  // a missing file ends the run here, on this thread, in the order the sequential feeder opens them (chromosome by chromosome,
-  // pair by pair, target before reference): the first missing one is named, whatever the pool's timing
-  {
-    std::set<std::string> checked;
-    for (size_t c = 0; c < rows.size(); c++)
-      for (auto& pfp : fills)
-        for (const std::vector<std::string>* files : {&pairs[pfp->index].target_masks, &pairs[pfp->index].ref_masks})
-          if (c < files->size() && checked.insert((*files)[c]).second) check_fasta_mask((*files)[c]);
-  }
-  for (auto& pfp : fills) {
-    const PairSpec& ps = pairs[pfp->index];
-    for (const std::vector<std::string>* files : {&ps.target_masks, &ps.ref_masks}) {
-      if (files->empty()) continue;
-      std::unique_ptr<MaskBits>& m = masks[*files];
-      if (!m) {
-        m.reset(new MaskBits);
-        m->pass.resize(rows.size());
-        for (size_t c = 0; c < rows.size(); c++) {
-          MaskBits* mb = m.get();
-          const std::string* path = c < files->size() ? &(*files)[c] : nullptr;  // (none: every row passes)
-          pool.submit([&rows, &mask_reads, mb, path, c] {
-            const double t0 = now_s();
-            const HugeVector<CompactRow>& rr = rows[c];
-            std::vector<uint64_t>& bits = mb->pass[c];
-            bits.assign((rr.size() + 63) / 64, 0);
-            std::string seq;
-            if (path) {
-              read_fasta_mask(*path, seq);  // (a missing file: the reference's message, exit 1)
-              mask_reads++;
-            }
-            for (size_t i = 0; i < rr.size(); i++) {
-              const int bp = rr[i].pos;
-              const bool removed = bp >= 1 && (size_t)bp < seq.size() && seq[(size_t)bp - 1] != 'P';
-              if (!removed) bits[i >> 6] |= uint64_t(1) << (i & 63);
-            }
-            WorkSeconds::add(g_work.mask, now_s() - t0);
-          });
-        }
-      }
-      (files == &ps.target_masks ? pfp->tmask : pfp->rmask) = m.get();
-    }
-  }
-  // ---- what the walks find in each file, once per file (build_walk_index)
+  DeviceSampler sampler(opt, mut_files, todo.size(), fastbin, stream, pool);
+
+  // ---- every input file once, and the pairs
   const char* e_idx = std::getenv("COLATE_INDEXED_WALK");
-  const bool use_index = !(e_idx && std::atoi(e_idx) == 0);
-  size_t n_indexed = 0;
-  if (use_index) {
-    WalkRows wr{&names, &rows, true};
-    for (const HugeVector<CompactRow>& r : rows)
-      for (size_t i = 1; i < r.size() && wr.rows_ascend; i++) wr.rows_ascend = r[i].pos >= r[i - 1].pos && r[i - 1].pos >= 0;
-    for (auto& pf : fills) {  // (a masked pair reads the lower bounds, TgtIdx, of its reference sample too)
-      TmpFile& t = *tmp_files[pairs[pf->index].target];
-      TmpFile& r = *tmp_files[pairs[pf->index].reference];
-      t.want_tgt = true;
-      (pf->masked() ? r.want_tgt : r.want_ref) = true;
-    }
-    for (auto& kv : tmp_files) {
-      TmpFile* f = kv.second.get();
-      if (f->ok && (f->want_ref || f->want_tgt)) pool.submit([f, wr] {
-        const double t0 = now_s();
-        build_walk_index(*f, wr);
-        WorkSeconds::add(g_work.index, now_s() - t0);
-      });
-    }
-  }
-  pool.wait_idle();  // (the indices and the masks' rows)
-  for (auto& kv : tmp_files) n_indexed += kv.second->indexable ? 1 : 0;
-  size_t n_pairs_indexed = 0, n_masked = 0;
-  for (auto& pf : fills) {
-    pf->indexed = use_index && pf->tgt_file->tgt_ok && (pf->masked() ? pf->ref_file->tgt_ok : pf->ref_file->ref_ok);
-    n_pairs_indexed += pf->indexed ? 1 : 0;
-    n_masked += pf->masked() ? 1 : 0;
-  }
+  const Inputs in = load_inputs(pool, names, mut_files, pairs, todo, !(e_idx && std::atoi(e_idx) == 0));
+  Fills fills = open_pairs(in, pairs, todo);
   const double t1 = now_s();
-  size_t n_rows = 0, n_kept = 0, n_rec = 0;
-  for (size_t c = 0; c < rows.size(); c++) n_rows += rows_total[c], n_kept += rows[c].size();
-  for (auto& kv : tmp_files) n_rec += kv.second->size;
 
   // ---- the pairs, window by window through the shared uniform stream
-  bool dev_failed = false;
-  if (dev_pending) {
-    const double t0m = now_s();
-    const uint64_t max_uniforms = ((uint64_t)n_kept * 100 / SharedUniforms::kChunk + W + 3) * SharedUniforms::kChunk;  // a pair uses at most every kept row
-    dev.reset(DeviceFill::create(dev_device, A, fastbin.guard_lo(), fastbin.guard_hi(), todo.size() * DevQueue::kMaxBlocks,
-                                 std::min<uint64_t>(dev_batch, std::max<uint64_t>(1024, (uint64_t)n_kept * todo.size())), dev_note));
-    if (!dev || !dev->alloc_uniforms(max_uniforms)) {
-      std::cerr << "Note: age sampling on the GPU could not be set up (" << (dev ? dev->error() : dev_note) << "); sampling on the host." << std::endl;
-      if (dev) dev_note = dev->error();
-      dev.reset();
-      dev_pending = false;
-    } else {
-      stream.for_each_buffer([&](double* p, size_t bytes) { dev->pin(p, bytes); });
-      dev_make_s = now_s() - t0m;
-      // (the record buffers -- gigabytes to page-lock -- beside the first windows: the first hand-over waits for them)
-      dev_maker = std::thread([&] {
-        const double t1m = now_s();
-        dev_staging_ok = dev->alloc_staging();
-        dev_staging_s = now_s() - t1m;
-      });
-    }
-  }
-  Engine eng{names, rows, A, C, num_bases_per_block, stream, fastbin, pool, fastbin.ok() ? pick_bin_snp() : nullptr, fastbin.ok() ? pick_add_snp() : nullptr,
-             dev_pending ? &devq : nullptr, use_index};
+  DeviceSampler* dev = sampler.start(A, todo.size(), in.n_kept, W) ? &sampler : nullptr;
+  Engine eng{names, in.rows, A, C, num_bases_per_block, stream, fastbin, pool, fastbin.ok() ? pick_bin_snp() : nullptr,
+             fastbin.ok() ? pick_add_snp() : nullptr, dev};
   int windows = 0;
-  uint64_t dev_next_chunk = 0;
-  size_t dev_jobs = 0, dev_recs = 0, dev_launches = 0;
-  double dev_upload_s = 0, dev_finish_s = 0;
-  // Hand-over to the device.  A job is a chain of dependent additions, SNP after SNP, on one wave: what makes the GPU fast is the
-  // number of chains in flight.  A window completes ~2 blocks per pair -- 180 jobs for 1024 SIMDs, 145 ms per launch however few
-  // they are --, so the completed blocks are kept until half a staging buffer of records has come together (some 2000 jobs at
-  // BASELINE configs[4]) and go in one launch: their records side by side into the pinned buffer (the pool copies).
-  std::vector<DevQueue::Item> backlog;
-  size_t backlog_recs = 0;
-  auto hand_over = [&](bool all) {
-    while (dev && !dev_failed && !backlog.empty() && (all || backlog_recs >= dev->staging_capacity() / 2)) {
-      if (dev_maker.joinable()) {
-        dev_maker.join();
-        if (!dev_staging_ok) {
-          dev_failed = true;
-          break;
-        }
-      }
-      std::vector<FillJob> jobs;
-      size_t nrecs = 0, taken = 0;
-      for (; taken < backlog.size() && jobs.size() < 60000; taken++) {
-        DevQueue::Item& it = backlog[taken];
-        if (it.recs.size() > dev->staging_capacity()) {  // (a block larger than a batch: the host takes the pair)
-          fills[it.job.table / DevQueue::kMaxBlocks]->redo.store(true);
-          backlog_recs -= it.recs.size();
-          it.recs.clear();
-          continue;
-        }
-        if (nrecs + it.recs.size() > dev->staging_capacity()) break;
-        it.job.rec_off = nrecs;
-        nrecs += it.recs.size();
-        if (!it.recs.empty()) jobs.push_back(it.job);
-      }
-      FillRec* const dst = dev->staging();
-      for (size_t i = 0; i < taken; i++)
-        if (!backlog[i].recs.empty()) {
-          DevQueue::Item* itp = &backlog[i];
-          pool.submit([dst, itp] { std::memcpy(dst + itp->job.rec_off, itp->recs.data(), itp->recs.size() * sizeof(FillRec)); });
-        }
-      pool.wait_idle();
-      dev_jobs += jobs.size(), dev_recs += nrecs, dev_launches += jobs.empty() ? 0 : 1;
-      if (!dev->submit(jobs, nrecs)) dev_failed = true;
-      backlog_recs -= nrecs;
-      {
-        std::lock_guard<std::mutex> lk(devq.m);
-        for (size_t i = 0; i < taken; i++)
-          if (backlog[i].recs.capacity() > 0) {
-            backlog[i].recs.clear();
-            devq.spare.push_back(std::move(backlog[i].recs));
-          }
-      }
-      backlog.erase(backlog.begin(), backlog.begin() + (long)taken);
-    }
-  };
-  for (uint64_t w = 0;; w++) {
+  for (uint64_t w = 0;; w++, windows++) {
     const uint64_t limit = (w + 1) * W * SharedUniforms::kChunk;
     bool any = false;
     for (auto& pf : fills)
@@ -1523,106 +1547,32 @@ bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const
       }
     if (!any) break;
     pool.wait_idle();
-    if (dev && !dev_failed) {
-      // the uniforms this window's jobs read (a pair's last SNP of the window may reach 100 into the next chunk): their copies are
-      // enqueued and run beside the next window's walks; the ring's chunks are handed back to the producer one window late, when
-      // the copies out of them have completed ...
-      const double tu = now_s();
-      if (!dev->sync_uploads()) dev_failed = true;
-      stream.release_before(dev_next_chunk > 0 ? dev_next_chunk - 1 : 0);  // (the overlap chunk is uploaded twice: kept)
-      while (dev_next_chunk <= (w + 1) * W) {  // (runs of chunks that are consecutive in the ring's memory: one copy each)
-        const uint64_t first = dev_next_chunk;
-        uint64_t n = 0;
-        const double* p0 = stream.chunk(first);
-        while (first + n <= (w + 1) * W && (first + n) % stream.ring_chunks() == first % stream.ring_chunks() + n) {
-          (void)stream.chunk(first + n);  // (waits until it has been generated)
-          n++;
-        }
-        if (!dev->upload_uniforms(first * SharedUniforms::kChunk, p0, n * SharedUniforms::kChunk)) dev_failed = true;
-        dev_next_chunk += n;
-      }
-      dev_upload_s += now_s() - tu;
-      // ... and the blocks that were completed in it join the backlog
-      {
-        std::lock_guard<std::mutex> lk(devq.m);
-        for (DevQueue::Item& it : devq.ready) {
-          backlog_recs += it.recs.size();
-          backlog.push_back(std::move(it));
-        }
-        devq.ready.clear();
-      }
-      hand_over(false);
-    }
-    if (!dev) stream.release_before((w + 1) * W);
-    if (dev && dev_failed)  // (the device is out: every pair goes through the host's sequential feeder; no walk waits for the stream)
-      for (auto& pf : fills) pf->redo.store(true);
-    windows++;
+    if (dev) dev->end_window(w, fills);
+    else stream.release_before((w + 1) * W);
   }
-  if (dev) {  // the tables of every (pair, block) back from the device; a pair with a flagged block is filled again on the host
-    const double tf = now_s();
-    hand_over(true);
-    std::vector<double> dtab;
-    std::vector<int> dflags;
-    if (dev_failed || !dev->finish(dtab, dflags)) {
-      std::cerr << "Note: age sampling on the GPU failed (" << dev->error() << "); filling the pairs on the host." << std::endl;
-      for (auto& pf : fills) pf->redo.store(true);
-    } else {
-      for (auto& pfp : fills) {
-        PairFill& pf = *pfp;
-        if (pf.redo.load()) continue;
-        if (pf.num_blocks > (int)DevQueue::kMaxBlocks) {  // (advance_block has marked it already: its tables do not fit its slot)
-          pf.redo.store(true);
-          continue;
-        }
-        for (int j = 0; j < pf.num_blocks && !pf.redo.load(); j++) {
-          const size_t t = pf.slot * DevQueue::kMaxBlocks + (size_t)j;
-          if (dflags[t]) pf.redo.store(true);
-          else std::copy(dtab.begin() + t * 2 * A, dtab.begin() + (t + 1) * 2 * A, pf.blocks[(size_t)j]->t.begin());
-        }
-      }
-    }
-    dev_finish_s = now_s() - tf;
-  }
+  if (dev) dev->finish(fills);
+
+  // ---- the tables; the pairs the engine could not fill go through the sequential feeder
   const double t2 = now_s();
-  size_t redone = 0, used = 0;
-  for (auto& pfp : fills) {
-    PairFill& pf = *pfp;
-    if (pf.redo.load()) {
-      redone++;
-      fill_sequentially(pf.index);
-      continue;
-    }
-    PairTables& pt = out[pf.index];
-    const int nb = pf.num_blocks;
-    pt.nb = nb;
-    pt.sh.resize((size_t)nb * A), pt.ns.resize(pt.sh.size()), pt.she.resize(pt.sh.size()), pt.nse.resize(pt.sh.size());
-    for (int j = 0; j < nb; j++) {
-      const double* t = pf.blocks[(size_t)j]->t.data();
-      std::copy(t, t + A, pt.sh.begin() + (size_t)j * A);
-      std::copy(t + A, t + 2 * A, pt.ns.begin() + (size_t)j * A);
-      std::copy(t + 2 * A, t + 3 * A, pt.she.begin() + (size_t)j * A);
-      std::copy(t + 3 * A, t + 4 * A, pt.nse.begin() + (size_t)j * A);
-    }
-    pt.rng = pf.rng_end;
-    used += pf.used_snps;
+  size_t redone = 0, used = 0, n_pairs_indexed = 0, n_masked = 0;
+  for (auto& pf : fills) {
+    if (collect(*pf, A, out[pf->index])) used += pf->used_snps;
+    else redone++, fill_sequentially(pf->index);
+    n_pairs_indexed += pf->indexed ? 1 : 0;
+    n_masked += pf->masked() ? 1 : 0;
   }
   if (g_times.on)
-    std::cerr << "Timing: pairs front end on " << T << " threads: " << mut_files.size() << " .mut files (" << n_rows << " rows, "
-              << n_kept << " kept) and " << tmp_files.size() << " .colate.in files (" << n_rec / 1000000 << " MB) read once in "
+    std::cerr << "Timing: pairs front end on " << T << " threads: " << mut_files.size() << " .mut files (" << in.n_rows << " rows, "
+              << in.n_kept << " kept) and " << in.tmp_files.size() << " .colate.in files (" << in.tmp_bytes / 1000000 << " MB) read once in "
               << t1 - t0 << " s; " << todo.size() << " pairs filled in " << t2 - t1 << " s (" << used << " used SNPs, " << windows
-              << " stream window(s) of " << window_mb << " MB, waited " << stream.waited() << " thread-s for uniforms (generated in " << stream.generate_seconds() << " s, converted in "
-              << stream.convert_seconds() << " s), " << redone
+              << " stream window(s) of " << window_mb << " MB, waited " << stream.waited() << " thread-s for uniforms (generated in "
+              << stream.generate_seconds() << " s, converted in " << stream.convert_seconds() << " s), " << redone
               << " pair(s) redone sequentially in " << now_s() - t2 << " s); thread-seconds: .mut parse " << g_work.parse_mut.load()
-              << ", .colate.in decode " << g_work.load_tmp.load() << ", walk indices " << g_work.index.load() << " (" << n_indexed << " of "
-              << tmp_files.size() << " files)" << ", " << n_pairs_indexed << " of " << fills.size() << " pairs walked through indices ("
-              << n_masked << " masked), masks " << g_work.mask.load() << " (" << masks.size() << " masks decoded once: " << mask_reads.load()
-              << " FASTA reads)" << ", SNP walks " << g_work.walk.load() << ", age sampling "
-              << g_work.sample.load()
-              << (dev ? "; age sampling on the GPU: " + std::to_string(dev_jobs) + " (pair, block) jobs, " + std::to_string(dev_recs) + " SNPs in " + std::to_string(dev_launches) + " launches, " +
-                            std::to_string(dev->gpu_seconds()) + " s of copies and kernels, " + std::to_string(dev_upload_s) + " s uploading the uniform stream, " + std::to_string(dev_make_s) + " s setting up, " + std::to_string(dev_staging_s) + " s page-locking the record buffers beside the first windows, " +
-                            std::to_string(dev_finish_s) + " s for the last launch and the tables"
-                      : "; age sampling on the host (" + dev_note + ")")
-              << std::endl;
+              << ", .colate.in decode " << g_work.load_tmp.load() << ", walk indices " << g_work.index.load() << " (" << in.n_indexed
+              << " of " << in.tmp_files.size() << " files), " << n_pairs_indexed << " of " << fills.size()
+              << " pairs walked through indices (" << n_masked << " masked), masks " << g_work.mask.load() << " (" << in.masks.size()
+              << " masks decoded once: " << in.mask_reads << " FASTA reads), SNP walks " << g_work.walk.load() << ", age sampling "
+              << g_work.sample.load() << sampler.timing() << std::endl;
   g_times.parse_mut = t1 - t0;
   g_times.table_fill = now_s() - t1;
   return true;

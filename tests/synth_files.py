@@ -147,3 +147,17 @@ if __name__ == "__main__":
     import sys
 
     write_inputs(sys.argv[1])
+
+
+def duplicate_rows(path, rng, frac):
+    """Writes a fraction of the rows of a .mut (or .mut.gz) file twice (rows at equal positions)."""
+    opener = gzip.open if path.endswith(".gz") else open
+    with opener(path, "rt") as f:
+        lines = f.read().rstrip("\n").split("\n")
+    out = [lines[0]]
+    for ln in lines[1:]:
+        out.append(ln)
+        if rng.uniform() < frac:
+            out.append(ln)
+    with opener(path, "wt") as f:
+        f.write("\n".join(out) + "\n")

@@ -148,7 +148,7 @@ def test_block_larger_than_a_batch_goes_to_the_host(tmp_path):
     _same(host, dev)
 
 
-N_CONTIGS = 520  # (DevQueue::kMaxBlocks = 512 tables per pair on the device; every --chr entry closes a block)
+N_CONTIGS = 520  # (DeviceSampler::kMaxBlocks = 512 tables per pair on the device; every --chr entry closes a block)
 
 
 def _many_contigs(d, empty_tail):
@@ -202,3 +202,35 @@ def test_masked_pair_flagged_by_the_device_keeps_its_masks(tmp_path):
     assert r.returncode == 0, r.stderr.decode()[-800:]
     assert "pairs front end on" not in r.stderr.decode()
     assert open(os.path.join(d, "mine.counts"), "rb").read() == dev["mine.counts"]
+
+
+_TOUCHED_CHILD = (
+    "import ctypes, os, sys\n"
+    "sys.path.insert(0, sys.argv[1])\n"
+    "from colate_amd._lib import lib\n"
+    "os.chdir(sys.argv[2])\n"
+    "argv = [b'Colate'] + [a.encode() for a in sys.argv[3:]]\n"
+    "rc = lib.colate_mut_main(len(argv), (ctypes.c_char_p * len(argv))(*argv))\n"
+    "print('touched', lib.colate_device_touched(), flush=True)\n"
+    "sys.exit(rc)\n"
+)
+
+
+@pytest.mark.parametrize("device_fill", [None, "0"])
+def test_device_fill_marks_the_process_as_device_touched(tmp_path, device_fill):
+    """`--pairs ... --counts_only` through colate_mut_main in a fresh process: the age sampling on the device brings up the HIP
+    runtime, so the process is marked (colate_device_touched() = 1, what keeps a later --ranks from forking it); with
+    COLATE_DEVICE_FILL=0 nothing in the run touches the device and the mark stays 0."""
+    meta = gl.l3_pairs_stage(str(tmp_path))
+    args = ["--mode", "mut", "--mut", "P"] + meta["common_args"] + ["--pairs", "pairs.txt", "--counts_only"]
+    env = dict(os.environ, COLATE_TIMING="1")
+    env.pop("COLATE_DEVICE_FILL", None)
+    if device_fill is not None:
+        env["COLATE_DEVICE_FILL"] = device_fill
+    r = subprocess.run([os.sys.executable, "-c", _TOUCHED_CHILD, ROOT, str(tmp_path)] + args, capture_output=True, text=True, env=env,
+                       timeout=600)
+    assert r.returncode == 0, (r.stdout, r.stderr[-1500:])
+    if device_fill is None:
+        assert "age sampling on the GPU:" in r.stderr and "touched 1" in r.stdout, (r.stdout, r.stderr[-1500:])
+    else:
+        assert "age sampling on the host (COLATE_DEVICE_FILL=0)" in r.stderr and "touched 0" in r.stdout, (r.stdout, r.stderr[-1500:])

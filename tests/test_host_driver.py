@@ -259,14 +259,19 @@ def _drop_out_of_order_records(path, dup_every=0):
     open(path, "wb").write(bytes(out))
 
 
-@pytest.mark.parametrize("seed", [11, 12, 13])
+@pytest.mark.parametrize("seed", [11, 12, 13, 14])
 def test_indexed_walk_equals_the_cursor_walk(tmp_path, seed):
     """Where every file of a pair is well-formed (each chromosome one run of records in ascending positions) the batched front end walks
     through per-file indices instead of the two cursors of coal.cpp:2125-2243 -- same used SNPs, same tables: against the cursor walk
     (COLATE_INDEXED_WALK=0, the code the reference-made fixtures pin) on inputs with absent records, allele mismatches, DAF = 0 and rows
-    whose record an earlier row's search had already reached, three targets x two references, several stream windows."""
+    whose record an earlier row's search had already reached, three targets x two references, several stream windows.  Seed 14 also
+    writes .mut rows twice (equal row positions: the second search of a cursor finds it on the lower bound already)."""
     d = str(tmp_path)
     synth_files.write_inputs(d, chroms=("1", "2", "3", "4"), snps_per_chr=6000, seed=seed, span=70_000_000, extra_targets=2, extra_refs=1)
+    if seed == 14:
+        rng = np.random.default_rng(seed)
+        for c in ("1", "2", "3", "4"):
+            synth_files.duplicate_rows(os.path.join(d, f"P_chr{c}.mut"), rng, 0.05)
     for f in ("T", "T1", "T2", "R", "R1"):
         _drop_out_of_order_records(os.path.join(d, f + ".colate.in"), dup_every=37 if seed != 11 else 0)
     pairs = [(f"{t}.colate.in", f"{r}.colate.in", f"out_{t}_{r}") for t in ("T", "T1", "T2") for r in ("R", "R1")]

@@ -1,7 +1,6 @@
 """`Colate --pairs` lines with per-pair masks and .coal warm starts (`target_mask=`, `reference_mask=`, `coal=`), on the CPU
 (--counts_only): the list grammar, the masks decoded once per file, masked pairs through the walk indices, and the tables against
 the single-pair CLI and -- through the oracle's EM -- against the reference run once per pair (fixture pairs_masks)."""
-import gzip
 import os
 import re
 import struct
@@ -189,18 +188,6 @@ def _sort_records(path, rng, dup_frac):
     open(path, "wb").write(bytes(out))
 
 
-def _duplicate_rows(path, rng, frac):
-    """Writes a fraction of the .mut rows twice (rows at equal positions)."""
-    lines = gzip.open(path, "rt").read().rstrip("\n").split("\n")
-    out = [lines[0]]
-    for ln in lines[1:]:
-        out.append(ln)
-        if rng.uniform() < frac:
-            out.append(ln)
-    with gzip.open(path, "wt") as g:
-        g.write("\n".join(out) + "\n")
-
-
 def _write_mask(path, n, rng, holes=(), lower=False):
     """Runs of P and N over n bases; `holes`: (begin, end) ranges set to N (a whole 30-Mb genome block)."""
     seq = np.empty(n, dtype="S1")
@@ -230,7 +217,7 @@ def test_masked_indexed_walk_equals_the_cursor_walk(tmp_path, seed):
     span = 70_000_000
     synth_files.write_inputs(d, chroms=("1", "2"), snps_per_chr=5000, seed=seed, span=span, gz=True, extra_targets=2, extra_refs=1)
     for c in ("1", "2"):
-        _duplicate_rows(os.path.join(d, f"P_chr{c}.mut.gz"), rng, 0.05)
+        synth_files.duplicate_rows(os.path.join(d, f"P_chr{c}.mut.gz"), rng, 0.05)
     for f in ("T", "T1", "T2", "R", "R1"):
         _sort_records(os.path.join(d, f + ".colate.in"), rng, 0.03 if seed != 21 else 0.0)
     _write_mask(os.path.join(d, "MT_chr1.fa"), span, rng, holes=[(30_000_000, 60_000_000)])
