@@ -86,6 +86,11 @@ SIGNATURES = {
                                             + [c_int, c_int, c_double, c_double] + [c_void_p] * 4),
     "colate_write_coal": (c_int, [c_char_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int]),
     "colate_mut_main": (c_int, [c_int, ctypes.POINTER(c_char_p)]),
+    "colate_condcoal_accumulate": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p, c_int, c_void_p, c_int]
+                                   + [c_void_p] * 2 + [c_int, c_void_p, c_int] + [c_void_p] * 3),
+    "colate_condcoal_accumulate_host": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p, c_int, c_void_p,
+                                                                                   c_int] + [c_void_p] * 2
+                                        + [c_int, c_void_p, c_int] + [c_void_p] * 3),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

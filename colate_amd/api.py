@@ -380,3 +380,33 @@ class coal_EM:
 
     def EM_notshared(self, age_begin, age_end, num, denom):
         return self._one(age_begin, age_end, num, denom, False)
+
+
+def condcoal_accumulate(parents, branch_lengths, factors, blocks, num_blocks, group_of_hap, num_groups, focal, cond,
+                        epochs, epochs_focal, sample_ages=None, device=True):
+    """`--mode CondCoalRates` per-block accumulators (colate_condcoal_accumulate[_host]): parents / branch_lengths [T, 2N-1]
+    (Relate labelling, root 2N-2), factors [T] (float32 tree weights), blocks [T]; group_of_hap [N]; focal / cond haplotype
+    lists (cond empty: the empty conditional group); epochs / epochs_focal float32; sample_ages [N] or None.
+    Returns (num, denom), float64 [num_blocks, EF, E, G].  device=False: the host twin."""
+    parents = np.ascontiguousarray(parents, dtype=np.int32)
+    T, nn = parents.shape if parents.ndim == 2 else (0, 1)
+    N = (nn + 1) // 2
+    if T == 0:
+        N = len(group_of_hap)
+    bl = _f64(branch_lengths).reshape(T, nn) if T else np.zeros((0, 1))
+    factors = np.ascontiguousarray(factors, dtype=np.float32)
+    blocks = np.ascontiguousarray(blocks, dtype=np.int32)
+    group_of_hap = np.ascontiguousarray(group_of_hap, dtype=np.int32)
+    focal = np.ascontiguousarray(focal, dtype=np.int32)
+    cond = np.ascontiguousarray(cond, dtype=np.int32)
+    epochs = np.ascontiguousarray(epochs, dtype=np.float32)
+    epochs_focal = np.ascontiguousarray(epochs_focal, dtype=np.float32)
+    ages = None if sample_ages is None else _f64(sample_ages)
+    E, EF, G = epochs.size, epochs_focal.size, int(num_groups)
+    num = np.zeros((int(num_blocks), EF, E, G))
+    denom = np.zeros_like(num)
+    fn = lib.colate_condcoal_accumulate if device else lib.colate_condcoal_accumulate_host
+    check(fn(N, T, _p(parents), _p(bl), _p(factors), _p(blocks), int(num_blocks), G, _p(group_of_hap), focal.size, _p(focal),
+             cond.size, _p(cond) if cond.size else None, _p(ages) if ages is not None else None, E, _p(epochs), EF,
+             _p(epochs_focal), _p(num), _p(denom)))
+    return num, denom

@@ -112,7 +112,7 @@ bool parse_options(int argc, char** argv, Options& o, std::string& err) {
 void print_help() {
   std::cout << "Usage:\n  Colate [OPTION...]\n\n"
             << "      --help                 Print help.\n"
-            << "      --mode arg             Choose which part of the algorithm to run (colate_amd: mut).\n"
+            << "      --mode arg             Choose which part of the algorithm to run (colate_amd: mut, make_tmp, CondCoalRates).\n"
             << "      --mut arg              Filename of file containing mut.\n"
             << "      --target_tmp arg       Filename of target tmp file\n"
             << "      --reference_tmp arg    Filename of reference tmp file\n"
@@ -140,6 +140,11 @@ void print_help() {
             << "      --write_colate_mat     Optional (colate_amd): write <output>.colate_mat as the reference does for BCF/BAM inputs.\n"
             << "      --target_table arg     (--mode make_tmp) Table `chr bp allele` of the target's calls.\n"
             << "      --ref_genome arg       (--mode make_tmp) Reference genome fasta (per chromosome with --chr).\n"
+            << "      --input arg            (--mode CondCoalRates) Prefix of the Relate .anc / .mut files.\n"
+            << "      --poplabels arg        (--mode CondCoalRates) Poplabels file (groups: its second column).\n"
+            << "      --groups arg           (--mode CondCoalRates) FOCAL,CONDITIONAL group names.\n"
+            << "      --lineage_bin arg      (--mode CondCoalRates) log10 of the focal epoch boundary in years (default 1e5).\n"
+            << "      --mask arg             (--mode CondCoalRates) Fasta mask (per chromosome with --chr).\n"
             << "  -o, --output arg           Filename of output.\n"
             << std::endl;
 }
@@ -238,8 +243,8 @@ inline bool parse_mut_line(char* b, char* e, MutRow& r) {
   int tmp;
   if (!parse_stoi(b, sep[0], tmp)) return false;
   if (!parse_stoi(sep[0] + 1, sep[1], r.pos)) return false;
-  if (!parse_stoi(sep[1] + 1, sep[2], tmp)) return false;
-  if (!parse_stoi(sep[3] + 1, sep[4], tmp)) return false;
+  if (!parse_stoi(sep[1] + 1, sep[2], r.dist)) return false;
+  if (!parse_stoi(sep[3] + 1, sep[4], r.tree)) return false;
   r.num_branches = 0;
   for (const char* q = sep[4] + 1; q < sep[5];) {  // white-space separated branch indices, each through stoi
     while (q < sep[5] && (*q == ' ' || (*q >= '\t' && *q <= '\r'))) q++;
@@ -1590,9 +1595,17 @@ extern "C" int colate_mut_main(int argc, char** argv) {
       return 1;
     }
   }
+  if (mode == "CondCoalRates") {
+    try {
+      return run_condcoal(opt);
+    } catch (const std::exception& e) {
+      std::cerr << "Error: " << e.what() << std::endl;
+      return 1;
+    }
+  }
   std::cout << "####### error #######" << std::endl;
-  std::cout << "colate_amd implements --mode mut and --mode make_tmp --target_table (preprocess_mut, make_tmp from "
-               "BCF/BAM, calc_depth, print_tmp, CondCoalRates stay with the reference build)."
+  std::cout << "colate_amd implements --mode mut, --mode make_tmp --target_table and --mode CondCoalRates (preprocess_mut, "
+               "make_tmp from BCF/BAM, calc_depth, print_tmp stay with the reference build)."
             << std::endl;
   return 1;
 }

@@ -33,6 +33,7 @@ extern StageTimes g_times;
 // snp;pos;dist;rs;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;anc/der;...
 struct MutRow {
   int pos = 0;
+  int dist = 0, tree = 0;  // (CondCoalRates: the tree weights, mutations.cpp:616-670)
   int num_branches = 0;
   int flipped = 0;
   float age_begin = 0.0f, age_end = 0.0f;  // stored as float in the reference (mutations.hpp:21)
@@ -158,7 +159,9 @@ std::vector<std::string> mask_files(const Options& opt, const std::vector<std::s
 
 void write_counts_file(const std::string& path, int B, int A, const std::vector<double>& grid, const double* csh,
                        const double* cns);
-void print_usage_footer();  // "CPU Time spent: ...; Max Memory usage: ..." (coal.cpp:3852-3861)
+void print_usage_footer();
+// condcoal.cpp: `--mode CondCoalRates`
+int run_condcoal(const Options& opt);  // "CPU Time spent: ...; Max Memory usage: ..." (coal.cpp:3852-3861)
 
 // mut_pairs.cpp: the engine.  The tables of the pairs listed in `todo` (indices into `pairs`; the others stay empty) and
 // each pair's generator as the fill leaves it; `names` / `mut_files`: the chromosomes (chromosome_files).  False after an

@@ -88,3 +88,17 @@ bool DeviceFill::submit(const std::vector<FillJob>&, size_t) { return false; }
 bool DeviceFill::finish(std::vector<double>&, std::vector<int>&) { return false; }
 bool DeviceFill::fail(const char*, int) { return false; }
 }  // namespace colate_drv
+
+// the CondCoalRates walks on the device (condcoal.h): none in this build, the host twin walks
+#include "condcoal.h"
+namespace colate_cc {
+CcDevice* CcDevice::create(int, const CcRun&, int, std::string& why) {
+  why = "built without a device";
+  return nullptr;
+}
+CcDevice::~CcDevice() {}
+bool CcDevice::submit(const CcChunk&) { return false; }
+bool CcDevice::finish(std::vector<std::vector<double>>&) { return false; }
+bool CcDevice::fail(const char*, int) { return false; }
+bool CcDevice::drain(int) { return false; }
+}  // namespace colate_cc

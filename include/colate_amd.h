@@ -298,6 +298,23 @@ int colate_bootstrap_em_batch_groups_allgather(void* comm, int G, int B, int gro
 int colate_write_coal(const char* path, int B, int E, const double* epochs, const double* rates,
                       int is_ancient, int ep_null);
 
+/* `Colate --mode CondCoalRates` (coal.cpp:4786-4999, GetConditionalCoalescentRate): the per-block accumulators of the
+ * conditional coalescence rates.  T trees of N haplotypes (2N-1 nodes each, Relate's labelling: leaves 0..N-1, root
+ * 2N-2): parents[T][2N-1] (-1 at the root), branch_lengths[T][2N-1], factors[T] (each tree's weight as the reference's
+ * float; -1 for its extra pass of the last tree), blocks[T] in [0, num_blocks).  G groups (group_of_hap[N]), the focal
+ * haplotypes focal[F], the conditional ones cond[C] (C = 0: the empty conditional group), sample_ages[N] or NULL (the
+ * modern path), epochs[E] and epochs_focal[EF] as floats.  Out: num / denom[num_blocks][EF][E][G] in double (the
+ * reference's float addends summed in double).  N up to 16384 (COLATE_ELIMIT beyond).  The walks run on the calling
+ * thread's device; COLATE_ENODEVICE without one.  _host: the same on the host (the CLI's host twin). */
+int colate_condcoal_accumulate(int N, int T, const int* parents, const double* branch_lengths, const float* factors,
+                               const int* blocks, int num_blocks, int G, const int* group_of_hap, int F, const int* focal,
+                               int C, const int* cond, const double* sample_ages, int E, const float* epochs, int EF,
+                               const float* epochs_focal, double* num, double* denom);
+int colate_condcoal_accumulate_host(int N, int T, const int* parents, const double* branch_lengths, const float* factors,
+                                    const int* blocks, int num_blocks, int G, const int* group_of_hap, int F,
+                                    const int* focal, int C, const int* cond, const double* sample_ages, int E,
+                                    const float* epochs, int EF, const float* epochs_focal, double* num, double* denom);
+
 /* The whole `Colate --mode mut` command line for the .colate.in / .colate_mat
  * inputs (Colate.cpp:6-116 -> coal.cpp:3071-3863): same option names, same
  * stderr progress lines, same .coal output.  Returns the process exit code. */
