@@ -91,6 +91,10 @@ SIGNATURES = {
     "colate_condcoal_accumulate_host": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p, c_int, c_void_p,
                                                                                    c_int] + [c_void_p] * 2
                                         + [c_int, c_void_p, c_int] + [c_void_p] * 3),
+    "colate_condcoal_accumulate_pairs": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p, c_int]
+                                         + [c_void_p] * 3 + [c_int, c_void_p, c_int] + [c_void_p] * 3),
+    "colate_condcoal_accumulate_pairs_host": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p, c_int]
+                                              + [c_void_p] * 3 + [c_int, c_void_p, c_int] + [c_void_p] * 3),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

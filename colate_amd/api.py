@@ -410,3 +410,34 @@ def condcoal_accumulate(parents, branch_lengths, factors, blocks, num_blocks, gr
              cond.size, _p(cond) if cond.size else None, _p(ages) if ages is not None else None, E, _p(epochs), EF,
              _p(epochs_focal), _p(num), _p(denom)))
     return num, denom
+
+
+def condcoal_accumulate_pairs(parents, branch_lengths, factors, blocks, num_blocks, group_of_hap, num_groups, focal_group,
+                              cond_group, epochs, epochs_focal, sample_ages=None, device=True):
+    """condcoal_accumulate for many (focal group, conditional group) pairs in one pass over the trees
+    (colate_condcoal_accumulate_pairs[_host]): focal_group / cond_group [P] group indices (cond_group -1: the empty
+    conditional group; the focal haplotypes of a pair are all of its focal group's); blocks must not decrease.
+    Returns (num, denom), float64 [P, num_blocks, EF, E, G]; pair p's part is bit for bit condcoal_accumulate's for it."""
+    parents = np.ascontiguousarray(parents, dtype=np.int32)
+    T, nn = parents.shape if parents.ndim == 2 else (0, 1)
+    N = (nn + 1) // 2
+    if T == 0:
+        N = len(group_of_hap)
+    bl = _f64(branch_lengths).reshape(T, nn) if T else np.zeros((0, 1))
+    factors = np.ascontiguousarray(factors, dtype=np.float32)
+    blocks = np.ascontiguousarray(blocks, dtype=np.int32)
+    group_of_hap = np.ascontiguousarray(group_of_hap, dtype=np.int32)
+    focal_group = np.ascontiguousarray(focal_group, dtype=np.int32).ravel()
+    cond_group = np.ascontiguousarray(cond_group, dtype=np.int32).ravel()
+    if focal_group.size != cond_group.size:
+        raise ValueError("focal_group and cond_group differ in length")
+    epochs = np.ascontiguousarray(epochs, dtype=np.float32)
+    epochs_focal = np.ascontiguousarray(epochs_focal, dtype=np.float32)
+    ages = None if sample_ages is None else _f64(sample_ages)
+    E, EF, G, P = epochs.size, epochs_focal.size, int(num_groups), focal_group.size
+    num = np.zeros((P, int(num_blocks), EF, E, G))
+    denom = np.zeros_like(num)
+    fn = lib.colate_condcoal_accumulate_pairs if device else lib.colate_condcoal_accumulate_pairs_host
+    check(fn(N, T, _p(parents), _p(bl), _p(factors), _p(blocks), int(num_blocks), G, _p(group_of_hap), P, _p(focal_group),
+             _p(cond_group), _p(ages) if ages is not None else None, E, _p(epochs), EF, _p(epochs_focal), _p(num), _p(denom)))
+    return num, denom

@@ -167,6 +167,32 @@ void host_accumulate(const CcRun& run, const CcChunk& c, std::vector<std::vector
   }
 }
 
+CcRun pair_run(const CcRun& base, int focal_group, int cond_group) {
+  CcRun run = base;
+  run.focal.clear();
+  run.is_cond.assign(run.N, 0);
+  for (int i = 0; i < run.N; i++) {
+    if (run.group[i] == focal_group) run.focal.push_back(i);
+    if (run.group[i] == cond_group) run.is_cond[i] = 1;
+  }
+  run.cond_empty = std::find(run.is_cond.begin(), run.is_cond.end(), 1) == run.is_cond.end();
+  return run;
+}
+
+int chunk_trees_for(int N, size_t per_tree_bytes) {
+  int trees = (int)std::max<size_t>(1, std::min<size_t>((4u << 20) / (unsigned)(2 * N - 1),
+                                                       ((size_t)256 << 20) / std::max<size_t>(1, per_tree_bytes)));
+  if (const char* e = std::getenv("COLATE_CONDCOAL_CHUNK_TREES")) {
+    const int k = std::atoi(e);
+    if (k >= 1) trees = std::min(trees, k);
+  }
+  return trees;
+}
+
+size_t CcPairsDevice::per_tree_bytes(int N, int G, int P, int slots) {
+  return sizeof(double) * (size_t)P * slots + sizeof(int) * (size_t)G * (N + 1);
+}
+
 }  // namespace colate_cc
 
 // ------------------------------------------------------------------ C ABI: per-block accumulators from raw trees
@@ -207,7 +233,7 @@ int condcoal_accumulate(bool device, int N, int T, const int* parents, const dou
   for (int t = 0; t < T; t++)
     if (blocks[t] < 0 || blocks[t] >= num_blocks) return fail(COLATE_EINVAL, "condcoal: tree %d in block %d", t, blocks[t]);
   const int S = run.slots(), nn = 2 * N - 1;
-  const int chunk_trees = std::max(1, std::min(T, (int)((4u << 20) / (unsigned)nn)));
+  const int chunk_trees = std::max(1, std::min(T, chunk_trees_for(N, 0)));
   std::unique_ptr<CcDevice> dev;
   if (device) {
     if (colate_device_count() <= 0) return fail(COLATE_ENODEVICE, "condcoal: no usable HIP device");
@@ -249,7 +275,118 @@ int condcoal_accumulate(bool device, int N, int T, const int* parents, const dou
   return COLATE_OK;
 }
 
+// The same for P (focal group, conditional group) pairs: out [P][num_blocks][EF][E][G].  The host twin runs each pair
+// as its own CcRun (condcoal_accumulate's host path, bit for bit); the device walks all pairs in one pass (CcPairsDevice).
+int condcoal_accumulate_pairs(bool device, int N, int T, const int* parents, const double* branch_lengths, const float* factors,
+                              const int* blocks, int num_blocks, int G, const int* group_of_hap, int P, const int* focal_group,
+                              const int* cond_group, const double* sample_ages, int E, const float* epochs, int EF,
+                              const float* epochs_focal, double* num, double* denom) {
+  using colate::fail;
+  if (N < 2 || N > kMaxHaplotypes)
+    return fail(N < 2 ? COLATE_EINVAL : COLATE_ELIMIT, "condcoal: N = %d haplotypes (supported: 2 .. %d)", N, kMaxHaplotypes);
+  if (T < 0 || num_blocks < 1 || G < 1 || P < 1 || E < 1 || EF < 1)
+    return fail(COLATE_EINVAL, "condcoal: bad sizes (T %d, blocks %d, G %d, P %d, E %d, EF %d)", T, num_blocks, G, P, E, EF);
+  if ((T && (!parents || !branch_lengths || !factors || !blocks)) || !group_of_hap || !focal_group || !cond_group || !epochs ||
+      !epochs_focal || !num || !denom)
+    return fail(COLATE_EINVAL, "condcoal: NULL argument");
+  CcRun base;
+  base.N = N;
+  base.G = G;
+  base.group.assign(group_of_hap, group_of_hap + N);
+  for (int g : base.group)
+    if (g < 0 || g >= G) return fail(COLATE_EINVAL, "condcoal: group index %d outside 0..%d", g, G - 1);
+  if (sample_ages) base.ages.assign(sample_ages, sample_ages + N);
+  base.epochs.assign(epochs, epochs + E);
+  base.efocal.assign(epochs_focal, epochs_focal + EF);
+  std::vector<int> fg(focal_group, focal_group + P), cg(cond_group, cond_group + P);
+  for (int p = 0; p < P; p++) {
+    if (fg[p] < 0 || fg[p] >= G) return fail(COLATE_EINVAL, "condcoal: pair %d: focal group %d outside 0..%d", p, fg[p], G - 1);
+    if (cg[p] < -1 || cg[p] >= G)
+      return fail(COLATE_EINVAL, "condcoal: pair %d: conditional group %d outside -1..%d", p, cg[p], G - 1);
+    if (std::find(base.group.begin(), base.group.end(), fg[p]) == base.group.end())
+      return fail(COLATE_EINVAL, "condcoal: pair %d: focal group %d has no haplotype", p, fg[p]);
+  }
+  for (int t = 0; t < T; t++) {
+    if (blocks[t] < 0 || blocks[t] >= num_blocks) return fail(COLATE_EINVAL, "condcoal: tree %d in block %d", t, blocks[t]);
+    if (t && blocks[t] < blocks[t - 1]) return fail(COLATE_EINVAL, "condcoal: tree %d: blocks decrease (%d after %d)", t, blocks[t], blocks[t - 1]);
+  }
+  const int S = base.slots(), nn = 2 * N - 1;
+  std::unique_ptr<CcPairsDevice> dev;
+  std::vector<CcRun> runs;
+  std::vector<std::vector<std::vector<double>>> acc_host;  // [P][block][S]
+  int chunk_trees = std::max(1, std::min(T, chunk_trees_for(N, 0)));
+  if (device) {
+    if (colate_device_count() <= 0) return fail(COLATE_ENODEVICE, "condcoal: no usable HIP device");
+    chunk_trees = std::max(1, std::min(T, chunk_trees_for(N, CcPairsDevice::per_tree_bytes(N, G, P, S))));
+    std::string why;
+    dev.reset(CcPairsDevice::create(-1, base, fg, cg, chunk_trees, why));  // (-1: the calling thread's device)
+    if (!dev) return fail(COLATE_EHIP, "condcoal: %s", why.c_str());
+  } else {
+    for (int p = 0; p < P; p++) runs.push_back(pair_run(base, fg[p], cg[p]));
+    acc_host.resize(P);
+  }
+  CcChunk c;
+  std::string err;
+  for (int t0 = 0; t0 < T; t0 += chunk_trees) {
+    c.clear();
+    const int t1 = std::min(T, t0 + chunk_trees);
+    for (int t = t0; t < t1; t++) {
+      const int k = c.append(N);
+      std::memcpy(c.parent.data() + (size_t)k * nn, parents + (size_t)t * nn, sizeof(int) * nn);
+      std::memcpy(c.bl.data() + (size_t)k * nn, branch_lengths + (size_t)t * nn, sizeof(double) * nn);
+      c.factor[k] = factors[t];
+      c.block[k] = blocks[t];
+      if (!prepare_tree(N, c.parent.data() + (size_t)k * nn, c.lo.data() + (size_t)k * nn, c.hi.data() + (size_t)k * nn,
+                        c.leaf.data() + (size_t)k * N, err))
+        return fail(COLATE_EINVAL, "condcoal: tree %d: %s", t, err.c_str());
+    }
+    if (dev) {
+      if (!dev->submit(c)) return fail(dev->error_code() ? dev->error_code() : COLATE_EHIP, "%s", dev->error().c_str());
+    } else {
+      for (int p = 0; p < P; p++) host_accumulate(runs[p], c, acc_host[p]);
+    }
+  }
+  std::vector<std::vector<double>> acc_dev;
+  if (dev && !dev->finish(acc_dev)) return fail(dev->error_code() ? dev->error_code() : COLATE_EHIP, "%s", dev->error().c_str());
+  const size_t NS = (size_t)S / 2;
+  for (int p = 0; p < P; p++)
+    for (int b = 0; b < num_blocks; b++) {
+      const double* src = nullptr;
+      if (dev) {
+        if (b < (int)acc_dev.size() && !acc_dev[b].empty()) src = acc_dev[b].data() + (size_t)p * S;
+      } else if (b < (int)acc_host[p].size() && !acc_host[p][b].empty()) {
+        src = acc_host[p][b].data();
+      }
+      double* n = num + ((size_t)p * num_blocks + b) * NS;
+      double* d = denom + ((size_t)p * num_blocks + b) * NS;
+      for (size_t i = 0; i < NS; i++) {
+        n[i] = src ? src[i] : 0.0;
+        d[i] = src ? src[NS + i] : 0.0;
+      }
+    }
+  return COLATE_OK;
+}
+
 }  // namespace
+
+extern "C" int colate_condcoal_accumulate_pairs(int N, int T, const int* parents, const double* branch_lengths,
+                                                const float* factors, const int* blocks, int num_blocks, int G,
+                                                const int* group_of_hap, int P, const int* focal_group, const int* cond_group,
+                                                const double* sample_ages, int E, const float* epochs, int EF,
+                                                const float* epochs_focal, double* num, double* denom) {
+  return condcoal_accumulate_pairs(true, N, T, parents, branch_lengths, factors, blocks, num_blocks, G, group_of_hap, P,
+                                   focal_group, cond_group, sample_ages, E, epochs, EF, epochs_focal, num, denom);
+}
+
+extern "C" int colate_condcoal_accumulate_pairs_host(int N, int T, const int* parents, const double* branch_lengths,
+                                                     const float* factors, const int* blocks, int num_blocks, int G,
+                                                     const int* group_of_hap, int P, const int* focal_group,
+                                                     const int* cond_group, const double* sample_ages, int E,
+                                                     const float* epochs, int EF, const float* epochs_focal, double* num,
+                                                     double* denom) {
+  return condcoal_accumulate_pairs(false, N, T, parents, branch_lengths, factors, blocks, num_blocks, G, group_of_hap, P,
+                                   focal_group, cond_group, sample_ages, E, epochs, EF, epochs_focal, num, denom);
+}
 
 extern "C" int colate_condcoal_accumulate(int N, int T, const int* parents, const double* branch_lengths, const float* factors,
                                           const int* blocks, int num_blocks, int G, const int* group_of_hap, int F,
@@ -484,22 +621,55 @@ bool plan_trees(const std::vector<MutRow>& rows, int num_trees, int chr_bin, con
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-}  // namespace
+// One table to write: the single run's --groups / --output, or one line of the --pairs list.
+struct CcJob {
+  std::string g1, g2, output;
+  int line = 0;  // line of the --pairs list (0: the single run)
+  std::string where() const { return line ? " (line " + std::to_string(line) + " of the --pairs list)" : ""; }
+};
 
-int run_condcoal(const Options& opt) {
-  if (opt.has("map")) {
-    std::cerr << "Error: --map (the recombination-rate filter of CondCoalRates) is not supported by colate_amd." << std::endl;
-    return 1;
+// `FOCAL,COND OUTPUT` per line, blank lines skipped; the groups token splits as --groups does.
+bool read_condcoal_pairs(const std::string& path, std::vector<CcJob>& jobs, std::string& err) {
+  std::ifstream is(path);
+  if (!is) {
+    err = "cannot read the --pairs list " + path;
+    return false;
   }
-  if (!opt.has("input") || !opt.has("output")) {
-    std::cout << "Not enough arguments supplied." << std::endl;
-    std::cout << "Needed: input, output. Optional: years_per_gen, dist, bins, mask, mask_cutof, mask, mask_cutofff." << std::endl;
-    return 0;
+  std::string line;
+  for (int k = 1; std::getline(is, line); k++) {
+    std::istringstream ss(line);
+    std::vector<std::string> tok;
+    std::string w;
+    while (ss >> w) tok.push_back(w);
+    if (tok.empty()) continue;
+    if (tok.size() != 2) {
+      err = "line " + std::to_string(k) + " of the --pairs list: expected `FOCAL,CONDITIONAL OUTPUT`, got " +
+            std::to_string(tok.size()) + " tokens";
+      return false;
+    }
+    for (const CcJob& j : jobs)
+      if (j.output == tok[1]) {
+        err = "line " + std::to_string(k) + " of the --pairs list: output " + tok[1] + " is also line " + std::to_string(j.line) + "'s";
+        return false;
+      }
+    CcJob j;
+    const size_t comma = tok[0].find(',');
+    j.g1 = tok[0].substr(0, comma);
+    j.g2 = comma == std::string::npos ? "" : tok[0].substr(comma + 1);
+    j.output = tok[1];
+    j.line = k;
+    jobs.push_back(j);
   }
-  if (!opt.has("poplabels") || !opt.has("groups")) {
-    std::cerr << "Error: --mode CondCoalRates needs --poplabels and --groups." << std::endl;
-    return 1;
+  if (jobs.empty()) {
+    err = "the --pairs list " + path + " has no pairs";
+    return false;
   }
+  return true;
+}
+
+// The run for a list of tables (one: the single run; several: --pairs): every input file is read once and every tree
+// walked once for all tables.  Each table is the one its single run writes, byte for byte.
+int condcoal_tables(const Options& opt, const std::vector<CcJob>& jobs, bool pairs_mode) {
   const double t_begin = now_s();
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating conditional coalescence rate for " << opt.get("input") << " ..." << std::endl;
@@ -524,31 +694,39 @@ int run_condcoal(const Options& opt) {
   float years_per_gen = 28.0;
   if (opt.has("years_per_gen")) years_per_gen = std::stof(opt.get("years_per_gen"));
   std::string err;
-  CcRun run;
-  if (!condcoal_epochs(opt, years_per_gen, run.epochs, err)) {
+  CcRun base;  // what every table shares (N, G, groups, ages, epochs)
+  if (!condcoal_epochs(opt, years_per_gen, base.epochs, err)) {
     std::cerr << err << std::endl;
     return 1;
   }
   const float log_10 = std::log(10);
   float lineage_bin = 1e5;
   if (opt.has("lineage_bin")) lineage_bin = std::stof(opt.get("lineage_bin"));
-  run.efocal = {0, std::exp(log_10 * lineage_bin)};  // coal.cpp:5148-5156 (float: the default's 10^1e5 is inf)
-  for (float& e : run.efocal) e /= years_per_gen;
+  base.efocal = {0, std::exp(log_10 * lineage_bin)};  // coal.cpp:5148-5156 (float: the default's 10^1e5 is inf)
+  for (float& e : base.efocal) e /= years_per_gen;
 
-  std::mt19937 rng;
+  // the rng serves the bootstrap only: every table starts from the same seed (without --seed: one drawn for the run)
   int seed = std::time(0) + getpid();
   if (opt.has("seed")) seed = std::stoi(opt.get("seed"));
-  rng.seed(seed);
 
   Poplabels pl;
   if (!read_poplabels(opt.get("poplabels"), pl, err)) {
     std::cerr << err << std::endl;
     return 1;
   }
-  const std::string& groups = opt.get("groups");
-  const size_t comma = groups.find(',');
-  const std::string g1 = groups.substr(0, comma), g2 = comma == std::string::npos ? "" : groups.substr(comma + 1);
-  std::cerr << g1 << "|" << g2 << std::endl;
+  const size_t P = jobs.size();
+  std::vector<int> fg(P), cg(P);  // group indices (-1: not in the poplabels)
+  for (size_t k = 0; k < P; k++) {
+    const CcJob& j = jobs[k];
+    std::cerr << j.g1 << "|" << j.g2 << std::endl;
+    const auto f = std::find(pl.groups.begin(), pl.groups.end(), j.g1), c = std::find(pl.groups.begin(), pl.groups.end(), j.g2);
+    fg[k] = f == pl.groups.end() ? -1 : (int)(f - pl.groups.begin());
+    cg[k] = c == pl.groups.end() ? -1 : (int)(c - pl.groups.begin());
+    if (pairs_mode && fg[k] < 0) {
+      std::cerr << "Error: groups not found" << j.where() << std::endl;
+      return 1;
+    }
+  }
 
   // device or host twin
   bool use_device = true;
@@ -559,23 +737,25 @@ int run_condcoal(const Options& opt) {
   const int nthreads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
   const bool timing = std::getenv("COLATE_TIMING") != nullptr;
 
-  std::unique_ptr<CcDevice> dev;
-  std::vector<std::vector<double>> acc;
+  std::vector<CcRun> runs(P);
+  std::unique_ptr<CcDevice> dev;         // the single run
+  std::unique_ptr<CcPairsDevice> pdev;   // --pairs
+  std::vector<std::vector<std::vector<double>>> acc(P);  // [table][block][slots]
   double t_parse = 0, t_walk = 0;
-  int bin = 0, chr_bin = 0, N = 0;
+  int bin = 0, chr_bin = 0, N = 0, chunk_trees = 1;
   for (size_t chr = 0; chr < chr_names.size(); chr++) {
     std::cerr << "CHR: " << chr_names[chr] << std::endl;
-    const std::string base = per_chr ? opt.get("input") + "_chr" + chr_names[chr] : opt.get("input");
+    const std::string base_name = per_chr ? opt.get("input") + "_chr" + chr_names[chr] : opt.get("input");
     double t0 = now_s();
     std::vector<MutRow> rows;
-    read_mut_file(base + ".mut", rows);
+    read_mut_file(base_name + ".mut", rows);
     if (rows.empty()) {
-      std::cerr << "Error: " << base << ".mut has no SNPs." << std::endl;
+      std::cerr << "Error: " << base_name << ".mut has no SNPs." << std::endl;
       return 1;
     }
     GzLines anc;
-    if (!anc.open(base + ".anc") && !anc.open(base + ".anc.gz")) {
-      std::cerr << "Failed to open file " << base << ".anc(.gz)" << std::endl;
+    if (!anc.open(base_name + ".anc") && !anc.open(base_name + ".anc.gz")) {
+      std::cerr << "Failed to open file " << base_name << ".anc(.gz)" << std::endl;
       return 1;
     }
     std::string line;
@@ -597,46 +777,46 @@ int run_condcoal(const Options& opt) {
       is2 >> tmp >> num_trees;
     }
     if (n_chr < 2 || n_chr > kMaxHaplotypes) {
-      std::cerr << "Error: " << base << ".anc: " << n_chr << " haplotypes (colate_amd supports 2 .. " << kMaxHaplotypes << ")."
-                << std::endl;
+      std::cerr << "Error: " << base_name << ".anc: " << n_chr << " haplotypes (colate_amd supports 2 .. " << kMaxHaplotypes
+                << ")." << std::endl;
       return 1;
     }
     if (num_trees < 1) {
-      std::cerr << "Error: " << base << ".anc has no trees." << std::endl;
+      std::cerr << "Error: " << base_name << ".anc has no trees." << std::endl;
       return 1;
     }
     if (chr == 0) {
       N = n_chr;
-      run.N = N;
-      run.G = (int)pl.groups.size();
-      run.ages = ages;
+      base.N = N;
+      base.G = (int)pl.groups.size();
+      base.ages = ages;
       if ((int)pl.group_of_haplotype.size() < N) {
         std::cerr << "Error: " << opt.get("poplabels") << " lists " << pl.group_of_haplotype.size() << " haplotypes, the .anc has "
                   << N << "." << std::endl;
         return 1;
       }
-      run.group.assign(pl.group_of_haplotype.begin(), pl.group_of_haplotype.begin() + N);
-      run.is_cond.assign(N, 0);
-      for (int i = 0; i < N; i++) {
-        if (pl.groups[run.group[i]] == g1) run.focal.push_back(i);
-        if (pl.groups[run.group[i]] == g2) run.is_cond[i] = 1;
-      }
-      run.cond_empty = std::find(run.is_cond.begin(), run.is_cond.end(), 1) == run.is_cond.end();
-      if (run.focal.empty()) {
-        std::cerr << "Error: groups not found" << std::endl;
-        return 1;
-      }
-      if (use_device) {
-        std::string why;
-        const int chunk = std::max(1, (int)((4u << 20) / (unsigned)(2 * N - 1)));
-        dev.reset(CcDevice::create(device, run, chunk, why));
-        if (!dev) {
-          std::cerr << "Error: CondCoalRates on device " << device << ": " << why << std::endl;
+      base.group.assign(pl.group_of_haplotype.begin(), pl.group_of_haplotype.begin() + N);
+      for (size_t k = 0; k < P; k++) {
+        runs[k] = pair_run(base, fg[k], cg[k]);
+        if (runs[k].focal.empty()) {
+          std::cerr << "Error: groups not found" << jobs[k].where() << std::endl;
           return 1;
         }
       }
-    } else if (n_chr != N || ages != run.ages) {
-      std::cerr << "Error: " << base << ".anc has other haplotypes (or sample ages) than the first chromosome's." << std::endl;
+      std::string why;
+      if (!pairs_mode) {
+        chunk_trees = chunk_trees_for(N, 0);
+        if (use_device) dev.reset(CcDevice::create(device, runs[0], chunk_trees, why));
+      } else {
+        chunk_trees = chunk_trees_for(N, CcPairsDevice::per_tree_bytes(N, base.G, (int)P, base.slots()));
+        if (use_device) pdev.reset(CcPairsDevice::create(device, base, fg, cg, chunk_trees, why));
+      }
+      if (use_device && !dev && !pdev) {
+        std::cerr << "Error: CondCoalRates on device " << device << ": " << why << std::endl;
+        return 1;
+      }
+    } else if (n_chr != N || ages != base.ages) {
+      std::cerr << "Error: " << base_name << ".anc has other haplotypes (or sample ages) than the first chromosome's." << std::endl;
       return 1;
     }
     std::string mask_seq;
@@ -650,7 +830,6 @@ int run_condcoal(const Options& opt) {
 
     // stream the trees that contribute: parse a chunk on the pool, hand it over, read on
     const int nn = 2 * N - 1;
-    const int chunk_trees = std::max(1, (int)((4u << 20) / (unsigned)nn));
     std::vector<std::string> lines;
     std::vector<int> which;  // tree index of each line
     CcChunk c;
@@ -714,8 +893,13 @@ int run_condcoal(const Options& opt) {
           err = dev->error();
           return false;
         }
+      } else if (pdev) {
+        if (!pdev->submit(c)) {
+          err = pdev->error();
+          return false;
+        }
       } else {
-        host_accumulate(run, c, acc);
+        for (size_t k = 0; k < P; k++) host_accumulate(runs[k], c, acc[k]);
       }
       t_walk += now_s() - tw;
       return true;
@@ -723,7 +907,7 @@ int run_condcoal(const Options& opt) {
     t0 = now_s();
     for (int t = 0; t < num_trees; t++) {
       if (!anc.getline(line)) {
-        std::cerr << "Error: " << base << ".anc ends after " << t << " of " << num_trees << " trees." << std::endl;
+        std::cerr << "Error: " << base_name << ".anc ends after " << t << " of " << num_trees << " trees." << std::endl;
         return 1;
       }
       const bool last = (t == num_trees - 1);
@@ -749,65 +933,126 @@ int run_condcoal(const Options& opt) {
     chr_bin = bin + 1;
   }
   const double tw = now_s();
-  if (dev && !dev->finish(acc)) {
+  if (dev && !dev->finish(acc[0])) {
     std::cerr << "Error: " << dev->error() << std::endl;
     return 1;
   }
+  if (pdev) {
+    std::vector<std::vector<double>> all;  // [block][table][slots]
+    if (!pdev->finish(all)) {
+      std::cerr << "Error: " << pdev->error() << std::endl;
+      return 1;
+    }
+    const size_t S = base.slots();
+    for (size_t k = 0; k < P; k++) {
+      acc[k].resize(all.size());
+      for (size_t b = 0; b < all.size(); b++)
+        if (!all[b].empty()) acc[k][b].assign(all[b].begin() + k * S, all[b].begin() + (k + 1) * S);
+    }
+  }
   t_walk += now_s() - tw;
-  const double gpu_s = dev ? dev->gpu_seconds() : 0.0;
+  const double gpu_s = dev ? dev->gpu_seconds() : pdev ? pdev->gpu_seconds() : 0.0;
   dev.reset();
+  pdev.reset();
 
-  // bootstrap and table (coal.cpp:5513-5568), float as there
+  // bootstrap and tables (coal.cpp:5513-5568), float as there
   const double t_out = now_s();
   const int num_blocks = bin + 1;
-  const int E = run.E(), EF = run.EF(), G = run.G, NS = EF * E * G;
-  std::vector<float> bnum((size_t)num_blocks * NS, 0.f), bden((size_t)num_blocks * NS, 0.f);
-  for (int b = 0; b < num_blocks && b < (int)acc.size(); b++)
-    if (!acc[b].empty())
-      for (int i = 0; i < NS; i++) {
-        bnum[(size_t)b * NS + i] = (float)acc[b][i];
-        bden[(size_t)b * NS + i] = (float)acc[b][NS + i];
-      }
+  const int E = base.E(), EF = base.EF(), G = base.G, NS = EF * E * G;
   int num_bootstrap = 1;
   if (opt.has("num_bootstraps")) num_bootstrap = std::stoi(opt.get("num_bootstraps"));
-  std::uniform_int_distribution<int> dist_blocks(0, num_blocks - 1);
-  std::vector<int> blocks(num_blocks);
-  std::ofstream os(opt.get("output"));
-  if (!os) {
-    std::cerr << "Error: cannot write " << opt.get("output") << std::endl;
-    return 1;
-  }
-  os << "boot lineage_epoch epoch.start group rate" << std::endl;
-  std::vector<float> res_num(NS), res_den(NS);
-  for (int iter = 0; iter < num_bootstrap; iter++) {
-    if (num_bootstrap == 1) {
-      std::fill(blocks.begin(), blocks.end(), 1.0);
-    } else {
-      std::fill(blocks.begin(), blocks.end(), 0.0);
-      for (int block = 0; block < num_blocks; block++) blocks[dist_blocks(rng)] += 1.0;
-    }
-    std::fill(res_num.begin(), res_num.end(), 0.f);
-    std::fill(res_den.begin(), res_den.end(), 0.f);
-    for (int block = 0; block < num_blocks; block++)
-      for (int i = 0; i < NS; i++) {
-        res_num[i] += blocks[block] * bnum[(size_t)block * NS + i];
-        res_den[i] += blocks[block] * bden[(size_t)block * NS + i];
-      }
-    for (int ep1 = 0; ep1 < EF; ep1++)
-      for (int ep2 = 0; ep2 < E; ep2++)
-        for (int i = 0; i < G; i++) {
-          const int k = (ep1 * E + ep2) * G + i;
-          os << iter << " " << run.efocal[ep1] << " " << run.epochs[ep2] << " " << pl.groups[i] << " " << res_num[k] / res_den[k]
-             << std::endl;
+  for (size_t k = 0; k < P; k++) {
+    std::vector<float> bnum((size_t)num_blocks * NS, 0.f), bden((size_t)num_blocks * NS, 0.f);
+    for (int b = 0; b < num_blocks && b < (int)acc[k].size(); b++)
+      if (!acc[k][b].empty())
+        for (int i = 0; i < NS; i++) {
+          bnum[(size_t)b * NS + i] = (float)acc[k][b][i];
+          bden[(size_t)b * NS + i] = (float)acc[k][b][NS + i];
         }
+    std::mt19937 rng;
+    rng.seed(seed);
+    std::uniform_int_distribution<int> dist_blocks(0, num_blocks - 1);
+    std::vector<int> blocks(num_blocks);
+    std::ofstream os(jobs[k].output);
+    if (!os) {
+      std::cerr << "Error: cannot write " << jobs[k].output << std::endl;
+      return 1;
+    }
+    os << "boot lineage_epoch epoch.start group rate" << std::endl;
+    std::vector<float> res_num(NS), res_den(NS);
+    for (int iter = 0; iter < num_bootstrap; iter++) {
+      if (num_bootstrap == 1) {
+        std::fill(blocks.begin(), blocks.end(), 1.0);
+      } else {
+        std::fill(blocks.begin(), blocks.end(), 0.0);
+        for (int block = 0; block < num_blocks; block++) blocks[dist_blocks(rng)] += 1.0;
+      }
+      std::fill(res_num.begin(), res_num.end(), 0.f);
+      std::fill(res_den.begin(), res_den.end(), 0.f);
+      for (int block = 0; block < num_blocks; block++)
+        for (int i = 0; i < NS; i++) {
+          res_num[i] += blocks[block] * bnum[(size_t)block * NS + i];
+          res_den[i] += blocks[block] * bden[(size_t)block * NS + i];
+        }
+      for (int ep1 = 0; ep1 < EF; ep1++)
+        for (int ep2 = 0; ep2 < E; ep2++)
+          for (int i = 0; i < G; i++) {
+            const int q = (ep1 * E + ep2) * G + i;
+            os << iter << " " << base.efocal[ep1] << " " << base.epochs[ep2] << " " << pl.groups[i] << " "
+               << res_num[q] / res_den[q] << std::endl;
+          }
+    }
+    os.close();
   }
-  os.close();
   const double t_end = now_s();
   if (timing)
     std::fprintf(stderr, "condcoal timing: parse %.3f s, walk %.3f s (%s %.3f s), bootstrap+write %.3f s, total %.3f s\n", t_parse,
                  t_walk, gpu_s > 0 ? "device kernels" : "host twin", gpu_s, t_end - t_out, t_end - t_begin);
   print_usage_footer();
   return 0;
+}
+
+}  // namespace
+
+int run_condcoal(const Options& opt) {
+  if (opt.has("map")) {
+    std::cerr << "Error: --map (the recombination-rate filter of CondCoalRates) is not supported by colate_amd." << std::endl;
+    return 1;
+  }
+  std::vector<CcJob> jobs;
+  if (opt.has("pairs")) {
+    if (opt.has("groups") || opt.has("output")) {
+      std::cerr << "Error: --pairs takes the groups and outputs from its list: no --groups or --output with it." << std::endl;
+      return 1;
+    }
+    if (!opt.has("input") || !opt.has("poplabels")) {
+      std::cerr << "Error: --mode CondCoalRates needs --input and --poplabels." << std::endl;
+      return 1;
+    }
+    std::string err;
+    if (!read_condcoal_pairs(opt.get("pairs"), jobs, err)) {
+      std::cerr << "Error: " << err << std::endl;
+      return 1;
+    }
+    return condcoal_tables(opt, jobs, true);
+  }
+  if (!opt.has("input") || !opt.has("output")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed: input, output. Optional: years_per_gen, dist, bins, mask, mask_cutof, mask, mask_cutofff." << std::endl;
+    return 0;
+  }
+  if (!opt.has("poplabels") || !opt.has("groups")) {
+    std::cerr << "Error: --mode CondCoalRates needs --poplabels and --groups." << std::endl;
+    return 1;
+  }
+  CcJob j;
+  const std::string& groups = opt.get("groups");
+  const size_t comma = groups.find(',');
+  j.g1 = groups.substr(0, comma);
+  j.g2 = comma == std::string::npos ? "" : groups.substr(comma + 1);
+  j.output = opt.get("output");
+  jobs.push_back(j);
+  return condcoal_tables(opt, jobs, false);
 }
 
 }  // namespace colate_drv

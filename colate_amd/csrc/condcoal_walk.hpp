@@ -143,17 +143,16 @@ CC_HD inline void cc_class_walk(const CcShared& sh, const CcTree& t, int f, int 
   }
 }
 
-// The whole contribution of focal leaf f to one tree's accumulators.
+// The whole contribution of focal leaf f to one tree's accumulators, with the conditional group's prefix row `cpre`
+// ([N+1]) and `self` = 1 if f is itself a conditional (neither is read when sh.cond_empty).
 template <class Acc>
-CC_HD inline void cc_focal_walk(const CcShared& sh, const CcTree& t, int f, Acc& acc) {
+CC_HD inline void cc_focal_walk_cond(const CcShared& sh, const CcTree& t, int f, const int* cpre, int self, Acc& acc) {
   const int root = 2 * sh.N - 2;
   float coord = sh.ages ? (float)sh.ages[f] : 0.0f;
   if (sh.cond_empty) {  // one virtual conditional, in use from the start, focal epoch 0
     cc_class_walk(sh, t, f, f, coord, 0, 1.0, acc);
     return;
   }
-  const int* cpre = t.prefix + sh.G * (sh.N + 1);
-  const int self = sh.is_cond[f] ? 1 : 0;
   int prev = 0;  // conditionals below the previous node of the path, f itself excluded
   int node = f;
   for (;;) {
@@ -186,6 +185,16 @@ CC_HD inline void cc_focal_walk(const CcShared& sh, const CcTree& t, int f, Acc&
     node = t.parent[node];
     if (node == root) break;  // (coal.cpp:4871: the root itself is never tested, so its conditionals are not used)
   }
+}
+
+// The same with the run's conditional group: prefix row G and is_cond.
+template <class Acc>
+CC_HD inline void cc_focal_walk(const CcShared& sh, const CcTree& t, int f, Acc& acc) {
+  if (sh.cond_empty) {
+    cc_focal_walk_cond(sh, t, f, nullptr, 0, acc);
+    return;
+  }
+  cc_focal_walk_cond(sh, t, f, t.prefix + sh.G * (sh.N + 1), sh.is_cond[f] ? 1 : 0, acc);
 }
 
 }  // namespace colate_cc

@@ -145,6 +145,8 @@ void print_help() {
             << "      --groups arg           (--mode CondCoalRates) FOCAL,CONDITIONAL group names.\n"
             << "      --lineage_bin arg      (--mode CondCoalRates) log10 of the focal epoch boundary in years (default 1e5).\n"
             << "      --mask arg             (--mode CondCoalRates) Fasta mask (per chromosome with --chr).\n"
+            << "                             (--mode CondCoalRates) --pairs FILE: `FOCAL,CONDITIONAL OUTPUT` per line, in place of\n"
+            << "                             --groups / --output; every table is its single run's, from one pass over the trees.\n"
             << "  -o, --output arg           Filename of output.\n"
             << std::endl;
 }

@@ -101,4 +101,14 @@ bool CcDevice::submit(const CcChunk&) { return false; }
 bool CcDevice::finish(std::vector<std::vector<double>>&) { return false; }
 bool CcDevice::fail(const char*, int) { return false; }
 bool CcDevice::drain(int) { return false; }
+CcPairsDevice* CcPairsDevice::create(int, const CcRun&, const std::vector<int>&, const std::vector<int>&, int, std::string& why) {
+  why = "built without a device";
+  return nullptr;
+}
+CcPairsDevice::~CcPairsDevice() {}
+bool CcPairsDevice::submit(const CcChunk&) { return false; }
+bool CcPairsDevice::finish(std::vector<std::vector<double>>&) { return false; }
+bool CcPairsDevice::fail(const char*, int) { return false; }
+bool CcPairsDevice::drain(int) { return false; }
+bool CcPairsDevice::launch(const CcChunk&, int, int) { return false; }
 }  // namespace colate_cc

@@ -315,6 +315,21 @@ int colate_condcoal_accumulate_host(int N, int T, const int* parents, const doub
                                     const int* focal, int C, const int* cond, const double* sample_ages, int E,
                                     const float* epochs, int EF, const float* epochs_focal, double* num, double* denom);
 
+/* The same for P (focal group, conditional group) pairs in one pass over the trees (`Colate --mode CondCoalRates
+ * --pairs`): focal_group[P] in [0, G), each with at least one haplotype (its focal haplotypes: all of the group's,
+ * ascending), cond_group[P] in [-1, G) (-1: the empty conditional group).  blocks[T] must not decrease.  Out: num /
+ * denom[P][num_blocks][EF][E][G]; pair p's part is bit for bit what colate_condcoal_accumulate (device) or
+ * colate_condcoal_accumulate_host (_host) gives for that pair alone. */
+int colate_condcoal_accumulate_pairs(int N, int T, const int* parents, const double* branch_lengths, const float* factors,
+                                     const int* blocks, int num_blocks, int G, const int* group_of_hap, int P,
+                                     const int* focal_group, const int* cond_group, const double* sample_ages, int E,
+                                     const float* epochs, int EF, const float* epochs_focal, double* num, double* denom);
+int colate_condcoal_accumulate_pairs_host(int N, int T, const int* parents, const double* branch_lengths,
+                                          const float* factors, const int* blocks, int num_blocks, int G,
+                                          const int* group_of_hap, int P, const int* focal_group, const int* cond_group,
+                                          const double* sample_ages, int E, const float* epochs, int EF,
+                                          const float* epochs_focal, double* num, double* denom);
+
 /* The whole `Colate --mode mut` command line for the .colate.in / .colate_mat
  * inputs (Colate.cpp:6-116 -> coal.cpp:3071-3863): same option names, same
  * stderr progress lines, same .coal output.  Returns the process exit code. */
