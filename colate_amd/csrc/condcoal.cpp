@@ -11,7 +11,6 @@
 //     the host twin here (no device, or COLATE_DEVICE_CONDCOAL=0);
 //   * the block bootstrap and the table, in the reference's float arithmetic.
 #include <unistd.h>
-#include <zlib.h>
 
 #include <algorithm>
 #include <chrono>
@@ -21,6 +20,7 @@
 #include <cstring>
 #include <ctime>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <memory>
 #include <random>
@@ -48,6 +48,19 @@ int CcChunk::append(int n) {
   factor.push_back(0.f);
   block.push_back(0);
   return T++;
+}
+
+int CcChunk::append_copy(int k) {
+  const size_t n = N, nn = 2 * n - 1;
+  const int x = append(N);
+  std::copy_n(parent.begin() + k * nn, nn, parent.begin() + x * nn);
+  std::copy_n(lo.begin() + k * nn, nn, lo.begin() + x * nn);
+  std::copy_n(hi.begin() + k * nn, nn, hi.begin() + x * nn);
+  std::copy_n(bl.begin() + k * nn, nn, bl.begin() + x * nn);
+  std::copy_n(leaf.begin() + k * n, n, leaf.begin() + x * n);
+  factor[x] = factor[k];
+  block[x] = block[k];
+  return x;
 }
 
 bool prepare_tree(int N, const int* parent, int* lo, int* hi, int* leaf, std::string& err) {
@@ -134,8 +147,7 @@ CcShared shared_of(const CcRun& run) {
   return sh;
 }
 
-}  // namespace
-
+// The host twin: adds the chunk's trees into acc[block][slots] (acc grows to the largest block).
 void host_accumulate(const CcRun& run, const CcChunk& c, std::vector<std::vector<double>>& acc) {
   const CcShared sh = shared_of(run);
   const int N = run.N, nn = 2 * N - 1, G = run.G, S = run.slots();
@@ -167,6 +179,28 @@ void host_accumulate(const CcRun& run, const CcChunk& c, std::vector<std::vector
   }
 }
 
+class HostWalker final : public CcWalker {
+ public:
+  explicit HostWalker(std::vector<CcRun> runs) : runs_(std::move(runs)), acc_(runs_.size()) {}
+  bool submit(const CcChunk& c) override {
+    for (size_t k = 0; k < runs_.size(); k++) host_accumulate(runs_[k], c, acc_[k]);
+    return true;
+  }
+  bool finish(CcTables& acc) override {
+    acc = std::move(acc_);
+    acc_.assign(runs_.size(), {});
+    return true;
+  }
+
+ private:
+  std::vector<CcRun> runs_;
+  CcTables acc_;
+};
+
+}  // namespace
+
+std::unique_ptr<CcWalker> make_host_walker(std::vector<CcRun> runs) { return std::make_unique<HostWalker>(std::move(runs)); }
+
 CcRun pair_run(const CcRun& base, int focal_group, int cond_group) {
   CcRun run = base;
   run.focal.clear();
@@ -189,7 +223,7 @@ int chunk_trees_for(int N, size_t per_tree_bytes) {
   return trees;
 }
 
-size_t CcPairsDevice::per_tree_bytes(int N, int G, int P, int slots) {
+size_t pairs_per_tree_bytes(int N, int G, int P, int slots) {
   return sizeof(double) * (size_t)P * slots + sizeof(int) * (size_t)G * (N + 1);
 }
 
@@ -199,25 +233,96 @@ size_t CcPairsDevice::per_tree_bytes(int N, int G, int P, int slots) {
 namespace {
 
 using namespace colate_cc;
+using colate::fail;
+
+struct RawTrees {  // the trees as the ABI takes them
+  int N, T;
+  const int* parents;
+  const double* branch_lengths;
+  const float* factors;
+  const int* blocks;
+  int num_blocks;
+};
+
+int check_haplotypes(int N) {
+  if (N >= 2 && N <= kMaxHaplotypes) return COLATE_OK;
+  return fail(N < 2 ? COLATE_EINVAL : COLATE_ELIMIT, "condcoal: N = %d haplotypes (supported: 2 .. %d)", N, kMaxHaplotypes);
+}
+
+// what every table of a call shares
+int base_run(CcRun& base, int N, int G, const int* group_of_hap, const double* sample_ages, int E, const float* epochs, int EF,
+             const float* epochs_focal) {
+  base.N = N;
+  base.G = G;
+  base.group.assign(group_of_hap, group_of_hap + N);
+  for (int g : base.group)
+    if (g < 0 || g >= G) return fail(COLATE_EINVAL, "condcoal: group index %d outside 0..%d", g, G - 1);
+  if (sample_ages) base.ages.assign(sample_ages, sample_ages + N);
+  base.epochs.assign(epochs, epochs + E);
+  base.efocal.assign(epochs_focal, epochs_focal + EF);
+  return COLATE_OK;
+}
+
+// The trees through a walker, and its tables into num / denom [P][num_blocks][EF][E][G].  `ordered`: the blocks must not
+// decrease (the pairs walkers sum a block while it is open; the single ones by index).  make(chunk_trees, why): the walker
+// for chunks of that size, or null; per_tree_bytes: what a device walker keeps per tree of a chunk.
+int accumulate_tables(const RawTrees& in, bool ordered, bool device, size_t per_tree_bytes, int P, int S,
+                      const std::function<std::unique_ptr<CcWalker>(int, std::string&)>& make, double* num, double* denom) {
+  const int N = in.N, T = in.T, nn = 2 * N - 1;
+  for (int t = 0; t < T; t++) {
+    if (in.blocks[t] < 0 || in.blocks[t] >= in.num_blocks) return fail(COLATE_EINVAL, "condcoal: tree %d in block %d", t, in.blocks[t]);
+    if (ordered && t && in.blocks[t] < in.blocks[t - 1])
+      return fail(COLATE_EINVAL, "condcoal: tree %d: blocks decrease (%d after %d)", t, in.blocks[t], in.blocks[t - 1]);
+  }
+  if (device && colate_device_count() <= 0) return fail(COLATE_ENODEVICE, "condcoal: no usable HIP device");
+  const int chunk_trees = std::max(1, std::min(T, chunk_trees_for(N, device ? per_tree_bytes : 0)));
+  std::string err;
+  const std::unique_ptr<CcWalker> w = make(chunk_trees, err);
+  if (!w) return fail(COLATE_EHIP, "condcoal: %s", err.c_str());
+  CcChunk c;
+  for (int t0 = 0; t0 < T; t0 += chunk_trees) {
+    c.clear();
+    const int t1 = std::min(T, t0 + chunk_trees);
+    for (int t = t0; t < t1; t++) {
+      const int k = c.append(N);
+      std::memcpy(c.parent.data() + (size_t)k * nn, in.parents + (size_t)t * nn, sizeof(int) * nn);
+      std::memcpy(c.bl.data() + (size_t)k * nn, in.branch_lengths + (size_t)t * nn, sizeof(double) * nn);
+      c.factor[k] = in.factors[t];
+      c.block[k] = in.blocks[t];
+      if (!prepare_tree(N, c.parent.data() + (size_t)k * nn, c.lo.data() + (size_t)k * nn, c.hi.data() + (size_t)k * nn,
+                        c.leaf.data() + (size_t)k * N, err))
+        return fail(COLATE_EINVAL, "condcoal: tree %d: %s", t, err.c_str());
+    }
+    if (!w->submit(c)) return fail(w->error_code() ? w->error_code() : COLATE_EHIP, "%s", w->error().c_str());
+  }
+  CcTables acc;
+  if (!w->finish(acc)) return fail(w->error_code() ? w->error_code() : COLATE_EHIP, "%s", w->error().c_str());
+  const size_t NS = (size_t)S / 2;
+  for (int p = 0; p < P; p++)
+    for (int b = 0; b < in.num_blocks; b++) {
+      const bool have = b < (int)acc[p].size() && !acc[p][b].empty();
+      double* n = num + ((size_t)p * in.num_blocks + b) * NS;
+      double* d = denom + ((size_t)p * in.num_blocks + b) * NS;
+      for (size_t i = 0; i < NS; i++) {
+        n[i] = have ? acc[p][b][i] : 0.0;
+        d[i] = have ? acc[p][b][NS + i] : 0.0;
+      }
+    }
+  return COLATE_OK;
+}
 
 int condcoal_accumulate(bool device, int N, int T, const int* parents, const double* branch_lengths, const float* factors,
                         const int* blocks, int num_blocks, int G, const int* group_of_hap, int F, const int* focal, int C,
                         const int* cond, const double* sample_ages, int E, const float* epochs, int EF,
                         const float* epochs_focal, double* num, double* denom) {
-  using colate::fail;
-  if (N < 2 || N > kMaxHaplotypes)
-    return fail(N < 2 ? COLATE_EINVAL : COLATE_ELIMIT, "condcoal: N = %d haplotypes (supported: 2 .. %d)", N, kMaxHaplotypes);
+  if (int rc = check_haplotypes(N)) return rc;
   if (T < 0 || num_blocks < 1 || G < 1 || F < 1 || C < 0 || E < 1 || EF < 1)
     return fail(COLATE_EINVAL, "condcoal: bad sizes (T %d, blocks %d, G %d, F %d, C %d, E %d, EF %d)", T, num_blocks, G, F, C, E, EF);
   if ((T && (!parents || !branch_lengths || !factors || !blocks)) || !group_of_hap || !focal || (C && !cond) || !epochs ||
       !epochs_focal || !num || !denom)
     return fail(COLATE_EINVAL, "condcoal: NULL argument");
   CcRun run;
-  run.N = N;
-  run.G = G;
-  run.group.assign(group_of_hap, group_of_hap + N);
-  for (int g : run.group)
-    if (g < 0 || g >= G) return fail(COLATE_EINVAL, "condcoal: group index %d outside 0..%d", g, G - 1);
+  if (int rc = base_run(run, N, G, group_of_hap, sample_ages, E, epochs, EF, epochs_focal)) return rc;
   run.is_cond.assign(N, 0);
   for (int i = 0; i < C; i++) {
     if (cond[i] < 0 || cond[i] >= N) return fail(COLATE_EINVAL, "condcoal: conditional haplotype %d", cond[i]);
@@ -227,77 +332,27 @@ int condcoal_accumulate(bool device, int N, int T, const int* parents, const dou
   for (int i = 0; i < F; i++)
     if (focal[i] < 0 || focal[i] >= N) return fail(COLATE_EINVAL, "condcoal: focal haplotype %d", focal[i]);
   run.focal.assign(focal, focal + F);
-  if (sample_ages) run.ages.assign(sample_ages, sample_ages + N);
-  run.epochs.assign(epochs, epochs + E);
-  run.efocal.assign(epochs_focal, epochs_focal + EF);
-  for (int t = 0; t < T; t++)
-    if (blocks[t] < 0 || blocks[t] >= num_blocks) return fail(COLATE_EINVAL, "condcoal: tree %d in block %d", t, blocks[t]);
-  const int S = run.slots(), nn = 2 * N - 1;
-  const int chunk_trees = std::max(1, std::min(T, chunk_trees_for(N, 0)));
-  std::unique_ptr<CcDevice> dev;
-  if (device) {
-    if (colate_device_count() <= 0) return fail(COLATE_ENODEVICE, "condcoal: no usable HIP device");
-    std::string why;
-    dev.reset(CcDevice::create(-1, run, chunk_trees, why));  // (-1: the calling thread's device, colate_set_device)
-    if (!dev) return fail(COLATE_EHIP, "condcoal: %s", why.c_str());
-  }
-  std::vector<std::vector<double>> acc;
-  CcChunk c;
-  std::string err;
-  for (int t0 = 0; t0 < T; t0 += chunk_trees) {
-    c.clear();
-    const int t1 = std::min(T, t0 + chunk_trees);
-    for (int t = t0; t < t1; t++) {
-      const int k = c.append(N);
-      std::memcpy(c.parent.data() + (size_t)k * nn, parents + (size_t)t * nn, sizeof(int) * nn);
-      std::memcpy(c.bl.data() + (size_t)k * nn, branch_lengths + (size_t)t * nn, sizeof(double) * nn);
-      c.factor[k] = factors[t];
-      c.block[k] = blocks[t];
-      if (!prepare_tree(N, c.parent.data() + (size_t)k * nn, c.lo.data() + (size_t)k * nn, c.hi.data() + (size_t)k * nn,
-                        c.leaf.data() + (size_t)k * N, err))
-        return fail(COLATE_EINVAL, "condcoal: tree %d: %s", t, err.c_str());
-    }
-    if (dev) {
-      if (!dev->submit(c)) return fail(dev->error_code() ? dev->error_code() : COLATE_EHIP, "%s", dev->error().c_str());
-    } else {
-      host_accumulate(run, c, acc);
-    }
-  }
-  if (dev && !dev->finish(acc)) return fail(dev->error_code() ? dev->error_code() : COLATE_EHIP, "%s", dev->error().c_str());
-  const size_t NS = (size_t)S / 2;
-  for (int b = 0; b < num_blocks; b++) {
-    const bool have = b < (int)acc.size() && !acc[b].empty();
-    for (size_t i = 0; i < NS; i++) {
-      num[(size_t)b * NS + i] = have ? acc[b][i] : 0.0;
-      denom[(size_t)b * NS + i] = have ? acc[b][NS + i] : 0.0;
-    }
-  }
-  return COLATE_OK;
+  auto make = [&](int chunk_trees, std::string& why) {
+    return device ? make_device_walker(-1, run, chunk_trees, why) : make_host_walker({run});  // (-1: the calling thread's device)
+  };
+  return accumulate_tables({N, T, parents, branch_lengths, factors, blocks, num_blocks}, false, device, 0, 1, run.slots(), make,
+                           num, denom);
 }
 
 // The same for P (focal group, conditional group) pairs: out [P][num_blocks][EF][E][G].  The host twin runs each pair
-// as its own CcRun (condcoal_accumulate's host path, bit for bit); the device walks all pairs in one pass (CcPairsDevice).
+// as its own CcRun (condcoal_accumulate's host path, bit for bit); the device walks all pairs in one pass.
 int condcoal_accumulate_pairs(bool device, int N, int T, const int* parents, const double* branch_lengths, const float* factors,
                               const int* blocks, int num_blocks, int G, const int* group_of_hap, int P, const int* focal_group,
                               const int* cond_group, const double* sample_ages, int E, const float* epochs, int EF,
                               const float* epochs_focal, double* num, double* denom) {
-  using colate::fail;
-  if (N < 2 || N > kMaxHaplotypes)
-    return fail(N < 2 ? COLATE_EINVAL : COLATE_ELIMIT, "condcoal: N = %d haplotypes (supported: 2 .. %d)", N, kMaxHaplotypes);
+  if (int rc = check_haplotypes(N)) return rc;
   if (T < 0 || num_blocks < 1 || G < 1 || P < 1 || E < 1 || EF < 1)
     return fail(COLATE_EINVAL, "condcoal: bad sizes (T %d, blocks %d, G %d, P %d, E %d, EF %d)", T, num_blocks, G, P, E, EF);
   if ((T && (!parents || !branch_lengths || !factors || !blocks)) || !group_of_hap || !focal_group || !cond_group || !epochs ||
       !epochs_focal || !num || !denom)
     return fail(COLATE_EINVAL, "condcoal: NULL argument");
   CcRun base;
-  base.N = N;
-  base.G = G;
-  base.group.assign(group_of_hap, group_of_hap + N);
-  for (int g : base.group)
-    if (g < 0 || g >= G) return fail(COLATE_EINVAL, "condcoal: group index %d outside 0..%d", g, G - 1);
-  if (sample_ages) base.ages.assign(sample_ages, sample_ages + N);
-  base.epochs.assign(epochs, epochs + E);
-  base.efocal.assign(epochs_focal, epochs_focal + EF);
+  if (int rc = base_run(base, N, G, group_of_hap, sample_ages, E, epochs, EF, epochs_focal)) return rc;
   std::vector<int> fg(focal_group, focal_group + P), cg(cond_group, cond_group + P);
   for (int p = 0; p < P; p++) {
     if (fg[p] < 0 || fg[p] >= G) return fail(COLATE_EINVAL, "condcoal: pair %d: focal group %d outside 0..%d", p, fg[p], G - 1);
@@ -306,65 +361,15 @@ int condcoal_accumulate_pairs(bool device, int N, int T, const int* parents, con
     if (std::find(base.group.begin(), base.group.end(), fg[p]) == base.group.end())
       return fail(COLATE_EINVAL, "condcoal: pair %d: focal group %d has no haplotype", p, fg[p]);
   }
-  for (int t = 0; t < T; t++) {
-    if (blocks[t] < 0 || blocks[t] >= num_blocks) return fail(COLATE_EINVAL, "condcoal: tree %d in block %d", t, blocks[t]);
-    if (t && blocks[t] < blocks[t - 1]) return fail(COLATE_EINVAL, "condcoal: tree %d: blocks decrease (%d after %d)", t, blocks[t], blocks[t - 1]);
-  }
-  const int S = base.slots(), nn = 2 * N - 1;
-  std::unique_ptr<CcPairsDevice> dev;
-  std::vector<CcRun> runs;
-  std::vector<std::vector<std::vector<double>>> acc_host;  // [P][block][S]
-  int chunk_trees = std::max(1, std::min(T, chunk_trees_for(N, 0)));
-  if (device) {
-    if (colate_device_count() <= 0) return fail(COLATE_ENODEVICE, "condcoal: no usable HIP device");
-    chunk_trees = std::max(1, std::min(T, chunk_trees_for(N, CcPairsDevice::per_tree_bytes(N, G, P, S))));
-    std::string why;
-    dev.reset(CcPairsDevice::create(-1, base, fg, cg, chunk_trees, why));  // (-1: the calling thread's device)
-    if (!dev) return fail(COLATE_EHIP, "condcoal: %s", why.c_str());
-  } else {
+  auto make = [&](int chunk_trees, std::string& why) {
+    if (device) return make_pairs_device_walker(-1, base, fg, cg, chunk_trees, why);  // (-1: the calling thread's device)
+    std::vector<CcRun> runs;
     for (int p = 0; p < P; p++) runs.push_back(pair_run(base, fg[p], cg[p]));
-    acc_host.resize(P);
-  }
-  CcChunk c;
-  std::string err;
-  for (int t0 = 0; t0 < T; t0 += chunk_trees) {
-    c.clear();
-    const int t1 = std::min(T, t0 + chunk_trees);
-    for (int t = t0; t < t1; t++) {
-      const int k = c.append(N);
-      std::memcpy(c.parent.data() + (size_t)k * nn, parents + (size_t)t * nn, sizeof(int) * nn);
-      std::memcpy(c.bl.data() + (size_t)k * nn, branch_lengths + (size_t)t * nn, sizeof(double) * nn);
-      c.factor[k] = factors[t];
-      c.block[k] = blocks[t];
-      if (!prepare_tree(N, c.parent.data() + (size_t)k * nn, c.lo.data() + (size_t)k * nn, c.hi.data() + (size_t)k * nn,
-                        c.leaf.data() + (size_t)k * N, err))
-        return fail(COLATE_EINVAL, "condcoal: tree %d: %s", t, err.c_str());
-    }
-    if (dev) {
-      if (!dev->submit(c)) return fail(dev->error_code() ? dev->error_code() : COLATE_EHIP, "%s", dev->error().c_str());
-    } else {
-      for (int p = 0; p < P; p++) host_accumulate(runs[p], c, acc_host[p]);
-    }
-  }
-  std::vector<std::vector<double>> acc_dev;
-  if (dev && !dev->finish(acc_dev)) return fail(dev->error_code() ? dev->error_code() : COLATE_EHIP, "%s", dev->error().c_str());
-  const size_t NS = (size_t)S / 2;
-  for (int p = 0; p < P; p++)
-    for (int b = 0; b < num_blocks; b++) {
-      const double* src = nullptr;
-      if (dev) {
-        if (b < (int)acc_dev.size() && !acc_dev[b].empty()) src = acc_dev[b].data() + (size_t)p * S;
-      } else if (b < (int)acc_host[p].size() && !acc_host[p][b].empty()) {
-        src = acc_host[p][b].data();
-      }
-      double* n = num + ((size_t)p * num_blocks + b) * NS;
-      double* d = denom + ((size_t)p * num_blocks + b) * NS;
-      for (size_t i = 0; i < NS; i++) {
-        n[i] = src ? src[i] : 0.0;
-        d[i] = src ? src[NS + i] : 0.0;
-      }
-    }
-  return COLATE_OK;
+    return make_host_walker(std::move(runs));
+  };
+  const int S = base.slots();
+  return accumulate_tables({N, T, parents, branch_lengths, factors, blocks, num_blocks}, true, device,
+                           pairs_per_tree_bytes(N, G, P, S), P, S, make, num, denom);
 }
 
 }  // namespace
@@ -412,38 +417,6 @@ using namespace colate_cc;
 
 namespace {
 
-// igzstream semantics: plain and gzip files alike
-class GzLines {
- public:
-  bool open(const std::string& name) {
-    f_ = gzopen(name.c_str(), "rb");
-    if (f_) gzbuffer(f_, 1 << 20);
-    return f_ != nullptr;
-  }
-  bool getline(std::string& line) {
-    line.clear();
-    if (!f_) return false;
-    bool got = false;
-    while (gzgets(f_, buf_, sizeof(buf_))) {
-      got = true;
-      const size_t n = std::strlen(buf_);
-      if (n && buf_[n - 1] == '\n') {
-        line.append(buf_, n - 1);
-        return true;
-      }
-      line.append(buf_, n);
-    }
-    return got;
-  }
-  ~GzLines() {
-    if (f_) gzclose(f_);
-  }
-
- private:
-  gzFile f_ = nullptr;
-  char buf_[1 << 16];
-};
-
 // anc.cpp:6-45 (MarginalTree::Read + Tree::ReadTree): "pos: " then 2N-1 times "parent:(branch_length num_events SNP_begin SNP_end) "
 bool parse_tree_line(const std::string& line, int N, int* parent, double* bl) {
   const char* s = line.c_str();
@@ -475,7 +448,7 @@ struct Poplabels {  // sample.cpp:8-110
 bool read_poplabels(const std::string& path, Poplabels& pl, std::string& err) {
   std::vector<std::vector<std::string>> rows;
   {
-    GzLines is;
+    GzText is;
     if (!is.open(path)) {
       err = "Error while opening file " + path + ".";
       return false;
@@ -676,7 +649,7 @@ int condcoal_tables(const Options& opt, const std::vector<CcJob>& jobs, bool pai
 
   std::vector<std::string> chr_names;
   if (opt.has("chr")) {
-    GzLines is;
+    GzText is;
     if (!is.open(opt.get("chr"))) {
       std::cerr << "Error while opening file " << opt.get("chr") << std::endl;
       return 1;
@@ -737,10 +710,7 @@ int condcoal_tables(const Options& opt, const std::vector<CcJob>& jobs, bool pai
   const int nthreads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
   const bool timing = std::getenv("COLATE_TIMING") != nullptr;
 
-  std::vector<CcRun> runs(P);
-  std::unique_ptr<CcDevice> dev;         // the single run
-  std::unique_ptr<CcPairsDevice> pdev;   // --pairs
-  std::vector<std::vector<std::vector<double>>> acc(P);  // [table][block][slots]
+  std::unique_ptr<CcWalker> walker;
   double t_parse = 0, t_walk = 0;
   int bin = 0, chr_bin = 0, N = 0, chunk_trees = 1;
   for (size_t chr = 0; chr < chr_names.size(); chr++) {
@@ -753,7 +723,7 @@ int condcoal_tables(const Options& opt, const std::vector<CcJob>& jobs, bool pai
       std::cerr << "Error: " << base_name << ".mut has no SNPs." << std::endl;
       return 1;
     }
-    GzLines anc;
+    GzText anc;
     if (!anc.open(base_name + ".anc") && !anc.open(base_name + ".anc.gz")) {
       std::cerr << "Failed to open file " << base_name << ".anc(.gz)" << std::endl;
       return 1;
@@ -796,6 +766,7 @@ int condcoal_tables(const Options& opt, const std::vector<CcJob>& jobs, bool pai
         return 1;
       }
       base.group.assign(pl.group_of_haplotype.begin(), pl.group_of_haplotype.begin() + N);
+      std::vector<CcRun> runs(P);
       for (size_t k = 0; k < P; k++) {
         runs[k] = pair_run(base, fg[k], cg[k]);
         if (runs[k].focal.empty()) {
@@ -803,17 +774,17 @@ int condcoal_tables(const Options& opt, const std::vector<CcJob>& jobs, bool pai
           return 1;
         }
       }
-      std::string why;
-      if (!pairs_mode) {
-        chunk_trees = chunk_trees_for(N, 0);
-        if (use_device) dev.reset(CcDevice::create(device, runs[0], chunk_trees, why));
+      chunk_trees = chunk_trees_for(N, pairs_mode ? pairs_per_tree_bytes(N, base.G, (int)P, base.slots()) : 0);
+      if (!use_device) {
+        walker = make_host_walker(std::move(runs));
       } else {
-        chunk_trees = chunk_trees_for(N, CcPairsDevice::per_tree_bytes(N, base.G, (int)P, base.slots()));
-        if (use_device) pdev.reset(CcPairsDevice::create(device, base, fg, cg, chunk_trees, why));
-      }
-      if (use_device && !dev && !pdev) {
-        std::cerr << "Error: CondCoalRates on device " << device << ": " << why << std::endl;
-        return 1;
+        std::string why;
+        walker = pairs_mode ? make_pairs_device_walker(device, base, fg, cg, chunk_trees, why)
+                            : make_device_walker(device, runs[0], chunk_trees, why);
+        if (!walker) {
+          std::cerr << "Error: CondCoalRates on device " << device << ": " << why << std::endl;
+          return 1;
+        }
       }
     } else if (n_chr != N || ages != base.ages) {
       std::cerr << "Error: " << base_name << ".anc has other haplotypes (or sample ages) than the first chromosome's." << std::endl;
@@ -874,32 +845,17 @@ int condcoal_tables(const Options& opt, const std::vector<CcJob>& jobs, bool pai
         if (c.factor[k] == 0.0f) {
           c.factor[k] = -1.0f;  // (a weight-0 last tree: only the extra pass adds anything)
         } else {
-          const int x = c.append(N);
-          std::memcpy(c.parent.data() + (size_t)x * nn, c.parent.data() + k * nn, sizeof(int) * nn);
-          std::memcpy(c.bl.data() + (size_t)x * nn, c.bl.data() + k * nn, sizeof(double) * nn);
-          std::memcpy(c.lo.data() + (size_t)x * nn, c.lo.data() + k * nn, sizeof(int) * nn);
-          std::memcpy(c.hi.data() + (size_t)x * nn, c.hi.data() + k * nn, sizeof(int) * nn);
-          std::memcpy(c.leaf.data() + (size_t)x * N, c.leaf.data() + k * N, sizeof(int) * N);
+          const int x = c.append_copy((int)k);  // (its block is the last tree's too)
           c.factor[x] = -1.0f;
-          c.block[x] = plan.back().bin;
         }
       }
       lines.clear();
       which.clear();
       t_parse += now_s() - tp;
       const double tw = now_s();
-      if (dev) {
-        if (!dev->submit(c)) {
-          err = dev->error();
-          return false;
-        }
-      } else if (pdev) {
-        if (!pdev->submit(c)) {
-          err = pdev->error();
-          return false;
-        }
-      } else {
-        for (size_t k = 0; k < P; k++) host_accumulate(runs[k], c, acc[k]);
+      if (!walker->submit(c)) {
+        err = walker->error();
+        return false;
       }
       t_walk += now_s() - tw;
       return true;
@@ -933,27 +889,14 @@ int condcoal_tables(const Options& opt, const std::vector<CcJob>& jobs, bool pai
     chr_bin = bin + 1;
   }
   const double tw = now_s();
-  if (dev && !dev->finish(acc[0])) {
-    std::cerr << "Error: " << dev->error() << std::endl;
+  CcTables acc;  // [table][block][slots]
+  if (!walker->finish(acc)) {
+    std::cerr << "Error: " << walker->error() << std::endl;
     return 1;
   }
-  if (pdev) {
-    std::vector<std::vector<double>> all;  // [block][table][slots]
-    if (!pdev->finish(all)) {
-      std::cerr << "Error: " << pdev->error() << std::endl;
-      return 1;
-    }
-    const size_t S = base.slots();
-    for (size_t k = 0; k < P; k++) {
-      acc[k].resize(all.size());
-      for (size_t b = 0; b < all.size(); b++)
-        if (!all[b].empty()) acc[k][b].assign(all[b].begin() + k * S, all[b].begin() + (k + 1) * S);
-    }
-  }
   t_walk += now_s() - tw;
-  const double gpu_s = dev ? dev->gpu_seconds() : pdev ? pdev->gpu_seconds() : 0.0;
-  dev.reset();
-  pdev.reset();
+  const double gpu_s = walker->gpu_seconds();
+  walker.reset();
 
   // bootstrap and tables (coal.cpp:5513-5568), float as there
   const double t_out = now_s();

@@ -1,8 +1,10 @@
 // colate_amd/csrc/condcoal.h -- `Colate --mode CondCoalRates` inside libcolate_amd.so: what the host side (condcoal.cpp:
-// readers, tree preparation, host twin, bootstrap and writer) and the device side (condcoal_kernel.hip) share.
+// readers, tree preparation, host twin, bootstrap and writer) and the device side (condcoal_kernel.hip,
+// condcoal_pairs_kernel.hip; their common plumbing is condcoal_device.hpp) share.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -45,69 +47,58 @@ struct CcChunk {
   }
   // room for one more tree; returns its index
   int append(int n);
+  // a copy of tree k at the end; returns its index
+  int append_copy(int k);
 };
 
 // Checks one tree (2N-1 nodes, leaves 0..N-1 without children, every internal node with two children, the one root at
 // 2N-2, every node below it) and fills its DFS leaf ranges and order.  False with a message otherwise.
 bool prepare_tree(int N, const int* parent, int* lo, int* hi, int* leaf, std::string& err);
 
-// The host twin: adds the chunk's trees into acc[block][slots] (acc grows to the largest block).
-void host_accumulate(const CcRun& run, const CcChunk& c, std::vector<std::vector<double>>& acc);
+// The per-block sums of a run's tables: [table][block][slots], a block without trees empty.
+using CcTables = std::vector<std::vector<std::vector<double>>>;
 
-// The device side (condcoal_kernel.hip).  Chunks go in asynchronously (the caller prepares the next one meanwhile);
-// each tree's accumulators come back and are added into acc[block] in tree order at finish() (bit for bit reproducible).
-class CcDevice {
+// One way to walk: the trees of a run go in chunk by chunk, the per-block sums come out.  Every implementation sums in the
+// same order (per lane or focal haplotype in walk order, per tree over the focal haplotypes ascending, per block over the
+// trees in input order), so their tables agree bit for bit.
+class CcWalker {
  public:
-  // null, and the reason in `why`, when there is no device or the run does not fit (device -1: the calling thread's)
-  static CcDevice* create(int device, const CcRun& run, int max_trees, std::string& why);
-  ~CcDevice();
-  bool submit(const CcChunk& c);
-  bool finish(std::vector<std::vector<double>>& acc);
+  virtual ~CcWalker() = default;
+  virtual bool submit(const CcChunk& c) = 0;
+  virtual bool finish(CcTables& acc) = 0;  // one entry per table
   const std::string& error() const { return err_; }
   int error_code() const { return code_; }
-  double gpu_seconds() const { return gpu_s_; }
+  double gpu_seconds() const { return gpu_s_; }  // kernel time by events (0 for the host twin)
+
+ protected:
+  bool fail(const std::string& what, int code) {
+    err_ = what;
+    code_ = code;
+    return false;
+  }
+  double gpu_s_ = 0;
 
  private:
-  CcDevice() = default;
-  bool fail(const char* what, int code);
-  bool drain(int slot);
-  struct Impl;
-  Impl* p_ = nullptr;
   std::string err_;
   int code_ = 0;
-  double gpu_s_ = 0;
 };
 
-// The walks of many (focal group, conditional group) pairs on the device (condcoal_pairs_kernel.hip): one prefix pass per
-// tree serves every pair, and the (pair, focal haplotype) lanes of several pairs share a workgroup.  Each pair's sums are
-// the single path's (CcDevice), in the same order: per lane in walk order, per (tree, pair) over the pair's focal
-// haplotypes ascending, per (block, pair) over the trees in input order.  The per-block sums stay on the device while
-// the block is open; trees arrive in non-decreasing block order, and a block comes back when it closes.
-class CcPairsDevice {
- public:
-  // base: N, G, group, ages, epochs, efocal (its focal / is_cond are not read); cond_group -1: the empty group.
-  static CcPairsDevice* create(int device, const CcRun& base, const std::vector<int>& focal_group,
-                               const std::vector<int>& cond_group, int max_trees, std::string& why);
-  ~CcPairsDevice();
-  bool submit(const CcChunk& c);
-  // acc[block]: [P][slots] (empty for a block without trees)
-  bool finish(std::vector<std::vector<double>>& acc);
-  const std::string& error() const { return err_; }
-  int error_code() const { return code_; }
-  double gpu_seconds() const { return gpu_s_; }
-  // device bytes of results per tree of a chunk (for chunk_trees_for)
-  static size_t per_tree_bytes(int N, int G, int P, int slots);
+// The host twin: one table per run, each walked on the calling thread.
+std::unique_ptr<CcWalker> make_host_walker(std::vector<CcRun> runs);
 
- private:
-  CcPairsDevice() = default;
-  bool fail(const char* what, int code);
-  bool drain(int slot);
-  bool launch(const CcChunk& c, int t0, int t1);
-  struct Impl;
-  Impl* p_ = nullptr;
-  std::string err_;
-  int code_ = 0;
-  double gpu_s_ = 0;
-};
+// The device side.  Chunks of at most max_trees trees go in asynchronously (the caller prepares the next one meanwhile).
+// Null, and the reason in `why`, when there is no device or the run does not fit (device -1: the calling thread's).
+//   * one table (condcoal_kernel.hip): each tree's accumulators come back and are added into their block in tree order at
+//     finish(); the trees' blocks may come in any order.
+//   * one table per (focal group, conditional group) pair (condcoal_pairs_kernel.hip; cond_group -1: the empty group): one
+//     prefix pass per tree serves every pair, and the (pair, focal haplotype) lanes of several pairs share a workgroup.  Each
+//     pair's sums are the single walker's, in the same order.  The per-block sums stay on the device while the block is open;
+//     trees arrive in non-decreasing block order, and a block comes back when it closes.  base: N, G, group, ages, epochs,
+//     efocal (its focal / is_cond are not read).
+std::unique_ptr<CcWalker> make_device_walker(int device, const CcRun& run, int max_trees, std::string& why);
+std::unique_ptr<CcWalker> make_pairs_device_walker(int device, const CcRun& base, const std::vector<int>& focal_group,
+                                                   const std::vector<int>& cond_group, int max_trees, std::string& why);
+// device bytes of results per tree of a chunk of the pairs walker (for chunk_trees_for)
+size_t pairs_per_tree_bytes(int N, int G, int P, int slots);
 
 }  // namespace colate_cc

@@ -154,43 +154,6 @@ void print_help() {
 // ------------------------------------------------------------------ stage timing (COLATE_TIMING=1: one stderr line at the end)
 StageTimes g_times;
 
-// ------------------------------------------------------------------ gz text
-// igzstream semantics of the reference: zlib reads gzip and plain files alike.
-class GzText {
- public:
-  bool open(const std::string& name) {
-    close();
-    f_ = gzopen(name.c_str(), "rb");
-    if (f_) gzbuffer(f_, 1 << 20);
-    return f_ != nullptr;
-  }
-  bool is_open() const { return f_ != nullptr; }
-  bool getline(std::string& line) {
-    line.clear();
-    if (!f_) return false;
-    char buf[1 << 14];
-    bool got = false;
-    while (gzgets(f_, buf, sizeof(buf))) {
-      got = true;
-      size_t n = std::strlen(buf);
-      if (n && buf[n - 1] == '\n') {
-        line.append(buf, n - 1);
-        return true;
-      }
-      line.append(buf, n);
-    }
-    return got;
-  }
-  void close() {
-    if (f_) gzclose(f_);
-    f_ = nullptr;
-  }
-  ~GzText() { close(); }
-
- private:
-  gzFile f_ = nullptr;
-};
-
 // ------------------------------------------------------------------ .mut rows
 
 // (the readers run on their own threads: leave without running the static destructors under the other threads' feet)

@@ -4,8 +4,11 @@
 // section 8 f2 / BASELINE configs[4], which fills every table of a `--pairs` run and of a single pair, and hands a pair it cannot
 // fill exactly to the sequential feeder).
 #pragma once
+#include <zlib.h>
+
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <random>
@@ -28,6 +31,42 @@ struct StageTimes {
   static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 };
 extern StageTimes g_times;
+
+// igzstream semantics of the reference: zlib reads gzip and plain files alike.
+class GzText {
+ public:
+  bool open(const std::string& name) {
+    close();
+    f_ = gzopen(name.c_str(), "rb");
+    if (f_) gzbuffer(f_, 1 << 20);
+    return f_ != nullptr;
+  }
+  bool is_open() const { return f_ != nullptr; }
+  bool getline(std::string& line) {
+    line.clear();
+    if (!f_) return false;
+    char buf[1 << 14];
+    bool got = false;
+    while (gzgets(f_, buf, sizeof(buf))) {
+      got = true;
+      size_t n = std::strlen(buf);
+      if (n && buf[n - 1] == '\n') {
+        line.append(buf, n - 1);
+        return true;
+      }
+      line.append(buf, n);
+    }
+    return got;
+  }
+  void close() {
+    if (f_) gzclose(f_);
+    f_ = nullptr;
+  }
+  ~GzText() { close(); }
+
+ private:
+  gzFile f_ = nullptr;
+};
 
 // Only the columns parse_tmptmp looks at (mutations.cpp:77-246):
 // snp;pos;dist;rs;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;anc/der;...

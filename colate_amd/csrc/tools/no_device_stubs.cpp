@@ -92,23 +92,13 @@ bool DeviceFill::fail(const char*, int) { return false; }
 // the CondCoalRates walks on the device (condcoal.h): none in this build, the host twin walks
 #include "condcoal.h"
 namespace colate_cc {
-CcDevice* CcDevice::create(int, const CcRun&, int, std::string& why) {
+std::unique_ptr<CcWalker> make_device_walker(int, const CcRun&, int, std::string& why) {
   why = "built without a device";
   return nullptr;
 }
-CcDevice::~CcDevice() {}
-bool CcDevice::submit(const CcChunk&) { return false; }
-bool CcDevice::finish(std::vector<std::vector<double>>&) { return false; }
-bool CcDevice::fail(const char*, int) { return false; }
-bool CcDevice::drain(int) { return false; }
-CcPairsDevice* CcPairsDevice::create(int, const CcRun&, const std::vector<int>&, const std::vector<int>&, int, std::string& why) {
+std::unique_ptr<CcWalker> make_pairs_device_walker(int, const CcRun&, const std::vector<int>&, const std::vector<int>&, int,
+                                                   std::string& why) {
   why = "built without a device";
   return nullptr;
 }
-CcPairsDevice::~CcPairsDevice() {}
-bool CcPairsDevice::submit(const CcChunk&) { return false; }
-bool CcPairsDevice::finish(std::vector<std::vector<double>>&) { return false; }
-bool CcPairsDevice::fail(const char*, int) { return false; }
-bool CcPairsDevice::drain(int) { return false; }
-bool CcPairsDevice::launch(const CcChunk&, int, int) { return false; }
 }  // namespace colate_cc
