@@ -18,14 +18,13 @@
 
 #include "colate_amd.h"
 #include "colate_internal.h"
+#include "em_job.hpp"
 
 static_assert(COLATE_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
 
 namespace {
 
-using colate::check_grids;
-using colate::ensure_device;
-using colate::fail;
+using namespace colate;
 
 struct Rccl {
   void* handle = nullptr;
@@ -74,16 +73,11 @@ int rccl_ready() {
     ncclResult_t r_ = (expr);                                                                  \
     if (r_ != ncclSuccess) return fail(COLATE_EHIP, "%s: %s", #expr, rccl().GetErrorString(r_)); \
   } while (0)
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess) return fail(COLATE_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 struct Comm {
   ncclComm_t nccl = nullptr;
   int nranks = 1, rank = 0, device = 0;
-  hipStream_t stream = nullptr;
+  ArenaStore store;  // the rank's inputs and scratch (em_job.hpp); its stream is the communicator's
   char* d_send = nullptr;
   char* d_recv = nullptr;
   size_t cap = 0;  // bytes per rank the two buffers are sized for
@@ -120,53 +114,58 @@ int reserve_host(Comm* c, size_t per_rank) {
   return COLATE_OK;
 }
 
-// Run `local(n, lo, d_rates, d_ll, d_iters, d_flags, stream)` for this rank's replicates [lo, lo+n) with the four
-// outputs placed directly in the send buffer, all-gather, and scatter every rank's part into the caller's arrays.
-template <typename Local>
-int run_and_gather(Comm* c, int B, int E, double* out_rates, int* out_iters, double* out_loglik, int* out_flags,
-                   Local&& local) {
+// Run this rank's rows [lo, hi) of the job on the communicator's arena with the four outputs placed directly in the send
+// buffer, all-gather, and scatter every rank's part into the job's output arrays.  `early`: what this rank already
+// found wrong with its own inputs (message in colate_last_error()).
+int run_and_gather(Comm* c, const EmJob& job, int early = COLATE_OK) {
+  const std::string early_msg = early ? colate_last_error() : "";
+  if (int rc = ensure_device()) return rc;
+  if (job.R == 0) return COLATE_OK;
   // Everything that can fail on THIS rank before the collective is turned into `local_rc`, and the rank still joins the
   // all-gather with its code in the trailing slot: a rank that returned early would leave the others waiting in
   // ncclAllGather forever.  The one exception is a rank that cannot even get its two device buffers (or its device): it
   // has nothing to join with and returns -- `Colate --ranks` (run_ranked) then ends the remaining ranks after a grace
   // period; a host that drives the ranks itself needs the same watchdog.
   HIP_TRY(hipSetDevice(c->device));
+  const int B = job.R, E = job.E;
+  const hipStream_t stream = c->store.stream;
   const int n_max = (B + c->nranks - 1) / c->nranks;
   const size_t per_rank = packed_bytes(n_max, E);
   if (int rc = reserve_device(c, per_rank)) return rc;
   int local_rc = reserve_host(c, per_rank);
   int lo = 0, hi = 0;
   colate_shard_bounds(B, c->nranks, c->rank, &lo, &hi);
-  auto carve = [&](char* base, double*& rates, double*& ll, int*& iters, int*& flags) {
-    rates = reinterpret_cast<double*>(base);
-    ll = rates + (size_t)n_max * E;
-    iters = reinterpret_cast<int*>(ll + n_max);
-    flags = iters + n_max;
+  auto carve = [&](char* base) {
+    RowOut o;
+    o.rates = reinterpret_cast<double*>(base);
+    o.loglik = o.rates + (size_t)n_max * E;
+    o.iters = reinterpret_cast<int*>(o.loglik + n_max);
+    o.flags = o.iters + n_max;
+    return o;
   };
-  double *d_rates, *d_ll;
-  int *d_iters, *d_flags;
-  carve(c->d_send, d_rates, d_ll, d_iters, d_flags);
   if (!local_rc) {  // rows of a short shard beyond its n stay zero
-    const hipError_t e = hipMemsetAsync(c->d_send, 0, per_rank, c->stream);
-    if (e != hipSuccess) local_rc = fail(COLATE_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    const hipError_t e = hipMemsetAsync(c->d_send, 0, per_rank, stream);
+    if (e != hipSuccess) local_rc = hip_fail(e, "hipMemsetAsync");
   }
 #ifdef COLATE_TEST_HOOKS  // (only in lib/testhooks/libcolate_amd.so: failure injection for the tests of exactly this path)
   if (const char* inj = getenv("COLATE_TEST_FAIL_RANK")) {
     if (atoi(inj) == c->rank) local_rc = fail(COLATE_EHIP, "injected failure on rank %d (COLATE_TEST_FAIL_RANK)", c->rank);
   }
 #endif
+  Arena arena(c->store);
+  int status = 0;  // the bootstrap kernel's status word, read back after the collective
   if (!local_rc && hi > lo) {
-    colate::ProfRange range("colate shard: bootstrap + EM on this rank's replicates");
-    local_rc = local(hi - lo, lo, d_rates, d_ll, d_iters, d_flags, c->stream);
+    ProfRange range("colate shard: bootstrap + EM on this rank's replicates");
+    local_rc = early ? fail(early, "%s", early_msg.c_str()) : enqueue_rows(job, lo, hi, arena, &status, carve(c->d_send));
   }
   std::string local_msg = local_rc ? colate_last_error() : "";
-  if (local_rc) (void)hipMemcpyAsync(c->d_send + per_rank - 8, &local_rc, sizeof(int), hipMemcpyHostToDevice, c->stream);
+  if (local_rc) (void)hipMemcpyAsync(c->d_send + per_rank - 8, &local_rc, sizeof(int), hipMemcpyHostToDevice, stream);
   // the ONE collective of the path: per_rank bytes from every rank to every rank
-  colate::ProfRange gather_range("colate all-gather of the packed results (RCCL)");
-  NCCL_TRY(rccl().AllGather(c->d_send, c->d_recv, per_rank, ncclChar, c->nccl, c->stream));
+  ProfRange gather_range("colate all-gather of the packed results (RCCL)");
+  NCCL_TRY(rccl().AllGather(c->d_send, c->d_recv, per_rank, ncclChar, c->nccl, stream));
   if (c->h_recv && c->hcap >= per_rank * c->nranks)
-    HIP_TRY(hipMemcpyAsync(c->h_recv, c->d_recv, per_rank * c->nranks, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_recv, c->d_recv, per_rank * c->nranks, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
   if (local_rc) return fail(local_rc, "%s", local_msg.c_str());  // this rank's own message
   for (int r = 0; r < c->nranks; r++) {
     int code = 0;
@@ -177,33 +176,14 @@ int run_and_gather(Comm* c, int B, int E, double* out_rates, int* out_iters, dou
     int rlo = 0, rhi = 0;
     colate_shard_bounds(B, c->nranks, r, &rlo, &rhi);
     const size_t n = (size_t)(rhi - rlo);
-    double *h_rates, *h_ll;
-    int *h_iters, *h_flags;
-    carve(c->h_recv + (size_t)r * per_rank, h_rates, h_ll, h_iters, h_flags);
-    std::memcpy(out_rates + (size_t)rlo * E, h_rates, n * E * sizeof(double));
-    std::memcpy(out_loglik + rlo, h_ll, n * sizeof(double));
-    std::memcpy(out_iters + rlo, h_iters, n * sizeof(int));
-    std::memcpy(out_flags + rlo, h_flags, n * sizeof(int));
+    const RowOut h = carve(c->h_recv + (size_t)r * per_rank);
+    std::memcpy(job.out_rates + (size_t)rlo * E, h.rates, n * E * sizeof(double));
+    std::memcpy(job.out_loglik + rlo, h.loglik, n * sizeof(double));
+    std::memcpy(job.out_iters + rlo, h.iters, n * sizeof(int));
+    std::memcpy(job.out_flags + rlo, h.flags, n * sizeof(int));
   }
-  return COLATE_OK;
+  return finish_rows(arena, status);
 }
-
-// device copies of host arrays that live for one call
-struct Upload {
-  std::vector<void*> ptrs;
-  ~Upload() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <typename T>
-  int put(const T* host, size_t n, T** dev, hipStream_t s) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, n * sizeof(T) + 8));
-    ptrs.push_back(p);
-    if (host) HIP_TRY(hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    *dev = static_cast<T*>(p);
-    return COLATE_OK;
-  }
-};
 
 }  // namespace
 
@@ -236,14 +216,15 @@ int colate_comm_create(const void* id, int nranks, int rank, void** comm) {
   ncclUniqueId u;
   std::memcpy(&u, id, sizeof(u));
   hipError_t e = hipGetDevice(&c->device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->store.stream, hipStreamNonBlocking);
+  c->store.device = c->device;
   if (e != hipSuccess) {
     delete c;
     return fail(COLATE_ENODEVICE, "colate_comm_create: %s", hipGetErrorString(e));
   }
   ncclResult_t r = rccl().CommInitRank(&c->nccl, nranks, u, rank);
   if (r != ncclSuccess) {
-    (void)hipStreamDestroy(c->stream);
+    c->store.release();
     delete c;
     return fail(COLATE_EHIP, "ncclCommInitRank: %s", rccl().GetErrorString(r));
   }
@@ -256,7 +237,7 @@ int colate_comm_destroy(void* comm) {
   if (!c) return COLATE_OK;
   (void)hipSetDevice(c->device);
   if (c->nccl) (void)rccl().CommDestroy(c->nccl);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  c->store.release();
   if (c->d_send) (void)hipFree(c->d_send);
   if (c->d_recv) (void)hipFree(c->d_recv);
   if (c->h_recv) (void)hipHostFree(c->h_recv);
@@ -268,29 +249,12 @@ int colate_em_batch_allgather(void* comm, int B, int E, int A, const double* age
                               const double* cnt_notshared, const double* epochs, const double* init_rates,
                               int max_iter, int min_iter, double rel_tol, double rate_floor, double* out_rates,
                               int* out_iters, double* out_loglik, int* out_flags) {
-  Comm* c = static_cast<Comm*>(comm);
-  if (!age_grid || !cnt_shared || !cnt_notshared || !epochs || !init_rates || !out_rates || !out_iters ||
-      !out_loglik || !out_flags)
-    return fail(COLATE_EINVAL, "NULL pointer argument");
-  if (B < 0 || E < 1 || A < 1 || E > COLATE_MAX_EPOCHS || A > COLATE_MAX_AGE_BINS)
-    return fail(COLATE_EINVAL, "bad sizes B=%d E=%d A=%d", B, E, A);
-  // (the same inputs on every rank: a bad grid is refused by all of them alike, none enters the collective)
-  if (int rc = check_grids(E, A, age_grid, epochs)) return rc;
-  if (!c) return fail(COLATE_EINVAL, "NULL communicator");
-  if (int rc = ensure_device()) return rc;
-  if (B == 0) return COLATE_OK;
-  Upload up;
-  return run_and_gather(c, B, E, out_rates, out_iters, out_loglik, out_flags,
-                        [&](int n, int lo, double* d_rates, double* d_ll, int* d_iters, int* d_flags, hipStream_t s) {
-                          double *d_grid, *d_sh, *d_ns, *d_ep, *d_init;
-                          if (int rc = up.put(age_grid, A, &d_grid, s)) return rc;
-                          if (int rc = up.put(cnt_shared + (size_t)lo * A, (size_t)n * A, &d_sh, s)) return rc;
-                          if (int rc = up.put(cnt_notshared + (size_t)lo * A, (size_t)n * A, &d_ns, s)) return rc;
-                          if (int rc = up.put(epochs, E, &d_ep, s)) return rc;
-                          if (int rc = up.put(init_rates, E, &d_init, s)) return rc;
-                          return colate_em_batch_device(n, E, A, d_grid, d_sh, d_ns, d_ep, 0, d_init, 0, max_iter, min_iter,
-                                                        rel_tol, rate_floor, d_rates, d_iters, d_ll, d_flags, s);
-                        });
+  const EmJob j = tables_job(EmJob::kShared, B, E, A, age_grid, cnt_shared, cnt_notshared, epochs, init_rates, max_iter,
+                             min_iter, rel_tol, rate_floor, out_rates, out_iters, out_loglik, out_flags);
+  // (the same inputs on every rank: bad ones are refused by all of them alike, none enters the collective)
+  if (int rc = check(j)) return rc;
+  if (!comm) return fail(COLATE_EINVAL, "NULL communicator");
+  return run_and_gather(static_cast<Comm*>(comm), j);
 }
 
 int colate_bootstrap_em_batch_allgather(void* comm, int B, int nb, int E, int A, const double* age_grid, double age,
@@ -299,48 +263,12 @@ int colate_bootstrap_em_batch_allgather(void* comm, int B, int nb, int E, int A,
                                         const double* init_rates, int max_iter, int min_iter, double rel_tol,
                                         double rate_floor, double* out_rates, int* out_iters, double* out_loglik,
                                         int* out_flags) {
-  Comm* c = static_cast<Comm*>(comm);
-  if (!age_grid || !weights || !sh_block || !ns_block || !sh_emp_block || !ns_emp_block || !epochs ||
-      !init_rates || !out_rates || !out_iters || !out_loglik || !out_flags)
-    return fail(COLATE_EINVAL, "NULL pointer argument");
-  if (B < 0 || nb < 1 || E < 1 || A < 2 || E > COLATE_MAX_EPOCHS || A > COLATE_MAX_AGE_BINS)
-    return fail(COLATE_EINVAL, "bad sizes B=%d nb=%d E=%d A=%d", B, nb, E, A);
-  if (int rc = check_grids(E, A, age_grid, epochs)) return rc;
-  if (!c) return fail(COLATE_EINVAL, "NULL communicator");
-  if (int rc = ensure_device()) return rc;
-  if (B == 0) return COLATE_OK;
-  Upload up;
-  int* d_status = nullptr;
-  int rc = run_and_gather(
-      c, B, E, out_rates, out_iters, out_loglik, out_flags,
-      [&](int n, int lo, double* d_rates, double* d_ll, int* d_iters, int* d_flags, hipStream_t s) {
-        const size_t nT = (size_t)nb * A;
-        double *d_grid, *d_w, *d_t0, *d_t1, *d_t2, *d_t3, *d_ep, *d_init, *d_sh, *d_ns;
-        const int zero = 0;
-        if (int r = up.put(age_grid, A, &d_grid, s)) return r;
-        if (int r = up.put(weights + (size_t)lo * nb, (size_t)n * nb, &d_w, s)) return r;  // this rank's rows of w[B][nb]
-        if (int r = up.put(sh_block, nT, &d_t0, s)) return r;
-        if (int r = up.put(ns_block, nT, &d_t1, s)) return r;
-        if (int r = up.put(sh_emp_block, nT, &d_t2, s)) return r;
-        if (int r = up.put(ns_emp_block, nT, &d_t3, s)) return r;
-        if (int r = up.put(epochs, E, &d_ep, s)) return r;
-        if (int r = up.put(init_rates, E, &d_init, s)) return r;
-        if (int r = up.put<double>(nullptr, (size_t)n * A, &d_sh, s)) return r;
-        if (int r = up.put<double>(nullptr, (size_t)n * A, &d_ns, s)) return r;
-        if (int r = up.put(&zero, 1, &d_status, s)) return r;
-        HIP_TRY(hipStreamSynchronize(s));  // (`zero` leaves scope)
-        if (int r = colate_bootstrap_counts_device(n, nb, A, d_grid, age, d_w, d_t0, d_t1, d_t2, d_t3, d_sh, d_ns, d_status, s))
-          return r;
-        return colate_em_batch_device(n, E, A, d_grid, d_sh, d_ns, d_ep, 0, d_init, 0, max_iter, min_iter, rel_tol,
-                                      rate_floor, d_rates, d_iters, d_ll, d_flags, s);
-      });
-  if (rc) return rc;
-  if (d_status) {
-    int status = 0;
-    HIP_TRY(hipMemcpy(&status, d_status, sizeof(int), hipMemcpyDeviceToHost));
-    if (status) return fail(COLATE_EINVAL, "sample age outside the age grid");
-  }
-  return COLATE_OK;
+  const EmJob j = genome_job(B, nb, E, A, age_grid, age, weights, sh_block, ns_block, sh_emp_block, ns_emp_block, epochs,
+                             init_rates, max_iter, min_iter, rel_tol, rate_floor, out_rates, out_iters, out_loglik,
+                             out_flags);
+  if (int rc = check(j)) return rc;
+  if (!comm) return fail(COLATE_EINVAL, "NULL communicator");
+  return run_and_gather(static_cast<Comm*>(comm), j);
 }
 
 int colate_bootstrap_em_batch_groups_allgather(void* comm, int G, int B, int group_first, int group_count, int E, int A,
@@ -351,14 +279,15 @@ int colate_bootstrap_em_batch_groups_allgather(void* comm, int G, int B, int gro
                                                int min_iter, double rel_tol, double rate_floor, double* out_rates,
                                                int* out_iters, double* out_loglik, int* out_flags) {
   Comm* c = static_cast<Comm*>(comm);
-  if (!c) return fail(COLATE_EINVAL, "NULL communicator");
-  if (G < 0 || B < 1 || E < 1 || A < 2 || E > COLATE_MAX_EPOCHS || A > COLATE_MAX_AGE_BINS || (long long)G * B > 0x7fffffffLL)
+  if (G < 0 || B < 1 || (long long)G * B > 0x7fffffffLL)
     return fail(COLATE_EINVAL, "bad sizes G=%d B=%d E=%d A=%d", G, B, E, A);
-  if (!age_grid || !out_rates || !out_iters || !out_loglik || !out_flags) return fail(COLATE_EINVAL, "NULL pointer argument");
-  if (max_iter < 1) return fail(COLATE_EINVAL, "max_iter must be >= 1");
-  const int R = G * B;
+  const EmJob j = groups_job(G, B, group_first, group_count, E, A, age_grid, group_nb, group_age, weights, sh_block,
+                             ns_block, sh_emp_block, ns_emp_block, epochs, init_rates, max_iter, min_iter, rel_tol,
+                             rate_floor, out_rates, out_iters, out_loglik, out_flags);
+  if (int rc = check_call(j)) return rc;  // (what every rank is given alike)
+  if (!c) return fail(COLATE_EINVAL, "NULL communicator");
   int lo = 0, hi = 0;
-  colate_shard_bounds(R, c->nranks, c->rank, &lo, &hi);
+  colate_shard_bounds(j.R, c->nranks, c->rank, &lo, &hi);
   // A rank with rows must bring exactly the groups they belong to.  A mismatch is this rank's own error and is found on
   // its inputs alone, but the other ranks may be fine: it joins the collective with its code (run_and_gather) instead of
   // leaving them waiting.
@@ -367,68 +296,10 @@ int colate_bootstrap_em_batch_groups_allgather(void* comm, int G, int B, int gro
     if (group_first != lo / B || group_count != (hi - 1) / B - lo / B + 1)
       early = fail(COLATE_EINVAL, "rank %d computes rows [%d, %d) = groups [%d, %d], but was given groups [%d, %d)", c->rank, lo, hi,
                    lo / B, (hi - 1) / B, group_first, group_first + group_count);
-    else if (!group_nb || !group_age || !weights || !sh_block || !ns_block || !sh_emp_block || !ns_emp_block || !epochs || !init_rates)
-      early = fail(COLATE_EINVAL, "NULL pointer argument");
-    for (int g = 0; g < group_count && !early; g++) {
-      if (group_nb[g] < 1) early = fail(COLATE_EINVAL, "group %d has %d genome blocks", group_first + g, group_nb[g]);
-      if (!early) early = check_grids(E, A, age_grid, epochs + (size_t)g * E);
-    }
+    else
+      early = check_inputs(j);
   }
-  const std::string early_msg = early ? colate_last_error() : "";
-  if (int rc = ensure_device()) return rc;
-  if (R == 0) return COLATE_OK;
-  Upload up;
-  int* d_status = nullptr;
-  int rc = run_and_gather(
-      c, R, E, out_rates, out_iters, out_loglik, out_flags,
-      [&](int n, int row_lo, double* d_rates, double* d_ll, int* d_iters, int* d_flags, hipStream_t s) {
-        if (early) return fail(early, "%s", early_msg.c_str());
-        std::vector<long long> block_off(group_count), weight_off(group_count);
-        long long nblocks = 0, nweights = 0;
-        for (int g = 0; g < group_count; g++) {
-          block_off[g] = nblocks, weight_off[g] = nweights;
-          nblocks += group_nb[g], nweights += (long long)B * group_nb[g];
-        }
-        const size_t nT = (size_t)nblocks * A;
-        std::vector<double> row_ep((size_t)n * E), row_init((size_t)n * E);
-        for (int r = 0; r < n; r++) {
-          const size_t g = (size_t)((row_lo + r) / B - group_first);
-          std::memcpy(row_ep.data() + (size_t)r * E, epochs + g * E, (size_t)E * sizeof(double));
-          std::memcpy(row_init.data() + (size_t)r * E, init_rates + g * E, (size_t)E * sizeof(double));
-        }
-        double *d_grid, *d_w, *d_t0, *d_t1, *d_t2, *d_t3, *d_ep, *d_init, *d_sh, *d_ns, *d_age;
-        int* d_nb;
-        long long *d_bo, *d_wo;
-        const int zero = 0;
-        if (int r = up.put(age_grid, A, &d_grid, s)) return r;
-        if (int r = up.put(weights, (size_t)nweights, &d_w, s)) return r;
-        if (int r = up.put(sh_block, nT, &d_t0, s)) return r;
-        if (int r = up.put(ns_block, nT, &d_t1, s)) return r;
-        if (int r = up.put(sh_emp_block, nT, &d_t2, s)) return r;
-        if (int r = up.put(ns_emp_block, nT, &d_t3, s)) return r;
-        if (int r = up.put(group_nb, group_count, &d_nb, s)) return r;
-        if (int r = up.put(block_off.data(), group_count, &d_bo, s)) return r;
-        if (int r = up.put(weight_off.data(), group_count, &d_wo, s)) return r;
-        if (int r = up.put(group_age, group_count, &d_age, s)) return r;
-        if (int r = up.put(row_ep.data(), (size_t)n * E, &d_ep, s)) return r;
-        if (int r = up.put(row_init.data(), (size_t)n * E, &d_init, s)) return r;
-        if (int r = up.put<double>(nullptr, (size_t)n * A, &d_sh, s)) return r;
-        if (int r = up.put<double>(nullptr, (size_t)n * A, &d_ns, s)) return r;
-        if (int r = up.put(&zero, 1, &d_status, s)) return r;
-        HIP_TRY(hipStreamSynchronize(s));  // (the host vectors of this scope leave it)
-        if (int r = colate_bootstrap_counts_groups_device(group_count, B, group_first, row_lo, row_lo + n, A, d_grid, d_nb, d_bo, d_wo,
-                                                          d_age, d_w, d_t0, d_t1, d_t2, d_t3, d_sh, d_ns, d_status, s))
-          return r;
-        return colate_em_batch_device(n, E, A, d_grid, d_sh, d_ns, d_ep, 1, d_init, 1, max_iter, min_iter, rel_tol, rate_floor,
-                                      d_rates, d_iters, d_ll, d_flags, s);
-      });
-  if (rc) return rc;
-  if (d_status) {
-    int status = 0;
-    HIP_TRY(hipMemcpy(&status, d_status, sizeof(int), hipMemcpyDeviceToHost));
-    if (status) return fail(COLATE_EINVAL, "sample age outside the age grid");
-  }
-  return COLATE_OK;
+  return run_and_gather(c, j, early);
 }
 
 }  // extern "C"

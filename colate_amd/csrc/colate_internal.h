@@ -1,5 +1,7 @@
 // colate_amd/csrc/colate_internal.h -- shared between the translation units of libcolate_amd.so
 #pragma once
+#include <cstddef>
+#include <cstring>
 namespace colate {
 // records the message for colate_last_error() and returns `code`
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -20,4 +22,10 @@ struct ProfRange {
   ProfRange(const ProfRange&) = delete;
   ProfRange& operator=(const ProfRange&) = delete;
 };
+// rows [lo, hi) of a per-group [.][E] array (its first row is group `group_first`; row r belongs to group r / B) as
+// the per-row [hi - lo][E] array the EM kernel reads
+inline void expand_group_rows(const double* per_group, int B, int group_first, long lo, long hi, int E, double* per_row) {
+  for (long r = lo; r < hi; r++)
+    std::memcpy(per_row + (size_t)(r - lo) * E, per_group + (size_t)(r / B - group_first) * E, (size_t)E * sizeof(double));
+}
 }  // namespace colate

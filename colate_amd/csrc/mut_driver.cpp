@@ -1144,10 +1144,8 @@ int run_mut_pairs(const Options& opt) {
                                                   g_ns.data() + (size_t)bo * A, g_she.data() + (size_t)bo * A, g_nse.data() + (size_t)bo * A,
                                                   csh.data() + (size_t)g * B * A, cns.data() + (size_t)g * B * A);
       std::vector<double> r_ep(R * E), r_init(R * E);
-      for (size_t r = 0; r < R; r++) {
-        std::copy(g_ep.begin() + (r / B) * E, g_ep.begin() + (r / B + 1) * E, r_ep.begin() + r * E);
-        std::copy(g_init.begin() + (r / B) * E, g_init.begin() + (r / B + 1) * E, r_init.begin() + r * E);
-      }
+      colate::expand_group_rows(g_ep.data(), (int)B, 0, 0, (long)R, E, r_ep.data());
+      colate::expand_group_rows(g_init.data(), (int)B, 0, 0, (long)R, E, r_init.data());
       if (!rc)
         rc = colate_em_batch_rows_sharded((int)dev_list.size(), dev_list.data(), (int)R, E, A, age_grid.data(), csh.data(), cns.data(),
                                           r_ep.data(), r_init.data(), COLATE_DEFAULT_MAX_ITER, COLATE_DEFAULT_MIN_ITER,

@@ -461,6 +461,66 @@ def test_allgather_entry_points_check_their_grids():
     assert rc == -1 and b"non-decreasing" in lib.colate_last_error()
 
 
+def _em_entry_points():
+    """The nine host-pointer EM entry points as `call(**faults)` closures over small valid arguments; a fault replaces one
+    argument: null=True (a NULL array), E=1100, bad_epochs=True (unsorted), max_iter=0.  The sharded calls get the valid
+    device list [0], the all-gather calls a NULL communicator."""
+    from colate_amd._lib import lib
+
+    A, B, nb, G = 185, 2, 3, 2
+    grid = np.ascontiguousarray(ol.age_grid())
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    dev = (ctypes.c_int * 1)(0)
+
+    def entry(name, kind, rows, epoch_rows, lead):
+        def call(null=False, E=23, bad_epochs=False, max_iter=10):
+            ep = np.linspace(0.0, 1e5, E) if E != 23 else ol.epochs_from_bins("3,7,0.2", 0.0, 28.0)[0]
+            ep = np.ascontiguousarray(np.tile(ep[::-1] if bad_epochs else ep, (epoch_rows, 1)))
+            init = np.full((epoch_rows, E), 5e-5)
+            cnt, tabs, w = np.ones((rows, A)), np.ones((G * nb, A)), np.ones((rows, nb))
+            rates, ll = np.zeros((rows, E)), np.zeros(rows)
+            iters, flags = np.zeros(rows, np.int32), np.zeros(rows, np.int32)
+            first = None if null else ptr(grid)  # the NULL array: age_grid, which every entry point takes
+            em = (ptr(ep), ptr(init), max_iter, 0, 1e-7, 5e-9, ptr(rates), ptr(iters), ptr(ll), ptr(flags))
+            if kind == "tables":
+                args = (rows, E, A, first, ptr(cnt), ptr(cnt)) + em
+            elif kind == "genome":
+                args = (rows, nb, E, A, first, 0.0, ptr(w)) + (ptr(tabs),) * 4 + em
+            else:
+                gnb, gage = np.full(G, nb, np.int32), np.zeros(G)
+                args = (E, A, first, ptr(gnb), ptr(gage), ptr(w)) + (ptr(tabs),) * 4 + em
+            if name in ("colate_bootstrap_em_batch", "colate_bootstrap_em_batch_groups"):
+                args += (None, None)  # no count outputs
+            return getattr(lib, name)(*lead, *args)
+
+        return call
+
+    return {
+        "colate_em_batch": entry("colate_em_batch", "tables", B, 1, ()),
+        "colate_em_batch_rows": entry("colate_em_batch_rows", "tables", B, B, ()),
+        "colate_em_batch_sharded": entry("colate_em_batch_sharded", "tables", B, 1, (1, dev)),
+        "colate_em_batch_rows_sharded": entry("colate_em_batch_rows_sharded", "tables", B, B, (1, dev)),
+        "colate_em_batch_allgather": entry("colate_em_batch_allgather", "tables", B, 1, (None,)),
+        "colate_bootstrap_em_batch": entry("colate_bootstrap_em_batch", "genome", B, 1, ()),
+        "colate_bootstrap_em_batch_allgather": entry("colate_bootstrap_em_batch_allgather", "genome", B, 1, (None,)),
+        "colate_bootstrap_em_batch_groups": entry("colate_bootstrap_em_batch_groups", "groups", G * B, G, (G, B)),
+        "colate_bootstrap_em_batch_groups_allgather": entry("colate_bootstrap_em_batch_groups_allgather", "groups", G * B, G,
+                                                            (None, G, B, 0, G)),
+    }
+
+
+@pytest.mark.parametrize("fault, code", [(dict(null=True), -1), (dict(E=1100), -4), (dict(bad_epochs=True), -1),
+                                         (dict(max_iter=0), -1)], ids=["null_array", "E_1100", "unsorted_epochs", "max_iter_0"])
+def test_host_pointer_entry_points_validate_alike(fault, code):
+    """Every host-pointer EM entry point refuses a NULL array, E above the compiled limit, unsorted epochs and max_iter = 0
+    with the same code (COLATE_EINVAL, COLATE_ELIMIT, COLATE_EINVAL, COLATE_EINVAL), before a device is asked for (a check
+    that came after it would show as COLATE_ENODEVICE = -2 where there is no device) and before the communicator is
+    looked at."""
+    got = {name: call(**fault) for name, call in _em_entry_points().items()}
+    assert len(got) == 9
+    assert got == {name: code for name in got}
+
+
 def test_status_flags_macro_matches_python(ca):
     header = open(os.path.join(ROOT, "include", "colate_amd.h")).read()
     m = re.search(r"#define COLATE_STATUS_FLAGS\(flags\) \(\(flags\) & (0x[0-9a-f]+)\)", header)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Bit-for-bit comparison of two builds of libcolate_amd.so on the same inputs (GPU box): every EM output (rates, iteration counts,
 log-likelihoods, flags) of a set of workloads that reach every build of the kernel -- the latency builds for up to 64 and 65..128 epochs
-with and without the register cap, the throughput variant, four epochs per lane, sparse tables, zero starting rates.
+with and without the register cap, the throughput variant, four epochs per lane, sparse tables, zero starting rates -- and of every
+placement of the host-pointer calls that one GPU reaches (per-row epochs, a devices list, the bootstrap kernels in front of the EM).
 
     gpurun -- 'python3 tools/compare_libs.py colate_amd/lib_r03/libcolate_amd.so colate_amd/lib/libcolate_amd.so'
 
@@ -45,6 +46,27 @@ def worker(out):
     csh2, cns2 = workloads.bootstrap_tables(grid, 16, nb=9, scale=1.0)
     r, it, ll, fl = colate_amd.em_batch(grid, csh2, cns2, ep, init_rates=init, max_iter=50, min_iter=10)
     res["zero_r"], res["zero_it"], res["zero_ll"], res["zero_fl"] = r, it, ll, fl
+    # the other host-pointer placements that one GPU reaches: per-row epochs, the devices list (two shards on GPU 0), and the
+    # bootstrap kernels in front of the EM (one genome; groups with their counts returned)
+    keys = ("_r", "_it", "_ll", "_fl", "_csh", "_cns")
+    csh, cns = workloads.bootstrap_tables(grid, 37, nb=115, scale=1.0)
+    ep_rows = np.stack([ol.epochs_from_bins("3,7,0.2", (0.0, 7000.0, 1200.0)[b % 3] / 28.0, 28.0)[0] for b in range(37)])
+    init_rows = np.full(ep_rows.shape, 5e-5) * rng.uniform(0.5, 2.0, ep_rows.shape)
+    calls = {"rows": lambda: colate_amd.em_batch_rows(grid, csh, cns, ep_rows, init_rows),
+             "sharded": lambda: colate_amd.em_batch_sharded([0, 0], grid, csh, cns, ep),
+             "rows_sharded": lambda: colate_amd.em_batch_rows_sharded([0, 0], grid, csh, cns, ep_rows, init_rows)}
+    groups = []
+    for g, (nb, age_years) in enumerate([(9, 0.0), (23, 7000.0), (1, 0.0), (115, 1200.0)]):
+        sh = rng.uniform(0, 3, (nb, grid.size)) * (rng.uniform(size=(nb, grid.size)) < 0.6) * (1 - np.exp(-grid / 9000.0))
+        ns, she, nse = (rng.uniform(0, hi, (nb, grid.size)) * (rng.uniform(size=(nb, grid.size)) < p) for hi, p in ((9, 0.6), (1, 0.2), (1, 0.2)))
+        groups.append(dict(age=age_years / 28.0, tabs=(sh, ns, she, nse), ep=ol.epochs_from_bins("3,7,0.2", age_years / 28.0, 28.0)[0],
+                           w=colate_amd.bootstrap_weights(colate_amd.Rng(100 + g), 5, nb)))
+    g3 = groups[3]
+    calls["boot"] = lambda: colate_amd.bootstrap_em_batch(grid, g3["age"], g3["w"], *g3["tabs"], g3["ep"], max_iter=1200)
+    calls["groups"] = lambda: colate_amd.bootstrap_em_batch_groups(grid, [g["age"] for g in groups], [g["w"] for g in groups], [g["tabs"] for g in groups],
+                                                                   np.stack([g["ep"] for g in groups]), want_counts=True, max_iter=1200)
+    for name, call in calls.items():
+        res.update({name + k: v for k, v in zip(keys, call())})
     np.savez(out, **res)
 
 
