@@ -1,5 +1,6 @@
 #!/bin/bash
-# builds the product library, the CLI and the diagnostic probe; stops at the first error
+# builds the product library, the CLI, the call-site tools (coal_EM_shim_check, coal_EM_interval_check: csrc/Makefile `all`)
+# and the diagnostic probes; stops at the first error
 set -euo pipefail
 cd "$(dirname "$0")"
 make -C colate_amd/csrc -j4

@@ -302,6 +302,28 @@ def em_estep(age_grid_, cnt_shared, cnt_notshared, epochs, rates):
     return num, den, ll, flags
 
 
+def em_interval_calls(kinds, age_begin, age_end, epochs, rates, weights=None, device=True, math=1):
+    """colate_em_interval_calls: coal_EM::EM_shared (kind 0) / EM_notshared (kind 1) for R calls (age_begin[r], age_end[r])
+    against one (epochs[E], rates[E]) -- interval-dated mutations, age uniform on [age_begin, age_end]; rows with equal ages
+    are the point form.  Returns (num[R][E], den[R][E], logl[R], flags[R]) and, with weights[R], also (num_acc[E],
+    den_acc[E], ll): the calls summed as one E-step, rows in ascending order.  device=False: the host twins
+    (colate_em_interval_calls_host; math 0 = <cmath>, bit for bit the reference; math 1 = em_math, bit for bit the device)."""
+    k = np.ascontiguousarray(np.atleast_1d(kinds), dtype=np.int32)
+    a0, a1, ep, r = _f64(np.atleast_1d(age_begin)), _f64(np.atleast_1d(age_end)), _f64(epochs), _f64(rates)
+    R, E = k.size, ep.size
+    if a0.shape != (R,) or a1.shape != (R,) or r.shape != (E,):
+        raise ValueError("kinds, age_begin, age_end must have one entry per call and rates one per epoch")
+    w = None if weights is None else _f64(np.atleast_1d(weights))
+    if w is not None and w.shape != (R,):
+        raise ValueError("weights must have one entry per call")
+    num, den, ll, flags = np.zeros((R, E)), np.zeros((R, E)), np.zeros(R), np.zeros(R, dtype=np.int32)
+    nacc, dacc, lls = np.zeros(E), np.zeros(E), np.zeros(1)
+    args = [R, E, _p(k), _p(a0), _p(a1), _p(ep), _p(r), None if w is None else _p(w), _p(num), _p(den), _p(ll), _p(flags),
+            None if w is None else _p(nacc), None if w is None else _p(dacc), None if w is None else _p(lls)]
+    check(lib.colate_em_interval_calls(*args) if device else lib.colate_em_interval_calls_host(*args, int(math)))
+    return (num, den, ll, flags) if w is None else (num, den, ll, flags, nacc, dacc, float(lls[0]))
+
+
 def _stream_ptr(stream):
     if stream is None:
         import torch
@@ -341,9 +363,10 @@ class coal_EM:
     E-step, so that parity tests read like include/test/test_aDNA.cpp: construct with (epochs, rates),
     call EM_shared / EM_notshared(age_begin, age_end, num, denom) -> log-normaliser.
 
-    Only age_begin == age_end is implemented -- the only way mut() calls it (coal.cpp:3708, 3721).
-    A call is one E-step over a one-bin age grid with count 1, so num/denom/logl are exactly the
-    reference's per-bin outputs.  `EM_many` evaluates a whole list of ages in one launch."""
+    age_begin == age_end -- the only way mut() calls it (coal.cpp:3708, 3721) -- is one E-step over a one-bin
+    age grid with count 1, so num/denom/logl are exactly the reference's per-bin outputs; `EM_many` evaluates a
+    whole list of ages in one launch.  age_begin < age_end (a mutation dated uniformly on its branch,
+    coal_EM.cpp:212-242, 359-433) is one call of `em_interval_calls`, which takes whole batches of them."""
 
     def __init__(self, epochs, coal):
         self.epochs = _f64(epochs).copy()
@@ -368,9 +391,9 @@ class coal_EM:
 
     def _one(self, age_begin, age_end, num, denom, shared):
         if age_begin != age_end:
-            raise NotImplementedError("colate_amd implements the age_begin == age_end path of coal_EM only "
-                                      "(the one mut() uses, coal.cpp:3708/3721)")
-        n, d, ll, _ = self.EM_many([age_begin], shared)
+            n, d, ll, _ = em_interval_calls([0 if shared else 1], [age_begin], [age_end], self.epochs, self.coal_rates)
+        else:
+            n, d, ll, _ = self.EM_many([age_begin], shared)
         num[:] = n[0]
         denom[:] = d[0]
         return float(ll[0])

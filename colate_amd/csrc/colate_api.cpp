@@ -627,4 +627,35 @@ int colate_em_estep(int B, int E, int A, const double* age_grid, const double* c
   return st.finish();
 }
 
+int colate_em_interval_calls(int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                             const double* epochs, const double* rates, const double* weights, double* out_num,
+                             double* out_den, double* out_logl, int* out_flags, double* out_num_acc, double* out_den_acc,
+                             double* out_ll) {
+  if (int rc = check_interval_calls(R, E, kinds, age_begin, age_end, epochs, rates, weights, out_num, out_den, out_logl,
+                                    out_flags, out_num_acc, out_den_acc, out_ll))
+    return rc;
+  if (int rc = ensure_device()) return rc;
+  const size_t nE = (size_t)E, nRE = (size_t)R * E, nacc = weights ? nE : 0;
+  if (R == 0) {
+    for (size_t e = 0; e < nacc; e++) out_num_acc[e] = 0.0, out_den_acc[e] = 0.0;
+    if (weights) *out_ll = 0.0;
+    return COLATE_OK;
+  }
+  ProfRange range("colate_em_interval_calls: H2D + interval E-step kernel + D2H");
+  Arena st(g_ws);
+  const int i_kind = st.in(kinds, R), i_a0 = st.in(age_begin, R), i_a1 = st.in(age_end, R);
+  const int i_ep = st.in(epochs, nE), i_rates = st.in(rates, nE), i_w = st.in(weights, weights ? (size_t)R : 0);
+  const int o_num = st.out(out_num, nRE), o_den = st.out(out_den, nRE), o_ll = st.out(out_logl, R), o_flags = st.out(out_flags, R);
+  const int o_nacc = st.out(out_num_acc, nacc), o_dacc = st.out(out_den_acc, nacc), o_llsum = st.out(out_ll, weights ? 1 : 0);
+  if (int rc = st.commit()) return rc;
+  const hipError_t e = colate_em_interval_launch(R, E, st.dev<int>(i_kind), st.dev<double>(i_a0), st.dev<double>(i_a1),
+                                                 st.dev<double>(i_ep), st.dev<double>(i_rates),
+                                                 weights ? st.dev<double>(i_w) : nullptr, st.dev<double>(o_num),
+                                                 st.dev<double>(o_den), st.dev<double>(o_ll), st.dev<int>(o_flags),
+                                                 st.dev<double>(o_nacc), st.dev<double>(o_dacc), st.dev<double>(o_llsum),
+                                                 st.stream());
+  if (e != hipSuccess) return hip_fail(e, "interval E-step kernel launch");
+  return st.finish();
+}
+
 }  // extern "C"

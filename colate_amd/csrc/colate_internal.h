@@ -10,6 +10,12 @@ int ensure_device();
 // the grids the kernel's contiguous-segment logic relies on: age_grid non-negative and non-decreasing, epochs
 // non-decreasing, epochs[0] <= age_grid[0] (every host-pointer entry point runs this before anything is launched)
 int check_grids(int E, int A, const double* age_grid, const double* epochs);
+// the argument checks of colate_em_interval_calls[_host] (em_interval_host.cpp): sizes, NULLs, non-decreasing epochs,
+// kinds 0 / 1, finite ages with 0 <= epochs[0] <= age_begin <= age_end
+int check_interval_calls(int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                         const double* epochs, const double* rates, const double* weights, const double* out_num,
+                         const double* out_den, const double* out_logl, const int* out_flags, const double* out_num_acc,
+                         const double* out_den_acc, const double* out_ll);
 // Set (process-wide, never cleared) by every entry point that makes this process talk to the HIP runtime.  A process
 // that has done so must not fork() children that use the GPU: `Colate --ranks N` (run_ranked, mut_driver.cpp) refuses
 // when it is set (colate_device_touched, include/colate_amd.h).

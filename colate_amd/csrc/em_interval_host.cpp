@@ -1,0 +1,87 @@
+// colate_amd/csrc/em_interval_host.cpp -- the host side of the interval-dated E-step calls: the argument checks of
+// colate_em_interval_calls[_host] and the two host twins of em_interval_kernel.hip (em_interval.hpp with <cmath> and
+// with em_math.hpp).  Plain C++: no device pass sees the <cmath> instantiation.
+#include <vector>
+
+#include "colate_amd.h"
+#include "colate_internal.h"
+#include "em_interval.hpp"
+
+namespace colate {
+
+int check_interval_calls(int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                         const double* epochs, const double* rates, const double* weights, const double* out_num,
+                         const double* out_den, const double* out_logl, const int* out_flags, const double* out_num_acc,
+                         const double* out_den_acc, const double* out_ll) {
+  if (R < 0 || E < 1) return fail(COLATE_EINVAL, "bad sizes R=%d E=%d", R, E);
+  if (E > 1024) return fail(COLATE_ELIMIT, "E=%d above the compiled limit (1024)", E);
+  if (!kinds || !age_begin || !age_end || !epochs || !rates || !out_num || !out_den || !out_logl || !out_flags)
+    return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (weights && (!out_num_acc || !out_den_acc || !out_ll))
+    return fail(COLATE_EINVAL, "weights given without out_num_acc / out_den_acc / out_ll");
+  for (int e = 1; e < E; e++)
+    if (!(epochs[e] >= epochs[e - 1])) return fail(COLATE_EINVAL, "epochs must be non-decreasing (index %d)", e);
+  if (!(epochs[0] >= 0.0)) return fail(COLATE_EINVAL, "epochs[0] must not be negative");
+  for (int r = 0; r < R; r++) {
+    const double a0 = age_begin[r], a1 = age_end[r];
+    if (kinds[r] != 0 && kinds[r] != 1) return fail(COLATE_EINVAL, "call %d: kind %d is neither 0 (shared) nor 1 (not shared)", r, kinds[r]);
+    if (!(a0 >= 0.0) || !(a1 >= 0.0)) return fail(COLATE_EINVAL, "call %d: negative age (%g, %g)", r, a0, a1);
+    if (!(a0 <= a1)) return fail(COLATE_EINVAL, "call %d: age_begin %g > age_end %g", r, a0, a1);
+    if (!(a1 <= 0x1.fffffffffffffp+1023)) return fail(COLATE_EINVAL, "call %d: infinite age", r);
+    if (!(epochs[0] <= a0)) return fail(COLATE_EINVAL, "call %d: age_begin %g lies before epochs[0]", r, a0);
+  }
+  return COLATE_OK;
+}
+
+namespace {
+template <class M>
+void run_calls(const M& m, int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+               const double* epochs, const double* rates, const double* weights, double* out_num, double* out_den,
+               double* out_logl, int* out_flags, double* out_num_acc, double* out_den_acc, double* out_ll) {
+  std::vector<double> A(E), B(E), work(E);
+  em_interval::ab_prefix(E, epochs, rates, work.data());
+  for (int e = 0; e < E; e++) em_interval::ab_at(m, E, epochs, rates, work.data(), e, A.data(), B.data());
+  const em_interval::View v{E, epochs, rates, A.data(), B.data()};
+  for (int r = 0; r < R; r++) {
+    double *num = out_num + (size_t)r * E, *den = out_den + (size_t)r * E;
+    out_logl[r] = em_interval::call(m, v, kinds[r], age_begin[r], age_end[r], num, den, work.data());
+    int flags = 0;
+    for (int e = 0; e < E; e++) flags |= em_interval::value_flags(num[e], den[e]);
+    out_flags[r] = flags;
+  }
+  if (!weights) return;
+  // coal.cpp:3704-3733 with weights for counts: rows in ascending order, rows without weight not visited
+  double ll = 0.0;
+  for (int e = 0; e < E; e++) out_num_acc[e] = 0.0, out_den_acc[e] = 0.0;
+  for (int r = 0; r < R; r++) {
+    const double w = weights[r];
+    if (!(w > 0)) continue;
+    ll += w * out_logl[r];
+    for (int e = 0; e < E; e++) {
+      out_num_acc[e] += w * out_num[(size_t)r * E + e];
+      out_den_acc[e] += w * out_den[(size_t)r * E + e];
+    }
+  }
+  *out_ll = ll;
+}
+}  // namespace
+
+}  // namespace colate
+
+extern "C" int colate_em_interval_calls_host(int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                                             const double* epochs, const double* rates, const double* weights,
+                                             double* out_num, double* out_den, double* out_logl, int* out_flags,
+                                             double* out_num_acc, double* out_den_acc, double* out_ll, int math) {
+  using namespace colate;
+  if (math != 0 && math != 1) return fail(COLATE_EINVAL, "math must be 0 (<cmath>) or 1 (em_math)");
+  if (int rc = check_interval_calls(R, E, kinds, age_begin, age_end, epochs, rates, weights, out_num, out_den, out_logl,
+                                    out_flags, out_num_acc, out_den_acc, out_ll))
+    return rc;
+  if (math == 0)
+    run_calls(em_interval::LibmMath{}, R, E, kinds, age_begin, age_end, epochs, rates, weights, out_num, out_den, out_logl,
+              out_flags, out_num_acc, out_den_acc, out_ll);
+  else
+    run_calls(em_interval::EmMath{em::kExpTableHost}, R, E, kinds, age_begin, age_end, epochs, rates, weights, out_num,
+              out_den, out_logl, out_flags, out_num_acc, out_den_acc, out_ll);
+  return COLATE_OK;
+}

@@ -58,3 +58,11 @@ hipError_t colate_bootstrap_groups_launch(int B, int row_lo, int rows, int group
                                           const double* weights, const double* sh_block, const double* ns_block,
                                           const double* sh_emp_block, const double* ns_emp_block, double* cnt_sh,
                                           double* cnt_ns, int* status, hipStream_t stream);
+
+// coal_EM::EM_shared / EM_notshared for R calls (kind, age_begin, age_end) against one (epochs[E], rates[E]), one
+// wavefront per call (em_interval_kernel.hip; the arithmetic is em_interval.hpp).  Device pointers; weights NULL = no
+// accumulated outputs.  The caller has validated the ages (colate::check_interval_calls).
+hipError_t colate_em_interval_launch(int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                                     const double* epochs, const double* rates, const double* weights, double* out_num,
+                                     double* out_den, double* out_logl, int* out_flags, double* out_num_acc,
+                                     double* out_den_acc, double* out_ll, hipStream_t stream);

@@ -156,6 +156,29 @@ int colate_em_estep_device(int B, int E, int A, const double* age_grid, const do
                            double* num_acc, double* den_acc, double* loglik, int* flags,
                            void* hip_stream);
 
+/* Interval-dated mutations: coal_EM::EM_shared (kinds[r] = 0) / EM_notshared (kinds[r] = 1) of the reference
+ * (coal_EM.cpp:153-468) for R calls (age_begin[r], age_end[r]) against one (epochs[E], rates[E]) -- the reference's
+ * exact treatment of a mutation whose age is uniform on its branch.  out_num[R][E], out_den[R][E] and out_logl[R] are
+ * what one call of the reference leaves in num / denom and returns (zeros and 0 where its normaliser is not finite);
+ * out_flags[R] carries COLATE_FLAG_NAN / COLATE_FLAG_NEG.  With weights[R] (NULL: none, the three outputs are not
+ * touched) the calls are also summed as one E-step of coal.cpp:3704-3733 with weights for counts, rows with
+ * weight > 0 in ascending order: out_num_acc[E], out_den_acc[E], *out_ll.
+ * Refused (COLATE_EINVAL): age_begin > age_end, a negative, infinite or NaN age, an age before epochs[0].  An interval
+ * may reach into the open last epoch: the reference's own test does (test_aDNA.cpp:187-208; coal_EM.cpp:406-416).
+ * Rows with age_begin == age_end are allowed and give colate_em_estep's per-bin result (same formulas, to the last
+ * few bits).
+ * colate_em_interval_calls runs on the calling thread's device (one wavefront per call, csrc/em_interval_kernel.hip);
+ * _host runs the same source (csrc/em_interval.hpp) on the CPU, math = 0 with <cmath> -- bit for bit the reference
+ * on the same libm -- and math = 1 with the kernels' own exp / log -- bit for bit the device. */
+int colate_em_interval_calls(int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                             const double* epochs, const double* rates, const double* weights, double* out_num,
+                             double* out_den, double* out_logl, int* out_flags, double* out_num_acc,
+                             double* out_den_acc, double* out_ll);
+int colate_em_interval_calls_host(int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                                  const double* epochs, const double* rates, const double* weights, double* out_num,
+                                  double* out_den, double* out_logl, int* out_flags, double* out_num_acc,
+                                  double* out_den_acc, double* out_ll, int math);
+
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
 int colate_age_grid(double* age_grid, int cap);
