@@ -97,6 +97,11 @@ SIGNATURES = {
                                          + [c_void_p] * 3 + [c_int, c_void_p, c_int] + [c_void_p] * 3),
     "colate_condcoal_accumulate_pairs_host": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p, c_int]
                                               + [c_void_p] * 3 + [c_int, c_void_p, c_int] + [c_void_p] * 3),
+    "colate_coalrate_accumulate": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                           c_int] + [c_void_p] * 3),
+    "colate_coalrate_accumulate_host": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int, c_void_p, c_int,
+                                                c_void_p, c_int] + [c_void_p] * 3),
+    "colate_coalrate_main": (c_int, [c_int, ctypes.POINTER(c_char_p)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -464,3 +464,37 @@ def condcoal_accumulate_pairs(parents, branch_lengths, factors, blocks, num_bloc
     check(fn(N, T, _p(parents), _p(bl), _p(factors), _p(blocks), int(num_blocks), G, _p(group_of_hap), P, _p(focal_group),
              _p(cond_group), _p(ages) if ages is not None else None, E, _p(epochs), EF, _p(epochs_focal), _p(num), _p(denom)))
     return num, denom
+
+
+def coalrate_accumulate(parents, branch_lengths, weights, blocks, num_blocks, group_vector_ids, group_vectors, num_groups,
+                        epochs, sample_ages=None, device=True):
+    """`CoalRate --mode local_ancestry` per-block sums (colate_coalrate_accumulate[_host]): parents / branch_lengths
+    [T, 2N-1] (Relate labelling, root 2N-2), weights [T] (float64, bases), blocks [T], group_vector_ids [T] into
+    group_vectors [S, N] (labels in [0, num_groups)); epochs float64 from 0, increasing; sample_ages [N] or None.
+    Returns (num, denom), float64 [num_blocks, G, G, E], filled for g1 >= g2.  device=False: the host twin (bit for bit
+    the same sums)."""
+    parents = np.ascontiguousarray(parents, dtype=np.int32)
+    group_vectors = np.ascontiguousarray(group_vectors, dtype=np.int32)
+    if group_vectors.ndim != 2:
+        raise ValueError("group_vectors must be [S, N]")
+    S, N = group_vectors.shape
+    T = parents.shape[0] if parents.ndim == 2 else 0
+    if T and parents.shape[1] != 2 * N - 1:
+        raise ValueError("parents must be [T, 2N-1]")
+    bl = _f64(branch_lengths).reshape(T, 2 * N - 1) if T else np.zeros((0, 1))
+    weights = _f64(weights).ravel()
+    blocks = np.ascontiguousarray(blocks, dtype=np.int32).ravel()
+    gv = np.ascontiguousarray(group_vector_ids, dtype=np.int32).ravel()
+    if not (weights.size == blocks.size == gv.size == T):
+        raise ValueError("weights, blocks and group_vector_ids must have one entry per tree")
+    epochs = _f64(epochs).ravel()
+    ages = None if sample_ages is None else _f64(sample_ages).ravel()
+    if ages is not None and ages.size != N:
+        raise ValueError("sample_ages must be [N]")
+    E, G = epochs.size, int(num_groups)
+    num = np.zeros((int(num_blocks), G, G, E))
+    denom = np.zeros_like(num)
+    fn = lib.colate_coalrate_accumulate if device else lib.colate_coalrate_accumulate_host
+    check(fn(N, T, _p(parents), _p(bl), _p(weights), _p(blocks), int(num_blocks), _p(gv), S, _p(group_vectors), G,
+             _p(ages) if ages is not None else None, E, _p(epochs), _p(num), _p(denom)))
+    return num, denom

@@ -1,0 +1,173 @@
+// colate_amd/csrc/coalrate.h -- `CoalRate --mode local_ancestry` inside libcolate_amd.so (coal_LA::populate,
+// include/coal/coal_tree.cpp:447-527): what the host side (coalrate.cpp: preparation of the calls, host twin, driver) and
+// the device side (coalrate_kernel.hip) share.  DESIGN.md ("CoalRate") derives the count formulation used here.
+//
+// One call = one tree with a weight w, a group vector s and a block.  Per (group pair gp = {g1 >= g2}, epoch e) it adds
+//   num   += B * wq                                              wq = w / 1e9
+//   denom += ((K * width[e] + R) * wq) - sub * wq
+// with B the leaf pairs of gp whose MRCA lies in epoch e, R the sum over those MRCAs v, ordered by (epoch, label), of
+// m_v * (t_v - epochs[e]) (m_v: the pairs of gp meeting at v), K = cumA - cumB the pairs that cross the whole of e (cumA:
+// the pairs of gp whose older sample has its age in an epoch <= e, a table per group vector; cumB: the pairs coalesced in
+// an epoch <= e) and sub the pairs' sum of (age - epochs[e_age]) in epoch e (a table per group vector).  All counts are
+// exact integers; every double sum has the one order written here, for the kernel and the host twin alike.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "condcoal.h"
+
+#if defined(__HIPCC__)
+#define CR_HD __host__ __device__ __forceinline__
+#else
+#define CR_HD inline
+#endif
+
+namespace colate_cr {
+
+using colate_cc::kMaxHaplotypes;  // (pair counts per node stay below 2^27, per call below 2^28: int32, exact in double)
+
+// An internal node of a prepared call: the DFS leaf ranges [lo, mid) and [mid, hi) of its two children, its epoch and
+// t_v - epochs[ev].
+struct CrNode {
+  unsigned short lo, mid, hi, ev;
+  double dt;
+};
+static_assert(sizeof(CrNode) == 16, "one 16-byte load per node");
+
+// What every call of a run shares.
+struct CrRun {
+  int N = 0, G = 0, S = 0;
+  std::vector<double> epochs;  // [E]
+  std::vector<double> ages;    // [N] or empty (modern samples)
+  std::vector<int> groups;     // [S][N] group vectors
+  int E() const { return (int)epochs.size(); }
+  int GP() const { return G * (G + 1) / 2; }
+};
+
+// group pair index of g1 >= g2
+CR_HD int cr_pair(int g1, int g2) { return g1 * (g1 + 1) / 2 + g2; }
+
+// The per-group-vector tables: over the occupied age epochs oa (ascending), the pairs of each group pair whose older
+// sample's age lies there, and their sum of (age - epochs[epoch]).  Modern samples: one occupied epoch, 0, without sums.
+struct CrTables {
+  int OA = 0;
+  std::vector<int> oa_epoch;        // [OA]
+  std::vector<long long> pairs;     // [S][OA][GP]
+  std::vector<double> sub;          // [S][OA][GP]
+  std::vector<double> width;        // [E]: epochs[e+1] - epochs[e], 0 for the last
+};
+// False with a message when a group label or an age is out of range.
+bool make_tables(const CrRun& run, CrTables& tab, std::string& err);
+
+// A chunk of prepared calls, back to back.
+struct CrChunk {
+  int N = 0, T = 0;
+  std::vector<int> leaf;     // [T][N] DFS leaf order
+  std::vector<CrNode> node;  // [T][N-1] internal nodes by (epoch, label)
+  std::vector<double> w;     // [T]
+  std::vector<int> gv, block;
+  void clear() {
+    T = 0;
+    leaf.clear(), node.clear(), w.clear(), gv.clear(), block.clear();
+  }
+  int append(int n);  // room for one more call; returns its index
+  // a copy of call k of `src` at the end (a tree makes one call per local-ancestry segment it reaches); returns its index
+  int append_from(const CrChunk& src, int k);
+};
+
+// Call k of the chunk from a raw tree (Relate labelling): checks it (colate_cc::prepare_tree), dates its nodes as
+// Tree::GetCoordinates does (float), finds their epochs and sorts them.  False with a message for a malformed tree, a
+// node older than the last epoch boundary, or a node in an epoch below that of a sample age under it.
+bool prepare_call(const CrRun& run, const int* parent, const double* bl, CrChunk& c, int k, std::string& err);
+
+// One lane's walk over the nodes of a call for one group pair: cumB[e * stride] and R[e * stride] for every epoch.
+// pre(g, q): the leaves of group g among the first q of the leaf order.
+template <class Pre>
+CR_HD void cr_count_pair(int nodes, int E, const CrNode* node, int g1, int g2, Pre pre, int* cumB, double* R, size_t stride) {
+  int cur = 0, b = 0, cum = 0;
+  double r = 0.0;
+  for (int j = 0; j < nodes; j++) {
+    const CrNode nd = node[j];
+    while (cur < (int)nd.ev) {
+      cum += b;
+      cumB[cur * stride] = cum;
+      R[cur * stride] = r;
+      b = 0, r = 0.0, cur++;
+    }
+    const int l1 = pre(g1, nd.mid) - pre(g1, nd.lo), r1 = pre(g1, nd.hi) - pre(g1, nd.mid);
+    int m;
+    if (g1 == g2) {
+      m = l1 * r1;
+    } else {
+      const int l2 = pre(g2, nd.mid) - pre(g2, nd.lo), r2 = pre(g2, nd.hi) - pre(g2, nd.mid);
+      m = l1 * r2 + l2 * r1;
+    }
+    b += m;
+    r += (double)m * nd.dt;
+  }
+  while (cur < E) {
+    cum += b;
+    cumB[cur * stride] = cum;
+    R[cur * stride] = r;
+    b = 0, r = 0.0, cur++;
+  }
+}
+
+// One call's addends of cell (e, gp): cb / cb_prev = cumB[e] / cumB[e-1] (0 at e = 0), ca = cumA[e], sub = the table's
+// entry where e is an occupied age epoch (0 otherwise).
+CR_HD void cr_fold_cell(int cb, int cb_prev, long long ca, double r, double sub, double width, double w, double& num, double& den) {
+  const double wq = w / 1e9;
+  num += (double)(cb - cb_prev) * wq;
+  double d = (double)(ca - (long long)cb) * width;
+  d = d + r;
+  d = d * wq;
+  d = d - sub * wq;
+  den += d;
+}
+
+// Per-block sums of a run: num / denom [block][E][GP].
+struct CrSums {
+  int blocks = 0;
+  std::vector<double> num, den;
+};
+
+// One way to accumulate: the prepared calls go in chunk by chunk, the per-block sums come out.  Both implementations sum
+// in the same order (per call and group pair over the nodes by (epoch, label); per cell over the calls in input order), so
+// their sums agree bit for bit.
+class CoalRateWalker {
+ public:
+  virtual ~CoalRateWalker() = default;
+  virtual bool submit(const CrChunk& c) = 0;
+  virtual bool finish(CrSums& out) = 0;
+  const std::string& error() const { return err_; }
+  int error_code() const { return code_; }
+  double gpu_seconds() const { return gpu_s_; }  // kernel time by events (0 for the host twin)
+
+ protected:
+  bool fail(const std::string& what, int code) {
+    err_ = what;
+    code_ = code;
+    return false;
+  }
+  double gpu_s_ = 0;
+
+ private:
+  std::string err_;
+  int code_ = 0;
+};
+
+std::unique_ptr<CoalRateWalker> make_host_walker(const CrRun& run, const CrTables& tab);
+// Null, the reason in `why` and its COLATE_E code in *code, when there is no device or the run does not fit it (device -1:
+// the calling thread's).
+std::unique_ptr<CoalRateWalker> make_device_walker(int device, const CrRun& run, const CrTables& tab, int max_calls, std::string& why,
+                                                   int* code = nullptr);
+// device bytes per call of a chunk
+size_t device_call_bytes(int N, int G, int E);
+// Calls per chunk: the most that fit 4M node entries and 256 MiB of device memory, or COLATE_COALRATE_CHUNK_TREES where
+// that is set and smaller (tests cross chunk and block boundaries on small inputs).
+int chunk_calls_for(int N, int G, int E);
+
+}  // namespace colate_cr

@@ -415,8 +415,6 @@ namespace colate_drv {
 
 using namespace colate_cc;
 
-namespace {
-
 // anc.cpp:6-45 (MarginalTree::Read + Tree::ReadTree): "pos: " then 2N-1 times "parent:(branch_length num_events SNP_begin SNP_end) "
 bool parse_tree_line(const std::string& line, int N, int* parent, double* bl) {
   const char* s = line.c_str();
@@ -439,11 +437,6 @@ bool parse_tree_line(const std::string& line, int N, int* parent, double* bl) {
   }
   return true;
 }
-
-struct Poplabels {  // sample.cpp:8-110
-  std::vector<std::string> groups;  // sorted
-  std::vector<int> group_of_haplotype;
-};
 
 bool read_poplabels(const std::string& path, Poplabels& pl, std::string& err) {
   std::vector<std::vector<std::string>> rows;
@@ -492,6 +485,8 @@ bool read_poplabels(const std::string& path, Poplabels& pl, std::string& err) {
   }
   return true;
 }
+
+namespace {
 
 // coal.cpp:5072-5146 (float epochs)
 bool condcoal_epochs(const Options& opt, float years_per_gen, std::vector<float>& epochs, std::string& err) {

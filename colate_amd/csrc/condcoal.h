@@ -102,3 +102,17 @@ std::unique_ptr<CcWalker> make_pairs_device_walker(int device, const CcRun& base
 size_t pairs_per_tree_bytes(int N, int G, int P, int slots);
 
 }  // namespace colate_cc
+
+// Readers that `CoalRate` (coalrate.cpp) shares with the CondCoalRates driver (condcoal.cpp).
+namespace colate_drv {
+
+// One line of a .anc file, "pos: " then 2N-1 times "parent:(branch_length num_events SNP_begin SNP_end) ".
+bool parse_tree_line(const std::string& line, int N, int* parent, double* bl);
+
+struct Poplabels {  // sample.cpp:8-110
+  std::vector<std::string> groups;  // sorted
+  std::vector<int> group_of_haplotype;
+};
+bool read_poplabels(const std::string& path, Poplabels& pl, std::string& err);
+
+}  // namespace colate_drv

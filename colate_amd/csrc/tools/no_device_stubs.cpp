@@ -102,3 +102,12 @@ std::unique_ptr<CcWalker> make_pairs_device_walker(int, const CcRun&, const std:
   return nullptr;
 }
 }  // namespace colate_cc
+
+// the pair counting of CoalRate on the device (coalrate.h): none in this build, the host twin counts
+#include "coalrate.h"
+namespace colate_cr {
+std::unique_ptr<CoalRateWalker> make_device_walker(int, const CrRun&, const CrTables&, int, std::string& why, int*) {
+  why = "built without a device";
+  return nullptr;
+}
+}  // namespace colate_cr

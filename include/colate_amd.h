@@ -353,6 +353,31 @@ int colate_condcoal_accumulate_pairs_host(int N, int T, const int* parents, cons
                                           const double* sample_ages, int E, const float* epochs, int EF,
                                           const float* epochs_focal, double* num, double* denom);
 
+/* `CoalRate --mode local_ancestry` (coal_tree.cpp:447-527, coal_LA::populate): the per-block sums of the pairwise
+ * coalescence rates between groups.  T calls, each a tree of N haplotypes (parents / branch_lengths[T][2N-1] as above)
+ * with a weight (weights[T], the bases it stands for; the sums take weight / 1e9), a block (blocks[T] in
+ * [0, num_blocks), any order) and a group vector (group_vector_ids[T] in [0, S)); group_vectors[S][N] holds labels in
+ * [0, G).  sample_ages[N] or NULL; epochs[E] in double, epochs[0] = 0, increasing.  Out: num / denom
+ * [num_blocks][G][G][E], filled for g1 >= g2 (the rest 0) -- per (pair of leaves, epoch) what populate adds, summed from
+ * exact pair counts ("CoalRate").  COLATE_EINVAL for a node older than epochs[E-1] or in an epoch below that
+ * of a sample age under it; COLATE_ELIMIT for N above 16384, G above 65535 or E * G * (G + 1) / 2 of 2^31 or more.  The
+ * counting runs on the calling thread's device: COLATE_ENODEVICE without one, and the device's own code (COLATE_ELIMIT where
+ * a tree does not fit it, COLATE_EHIP for a runtime error) where its walker cannot be made -- there is no fall-back to the
+ * host here; the `CoalRate` executable, by contrast, runs the host twin then after a line on stderr.  _host: the host twin,
+ * bit for bit the same sums. */
+int colate_coalrate_accumulate(int N, int T, const int* parents, const double* branch_lengths, const double* weights,
+                               const int* blocks, int num_blocks, const int* group_vector_ids, int S,
+                               const int* group_vectors, int G, const double* sample_ages, int E, const double* epochs,
+                               double* num, double* denom);
+int colate_coalrate_accumulate_host(int N, int T, const int* parents, const double* branch_lengths, const double* weights,
+                                    const int* blocks, int num_blocks, const int* group_vector_ids, int S,
+                                    const int* group_vectors, int G, const double* sample_ages, int E,
+                                    const double* epochs, double* num, double* denom);
+
+/* The `CoalRate` command line (CoalRate.cpp:6-58) for --mode local_ancestry: same option names, stderr lines and
+ * OUTPUT.coal.  Returns the process exit code. */
+int colate_coalrate_main(int argc, char** argv);
+
 /* The whole `Colate --mode mut` command line for the .colate.in / .colate_mat
  * inputs (Colate.cpp:6-116 -> coal.cpp:3071-3863): same option names, same
  * stderr progress lines, same .coal output.  Returns the process exit code. */
