@@ -498,3 +498,30 @@ def coalrate_accumulate(parents, branch_lengths, weights, blocks, num_blocks, gr
     check(fn(N, T, _p(parents), _p(bl), _p(weights), _p(blocks), int(num_blocks), _p(gv), S, _p(group_vectors), G,
              _p(ages) if ages is not None else None, E, _p(epochs), _p(num), _p(denom)))
     return num, denom
+
+
+def coalrate_tree_accumulate(parents, branch_lengths, weights, blocks, num_blocks, epochs, sample_ages=None, device=True):
+    """`CoalRate --mode tree` per-block sums (colate_coalrate_tree_accumulate[_host]): parents / branch_lengths [T, 2N-1]
+    (Relate labelling, root 2N-2), weights [T] (float64, bases), blocks [T]; epochs float64 from 0, increasing; sample_ages
+    [N] or None.  Returns (num, denom), float64 [num_blocks, E].  device=False: the host twin (bit for bit the same sums)."""
+    parents = np.ascontiguousarray(parents, dtype=np.int32)
+    if parents.ndim != 2 or parents.shape[1] % 2 != 1:
+        raise ValueError("parents must be [T, 2N-1]")
+    T, nn = parents.shape
+    N = (nn + 1) // 2
+    bl = _f64(branch_lengths).reshape(T, nn)
+    weights = _f64(weights).ravel()
+    blocks = np.ascontiguousarray(blocks, dtype=np.int32).ravel()
+    if not (weights.size == blocks.size == T):
+        raise ValueError("weights and blocks must have one entry per tree")
+    epochs = _f64(epochs).ravel()
+    ages = None if sample_ages is None else _f64(sample_ages).ravel()
+    if ages is not None and ages.size != N:
+        raise ValueError("sample_ages must be [N]")
+    E = epochs.size
+    num = np.zeros((int(num_blocks), E))
+    denom = np.zeros_like(num)
+    fn = lib.colate_coalrate_tree_accumulate if device else lib.colate_coalrate_tree_accumulate_host
+    check(fn(N, T, _p(parents), _p(bl), _p(weights), _p(blocks), int(num_blocks), _p(ages) if ages is not None else None, E,
+             _p(epochs), _p(num), _p(denom)))
+    return num, denom

@@ -1,4 +1,6 @@
-// colate_amd/csrc/coalrate.cpp -- `CoalRate --mode local_ancestry` (include/coal/CoalRate.cpp, coal_localancestry at
+// colate_amd/csrc/coalrate.cpp -- `CoalRate` (include/coal/CoalRate.cpp).  --mode tree: coal at include/coal/coal.cpp:21-204
+// over coal_tree (coalrate_tree.h / coalrate_tree.cpp: the computation; here its driver, run_tree).  --mode local_ancestry
+// (coal_localancestry at
 // include/coal/coal.cpp:206-590, coal_LA at include/coal/coal_tree.cpp:300-654): coalescence rates for every pair of
 // groups from Relate genealogies, the groups being population labels or local-ancestry labels that change along the genome.
 //
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "coalrate.h"
+#include "coalrate_tree.h"
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "mut_feeder.h"
@@ -421,7 +424,7 @@ bool parse_coalrate_options(int argc, char** argv, Options& o, std::string& err)
 void print_coalrate_help() {
   std::cout << "Usage:\n  CoalRate [OPTION...]\n\n"
             << "      --help                Print help.\n"
-            << "      --mode arg            Choose which part of the algorithm to run (colate_amd: local_ancestry).\n"
+            << "      --mode arg            Choose which part of the algorithm to run (colate_amd: tree, local_ancestry).\n"
             << "      --chr arg             Optional: File specifying chromosomes to use.\n"
             << "      --bins arg            Epoch boundaries 10^(seq(x,y,stepsize)) [format: x,y,stepsize].\n"
             << "      --years_per_gen arg   Optional: Years per generation.\n"
@@ -945,6 +948,269 @@ int run_local_ancestry(const Options& opt) {
   return 0;
 }
 
+// coal.cpp:21-204 over coal_tree (coal_tree.cpp:1-295): the coalescence rate of the whole sample.
+int run_tree(const Options& opt) {
+  if (!opt.has("input") || !opt.has("output") || !opt.has("bins")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed: input, output, bins. Optional: years_per_gen, chr, num_bootstraps" << std::endl;
+    print_coalrate_help();
+    std::cout << "Calculate coalescence rates for sample." << std::endl;
+    return 1;
+  }
+  if (opt.has("help")) {
+    print_coalrate_help();
+    std::cout << "Calculate coalescence rates for sample." << std::endl;
+    return 0;
+  }
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating coalescence rates for (ancient) sample.." << std::endl;
+
+  std::string err;
+  std::vector<double> epochs;
+  if (!coalrate_epochs(opt, epochs, err)) {
+    std::cerr << err << std::endl;
+    return 1;
+  }
+  int num_bootstrap = 1;
+  if (opt.has("num_bootstraps")) num_bootstrap = std::stoi(opt.get("num_bootstraps"));
+  if (opt.has("seed")) (void)std::stoi(opt.get("seed"));  // (accepted; coal_tree::init_bootstrap seeds with 1 whatever it is)
+  if (num_bootstrap < 1) {
+    std::cerr << "Error: --num_bootstraps must be at least 1." << std::endl;
+    return 1;
+  }
+  const int block_size = 5000;
+
+  std::vector<std::string> chromosomes;
+  if (opt.has("chr")) {
+    GzText is;
+    if (!is.open(opt.get("chr"))) {
+      std::cerr << "Error while opening file " << opt.get("chr") << std::endl;
+      return 1;
+    }
+    std::string line;
+    while (is.getline(line)) chromosomes.push_back(line);
+    if (chromosomes.empty()) {
+      std::cerr << "Error: no chromosome in " << opt.get("chr") << std::endl;
+      return 1;
+    }
+  } else {
+    chromosomes.push_back("1");
+  }
+
+  // The host twin is the default: at both measured shapes (profiles/coalrate/coalrate_tree_bench.json) opening the device
+  // costs more than the host twin's whole walk, and the run is slower end to end.  COLATE_DEVICE_COALRATE=1 asks for the kernel.
+  bool use_device = false;
+  if (const char* e = std::getenv("COLATE_DEVICE_COALRATE"))
+    if (std::string(e) == "1") use_device = true;
+  if (use_device && colate_device_count() <= 0) use_device = false;  // no device: the host twin
+  const int device = opt.has("device") ? std::stoi(opt.get("device")) : 0;
+  const int nthreads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  const bool timing = std::getenv("COLATE_TIMING") != nullptr;
+  const double t_begin = StageTimes::now();
+  double t_prepare = 0, t_walk = 0;
+  const int E = (int)epochs.size();
+
+  std::unique_ptr<colate_crt::CoalTreeWalker> walker;
+  std::vector<double> run_ages;
+  int N = 0, chunk_calls = 1, num_blocks = 0;
+  for (size_t chr = 0; chr < chromosomes.size(); chr++) {
+    std::cerr << "CHR " << chromosomes[chr] << ":\n";
+    const std::string prefix = opt.get("input") + "_chr" + chromosomes[chr];
+    GzText anc;
+    if (!anc.open(prefix + ".anc") && !anc.open(prefix + ".anc.gz")) {
+      std::cerr << "Error: --mode tree: failed to open " << prefix << ".anc(.gz)" << std::endl;
+      return 1;
+    }
+    {
+      GzText probe;
+      if (!probe.open(prefix + ".mut") && !probe.open(prefix + ".mut.gz")) {
+        std::cerr << "Error: --mode tree: failed to open " << prefix << ".mut(.gz)" << std::endl;
+        return 1;
+      }
+    }
+    std::vector<MutRow> rows;
+    read_mut_file(prefix + ".mut", rows);
+    if (rows.empty()) {
+      std::cerr << "Error: " << prefix << ".mut has no SNPs." << std::endl;
+      return 1;
+    }
+    std::string line;
+    int n_chr = 0, num_trees = 0;
+    std::vector<double> ages;
+    {  // mutations.cpp:555-581
+      anc.getline(line);
+      std::istringstream is(line);
+      std::string tmp;
+      is >> tmp >> n_chr;
+      if (n_chr >= 2) {
+        ages.resize(n_chr);
+        int i = 0;
+        while (i < n_chr && is >> ages[i]) i++;
+        if (i != n_chr) ages.clear();
+      }
+      anc.getline(line);
+      std::istringstream is2(line);
+      is2 >> tmp >> num_trees;
+    }
+    if (n_chr < 2 || n_chr > kMaxHaplotypes) {
+      std::cerr << "Error: " << prefix << ".anc: " << n_chr << " haplotypes (colate_amd supports 2 .. " << kMaxHaplotypes << ")."
+                << std::endl;
+      return 1;
+    }
+    if (num_trees < 1) {
+      std::cerr << "Error: " << prefix << ".anc has no trees." << std::endl;
+      return 1;
+    }
+    for (double a : ages)
+      if (!(a >= 0.0)) {
+        std::cerr << "Error: " << prefix << ".anc: sample age " << a << std::endl;
+        return 1;
+      }
+    if (!walker) {
+      N = n_chr;
+      run_ages = ages;
+      chunk_calls = colate_crt::chunk_calls_for(N, E);
+      if (use_device) {
+        std::string why;
+        walker = colate_crt::make_device_walker(device, N, epochs, chunk_calls, why);
+        if (!walker) std::cerr << "CoalRate: the host twin runs instead of device " << device << ": " << why << std::endl;
+      }
+      if (!walker) walker = colate_crt::make_host_walker(N, epochs);
+    } else if (n_chr != N || ages != run_ages) {
+      std::cerr << "Error: " << prefix << ".anc has other haplotypes (or sample ages) than the first chromosome's." << std::endl;
+      return 1;
+    }
+    // coal_tree::update_ancmut
+    int current_block = num_blocks, count_trees = 0;
+    num_blocks += (int)(num_trees / ((double)block_size) + 1);
+
+    std::vector<TreeSpan> plan;
+    plan_spans(rows, num_trees, plan);
+    const size_t nn = 2 * (size_t)N - 1;
+    colate_crt::CrtChunk out;
+    std::vector<std::string> lines;
+    std::vector<int> call_of;
+    int perc = -1, tree_count = 0;
+    for (int t0 = 0; t0 < num_trees; t0 += chunk_calls) {
+      const int t1 = std::min(num_trees, t0 + chunk_calls), nb = t1 - t0;
+      double ts = StageTimes::now();
+      lines.resize(nb);
+      for (int k = 0; k < nb; k++)
+        if (!anc.getline(lines[k])) {
+          std::cerr << "Error: " << prefix << ".anc ends after " << t0 + k << " of " << num_trees << " trees." << std::endl;
+          return 1;
+        }
+      // coal_tree::populate's block counter: every tree counts; a tree of weight 0 adds nothing and is not submitted
+      out.clear();
+      call_of.assign(nb, -1);
+      for (int k = 0; k < nb; k++) {
+        if ((int)(((double)tree_count) / num_trees * 100.0) > perc) {
+          perc = (int)(((double)tree_count) / num_trees * 100.0);
+          std::cerr << "[" << perc << "%]\r";
+        }
+        tree_count++;
+        if (count_trees == block_size) {
+          current_block++;
+          count_trees = 0;
+        }
+        if (plan[t0 + k].weight != 0.0f) {
+          const int x = out.append(N);
+          out.w[x] = plan[t0 + k].weight, out.block[x] = current_block;
+          call_of[k] = x;
+        }
+        count_trees++;
+      }
+      std::vector<std::string> errs(nthreads);
+      std::vector<std::thread> pool;
+      const int per = (nb + nthreads - 1) / nthreads;
+      for (int w = 0; w < nthreads; w++) {
+        const int a = w * per, b = std::min(nb, a + per);
+        if (a >= b) break;
+        pool.emplace_back([&, a, b, w] {
+          std::vector<int> par(nn);
+          std::vector<double> bl(nn);
+          for (int k = a; k < b; k++) {
+            if (call_of[k] < 0) continue;
+            if (!parse_tree_line(lines[k], N, par.data(), bl.data())) {
+              errs[w] = "cannot read tree " + std::to_string(t0 + k);
+              return;
+            }
+            std::string e;
+            if (!colate_crt::prepare_times(N, run_ages.empty() ? nullptr : run_ages.data(), epochs, par.data(), bl.data(),
+                                           out.t.data() + call_of[k] * nn, e)) {
+              errs[w] = "tree " + std::to_string(t0 + k) + ": " + e;
+              return;
+            }
+          }
+        });
+      }
+      for (auto& th : pool) th.join();
+      for (const std::string& e : errs)
+        if (!e.empty()) {
+          std::cerr << "Error: " << e << std::endl;
+          return 1;
+        }
+      t_prepare += StageTimes::now() - ts;
+      ts = StageTimes::now();
+      if (!walker->submit(out)) {
+        std::cerr << "Error: " << walker->error() << std::endl;
+        return 1;
+      }
+      t_walk += StageTimes::now() - ts;
+    }
+    std::cerr << std::endl;
+  }
+  double ts = StageTimes::now();
+  CrSums sums;
+  if (!walker || !walker->finish(sums)) {
+    std::cerr << "Error: " << (walker ? walker->error() : std::string("no chromosome was read")) << std::endl;
+    return 1;
+  }
+  t_walk += StageTimes::now() - ts;
+  const double gpu_s = walker->gpu_seconds();
+  walker.reset();
+
+  // coal_tree::init_bootstrap and Dump (coal_tree.cpp:180-295): draws in 0 .. num_blocks, the last of which selects no block
+  std::ofstream os(opt.get("output") + ".coal");
+  if (!os) {
+    std::cerr << "Error: cannot write " << opt.get("output") << ".coal" << std::endl;
+    return 1;
+  }
+  for (int i = 0; i < num_bootstrap; i++) os << i << " ";
+  os << "\n";
+  for (double e : epochs) os << e << " ";
+  os << "\n";
+  std::mt19937 rng;
+  rng.seed(1);
+  std::uniform_int_distribution<int> d(0, num_blocks);
+  std::vector<int> times(num_blocks);
+  std::vector<double> bnum(E), bden(E);
+  for (int iter = 0; iter < num_bootstrap; iter++) {
+    std::fill(times.begin(), times.end(), 0);
+    for (int b = 0; b < num_blocks; b++) {
+      const int x = d(rng);
+      if (x < num_blocks) times[x]++;
+    }
+    std::fill(bnum.begin(), bnum.end(), 0.0);
+    std::fill(bden.begin(), bden.end(), 0.0);
+    for (int b = 0; b < num_blocks; b++)
+      if (times[b] > 0)
+        for (int e = 0; e < E; e++) {
+          bnum[e] += times[b] * (b < sums.blocks ? sums.num[(size_t)b * E + e] : 0.0);
+          bden[e] += times[b] * (b < sums.blocks ? sums.den[(size_t)b * E + e] : 0.0);
+        }
+    os << "0 " << iter << " ";
+    for (int e = 0; e < E; e++) os << bnum[e] / bden[e] << " ";
+    os << "\n";
+  }
+  os.close();
+  if (timing)
+    std::fprintf(stderr, "coalrate timing: read+prepare %.3f s, walk %.3f s (%s %.3f s), total %.3f s\n", t_prepare, t_walk,
+                 gpu_s > 0 ? "device kernels" : "host twin", gpu_s, StageTimes::now() - t_begin);
+  print_usage_footer();
+  return 0;
+}
+
 }  // namespace
 
 }  // namespace colate_drv
@@ -972,12 +1238,16 @@ extern "C" int colate_coalrate_main(int argc, char** argv) {
     }
   }
   if (mode == "tree") {
-    std::cerr << "Error: colate_amd's CoalRate implements --mode local_ancestry; --mode tree stays with the reference build." << std::endl;
-    return 1;
+    try {
+      return run_tree(opt);
+    } catch (const std::exception& e) {
+      std::cerr << "Error: " << e.what() << std::endl;
+      return 1;
+    }
   }
   std::cout << "####### error #######" << std::endl;
   std::cout << "Invalid or missing mode." << std::endl;
   std::cout << "Options for --mode are:" << std::endl;
-  std::cout << "local_ancestry." << std::endl;
+  std::cout << "tree, local_ancestry." << std::endl;
   return 1;
 }

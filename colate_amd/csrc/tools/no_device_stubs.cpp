@@ -111,3 +111,12 @@ std::unique_ptr<CoalRateWalker> make_device_walker(int, const CrRun&, const CrTa
   return nullptr;
 }
 }  // namespace colate_cr
+
+// the per-tree sort of CoalRate --mode tree on the device (coalrate_tree.h): none in this build, the host twin sorts
+#include "coalrate_tree.h"
+namespace colate_crt {
+std::unique_ptr<CoalTreeWalker> make_device_walker(int, int, const std::vector<double>&, int, std::string& why, int*) {
+  why = "built without a device";
+  return nullptr;
+}
+}  // namespace colate_crt

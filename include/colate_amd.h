@@ -374,8 +374,25 @@ int colate_coalrate_accumulate_host(int N, int T, const int* parents, const doub
                                     const int* group_vectors, int G, const double* sample_ages, int E,
                                     const double* epochs, double* num, double* denom);
 
-/* The `CoalRate` command line (CoalRate.cpp:6-58) for --mode local_ancestry: same option names, stderr lines and
- * OUTPUT.coal.  Returns the process exit code. */
+/* `CoalRate --mode tree` (coal_tree.cpp:100-178, coal_tree::populate): the per-block sums of the whole sample's
+ * coalescence rate.  T calls, each a tree of N haplotypes (parents / branch_lengths[T][2N-1] as above) with a weight
+ * (weights[T]) and a block (blocks[T] in [0, num_blocks), any order); sample_ages[N] or NULL; epochs[E] in double,
+ * epochs[0] = 0, increasing.  Out: num / denom [num_blocks][E]: per epoch the internal nodes in it times weight / 1e9, and
+ * weight * L * (L - 1) / 2 * (upper - lower) / 1e9 over the pieces between consecutive node times and epoch boundaries, L
+ * the lineages alive there (csrc/coalrate_tree.h: the walk and the one summation order).  COLATE_EINVAL for a malformed
+ * tree or a node older than epochs[E-1]; COLATE_ELIMIT for N above 16384.  The device call sorts the node times of every
+ * tree in a HIP kernel on the calling thread's device: COLATE_ENODEVICE without one, the device walker's own code
+ * (COLATE_ELIMIT for more epochs than its LDS holds, COLATE_EHIP for a runtime error) where it cannot be made; no fall-back
+ * to the host here.  _host: the host twin, bit for bit the same sums. */
+int colate_coalrate_tree_accumulate(int N, int T, const int* parents, const double* branch_lengths, const double* weights,
+                                    const int* blocks, int num_blocks, const double* sample_ages, int E, const double* epochs,
+                                    double* num, double* denom);
+int colate_coalrate_tree_accumulate_host(int N, int T, const int* parents, const double* branch_lengths, const double* weights,
+                                         const int* blocks, int num_blocks, const double* sample_ages, int E,
+                                         const double* epochs, double* num, double* denom);
+
+/* The `CoalRate` command line (CoalRate.cpp:6-58) for --mode local_ancestry and --mode tree: same option names, stderr
+ * lines and OUTPUT.coal.  Returns the process exit code. */
 int colate_coalrate_main(int argc, char** argv);
 
 /* The whole `Colate --mode mut` command line for the .colate.in / .colate_mat
