@@ -157,6 +157,34 @@ __device__ __forceinline__ void wave_affine_scan(double& a, double& b, int rows 
   if (rows > 2) COLATE_AFF_STEP2(ROW_BCAST31, 0xc)
 #undef COLATE_AFF_STEP2
 }
+// The same scan in two parts (em_affine_split below).  The multiplier of every step -- the product of a window of the lanes' `a` -- does
+// not depend on `b`: wave_affine_scan_rates computes them, am[k] = what step k multiplies with (am[0] = the lane's own a), with the DPP
+// moves, fills, per-lane constants and operand order of the a-half above, and wave_affine_scan_data runs the b-half on them: the same
+// doubles in every lane as wave_affine_scan, whenever the first part ran.
+constexpr int kAffSteps = 6;  // four steps inside a 16-lane row, two across rows
+__device__ __forceinline__ void wave_affine_scan_rates(double a, double (&am)[kAffSteps], int rows, const double* nosrc) {
+  am[0] = a;
+#define COLATE_AFF_STEP(CTRL, RM, K)                                                                        \
+  {                                                                                                         \
+    const double as = nosrc ? dpp_d<CTRL, RM, true>(0.0, a) + nosrc[K] : dpp_d<CTRL, RM>(1.0, a);           \
+    a = a * as;                                                                                             \
+    am[K + 1] = a;                                                                                          \
+  }
+  COLATE_AFF_STEP(ROW_SHR1, 0xf, 0)
+  COLATE_AFF_STEP(ROW_SHR2, 0xf, 1)
+  COLATE_AFF_STEP(ROW_SHR4, 0xf, 2)
+  COLATE_AFF_STEP(ROW_SHR8, 0xf, 3)
+#undef COLATE_AFF_STEP
+  am[5] = rows > 2 ? a * dpp_d<ROW_BCAST15, 0xa>(1.0, a) : a;  // (am[4], am[5]: read with two / four rows of epochs only)
+}
+__device__ __forceinline__ void wave_affine_scan_data(const double (&am)[kAffSteps], double& b, int rows) {
+  b = em::fma_(am[0], dpp_d<ROW_SHR1, 0xf, true>(0.0, b), b);
+  b = em::fma_(am[1], dpp_d<ROW_SHR2, 0xf, true>(0.0, b), b);
+  b = em::fma_(am[2], dpp_d<ROW_SHR4, 0xf, true>(0.0, b), b);
+  b = em::fma_(am[3], dpp_d<ROW_SHR8, 0xf, true>(0.0, b), b);
+  if (rows > 1) b = em::fma_(am[4], dpp_d<ROW_BCAST15, 0xa>(0.0, b), b);
+  if (rows > 2) b = em::fma_(am[5], dpp_d<ROW_BCAST31, 0xc>(0.0, b), b);
+}
 
 // inclusive suffix maximum of non-negative values (lane l: max of lanes l..63)
 __device__ __forceinline__ double wave_suffix_max(double v, int lane) {
@@ -276,7 +304,12 @@ constexpr int em_loop_pad(int mode, int nch, int erows, bool tput, int wpe) {
   // E=23 B=100 0.896 0.899 0.910 0.914 0.916 0.890 0.906 0.922 (the build before: 0.893, round 3's: 0.881);
   // E=122 B=100 1.256 1.258 1.249 1.254 1.252 1.263 1.267 1.275 (the build before: 1.310, round 3's: 1.224);
   // E=23 B=400 1.149 1.156 1.155 1.142 1.147 1.156 1.139 1.150 (1.146, 1.140)
-  return nch == 1 ? (wpe == 2 ? 5 : 6) : 2;
+  // ... and with the rate-only half of role B's affine scan in front of barrier 2 (em_affine_split; only the loops of the build
+  // without the register cap changed; profiles/affine_split_ab.txt, the parent commit's library on the same box beside it):
+  // E=23 B=100 0.880 0.876 0.870 0.871 0.871 0.881 0.874 0.871 (parent: 0.898 0.898 0.906 0.912 0.912 0.888 0.901 0.916)
+  // (swept on the two-row instantiation, 17..32 epochs, only: the one- and the four-row instantiation of that build, whose loops
+  // changed as well, take the same pad without a sweep of their own, as they always have)
+  return nch == 1 ? (wpe == 2 ? 2 : 6) : 2;
 #else
   (void)nch;
   if (!tput) return 6;  // latency variant, default build (not picked by colate_em_variant any more; COLATE_EM_VARIANT=latency)
@@ -293,6 +326,19 @@ constexpr int em_loop_pad2(int mode, int nch, bool tput) {
 #else
   (void)mode, (void)nch, (void)tput;
   return -1;
+#endif
+}
+
+// Role B's affine scan in two parts, the rate-only one in front of barrier 2 (see `kHoist` in the iteration): on for the build
+// whose workgroups have a CU to themselves, where role B's leader idles in front of that barrier and is the wave the others wait
+// for behind it.  The other builds run role B's waves beside other work on the SIMD, where the extra registers and instructions
+// are not free: they keep the single scan.  Results are bit-identical either way.  -DCOLATE_AFFINE_SPLIT=0|1 overrides (A/B runs).
+constexpr bool em_affine_split(int nch, bool tput, int wpe) {
+#ifdef COLATE_AFFINE_SPLIT
+  (void)nch, (void)tput, (void)wpe;
+  return (COLATE_AFFINE_SPLIT) != 0;
+#else
+  return !tput && nch == 1 && wpe == 2;
 #endif
 }
 
@@ -883,6 +929,30 @@ __global__ __launch_bounds__(TPUT ? 2 * kWave : 2 * COLATE_EM_MAX_A, WPE ? WPE :
         }
       }
     }
+    // Role B's leader, steady-state loops (em_affine_split): the multipliers of the affine scan of P3 depend on the rates only, so
+    // they are computed here -- right behind the M-step, ahead of the bin terms and of where barrier 1 used to be, not next to
+    // barrier 2: this wave reaches that barrier first and waits there for role A's longer bin phase wherever they stand --
+    // and P3, the stretch every other wave waits for, runs the data half alone.  Where another wave computes role B's epoch
+    // values (free: wave 3, whose row arrives behind barrier 2) the leader takes q_e from its own copy of the rates: the same
+    // operation on the same operands, the same bits.
+    constexpr bool kHoist = em_affine_split(NCH, TPUT, WPE) && kSteady && kNeedLL == 0 && kRole == 1 && kLeader == 1;
+    double aff_m[kAffSteps];  // (written here and read in P3 where kHoist holds; no instruction anywhere else)
+    if constexpr (kHoist) {
+      double a = 1.0;
+#pragma unroll
+      for (int c = 0; c < NCH; c++) {
+        if (!P1B) {
+          const double qx = em::em_exp_t(-(lam_e[c] * dt_e[c]), s_exptab);
+          q_e[c] = (ep_of(c) < E - 1) ? qx : 0.0;
+        }
+        const double qa = ep_on[c] ? q_e[c] : 1.0;
+        a = (c == 0) ? qa : a * qa;
+      }
+      wave_affine_scan_rates(a, aff_m, erows, kFree ? aff_nosrc : nullptr);
+      // (pinned: the compiler otherwise sinks what is only read behind a barrier past that barrier)
+#pragma unroll
+      for (int k = 0; k < (erows > 2 ? 6 : (erows > 1 ? 5 : 4)); k++) asm volatile("" : "+v"(aff_m[k]));
+    }
     // The rate of this lane's own bin's epoch, lambda_k, is known to every wave before barrier 1 (each wave runs the
     // M-step itself): fetching it from the wave's own registers (ds_bpermute, issued here so that its latency falls into
     // the wait the barrier needs anyway) lets the bin's exp(-lambda_k (age - t_k)) start right behind the barrier instead
@@ -1166,7 +1236,7 @@ __global__ __launch_bounds__(TPUT ? 2 * kWave : 2 * COLATE_EM_MAX_A, WPE ? WPE :
           beta_e[c] = s_ep[G_BETA * EPAD + ep_of(c)];
         }
         if (ROLE == 1 && mine && !P1B) {  // (free: role B's epoch values are wave 3's work)
-          q_e[c] = s_ep[G_Q * EPAD + ep_of(c)];
+          if (!kHoist) q_e[c] = s_ep[G_Q * EPAD + ep_of(c)];  // (hoisted scan: computed in front of barrier 2, see there)
           p_e[c] = s_ep[G_P * EPAD + ep_of(c)];
           beta_e[c] = s_ep[G_BETA * EPAD + ep_of(c)];
         }
@@ -1259,7 +1329,11 @@ __global__ __launch_bounds__(TPUT ? 2 * kWave : 2 * COLATE_EM_MAX_A, WPE ? WPE :
             a = a * qa[c];
           }
 #if !COLATE_ABL_HAS(9)
-          wave_affine_scan(a, b, erows, kFree ? aff_nosrc : nullptr);
+          if constexpr (kHoist) {
+            wave_affine_scan_data(aff_m, b, erows);  // (the multipliers: in front of barrier 2)
+          } else {
+            wave_affine_scan(a, b, erows, kFree ? aff_nosrc : nullptr);
+          }
 #endif
           // (b of lane l: T after the epochs of lanes 0..l, starting from T = 0)
           T[0] = dpp_d<WAVE_SHR1, 0xf, true>(0.0, b);  // T at the lane's first epoch (lane 0: 0)

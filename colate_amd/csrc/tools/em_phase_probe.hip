@@ -2,12 +2,21 @@
 // (s_memtime) around the phases of an iteration.  Not part of the product library: it compiles
 // em_kernels.hip with -DCOLATE_EM_STAMPS into a stand-alone program and prints where the cycles of
 // an iteration go.  Only the SHARES are meaningful (the stamps serialise the phases).
-//   hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -I../../include -I.. tools/em_phase_probe.hip -o em_phase_probe
+// Build it as the Makefile builds em_kernels_ilp.hip, scheduler flag included (from colate_amd/csrc; build.sh does):
+//   hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -mllvm -force-precise-rotation-cost=true \
+//     -mllvm -amdgpu-sched-strategy=max-ilp -I../../include -I. -Wno-unused-value tools/em_phase_probe.hip -o ../bin/em_phase_probe
+// Without the max-ilp flag the loops are scheduled as no product build of the latency variant is.  All instantiations of this
+// unit take the max-ilp unit's pads (COLATE_EM_ILP_BUILD below), the E-step and the throughput variant included: for those two
+// the probe is not the product's placement.
 #ifndef COLATE_NO_STAMPS
 #define COLATE_EM_STAMPS 1
 #endif
+// (one translation unit, one copy of the template: built as the max-ilp unit is, so that a batch of up to #CUs replicates runs
+// the build the product runs there -- no register cap, two barriers per iteration -- and not the three-barrier code)
+#define COLATE_EM_ILP_BUILD 1
 #include "../em_kernels.hip"
-#include "../em_kernels_ilp.hip"  // (same template again: the probe builds one translation unit)
+hipError_t colate_em_launch_latency_ilp(const ColateEmArgs& args, hipStream_t stream, bool alone) { return launch_latency(args, stream, alone); }
+hipError_t colate_em_launch_big(const ColateEmArgs&, hipStream_t) { return hipErrorNotSupported; }  // (257+ epochs: not probed)
 
 #include <cmath>
 #include <cstdio>
