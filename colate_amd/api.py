@@ -324,6 +324,33 @@ def em_interval_calls(kinds, age_begin, age_end, epochs, rates, weights=None, de
     return (num, den, ll, flags) if w is None else (num, den, ll, flags, nacc, dacc, float(lls[0]))
 
 
+def em_interval_batch(kinds, age_begin, age_end, weights, epochs, init_rates=None, max_iter=DEFAULT_MAX_ITER,
+                      min_iter=DEFAULT_MIN_ITER, rel_tol=DEFAULT_REL_TOL, rate_floor=DEFAULT_RATE_FLOOR, device=True, math=1):
+    """colate_em_interval_batch: the EM fit on interval-dated mutations.  R rows (kinds[r], age_begin[r], age_end[r]) shared by
+    B replicates, weights[B][R] (1-D: B = 1) the bootstrap-weighted count of row r in replicate b; M-step, floor and stop
+    rule as in em_batch.  Returns (rates[B][E], iters[B], loglik[B], flags[B]).  device=False: the host twins
+    (colate_em_interval_batch_host; math 0 = <cmath>, bit for bit the reference's loop; math 1 = em_math, bit for bit the device)."""
+    k = np.ascontiguousarray(np.atleast_1d(kinds), dtype=np.int32)
+    a0, a1, ep = _f64(np.atleast_1d(age_begin)), _f64(np.atleast_1d(age_end)), _f64(epochs)
+    w = _f64(np.atleast_2d(weights))
+    R, E, B = k.size, ep.size, w.shape[0]
+    if a0.shape != (R,) or a1.shape != (R,) or w.shape != (B, R):
+        raise ValueError("kinds, age_begin, age_end must have one entry per row and weights one row of them per replicate")
+    init = _f64(np.full(E, DEFAULT_INIT_RATE) if init_rates is None else init_rates)
+    if init.shape != (E,):
+        raise ValueError("init_rates must have one entry per epoch")
+    rates, iters, ll, flags = np.zeros((B, E)), np.zeros(B, dtype=np.int32), np.zeros(B), np.zeros(B, dtype=np.int32)
+    args = [B, R, E, _p(k), _p(a0), _p(a1), _p(w), _p(ep), _p(init), int(max_iter), int(min_iter), float(rel_tol),
+            float(rate_floor), _p(rates), _p(iters), _p(ll), _p(flags)]
+    check(lib.colate_em_interval_batch(*args) if device else lib.colate_em_interval_batch_host(*args, int(math)))
+    return rates, iters, ll, flags
+
+
+def em_interval_batch_waves(E):
+    """How many rows a workgroup of em_interval_batch calls at a time for E epochs."""
+    return lib.colate_em_interval_batch_waves(int(E))
+
+
 def _stream_ptr(stream):
     if stream is None:
         import torch

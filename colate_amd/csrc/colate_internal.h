@@ -16,6 +16,12 @@ int check_interval_calls(int R, int E, const int* kinds, const double* age_begin
                          const double* epochs, const double* rates, const double* weights, const double* out_num,
                          const double* out_den, const double* out_logl, const int* out_flags, const double* out_num_acc,
                          const double* out_den_acc, const double* out_ll);
+// the argument checks of colate_em_interval_batch[_host] (em_interval_host.cpp): check_interval_calls for the rows and
+// the grid, plus B, R >= 1, finite weights >= 0, the iteration limits, rel_tol, rate_floor and the starting rates
+int check_interval_batch(int B, int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                         const double* weights, const double* epochs, const double* init_rates, int max_iter, int min_iter,
+                         double rel_tol, double rate_floor, const double* out_rates, const int* out_iters,
+                         const double* out_loglik, const int* out_flags);
 // Set (process-wide, never cleared) by every entry point that makes this process talk to the HIP runtime.  A process
 // that has done so must not fork() children that use the GPU: `Colate --ranks N` (run_ranked, mut_driver.cpp) refuses
 // when it is set (colate_device_touched, include/colate_amd.h).

@@ -1,11 +1,13 @@
-// colate_amd/csrc/em_interval_host.cpp -- the host side of the interval-dated E-step calls: the argument checks of
-// colate_em_interval_calls[_host] and the two host twins of em_interval_kernel.hip (em_interval.hpp with <cmath> and
-// with em_math.hpp).  Plain C++: no device pass sees the <cmath> instantiation.
+// colate_amd/csrc/em_interval_host.cpp -- the host side of the interval-dated E-step calls and of the EM fit over
+// them: the argument checks of colate_em_interval_calls[_host] and colate_em_interval_batch[_host], and the two host
+// twins of em_interval_kernel.hip and em_interval_fit_kernel.hip (em_interval.hpp / em_interval_fit.hpp with <cmath>
+// and with em_math.hpp).  Plain C++: no device pass sees the <cmath> instantiation.
 #include <vector>
 
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "em_interval.hpp"
+#include "em_interval_fit.hpp"
 
 namespace colate {
 
@@ -33,7 +35,71 @@ int check_interval_calls(int R, int E, const int* kinds, const double* age_begin
   return COLATE_OK;
 }
 
+int check_interval_batch(int B, int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                         const double* weights, const double* epochs, const double* init_rates, int max_iter, int min_iter,
+                         double rel_tol, double rate_floor, const double* out_rates, const int* out_iters,
+                         const double* out_loglik, const int* out_flags) {
+  const double huge = 0x1.fffffffffffffp+1023;
+  if (B < 1 || R < 1) return fail(COLATE_EINVAL, "bad sizes B=%d R=%d (at least one replicate and one row)", B, R);
+  if (!weights || !out_rates || !out_iters || !out_loglik || !out_flags) return fail(COLATE_EINVAL, "NULL pointer argument");
+  // (rows, grid and E: the checks of the calls; init_rates stands in for the rates, the outputs are those above)
+  if (int rc = check_interval_calls(R, E, kinds, age_begin, age_end, epochs, init_rates, nullptr, out_rates, out_rates,
+                                    out_loglik, out_flags, nullptr, nullptr, nullptr))
+    return rc;
+  if (min_iter < 0) return fail(COLATE_EINVAL, "min_iter %d is negative", min_iter);
+  if (max_iter < 1) return fail(COLATE_EINVAL, "max_iter %d: at least one iteration", max_iter);
+  if (!(rel_tol > 0.0) || !(rel_tol <= huge)) return fail(COLATE_EINVAL, "rel_tol %g must be positive and finite", rel_tol);
+  if (!(rate_floor >= 0.0)) return fail(COLATE_EINVAL, "rate_floor %g is negative", rate_floor);
+  for (int e = 0; e < E; e++)
+    if (!(init_rates[e] >= 0.0) || !(init_rates[e] <= huge))
+      return fail(COLATE_EINVAL, "init_rates[%d] = %g must be finite and not negative", e, init_rates[e]);
+  for (size_t i = 0; i < (size_t)B * R; i++)
+    if (!(weights[i] >= 0.0) || !(weights[i] <= huge))
+      return fail(COLATE_EINVAL, "weight %g of replicate %zu, row %zu must be finite and not negative", weights[i], i / R, i % R);
+  return COLATE_OK;
+}
+
 namespace {
+// coal.cpp:3675-3827 with rows for age bins, one replicate after the other (em_interval_fit_kernel.hip: one workgroup each)
+template <class M>
+void run_fit(const M& m, int B, int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+             const double* weights, const double* epochs, const double* init_rates, int max_iter, int min_iter,
+             double rel_tol, double rate_floor, double* out_rates, int* out_iters, double* out_loglik, int* out_flags) {
+  std::vector<double> A(E), Bv(E), work(E), num(E), den(E), num_acc(E), den_acc(E);
+  for (int b = 0; b < B; b++) {
+    double* rates = out_rates + (size_t)b * E;
+    const double* w_b = weights + (size_t)b * R;
+    for (int e = 0; e < E; e++) rates[e] = init_rates[e];
+    double ll = em_interval::log_zero(), prev_ll = ll;
+    int flags = 0, iter = 0;
+    for (; iter < max_iter; iter++) {
+      em_interval::ab_prefix(E, epochs, rates, work.data());
+      for (int e = 0; e < E; e++) em_interval::ab_at(m, E, epochs, rates, work.data(), e, A.data(), Bv.data());
+      const em_interval::View v{E, epochs, rates, A.data(), Bv.data()};
+      for (int e = 0; e < E; e++) num_acc[e] = 0.0, den_acc[e] = 0.0;
+      prev_ll = ll;
+      ll = 0.0;
+      for (int r = 0; r < R; r++) {
+        const double w = w_b[r];
+        if (!(w > 0)) continue;  // (the reference visits bins with a count only)
+        const double logl = em_interval::call(m, v, kinds[r], age_begin[r], age_end[r], num.data(), den.data(), work.data());
+        ll += w * logl;
+        for (int e = 0; e < E; e++) {
+          flags |= em_interval::value_flags(num[e], den[e]);
+          num_acc[e] += w * num[e];
+          den_acc[e] += w * den[e];
+        }
+      }
+      em_interval::mstep(E, num_acc.data(), den_acc.data(), rate_floor, rates);
+      if (em_interval::stop_rule(ll, prev_ll, rel_tol, iter, min_iter)) break;
+    }
+    if (iter == max_iter) flags |= COLATE_FLAG_MAXITER;
+    out_iters[b] = iter;
+    out_loglik[b] = ll;
+    out_flags[b] = flags;
+  }
+}
+
 template <class M>
 void run_calls(const M& m, int R, int E, const int* kinds, const double* age_begin, const double* age_end,
                const double* epochs, const double* rates, const double* weights, double* out_num, double* out_den,
@@ -83,5 +149,24 @@ extern "C" int colate_em_interval_calls_host(int R, int E, const int* kinds, con
   else
     run_calls(em_interval::EmMath{em::kExpTableHost}, R, E, kinds, age_begin, age_end, epochs, rates, weights, out_num,
               out_den, out_logl, out_flags, out_num_acc, out_den_acc, out_ll);
+  return COLATE_OK;
+}
+
+extern "C" int colate_em_interval_batch_host(int B, int R, int E, const int* kinds, const double* age_begin,
+                                             const double* age_end, const double* weights, const double* epochs,
+                                             const double* init_rates, int max_iter, int min_iter, double rel_tol,
+                                             double rate_floor, double* out_rates, int* out_iters, double* out_loglik,
+                                             int* out_flags, int math) {
+  using namespace colate;
+  if (math != 0 && math != 1) return fail(COLATE_EINVAL, "math must be 0 (<cmath>) or 1 (em_math)");
+  if (int rc = check_interval_batch(B, R, E, kinds, age_begin, age_end, weights, epochs, init_rates, max_iter, min_iter,
+                                    rel_tol, rate_floor, out_rates, out_iters, out_loglik, out_flags))
+    return rc;
+  if (math == 0)
+    run_fit(em_interval::LibmMath{}, B, R, E, kinds, age_begin, age_end, weights, epochs, init_rates, max_iter, min_iter,
+            rel_tol, rate_floor, out_rates, out_iters, out_loglik, out_flags);
+  else
+    run_fit(em_interval::EmMath{em::kExpTableHost}, B, R, E, kinds, age_begin, age_end, weights, epochs, init_rates,
+            max_iter, min_iter, rel_tol, rate_floor, out_rates, out_iters, out_loglik, out_flags);
   return COLATE_OK;
 }

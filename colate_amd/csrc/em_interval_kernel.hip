@@ -3,36 +3,17 @@
 // the 64 lanes of one wavefront.
 //
 // One wavefront per call, WAVES calls per workgroup.  A_ep / B_ep (get_AB) are computed once per workgroup into LDS.
-// Whatever the reference sums from left to right -- the cumulative rate, the logsumexp fold of the normaliser, the
-// `integ` recurrence -- is summed from left to right here too, by lane 0 of the call's wave over LDS, between phases
-// in which all lanes work on their epochs: the device then equals the host twin (em_interval::call<EmMath>) bit for
-// bit.  The addends of the cumulative rate are formed by all lanes; only the additions are serial.
-//
-// Every phase boundary is a workgroup barrier that all waves reach (the phase structure depends on E alone; a wave
-// whose call index is beyond R works on the last call and stores nothing).
+// The call itself (its phases and barriers) is wave_call() of em_interval_wave.hpp, which the EM fit shares: the device
+// equals the host twin (em_interval::call<EmMath>) bit for bit.  A wave whose call index is beyond R works on the last
+// call and stores nothing.
 #include <hip/hip_runtime.h>
 
-#include "em_interval.hpp"
+#include "em_interval_wave.hpp"
 #include "em_kernels.h"
 
 namespace {
 
 using namespace em_interval;
-
-__device__ __forceinline__ int wave_sum(int x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-__device__ __forceinline__ int wave_or(int x) {
-  for (int o = 32; o > 0; o >>= 1) x |= __shfl_xor(x, o, 64);
-  return x;
-}
-
-// LDS, in doubles: exp table [64] | epochs [E] | rates [E] | A_ep [E] | B_ep [E] | per wave: cse [E], num [E], den [E], misc [4]
-__host__ __device__ constexpr size_t wave_doubles(int E) { return 3 * (size_t)E + 4; }
-__host__ __device__ constexpr size_t lds_doubles(int E, int waves) {
-  return em::kExpTableDoubles + 4 * (size_t)E + waves * wave_doubles(E);
-}
 
 template <int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void em_interval_kernel(int R, int E, const int* __restrict__ kinds,
@@ -49,10 +30,7 @@ __global__ __launch_bounds__(WAVES * 64) void em_interval_kernel(int R, int E, c
   double* A = rt + E;
   double* B = A + E;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  double* cse = B + E + wave * wave_doubles(E);
-  double* num = cse + E;
-  double* den = num + E;
-  double* misc = den + E;
+  const WaveLds w = wave_lds(B + E, E, wave);
 
   // ---- per workgroup: the grid, the exp table, A_ep / B_ep
   for (int i = tid; i < em::kExpTableDoubles; i += WAVES * 64) tab[i] = em::kExpTableDevice[i];
@@ -70,45 +48,12 @@ __global__ __launch_bounds__(WAVES * 64) void em_interval_kernel(int R, int E, c
   const bool valid = r_raw < R;
   const int r = valid ? r_raw : R - 1;
   const View v{E, ep, rt, A, B};
-  Call c;
-  c.kind = kinds[r], c.a0 = age_begin[r], c.a1 = age_end[r];
-  c.point = c.a0 == c.a1;
-  c.csb = 0.0, c.csa = 0.0;
-  int nb = 0, ne = 0;  // epoch_of(), the count shared among the lanes
-  for (int e = lane; e < E; e += 64) nb += (ep[e] <= c.a0) ? 1 : 0, ne += (ep[e] <= c.a1) ? 1 : 0;
-  c.eb = wave_sum(nb) - 1, c.ee = wave_sum(ne) - 1;
-  for (int e = lane; e < E; e += 64)
-    if (e > 0) cse[e] = step_product(v, c, e);
-  __syncthreads();
+  double logl;
+  const int flags = wave_call(m, v, kinds[r], age_begin[r], age_end[r], true, lane, w, &logl);
+  if (!valid) return;
+  for (int e = lane; e < E; e += 64) out_num[(size_t)r * E + e] = w.num[e], out_den[(size_t)r * E + e] = w.den[e];
   if (lane == 0) {
-    cum_fold(v, c, cse);
-    misc[0] = c.csb, misc[1] = c.csa;
-  }
-  __syncthreads();
-  c.csb = misc[0], c.csa = misc[1];
-  for (int e = lane; e < E; e += 64) log_values(m, v, c, cse, e, num, den);
-  __syncthreads();
-  if (lane == 0) misc[2] = normaliser(m, v, c, num);
-  __syncthreads();
-  const double nc = misc[2];
-  const bool failed = inf_or_nan(nc);  // coal_EM.cpp:288-292, 461-465: zeros, and 0 for the log-normaliser
-  const Closing k = closing_of(v, c);
-  if (!failed)
-    for (int e = lane; e < E; e += 64) exp_at(m, v, k, nc, e, num, den);
-  __syncthreads();
-  if (lane == 0 && !failed) integ_fold(k, num, cse);
-  __syncthreads();
-  int flags = 0;
-  for (int e = lane; e < E; e += 64) {
-    if (failed) num[e] = 0.0, den[e] = 0.0;
-    else finish_at(v, c, k, cse, e, num, den);
-    const double n = num[e], d = den[e];
-    flags |= value_flags(n, d);
-    if (valid) out_num[(size_t)r * E + e] = n, out_den[(size_t)r * E + e] = d;
-  }
-  flags = wave_or(flags);
-  if (valid && lane == 0) {
-    out_logl[r] = failed ? 0.0 : nc;
+    out_logl[r] = logl;
     out_flags[r] = flags;
   }
 }

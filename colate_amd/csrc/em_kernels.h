@@ -66,3 +66,15 @@ hipError_t colate_em_interval_launch(int R, int E, const int* kinds, const doubl
                                      const double* epochs, const double* rates, const double* weights, double* out_num,
                                      double* out_den, double* out_logl, int* out_flags, double* out_num_acc,
                                      double* out_den_acc, double* out_ll, hipStream_t stream);
+
+// colate_em_interval_batch: the EM fit on interval-dated mutations for B replicates that share R rows and weight them
+// by weights[B][R], one persistent workgroup per replicate (em_interval_fit_kernel.hip; the calls are those of
+// em_interval_kernel.hip, M-step and stop rule are em_interval_fit.hpp).  Device pointers; the caller has validated
+// the arguments (colate::check_interval_batch).
+#define COLATE_EM_INTERVAL_FIT_WAVES 8  // calls in flight per workgroup at E <= 256 (one beyond)
+int colate_em_interval_fit_waves(int E);
+hipError_t colate_em_interval_fit_launch(int B, int R, int E, const int* kinds, const double* age_begin,
+                                         const double* age_end, const double* weights, const double* epochs,
+                                         const double* init_rates, int max_iter, int min_iter, double rel_tol,
+                                         double rate_floor, double* out_rates, int* out_iters, double* out_ll,
+                                         int* out_flags, hipStream_t stream);

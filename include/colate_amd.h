@@ -10,6 +10,10 @@
  * meaningless, so the replacement boundary is one coarse call per batch of
  * bootstrap replicates (colate_em_batch), plus the single E-step
  * (colate_em_estep) that corresponds to one pass of coal.cpp:3698-3733.
+ * Mutations dated to an interval (coal_EM with age_begin < age_end, which the
+ * reference wrote and tested but never put a loop around) have the same two
+ * levels: colate_em_interval_calls is one E-step over a list of calls,
+ * colate_em_interval_batch the whole EM fit for a batch of replicates.
  * INTEGRATION.md shows the patch a maintainer would apply to coal.cpp.
  *
  * Conventions: plain pointers and sizes, row-major, IEEE double; caller owns
@@ -178,6 +182,35 @@ int colate_em_interval_calls_host(int R, int E, const int* kinds, const double* 
                                   const double* epochs, const double* rates, const double* weights, double* out_num,
                                   double* out_den, double* out_logl, int* out_flags, double* out_num_acc,
                                   double* out_den_acc, double* out_ll, int math);
+
+/* The EM fit on interval-dated mutations: coal.cpp:3675-3827 with the R rows (kinds[r], age_begin[r], age_end[r]) of
+ * colate_em_interval_calls for age bins, for B replicates that share the rows and weight row r by weights[b][r] (the
+ * bootstrap-weighted count; finite, >= 0).  One iteration constructs coal_EM(epochs, rates_b), calls every row with
+ * weights[b][r] > 0 in ascending r, sums num_acc[e] += w * num[e], den_acc[e] += w * den[e], ll += w * logl in that
+ * order (a call whose normaliser is not finite contributes zeros and 0), then runs the M-step with its floor
+ * (coal.cpp:3771-3815, regularise == 2: num == 0 -> the rate of the epoch before, 0 at e == 0; den == 0 -> unchanged)
+ * and the stop test ll / prev_ll > 1 - rel_tol && iter > min_iter, prev_ll starting at log(0).
+ * out_rates[B][E], out_iters[B], out_loglik[B], out_flags[B] as for colate_em_batch: out_iters is the reference's
+ * "Total iterations", COLATE_FLAG_MAXITER says that max_iter ended the run, COLATE_FLAG_NAN / COLATE_FLAG_NEG are OR-ed
+ * over all calls of all iterations.  COLATE_FLAG_UNRESOLVED is never set here: the tail model behind it (DESIGN.md
+ * section 6) belongs to the point kernel of colate_em_batch, the interval fit has no such verdict.
+ * Refused (COLATE_EINVAL, before anything is staged): what colate_em_interval_calls refuses for the rows and epochs,
+ * B < 1, R < 1, a negative or non-finite weight, min_iter < 0, max_iter < 1, rel_tol not finite or <= 0,
+ * rate_floor < 0, a negative or non-finite init_rates entry.  E <= COLATE_MAX_EPOCHS (COLATE_ELIMIT).
+ * colate_em_interval_batch keeps the whole loop on the calling thread's device (one persistent workgroup per replicate,
+ * csrc/em_interval_fit_kernel.hip; COLATE_ENODEVICE without one, there is no fall-back); _host is the same loop on the
+ * CPU, math = 0 with <cmath> -- bit for bit the reference's loop on the same libm -- and math = 1 with the kernels' own
+ * exp / log -- bit for bit the device. */
+int colate_em_interval_batch(int B, int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                             const double* weights, const double* epochs, const double* init_rates, int max_iter,
+                             int min_iter, double rel_tol, double rate_floor, double* out_rates, int* out_iters,
+                             double* out_loglik, int* out_flags);
+int colate_em_interval_batch_host(int B, int R, int E, const int* kinds, const double* age_begin, const double* age_end,
+                                  const double* weights, const double* epochs, const double* init_rates, int max_iter,
+                                  int min_iter, double rel_tol, double rate_floor, double* out_rates, int* out_iters,
+                                  double* out_loglik, int* out_flags, int math);
+/* Diagnostic: how many rows a workgroup of colate_em_interval_batch calls at a time for this E (no device needed). */
+int colate_em_interval_batch_waves(int E);
 
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
