@@ -7,8 +7,9 @@
 //   * the preparation of a call (a tree dated as Tree::GetCoordinates dates it, its internal nodes by (epoch, label));
 //   * the tables per group vector, the host twin of the device's pair counting (coalrate.h: the formulas);
 //   * the C ABI over raw trees (colate_coalrate_accumulate[_host]);
-//   * the driver (colate_coalrate_main): options, epochs, both poplabels formats, the per-tree segment walk with its
-//     fractions and 5000-tree blocks, the block bootstrap and the .coal writer.
+//   * the drivers (colate_coalrate_main): options; run_local_ancestry with both poplabels formats, the per-tree segment
+//     walk with its fractions and its .coal rows; run_tree with its call packing and its rows.  What the two share (the
+//     .anc stream, settings, 5000-tree blocks, block bootstrap, the frame of the .coal) is anc_stream.h's.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -26,11 +27,11 @@
 #include <thread>
 #include <vector>
 
+#include "anc_stream.h"
 #include "coalrate.h"
 #include "coalrate_tree.h"
 #include "colate_amd.h"
 #include "colate_internal.h"
-#include "mut_feeder.h"
 
 namespace colate_cr {
 
@@ -288,52 +289,41 @@ using colate::fail;
 int coalrate_accumulate(bool device, int N, int T, const int* parents, const double* branch_lengths, const double* weights,
                         const int* blocks, int num_blocks, const int* group_vector_ids, int S, const int* group_vectors, int G,
                         const double* sample_ages, int E, const double* epochs, double* num, double* denom) {
-  if (N < 2 || N > kMaxHaplotypes)
-    return fail(N < 2 ? COLATE_EINVAL : COLATE_ELIMIT, "coalrate: N = %d haplotypes (supported: 2 .. %d)", N, kMaxHaplotypes);
+  const BlockAccumulate a{"coalrate", device, N, T, weights, blocks, num_blocks, E, epochs};
+  if (const int rc = a.check_N()) return rc;
   if (T < 0 || num_blocks < 1 || S < 1 || G < 1 || E < 2 || E > 65535)
     return fail(COLATE_EINVAL, "coalrate: bad sizes (T %d, blocks %d, S %d, G %d, E %d)", T, num_blocks, S, G, E);
   if (G > 65535 || (long long)E * ((long long)G * (G + 1) / 2) > std::numeric_limits<int>::max())
     return fail(COLATE_ELIMIT, "coalrate: G = %d groups with E = %d epochs (G up to 65535, E * G * (G + 1) / 2 below 2^31)", G, E);
   if ((T && (!parents || !branch_lengths || !weights || !blocks || !group_vector_ids)) || !group_vectors || !epochs || !num || !denom)
     return fail(COLATE_EINVAL, "coalrate: NULL argument");
-  for (int e = 0; e < E; e++)
-    if ((e == 0 && epochs[0] != 0.0) || (e && !(epochs[e] > epochs[e - 1])))
-      return fail(COLATE_EINVAL, "coalrate: epochs must start at 0 and increase");
-  for (int t = 0; t < T; t++) {
-    if (blocks[t] < 0 || blocks[t] >= num_blocks) return fail(COLATE_EINVAL, "coalrate: tree %d in block %d", t, blocks[t]);
+  const int rc_trees = a.check_trees([&](int t) {
     if (group_vector_ids[t] < 0 || group_vector_ids[t] >= S)
       return fail(COLATE_EINVAL, "coalrate: tree %d has group vector %d", t, group_vector_ids[t]);
-    if (!std::isfinite(weights[t])) return fail(COLATE_EINVAL, "coalrate: tree %d has weight %g", t, weights[t]);
-  }
+    return (int)COLATE_OK;
+  });
+  if (rc_trees) return rc_trees;
   CrRun run;
   run.N = N, run.G = G, run.S = S;
   run.epochs.assign(epochs, epochs + E);
   if (sample_ages) run.ages.assign(sample_ages, sample_ages + N);
   run.groups.assign(group_vectors, group_vectors + (size_t)S * N);
   CrTables tab;
-  std::string err;
-  if (!make_tables(run, tab, err)) return fail(COLATE_EINVAL, "coalrate: %s", err.c_str());
-  if (device && colate_device_count() <= 0) return fail(COLATE_ENODEVICE, "coalrate: no usable HIP device");
-  const int chunk = std::max(1, std::min(std::max(T, 1), chunk_calls_for(N, G, E)));
-  int code = 0;
-  std::unique_ptr<CoalRateWalker> w = device ? make_device_walker(-1, run, tab, chunk, err, &code) : make_host_walker(run, tab);
-  if (!w) return fail(code ? code : COLATE_EHIP, "coalrate: %s", err.c_str());
+  std::string why;
+  if (!make_tables(run, tab, why)) return fail(COLATE_EINVAL, "coalrate: %s", why.c_str());
   const int nn = 2 * N - 1;
-  CrChunk c;
-  for (int t0 = 0; t0 < T; t0 += chunk) {
-    c.clear();
-    const int t1 = std::min(T, t0 + chunk);
-    for (int t = t0; t < t1; t++) {
-      if (weights[t] == 0.0) continue;  // (every addend a zero)
-      const int k = c.append(N);
-      if (!prepare_call(run, parents + (size_t)t * nn, branch_lengths + (size_t)t * nn, c, k, err))
-        return fail(COLATE_EINVAL, "coalrate: tree %d: %s", t, err.c_str());
-      c.w[k] = weights[t], c.gv[k] = group_vector_ids[t], c.block[k] = blocks[t];
-    }
-    if (!w->submit(c)) return fail(w->error_code() ? w->error_code() : COLATE_EHIP, "%s", w->error().c_str());
-  }
   CrSums sums;
-  if (!w->finish(sums)) return fail(w->error_code() ? w->error_code() : COLATE_EHIP, "%s", w->error().c_str());
+  const int rc = a.run<CrChunk>(
+      chunk_calls_for(N, G, E),
+      [&](int chunk, std::string& err, int* code) { return device ? make_device_walker(-1, run, tab, chunk, err, code) : make_host_walker(run, tab); },
+      [&](int t, CrChunk& c, std::string& err) {
+        if (weights[t] == 0.0) return true;  // (every addend a zero)
+        const int k = c.append(N);
+        c.w[k] = weights[t], c.gv[k] = group_vector_ids[t], c.block[k] = blocks[t];
+        return prepare_call(run, parents + (size_t)t * nn, branch_lengths + (size_t)t * nn, c, k, err);
+      },
+      sums);
+  if (rc) return rc;
   const int GP = run.GP();
   const size_t cells = (size_t)E * GP;
   std::fill(num, num + (size_t)num_blocks * G * G * E, 0.0);
@@ -438,50 +428,6 @@ void print_coalrate_help() {
             << std::endl;
 }
 
-// coal.cpp:267-325: the epochs in double from --bins (each field through stof)
-bool coalrate_epochs(const Options& opt, std::vector<double>& epochs, std::string& err) {
-  const double log_10 = std::log(10);
-  double years_per_gen = 28.0;
-  if (opt.has("years_per_gen")) years_per_gen = std::stof(opt.get("years_per_gen"));
-  const std::string& str = opt.get("bins");
-  double v[3];
-  size_t i = 0;
-  for (int k = 0; k < 3; k++) {
-    std::string tmp;
-    while (i < str.size() && str[i] != ',') tmp += str[i++];
-    i++;
-    if (k < 2 && i >= str.size()) {
-      err = "Error: epochs format is wrong. Specify x,y,stepsize.";
-      return false;
-    }
-    try {
-      v[k] = std::stof(tmp);
-    } catch (...) {
-      err = "Error: epochs format is wrong. Specify x,y,stepsize.";
-      return false;
-    }
-  }
-  const double epoch_lower = v[0], epoch_upper = v[1], epoch_step = v[2];
-  if (!(epoch_step > 0)) {
-    err = "Error: the step of --bins must be positive.";
-    return false;
-  }
-  epochs.assign(1, 0.0);
-  double epoch_boundary = epoch_lower;
-  while (epoch_boundary < epoch_upper) {
-    epochs.push_back(std::exp(log_10 * epoch_boundary) / years_per_gen);
-    epoch_boundary += epoch_step;
-  }
-  epochs.push_back(std::exp(log_10 * epoch_upper) / years_per_gen);
-  epochs.push_back(std::max(1e8, 10 * epochs[epochs.size() - 1]) / years_per_gen);
-  for (size_t e = 1; e < epochs.size(); e++)
-    if (!(epochs[e] > epochs[e - 1])) {
-      err = "Error: the epochs of --bins do not increase.";
-      return false;
-    }
-  return true;
-}
-
 int count_tokens(const std::string& line) {
   std::istringstream is(line);
   std::string tok;
@@ -545,39 +491,13 @@ bool read_local_ancestry(const std::string& path, Segments& seg, std::string& er
   return true;
 }
 
-// NextTree's weight of every tree (mutations.cpp:616-670) and the .mut row it leaves it_mut at
-struct TreeSpan {
-  float weight = 0.f;
-  int it = 0;
-};
-void plan_spans(const std::vector<MutRow>& rows, int num_trees, std::vector<TreeSpan>& plan) {
-  const int L = (int)rows.size();
-  plan.assign(num_trees, TreeSpan());
-  int pit = 0, tim = rows[0].tree;
-  for (int t = 0; t < num_trees; t++) {
-    plan[t].it = std::min(pit, L - 1);  // (a tree after the last SNP: the reference dereferences the end of its list)
-    double w = 0.0;
-    if (t == tim && pit < L) {
-      w = (pit != 0) ? rows[pit - 1].dist / 2.0 : 0.0;
-      while (rows[pit].tree == tim) {
-        w += rows[pit].dist;
-        pit++;
-        if (pit == L) break;
-      }
-      if (pit != L) {
-        w -= rows[pit - 1].dist / 2.0;
-        tim = rows[pit].tree;
-      }
-    }
-    plan[t].weight = (float)w;  // (the driver's float num_bases_tree_persists)
-  }
-}
-
-int run_local_ancestry(const Options& opt) {
-  if (!opt.has("input") || !opt.has("output") || !opt.has("poplabels") || !opt.has("bins")) {
+// The banner of a mode, or why it does not start: the help, or the options it needs and has not got (-1: go on).
+int coalrate_preamble(const Options& opt, std::initializer_list<const char*> needed, const char* needed_text, bool explain) {
+  if (std::any_of(needed.begin(), needed.end(), [&](const char* k) { return !opt.has(k); })) {
     std::cout << "Not enough arguments supplied." << std::endl;
-    std::cout << "Needed: input, output, poplabels, bins. Optional: years_per_gen, chr, num_bootstraps" << std::endl;
+    std::cout << needed_text << std::endl;
     print_coalrate_help();
+    if (explain) std::cout << "Calculate coalescence rates for sample." << std::endl;
     return 1;
   }
   if (opt.has("help")) {
@@ -587,42 +507,26 @@ int run_local_ancestry(const Options& opt) {
   }
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating coalescence rates for (ancient) sample.." << std::endl;
+  return -1;
+}
 
+bool read_snps(const std::string& prefix, std::vector<MutRow>& rows) {
+  read_mut_file(prefix + ".mut", rows);
+  if (rows.empty()) std::cerr << "Error: " << prefix << ".mut has no SNPs." << std::endl;
+  return !rows.empty();
+}
+
+// coal.cpp:206-590 over coal_LA (coal_tree.cpp:300-654): the coalescence rates of every pair of groups.
+int run_local_ancestry(const Options& opt) {
+  const int rc = coalrate_preamble(opt, {"input", "output", "poplabels", "bins"},
+                                   "Needed: input, output, poplabels, bins. Optional: years_per_gen, chr, num_bootstraps", false);
+  if (rc >= 0) return rc;
+  CoalRateRun r;
+  if (!r.read_settings(opt, "NA", opt.get("input"))) return 1;
+  const std::vector<std::string>& chromosomes = r.chromosomes;
   std::string err;
   CrRun run;
-  if (!coalrate_epochs(opt, run.epochs, err)) {
-    std::cerr << err << std::endl;
-    return 1;
-  }
-  int num_bootstrap = 1;
-  if (opt.has("num_bootstraps")) num_bootstrap = std::stoi(opt.get("num_bootstraps"));
-  if (opt.has("seed")) (void)std::stoi(opt.get("seed"));  // (accepted; coal_LA::init_bootstrap seeds with 1 whatever it is)
-  if (num_bootstrap < 1) {
-    std::cerr << "Error: --num_bootstraps must be at least 1." << std::endl;
-    return 1;
-  }
-  const int block_size = 5000;
-
-  std::vector<std::string> chromosomes, filenames;
-  if (opt.has("chr")) {
-    GzText is;
-    if (!is.open(opt.get("chr"))) {
-      std::cerr << "Error while opening file " << opt.get("chr") << std::endl;
-      return 1;
-    }
-    std::string line;
-    while (is.getline(line)) {
-      chromosomes.push_back(line);
-      filenames.push_back(opt.get("input") + "_chr" + line);
-    }
-    if (chromosomes.empty()) {
-      std::cerr << "Error: no chromosome in " << opt.get("chr") << std::endl;
-      return 1;
-    }
-  } else {
-    chromosomes.push_back("NA");
-    filenames.push_back(opt.get("input"));
-  }
+  run.epochs = r.epochs;
 
   // the poplabels: four tokens in each of the first two lines mean the 4 column format (coal.cpp:364-381)
   Segments seg;
@@ -645,11 +549,7 @@ int run_local_ancestry(const Options& opt) {
       seg.labels = pl.groups;
       for (size_t chr = 0; chr < chromosomes.size(); chr++) {  // two pseudo-segments per chromosome (coal.cpp:392-401)
         std::vector<MutRow> rows;
-        read_mut_file(filenames[chr] + ".mut", rows);
-        if (rows.empty()) {
-          std::cerr << "Error: " << filenames[chr] << ".mut has no SNPs." << std::endl;
-          return 1;
-        }
+        if (!read_snps(r.prefixes[chr], rows)) return 1;
         seg.chrom.push_back(chromosomes[chr]);
         seg.bp.push_back(0);
         seg.chrom.push_back(chromosomes[chr]);
@@ -676,64 +576,29 @@ int run_local_ancestry(const Options& opt) {
     std::cerr << "Error: " << run.G << " groups with " << run.E() << " epochs are more than colate_amd supports." << std::endl;
     return 1;
   }
-
-  bool use_device = true;
-  if (const char* e = std::getenv("COLATE_DEVICE_COALRATE"))
-    if (std::string(e) == "0") use_device = false;
-  if (use_device && colate_device_count() <= 0) use_device = false;  // no device: the host twin
-  const int device = opt.has("device") ? std::stoi(opt.get("device")) : 0;
-  const int nthreads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  const bool timing = std::getenv("COLATE_TIMING") != nullptr;
-  const double t_begin = StageTimes::now();
-  double t_prepare = 0, t_walk = 0;
+  r.choose_device(opt, true);
 
   std::unique_ptr<CoalRateWalker> walker;
-  int N = 0, chunk_calls = 1, num_blocks = 0, local_index = 0;
+  int chunk_calls = 1, local_index = 0;
   for (size_t chr = 0; chr < chromosomes.size(); chr++) {
     if (local_index == S) break;
     std::cerr << "CHR " << chromosomes[chr] << ":\n";
+    const std::string& prefix = r.prefixes[chr];
     std::vector<MutRow> rows;
-    read_mut_file(filenames[chr] + ".mut", rows);
-    if (rows.empty()) {
-      std::cerr << "Error: " << filenames[chr] << ".mut has no SNPs." << std::endl;
+    if (!read_snps(prefix, rows)) return 1;
+    AncStream anc;
+    if (!anc.open(prefix)) {
+      std::cerr << "Failed to open file " << prefix << ".anc(.gz)" << std::endl;
       return 1;
     }
-    GzText anc;
-    if (!anc.open(filenames[chr] + ".anc") && !anc.open(filenames[chr] + ".anc.gz")) {
-      std::cerr << "Failed to open file " << filenames[chr] << ".anc(.gz)" << std::endl;
+    if (!anc.read_header(err)) {
+      std::cerr << "Error: " << err << std::endl;
       return 1;
     }
-    std::string line;
-    int n_chr = 0, num_trees = 0;
-    std::vector<double> ages;
-    {  // mutations.cpp:555-581
-      anc.getline(line);
-      std::istringstream is(line);
-      std::string tmp;
-      is >> tmp >> n_chr;
-      if (n_chr >= 2) {
-        ages.resize(n_chr);
-        int i = 0;
-        while (i < n_chr && is >> ages[i]) i++;
-        if (i != n_chr) ages.clear();
-      }
-      anc.getline(line);
-      std::istringstream is2(line);
-      is2 >> tmp >> num_trees;
-    }
-    if (n_chr < 2 || n_chr > kMaxHaplotypes) {
-      std::cerr << "Error: " << filenames[chr] << ".anc: " << n_chr << " haplotypes (colate_amd supports 2 .. " << kMaxHaplotypes
-                << ")." << std::endl;
-      return 1;
-    }
-    if (num_trees < 1) {
-      std::cerr << "Error: " << filenames[chr] << ".anc has no trees." << std::endl;
-      return 1;
-    }
+    const int N = anc.N;
     if (!walker) {
-      N = n_chr;
       run.N = N;
-      run.ages = ages;
+      run.ages = anc.ages;
       run.groups.clear();
       for (const std::vector<int>& g : seg.group) {
         if ((int)g.size() != N) {
@@ -749,16 +614,10 @@ int run_local_ancestry(const Options& opt) {
         return 1;
       }
       chunk_calls = chunk_calls_for(N, run.G, run.E());
-      if (use_device) {
-        std::string why;
-        walker = make_device_walker(device, run, tab, chunk_calls, why);
-        if (!walker) std::cerr << "CoalRate: the host twin runs instead of device " << device << ": " << why << std::endl;
-      }
-      if (!walker) walker = make_host_walker(run, tab);
-    } else if (n_chr != N || ages != run.ages) {
-      std::cerr << "Error: " << filenames[chr] << ".anc has other haplotypes (or sample ages) than the first chromosome's." << std::endl;
-      return 1;
+      walker = r.make_walker([&](int device, std::string& why) { return make_device_walker(device, run, tab, chunk_calls, why); },
+                             [&] { return make_host_walker(run, tab); });
     }
+    if (!r.same_samples(anc, prefix)) return 1;
 
     if (chromosomes.size() > 1 || chromosomes[chr] != "NA") {
       while (seg.chrom[local_index] != chromosomes[chr]) {
@@ -773,81 +632,42 @@ int run_local_ancestry(const Options& opt) {
       std::cerr << "Error: First entry for new chr has to start at BP = 0" << std::endl;
       return 1;
     }
-    // coal_LA::update_ancmut
-    int current_block = num_blocks, count_trees = 0;
-    num_blocks += (int)(num_trees / ((double)block_size) + 1);
-
+    r.begin_chromosome(anc.num_trees);
     std::vector<TreeSpan> plan;
-    plan_spans(rows, num_trees, plan);
-    const int L = (int)rows.size(), nn = 2 * N - 1;
+    plan_spans(rows, anc.num_trees, plan);
+    const int L = (int)rows.size();
     const bool any_chr = chromosomes[chr] == "NA";
     auto same_chr = [&](int k) { return seg.chrom[k] == chromosomes[chr] || any_chr; };
 
     CrChunk base, out;  // the trees of a batch as prepared; the calls made of them
-    std::vector<std::string> lines;
     bool stop = false;  // (the reference leaves a chromosome's loop when a cut tree reaches the last segment)
-    int perc = -1, tree_count = 0;
-    for (int t0 = 0; t0 < num_trees && !stop; t0 += chunk_calls) {
-      const int t1 = std::min(num_trees, t0 + chunk_calls), nb = t1 - t0;
-      double ts = StageTimes::now();
-      lines.resize(nb);
-      for (int k = 0; k < nb; k++)
-        if (!anc.getline(lines[k])) {
-          std::cerr << "Error: " << filenames[chr] << ".anc ends after " << t0 + k << " of " << num_trees << " trees." << std::endl;
-          return 1;
-        }
+    for (int t0 = 0; t0 < anc.num_trees && !stop; t0 += chunk_calls) {
+      const int nb = std::min(anc.num_trees, t0 + chunk_calls) - t0;
+      const double ts = StageTimes::now();
       base.clear();
       for (int k = 0; k < nb; k++) base.append(N);
-      std::vector<std::string> errs(nthreads);
-      std::vector<std::thread> pool;
-      const int per = (nb + nthreads - 1) / nthreads;
-      for (int w = 0; w < nthreads; w++) {
-        const int a = w * per, b = std::min(nb, a + per);
-        if (a >= b) break;
-        pool.emplace_back([&, a, b, w] {
-          std::vector<int> par(nn);
-          std::vector<double> bl(nn);
-          for (int k = a; k < b; k++) {
-            if (plan[t0 + k].weight == 0.0f) continue;  // (every call of it adds zeros: never submitted)
-            if (!parse_tree_line(lines[k], N, par.data(), bl.data())) {
-              errs[w] = "cannot read tree " + std::to_string(t0 + k);
-              return;
-            }
-            std::string e;
-            if (!prepare_call(run, par.data(), bl.data(), base, k, e)) {
-              errs[w] = "tree " + std::to_string(t0 + k) + ": " + e;
-              return;
-            }
-          }
-        });
+      // (a tree of weight 0: every call of it adds zeros, and it is never submitted)
+      if (!anc.read_lines(nb, err) ||
+          !anc.parse_lines(
+              r.nthreads, [&](int k) { return plan[t0 + k].weight != 0.0f; },
+              [&](int k, const int* par, const double* bl, std::string& e) { return prepare_call(run, par, bl, base, k, e); }, err)) {
+        std::cerr << "Error: " << err << std::endl;
+        return 1;
       }
-      for (auto& th : pool) th.join();
-      for (const std::string& e : errs)
-        if (!e.empty()) {
-          std::cerr << "Error: " << e << std::endl;
-          return 1;
-        }
-      // the segment walk (coal.cpp:489-566) and coal_LA::populate's block counter
+      // the segment walk (coal.cpp:489-566) and coal_LA::populate
       out.clear();
       for (int k = 0; k < nb && !stop; k++) {
         const int t = t0 + k;
         const double w_tree = plan[t].weight;
         auto populate = [&](double w, int s, bool new_tree) {
-          if (count_trees == block_size) {
-            current_block++;
-            count_trees = 0;
-          }
+          const int block = r.block();
           if (w != 0.0 && w_tree != 0.0) {
             const int x = out.append_from(base, k);
-            out.w[x] = w, out.gv[x] = s, out.block[x] = current_block;
+            out.w[x] = w, out.gv[x] = s, out.block[x] = block;
           }
-          if (new_tree) count_trees++;
+          if (new_tree) r.count_tree();
         };
-        if ((int)(((double)tree_count) / num_trees * 100.0) > perc) {
-          perc = (int)(((double)tree_count) / num_trees * 100.0);
-          std::cerr << "[" << perc << "%]\r";
-        }
-        tree_count++;
+        r.progress();
         const int it = plan[t].it;
         int bp_start = rows[it].pos;
         if (it != 0) bp_start = (bp_start + rows[it - 1].pos) / 2.0;
@@ -883,141 +703,52 @@ int run_local_ancestry(const Options& opt) {
           populate(w_tree, local_index, true);
         }
       }
-      t_prepare += StageTimes::now() - ts;
-      ts = StageTimes::now();
-      if (!walker->submit(out)) {
-        std::cerr << "Error: " << walker->error() << std::endl;
-        return 1;
-      }
-      t_walk += StageTimes::now() - ts;
+      if (!r.submit(*walker, out, ts)) return 1;
     }
     local_index++;
     std::cerr << std::endl;
   }
-  double ts = StageTimes::now();
   CrSums sums;
-  if (!walker || !walker->finish(sums)) {
-    std::cerr << "Error: " << (walker ? walker->error() : std::string("no chromosome was read")) << std::endl;
-    return 1;
-  }
-  t_walk += StageTimes::now() - ts;
-  const double gpu_s = walker->gpu_seconds();
-  walker.reset();
+  if (!r.finish(walker, sums)) return 1;
 
-  // coal_LA::init_bootstrap and Dump (coal_tree.cpp:529-654)
+  // coal_LA::init_bootstrap and Dump (coal_tree.cpp:529-654): draws in 0 .. num_blocks - 1
   const int G = run.G, E = run.E(), GP = run.GP();
-  const size_t cells = (size_t)E * GP;
-  std::ofstream os(opt.get("output") + ".coal");
-  if (!os) {
-    std::cerr << "Error: cannot write " << opt.get("output") << ".coal" << std::endl;
-    return 1;
-  }
-  for (const std::string& g : seg.labels) os << g << " ";
-  os << "\n";
-  for (double e : run.epochs) os << e << " ";
-  os << "\n";
-  std::mt19937 rng;
-  rng.seed(1);
-  std::uniform_int_distribution<int> d(0, num_blocks - 1);
-  std::vector<int> times(num_blocks);
-  std::vector<double> bnum(cells), bden(cells);
-  for (int iter = 0; iter < num_bootstrap; iter++) {
-    std::fill(times.begin(), times.end(), 0);
-    for (int b = 0; b < num_blocks; b++) times[d(rng)]++;
-    std::fill(bnum.begin(), bnum.end(), 0.0);
-    std::fill(bden.begin(), bden.end(), 0.0);
-    for (int b = 0; b < num_blocks; b++)
-      if (times[b] > 0 && b < sums.blocks)
-        for (size_t i = 0; i < cells; i++) {
-          bnum[i] += times[b] * sums.num[b * cells + i];
-          bden[i] += times[b] * sums.den[b * cells + i];
-        }
+  std::string labels;
+  for (const std::string& g : seg.labels) labels += g + " ";
+  const auto rows = [&](std::ostream& os, int, const double* num, const double* den) {
     for (int i = 0; i < G; i++)
       for (int j = 0; j < G; j++) {
         os << i << " " << j << " ";
         const int gp = cr_pair(std::max(i, j), std::min(i, j));
-        for (int e = 0; e < E; e++) os << bnum[(size_t)e * GP + gp] / bden[(size_t)e * GP + gp] << " ";
+        for (int e = 0; e < E; e++) os << num[(size_t)e * GP + gp] / den[(size_t)e * GP + gp] << " ";
         os << "\n";
       }
-  }
-  os.close();
-  if (timing)
-    std::fprintf(stderr, "coalrate timing: read+prepare %.3f s, walk %.3f s (%s %.3f s), total %.3f s\n", t_prepare, t_walk,
-                 gpu_s > 0 ? "device kernels" : "host twin", gpu_s, StageTimes::now() - t_begin);
-  print_usage_footer();
-  return 0;
+  };
+  if (!r.write_coal(opt.get("output"), labels, sums, (size_t)E * GP, r.num_blocks - 1, rows)) return 1;
+  return r.done();
 }
 
 // coal.cpp:21-204 over coal_tree (coal_tree.cpp:1-295): the coalescence rate of the whole sample.
 int run_tree(const Options& opt) {
-  if (!opt.has("input") || !opt.has("output") || !opt.has("bins")) {
-    std::cout << "Not enough arguments supplied." << std::endl;
-    std::cout << "Needed: input, output, bins. Optional: years_per_gen, chr, num_bootstraps" << std::endl;
-    print_coalrate_help();
-    std::cout << "Calculate coalescence rates for sample." << std::endl;
-    return 1;
-  }
-  if (opt.has("help")) {
-    print_coalrate_help();
-    std::cout << "Calculate coalescence rates for sample." << std::endl;
-    return 0;
-  }
-  std::cerr << "---------------------------------------------------------" << std::endl;
-  std::cerr << "Calculating coalescence rates for (ancient) sample.." << std::endl;
-
-  std::string err;
-  std::vector<double> epochs;
-  if (!coalrate_epochs(opt, epochs, err)) {
-    std::cerr << err << std::endl;
-    return 1;
-  }
-  int num_bootstrap = 1;
-  if (opt.has("num_bootstraps")) num_bootstrap = std::stoi(opt.get("num_bootstraps"));
-  if (opt.has("seed")) (void)std::stoi(opt.get("seed"));  // (accepted; coal_tree::init_bootstrap seeds with 1 whatever it is)
-  if (num_bootstrap < 1) {
-    std::cerr << "Error: --num_bootstraps must be at least 1." << std::endl;
-    return 1;
-  }
-  const int block_size = 5000;
-
-  std::vector<std::string> chromosomes;
-  if (opt.has("chr")) {
-    GzText is;
-    if (!is.open(opt.get("chr"))) {
-      std::cerr << "Error while opening file " << opt.get("chr") << std::endl;
-      return 1;
-    }
-    std::string line;
-    while (is.getline(line)) chromosomes.push_back(line);
-    if (chromosomes.empty()) {
-      std::cerr << "Error: no chromosome in " << opt.get("chr") << std::endl;
-      return 1;
-    }
-  } else {
-    chromosomes.push_back("1");
-  }
-
+  const int rc = coalrate_preamble(opt, {"input", "output", "bins"},
+                                   "Needed: input, output, bins. Optional: years_per_gen, chr, num_bootstraps", true);
+  if (rc >= 0) return rc;
+  CoalRateRun r;
+  if (!r.read_settings(opt, "1", opt.get("input") + "_chr1")) return 1;
   // The host twin is the default: at both measured shapes (profiles/coalrate/coalrate_tree_bench.json) opening the device
   // costs more than the host twin's whole walk, and the run is slower end to end.  COLATE_DEVICE_COALRATE=1 asks for the kernel.
-  bool use_device = false;
-  if (const char* e = std::getenv("COLATE_DEVICE_COALRATE"))
-    if (std::string(e) == "1") use_device = true;
-  if (use_device && colate_device_count() <= 0) use_device = false;  // no device: the host twin
-  const int device = opt.has("device") ? std::stoi(opt.get("device")) : 0;
-  const int nthreads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  const bool timing = std::getenv("COLATE_TIMING") != nullptr;
-  const double t_begin = StageTimes::now();
-  double t_prepare = 0, t_walk = 0;
+  r.choose_device(opt, false);
+  const std::vector<double>& epochs = r.epochs;
   const int E = (int)epochs.size();
 
+  std::string err;
   std::unique_ptr<colate_crt::CoalTreeWalker> walker;
-  std::vector<double> run_ages;
-  int N = 0, chunk_calls = 1, num_blocks = 0;
-  for (size_t chr = 0; chr < chromosomes.size(); chr++) {
-    std::cerr << "CHR " << chromosomes[chr] << ":\n";
-    const std::string prefix = opt.get("input") + "_chr" + chromosomes[chr];
-    GzText anc;
-    if (!anc.open(prefix + ".anc") && !anc.open(prefix + ".anc.gz")) {
+  int chunk_calls = 1;
+  for (size_t chr = 0; chr < r.chromosomes.size(); chr++) {
+    std::cerr << "CHR " << r.chromosomes[chr] << ":\n";
+    const std::string& prefix = r.prefixes[chr];
+    AncStream anc;
+    if (!anc.open(prefix)) {
       std::cerr << "Error: --mode tree: failed to open " << prefix << ".anc(.gz)" << std::endl;
       return 1;
     }
@@ -1029,186 +760,77 @@ int run_tree(const Options& opt) {
       }
     }
     std::vector<MutRow> rows;
-    read_mut_file(prefix + ".mut", rows);
-    if (rows.empty()) {
-      std::cerr << "Error: " << prefix << ".mut has no SNPs." << std::endl;
+    if (!read_snps(prefix, rows)) return 1;
+    if (!anc.read_header(err)) {
+      std::cerr << "Error: " << err << std::endl;
       return 1;
     }
-    std::string line;
-    int n_chr = 0, num_trees = 0;
-    std::vector<double> ages;
-    {  // mutations.cpp:555-581
-      anc.getline(line);
-      std::istringstream is(line);
-      std::string tmp;
-      is >> tmp >> n_chr;
-      if (n_chr >= 2) {
-        ages.resize(n_chr);
-        int i = 0;
-        while (i < n_chr && is >> ages[i]) i++;
-        if (i != n_chr) ages.clear();
-      }
-      anc.getline(line);
-      std::istringstream is2(line);
-      is2 >> tmp >> num_trees;
-    }
-    if (n_chr < 2 || n_chr > kMaxHaplotypes) {
-      std::cerr << "Error: " << prefix << ".anc: " << n_chr << " haplotypes (colate_amd supports 2 .. " << kMaxHaplotypes << ")."
-                << std::endl;
-      return 1;
-    }
-    if (num_trees < 1) {
-      std::cerr << "Error: " << prefix << ".anc has no trees." << std::endl;
-      return 1;
-    }
-    for (double a : ages)
+    const int N = anc.N;
+    for (double a : anc.ages)
       if (!(a >= 0.0)) {
         std::cerr << "Error: " << prefix << ".anc: sample age " << a << std::endl;
         return 1;
       }
     if (!walker) {
-      N = n_chr;
-      run_ages = ages;
       chunk_calls = colate_crt::chunk_calls_for(N, E);
-      if (use_device) {
-        std::string why;
-        walker = colate_crt::make_device_walker(device, N, epochs, chunk_calls, why);
-        if (!walker) std::cerr << "CoalRate: the host twin runs instead of device " << device << ": " << why << std::endl;
-      }
-      if (!walker) walker = colate_crt::make_host_walker(N, epochs);
-    } else if (n_chr != N || ages != run_ages) {
-      std::cerr << "Error: " << prefix << ".anc has other haplotypes (or sample ages) than the first chromosome's." << std::endl;
-      return 1;
+      walker = r.make_walker(
+          [&](int device, std::string& why) { return colate_crt::make_device_walker(device, N, epochs, chunk_calls, why); },
+          [&] { return colate_crt::make_host_walker(N, epochs); });
     }
-    // coal_tree::update_ancmut
-    int current_block = num_blocks, count_trees = 0;
-    num_blocks += (int)(num_trees / ((double)block_size) + 1);
-
+    if (!r.same_samples(anc, prefix)) return 1;
+    r.begin_chromosome(anc.num_trees);
     std::vector<TreeSpan> plan;
-    plan_spans(rows, num_trees, plan);
+    plan_spans(rows, anc.num_trees, plan);
     const size_t nn = 2 * (size_t)N - 1;
+    const double* ages = anc.ages.empty() ? nullptr : anc.ages.data();
     colate_crt::CrtChunk out;
-    std::vector<std::string> lines;
     std::vector<int> call_of;
-    int perc = -1, tree_count = 0;
-    for (int t0 = 0; t0 < num_trees; t0 += chunk_calls) {
-      const int t1 = std::min(num_trees, t0 + chunk_calls), nb = t1 - t0;
-      double ts = StageTimes::now();
-      lines.resize(nb);
-      for (int k = 0; k < nb; k++)
-        if (!anc.getline(lines[k])) {
-          std::cerr << "Error: " << prefix << ".anc ends after " << t0 + k << " of " << num_trees << " trees." << std::endl;
-          return 1;
-        }
-      // coal_tree::populate's block counter: every tree counts; a tree of weight 0 adds nothing and is not submitted
+    for (int t0 = 0; t0 < anc.num_trees; t0 += chunk_calls) {
+      const int nb = std::min(anc.num_trees, t0 + chunk_calls) - t0;
+      const double ts = StageTimes::now();
+      if (!anc.read_lines(nb, err)) {
+        std::cerr << "Error: " << err << std::endl;
+        return 1;
+      }
+      // coal_tree::populate: every tree counts; a tree of weight 0 adds nothing and is not submitted
       out.clear();
       call_of.assign(nb, -1);
       for (int k = 0; k < nb; k++) {
-        if ((int)(((double)tree_count) / num_trees * 100.0) > perc) {
-          perc = (int)(((double)tree_count) / num_trees * 100.0);
-          std::cerr << "[" << perc << "%]\r";
-        }
-        tree_count++;
-        if (count_trees == block_size) {
-          current_block++;
-          count_trees = 0;
-        }
+        r.progress();
+        const int block = r.block();
         if (plan[t0 + k].weight != 0.0f) {
           const int x = out.append(N);
-          out.w[x] = plan[t0 + k].weight, out.block[x] = current_block;
+          out.w[x] = plan[t0 + k].weight, out.block[x] = block;
           call_of[k] = x;
         }
-        count_trees++;
+        r.count_tree();
       }
-      std::vector<std::string> errs(nthreads);
-      std::vector<std::thread> pool;
-      const int per = (nb + nthreads - 1) / nthreads;
-      for (int w = 0; w < nthreads; w++) {
-        const int a = w * per, b = std::min(nb, a + per);
-        if (a >= b) break;
-        pool.emplace_back([&, a, b, w] {
-          std::vector<int> par(nn);
-          std::vector<double> bl(nn);
-          for (int k = a; k < b; k++) {
-            if (call_of[k] < 0) continue;
-            if (!parse_tree_line(lines[k], N, par.data(), bl.data())) {
-              errs[w] = "cannot read tree " + std::to_string(t0 + k);
-              return;
-            }
-            std::string e;
-            if (!colate_crt::prepare_times(N, run_ages.empty() ? nullptr : run_ages.data(), epochs, par.data(), bl.data(),
-                                           out.t.data() + call_of[k] * nn, e)) {
-              errs[w] = "tree " + std::to_string(t0 + k) + ": " + e;
-              return;
-            }
-          }
-        });
-      }
-      for (auto& th : pool) th.join();
-      for (const std::string& e : errs)
-        if (!e.empty()) {
-          std::cerr << "Error: " << e << std::endl;
-          return 1;
-        }
-      t_prepare += StageTimes::now() - ts;
-      ts = StageTimes::now();
-      if (!walker->submit(out)) {
-        std::cerr << "Error: " << walker->error() << std::endl;
+      if (!anc.parse_lines(
+              r.nthreads, [&](int k) { return call_of[k] >= 0; },
+              [&](int k, const int* par, const double* bl, std::string& e) {
+                return colate_crt::prepare_times(N, ages, epochs, par, bl, out.t.data() + call_of[k] * nn, e);
+              },
+              err)) {
+        std::cerr << "Error: " << err << std::endl;
         return 1;
       }
-      t_walk += StageTimes::now() - ts;
+      if (!r.submit(*walker, out, ts)) return 1;
     }
     std::cerr << std::endl;
   }
-  double ts = StageTimes::now();
   CrSums sums;
-  if (!walker || !walker->finish(sums)) {
-    std::cerr << "Error: " << (walker ? walker->error() : std::string("no chromosome was read")) << std::endl;
-    return 1;
-  }
-  t_walk += StageTimes::now() - ts;
-  const double gpu_s = walker->gpu_seconds();
-  walker.reset();
+  if (!r.finish(walker, sums)) return 1;
 
   // coal_tree::init_bootstrap and Dump (coal_tree.cpp:180-295): draws in 0 .. num_blocks, the last of which selects no block
-  std::ofstream os(opt.get("output") + ".coal");
-  if (!os) {
-    std::cerr << "Error: cannot write " << opt.get("output") << ".coal" << std::endl;
-    return 1;
-  }
-  for (int i = 0; i < num_bootstrap; i++) os << i << " ";
-  os << "\n";
-  for (double e : epochs) os << e << " ";
-  os << "\n";
-  std::mt19937 rng;
-  rng.seed(1);
-  std::uniform_int_distribution<int> d(0, num_blocks);
-  std::vector<int> times(num_blocks);
-  std::vector<double> bnum(E), bden(E);
-  for (int iter = 0; iter < num_bootstrap; iter++) {
-    std::fill(times.begin(), times.end(), 0);
-    for (int b = 0; b < num_blocks; b++) {
-      const int x = d(rng);
-      if (x < num_blocks) times[x]++;
-    }
-    std::fill(bnum.begin(), bnum.end(), 0.0);
-    std::fill(bden.begin(), bden.end(), 0.0);
-    for (int b = 0; b < num_blocks; b++)
-      if (times[b] > 0)
-        for (int e = 0; e < E; e++) {
-          bnum[e] += times[b] * (b < sums.blocks ? sums.num[(size_t)b * E + e] : 0.0);
-          bden[e] += times[b] * (b < sums.blocks ? sums.den[(size_t)b * E + e] : 0.0);
-        }
+  std::string replicates;
+  for (int i = 0; i < r.num_bootstrap; i++) replicates += std::to_string(i) + " ";
+  const auto rows = [&](std::ostream& os, int iter, const double* num, const double* den) {
     os << "0 " << iter << " ";
-    for (int e = 0; e < E; e++) os << bnum[e] / bden[e] << " ";
+    for (int e = 0; e < E; e++) os << num[e] / den[e] << " ";
     os << "\n";
-  }
-  os.close();
-  if (timing)
-    std::fprintf(stderr, "coalrate timing: read+prepare %.3f s, walk %.3f s (%s %.3f s), total %.3f s\n", t_prepare, t_walk,
-                 gpu_s > 0 ? "device kernels" : "host twin", gpu_s, StageTimes::now() - t_begin);
-  print_usage_footer();
-  return 0;
+  };
+  if (!r.write_coal(opt.get("output"), replicates, sums, (size_t)E, r.num_blocks, rows)) return 1;
+  return r.done();
 }
 
 }  // namespace

@@ -11,12 +11,16 @@
 // an epoch <= e) and sub the pairs' sum of (age - epochs[e_age]) in epoch e (a table per group vector).  All counts are
 // exact integers; every double sum has the one order written here, for the kernel and the host twin alike.
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "colate_amd.h"
+#include "colate_internal.h"
 #include "condcoal.h"
 
 #if defined(__HIPCC__)
@@ -134,13 +138,15 @@ struct CrSums {
   std::vector<double> num, den;
 };
 
-// One way to accumulate: the prepared calls go in chunk by chunk, the per-block sums come out.  Both implementations sum
-// in the same order (per call and group pair over the nodes by (epoch, label); per cell over the calls in input order), so
-// their sums agree bit for bit.
-class CoalRateWalker {
+// One way to accumulate, for both CoalRate modes (Chunk: CrChunk here, colate_crt::CrtChunk for --mode tree): the prepared
+// calls go in chunk by chunk, the per-block sums come out.  A mode's two implementations sum in the same order (here: per
+// call and group pair over the nodes by (epoch, label); per cell over the calls in input order), so their sums agree bit
+// for bit.
+template <class Chunk>
+class BlockSumWalker {
  public:
-  virtual ~CoalRateWalker() = default;
-  virtual bool submit(const CrChunk& c) = 0;
+  virtual ~BlockSumWalker() = default;
+  virtual bool submit(const Chunk& c) = 0;
   virtual bool finish(CrSums& out) = 0;
   const std::string& error() const { return err_; }
   int error_code() const { return code_; }
@@ -158,6 +164,7 @@ class CoalRateWalker {
   std::string err_;
   int code_ = 0;
 };
+using CoalRateWalker = BlockSumWalker<CrChunk>;
 
 std::unique_ptr<CoalRateWalker> make_host_walker(const CrRun& run, const CrTables& tab);
 // Null, the reason in `why` and its COLATE_E code in *code, when there is no device or the run does not fit it (device -1:
@@ -169,5 +176,60 @@ size_t device_call_bytes(int N, int G, int E);
 // Calls per chunk: the most that fit 4M node entries and 256 MiB of device memory, or COLATE_COALRATE_CHUNK_TREES where
 // that is set and smaller (tests cross chunk and block boundaries on small inputs).
 int chunk_calls_for(int N, int G, int E);
+
+
+// What the C ABI bodies of the two modes share (colate_coalrate_accumulate[_host], colate_coalrate_tree_accumulate[_host]):
+// the arguments both take, the checks both make, and the run itself.  A body makes the checks in its own order between
+// those of its own; every message starts with `name`.
+struct BlockAccumulate {
+  const char* name;  // "coalrate" / "coalrate tree"
+  bool device;
+  int N, T;
+  const double* weights;
+  const int* blocks;
+  int num_blocks, E;
+  const double* epochs;
+
+  int check_N() const {
+    if (N < 2 || N > kMaxHaplotypes)
+      return colate::fail(N < 2 ? COLATE_EINVAL : COLATE_ELIMIT, "%s: N = %d haplotypes (supported: 2 .. %d)", name, N, kMaxHaplotypes);
+    return COLATE_OK;
+  }
+  // the epochs; then per tree its block, what extra(t) checks (COLATE_OK or a failure's code) and its weight
+  template <class Extra>
+  int check_trees(Extra extra) const {
+    for (int e = 0; e < E; e++)
+      if ((e == 0 && epochs[0] != 0.0) || (e && !(epochs[e] > epochs[e - 1])))
+        return colate::fail(COLATE_EINVAL, "%s: epochs must start at 0 and increase", name);
+    for (int t = 0; t < T; t++) {
+      if (blocks[t] < 0 || blocks[t] >= num_blocks) return colate::fail(COLATE_EINVAL, "%s: tree %d in block %d", name, t, blocks[t]);
+      if (const int rc = extra(t)) return rc;
+      if (!std::isfinite(weights[t])) return colate::fail(COLATE_EINVAL, "%s: tree %d has weight %g", name, t, weights[t]);
+    }
+    return COLATE_OK;
+  }
+  // The sums over all trees: make(chunk, err, code) opens the device walker or the host twin for chunks of `chunk`
+  // calls; prepare(t, c, err) appends tree t to the chunk, or leaves it out.
+  template <class Chunk, class Make, class Prepare>
+  int run(int chunk_calls, Make make, Prepare prepare, CrSums& sums) const {
+    if (device && colate_device_count() <= 0) return colate::fail(COLATE_ENODEVICE, "%s: no usable HIP device", name);
+    const int chunk = std::max(1, std::min(std::max(T, 1), chunk_calls));
+    int code = 0;
+    std::string err;
+    std::unique_ptr<BlockSumWalker<Chunk>> w = make(chunk, err, &code);
+    if (!w) return colate::fail(code ? code : COLATE_EHIP, "%s: %s", name, err.c_str());
+    const auto walker_failed = [&] { return colate::fail(w->error_code() ? w->error_code() : COLATE_EHIP, "%s", w->error().c_str()); };
+    Chunk c;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+      c.clear();
+      const int t1 = std::min(T, t0 + chunk);
+      for (int t = t0; t < t1; t++)
+        if (!prepare(t, c, err)) return colate::fail(COLATE_EINVAL, "%s: tree %d: %s", name, t, err.c_str());
+      if (!w->submit(c)) return walker_failed();
+    }
+    if (!w->finish(sums)) return walker_failed();
+    return COLATE_OK;
+  }
+};
 
 }  // namespace colate_cr

@@ -8,24 +8,17 @@
 //     pairs share a workgroup once a chunk has more calls than the chip has wave slots.  Out: cumB / R [call][E][GP].
 //   * cr_fold: one lane per (epoch, group pair) cell adds the calls' addends into their blocks in call order; the
 //     per-block sums stay on the device until finish().
-// No atomics: every output word has one writer.
+// No atomics: every output word has one writer.  The walker around the two launches is coalrate_device.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 
-#include "coalrate.h"
-#include "condcoal_device.hpp"
+#include "coalrate_device.hpp"
 
 namespace colate_cr {
 
 namespace {
-
-using colate_cc::CcBuffers;
-
-constexpr int kMaxLanes = 256;            // lanes per workgroup
-constexpr size_t kLdsBytes = 160 * 1024;  // the LDS of a CU, which one workgroup may have whole (the launch opts in)
-constexpr int kWavesPerCu = 8;            // resident waves per CU beyond which packing calls into a workgroup pays
 
 struct CountArgs {
   int T, N, G, E, GP;
@@ -156,195 +149,69 @@ __global__ void __launch_bounds__(kMaxLanes) cr_fold(FoldArgs a) {
   }
 }
 
-#define CR_TRY(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_), COLATE_EHIP); \
-  } while (0)
+struct CrArrays {  // the calls of one launch
+  Staged<int> leaf, gv, block;
+  Staged<CrNode> node;
+  Staged<double> w;
+};
 
-class DeviceWalker final : public CoalRateWalker {
+class DeviceWalker final : public BlockSumDeviceWalker<CrChunk, CrArrays> {
  public:
-  ~DeviceWalker() override {
-    if (stream_) (void)hipStreamSynchronize(stream_);  // (before the buffers go)
-    for (Slot& s : slot_)
-      for (hipEvent_t e : {s.ev0, s.ev1})
-        if (e) (void)hipEventDestroy(e);
-    if (stream_) (void)hipStreamDestroy(stream_);
-    if (num_) (void)hipFree(num_);
-    if (den_) (void)hipFree(den_);
-  }
+  DeviceWalker() : BlockSumDeviceWalker("coalrate") {}
 
   bool open(int device, const CrRun& run, const CrTables& tab, int max_calls) {
-    colate::mark_device_touched();
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail("no HIP device", COLATE_EHIP);
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-    if (device >= n) return fail("no HIP device " + std::to_string(device), COLATE_EHIP);
-    device_ = device;
-    N_ = run.N, G_ = run.G, E_ = run.E(), GP_ = run.GP(), OA_ = tab.OA;
-    max_calls_ = std::max(1, max_calls);
+    if (!open_device(device)) return false;
+    G_ = run.G, E_ = run.E(), GP_ = run.GP(), OA_ = tab.OA;
+    const size_t N = run.N;
     lpc_ = 1;
     while (lpc_ < GP_ && lpc_ < kMaxLanes) lpc_ *= 2;
     // LDS per call: labels, per-lane group counts, and the prefix rows where all of it fits
-    const size_t lab_bytes = sizeof(unsigned short) * ((size_t)N_ + (size_t)lpc_ * G_);
-    const size_t pre_bytes = sizeof(unsigned short) * G_ * ((size_t)N_ + 1);
+    const size_t lab_bytes = sizeof(unsigned short) * (N + (size_t)lpc_ * G_);
+    const size_t pre_bytes = sizeof(unsigned short) * G_ * (N + 1);
     if (lab_bytes > kLdsBytes) return fail("the labels and group counts of one tree do not fit the LDS", COLATE_ELIMIT);
     lds_pre_ = lab_bytes + pre_bytes <= kLdsBytes;
     call_lds_ = lab_bytes + (lds_pre_ ? pre_bytes : 0);
     cpw_cap_ = (int)std::max<size_t>(1, std::min<size_t>(kMaxLanes / lpc_, kLdsBytes / call_lds_));
-    CR_TRY(hipSetDevice(device));
-    CR_TRY(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    hipDeviceProp_t prop;
-    CR_TRY(hipGetDeviceProperties(&prop, device));
-    wave_slots_ = std::max(1, prop.multiProcessorCount) * kWavesPerCu;
-    CR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&cr_count<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-    CR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&cr_count<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
+    const size_t cells = (size_t)E_ * GP_;
+    if (!open_sums(run.N, max_calls, cells)) return false;
+    WALKER_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&cr_count<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
+    WALKER_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&cr_count<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
     if (!upload(groups_, run.groups) || !upload(oa_epoch_, tab.oa_epoch) || !upload(pairs_, tab.pairs) || !upload(sub_, tab.sub) ||
         !upload(width_, tab.width))
       return false;
-    const size_t T = max_calls_, cells = (size_t)E_ * GP_;
-    for (Slot& s : slot_) {
-      CR_TRY(buf_.pinned(s.h_leaf, T * N_));
-      CR_TRY(buf_.pinned(s.h_node, T * (N_ - 1)));
-      CR_TRY(buf_.pinned(s.h_w, T));
-      CR_TRY(buf_.pinned(s.h_gv, T));
-      CR_TRY(buf_.pinned(s.h_block, T));
-      CR_TRY(buf_.device(s.leaf, T * N_));
-      CR_TRY(buf_.device(s.node, T * (N_ - 1)));
-      CR_TRY(buf_.device(s.w, T));
-      CR_TRY(buf_.device(s.gv, T));
-      CR_TRY(buf_.device(s.block, T));
-      CR_TRY(hipEventCreate(&s.ev0));
-      CR_TRY(hipEventCreate(&s.ev1));
-    }
-    // the kernels' intermediate results are used within the stream's order: one copy serves both slots
-    CR_TRY(buf_.device(cumB_, T * cells));
-    CR_TRY(buf_.device(R_, T * cells));
-    if (!lds_pre_) CR_TRY(buf_.device(gpre_, T * G_ * (N_ + 1)));
-    return true;
-  }
-
-  bool submit(const CrChunk& c) override {
-    if (c.T == 0) return true;
-    if (c.N != N_) return fail("coalrate: chunk of another N", COLATE_EINVAL);
-    CR_TRY(hipSetDevice(device_));
-    int max_block = 0;
-    for (int k = 0; k < c.T; k++) max_block = std::max(max_block, c.block[k]);
-    if (!grow(max_block + 1)) return false;
-    for (int t0 = 0; t0 < c.T; t0 += max_calls_) {
-      const int T = std::min(c.T - t0, max_calls_);
-      Slot& s = slot_[cur_];
-      cur_ ^= 1;
-      if (s.busy && !wait(s)) return false;
-      const size_t N = N_;
-      std::memcpy(s.h_leaf, c.leaf.data() + t0 * N, sizeof(int) * T * N);
-      std::memcpy(s.h_node, c.node.data() + t0 * (N - 1), sizeof(CrNode) * T * (N - 1));
-      std::memcpy(s.h_w, c.w.data() + t0, sizeof(double) * T);
-      std::memcpy(s.h_gv, c.gv.data() + t0, sizeof(int) * T);
-      std::memcpy(s.h_block, c.block.data() + t0, sizeof(int) * T);
-      CR_TRY(hipMemcpyAsync(s.leaf, s.h_leaf, sizeof(int) * T * N, hipMemcpyHostToDevice, stream_));
-      CR_TRY(hipMemcpyAsync(s.node, s.h_node, sizeof(CrNode) * T * (N - 1), hipMemcpyHostToDevice, stream_));
-      CR_TRY(hipMemcpyAsync(s.w, s.h_w, sizeof(double) * T, hipMemcpyHostToDevice, stream_));
-      CR_TRY(hipMemcpyAsync(s.gv, s.h_gv, sizeof(int) * T, hipMemcpyHostToDevice, stream_));
-      CR_TRY(hipMemcpyAsync(s.block, s.h_block, sizeof(int) * T, hipMemcpyHostToDevice, stream_));
-      CR_TRY(hipEventRecord(s.ev0, stream_));
-      // calls per workgroup: one while every call finds a wave slot of its own on the chip, beyond that as many as fill
-      // the lanes and the LDS
-      const int waves_per_call = (lpc_ + 63) / 64;
-      const int cpw = std::max(1, std::min(cpw_cap_, (int)(((long long)T * waves_per_call + wave_slots_ - 1) / wave_slots_)));
-      CountArgs ca{T, N_, G_, E_, GP_, cpw, lpc_, s.leaf, s.node, s.gv, groups_, gpre_, cumB_, R_};
-      const int lanes = std::max(64, cpw * lpc_);
-      const int grid = (T + cpw - 1) / cpw;
-      const size_t lds = call_lds_ * cpw;
-      if (lds_pre_) hipLaunchKernelGGL(cr_count<true>, dim3(grid), dim3(lanes), lds, stream_, ca);
-      else hipLaunchKernelGGL(cr_count<false>, dim3(grid), dim3(lanes), lds, stream_, ca);
-      CR_TRY(hipGetLastError());
-      FoldArgs fa{T, E_, GP_, OA_, cumB_, R_, s.w, s.gv, s.block, oa_epoch_, pairs_, sub_, width_, num_, den_};
-      const int cells = E_ * GP_;
-      hipLaunchKernelGGL(cr_fold, dim3((cells + 63) / 64), dim3(64), 0, stream_, fa);
-      CR_TRY(hipGetLastError());
-      CR_TRY(hipEventRecord(s.ev1, stream_));
-      s.busy = true;
-    }
-    return true;
-  }
-
-  bool finish(CrSums& out) override {
-    CR_TRY(hipSetDevice(device_));
+    const size_t T = max_calls_;
     for (Slot& s : slot_)
-      if (s.busy && !wait(s)) return false;
-    CR_TRY(hipStreamSynchronize(stream_));
-    const size_t n = (size_t)blocks_ * E_ * GP_;
-    out.blocks = blocks_;
-    out.num.assign(n, 0.0);
-    out.den.assign(n, 0.0);
-    if (n) {
-      CR_TRY(hipMemcpy(out.num.data(), num_, sizeof(double) * n, hipMemcpyDeviceToHost));
-      CR_TRY(hipMemcpy(out.den.data(), den_, sizeof(double) * n, hipMemcpyDeviceToHost));
-    }
+      if (!make(s.leaf, T * N) || !make(s.node, T * (N - 1)) || !make(s.w, T) || !make(s.gv, T) || !make(s.block, T)) return false;
+    // the kernels' intermediate results are used within the stream's order: one copy serves both slots
+    WALKER_TRY(buf_.device(cumB_, T * cells));
+    WALKER_TRY(buf_.device(R_, T * cells));
+    if (!lds_pre_) WALKER_TRY(buf_.device(gpre_, T * G_ * (N + 1)));
     return true;
   }
 
  private:
-  struct Slot {
-    int *h_leaf = nullptr, *h_gv = nullptr, *h_block = nullptr, *leaf = nullptr, *gv = nullptr, *block = nullptr;
-    CrNode *h_node = nullptr, *node = nullptr;
-    double *h_w = nullptr, *w = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // kernels start / kernels end
-    bool busy = false;
-  };
-  template <class T>
-  bool upload(T*& dst, const std::vector<T>& v) {
-    CR_TRY(buf_.device(dst, v.size()));
-    if (!v.empty()) CR_TRY(hipMemcpy(dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
-    return true;
+  bool stage(Slot& s, const CrChunk& c, int t0, int T) override {
+    const size_t N = N_;
+    return send(s.leaf, c.leaf.data() + t0 * N, T * N) && send(s.node, c.node.data() + t0 * (N - 1), T * (N - 1)) &&
+           send(s.w, c.w.data() + t0, T) && send(s.gv, c.gv.data() + t0, T) && send(s.block, c.block.data() + t0, T);
   }
-  bool wait(Slot& s) {
-    CR_TRY(hipEventSynchronize(s.ev1));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s.ev0, s.ev1) == hipSuccess) gpu_s_ += ms * 1e-3;
-    s.busy = false;
-    return true;
-  }
-  // the per-block sums for at least `blocks` blocks (new ones zero), in the stream's order
-  bool grow(int blocks) {
-    if (blocks <= cap_) {
-      blocks_ = std::max(blocks_, blocks);
-      return true;
-    }
-    const int cap = std::max(blocks, 2 * cap_);
-    const size_t cells = (size_t)E_ * GP_;
-    double *num = nullptr, *den = nullptr;
-    CR_TRY(hipMalloc((void**)&num, sizeof(double) * cap * cells));
-    if (hipMalloc((void**)&den, sizeof(double) * cap * cells) != hipSuccess) {
-      (void)hipFree(num);
-      return fail("hipMalloc of the per-block sums", COLATE_EHIP);
-    }
-    double* old_num = num_;
-    double* old_den = den_;
-    num_ = num, den_ = den;
-    CR_TRY(hipMemsetAsync(num_, 0, sizeof(double) * cap * cells, stream_));
-    CR_TRY(hipMemsetAsync(den_, 0, sizeof(double) * cap * cells, stream_));
-    if (blocks_) {
-      CR_TRY(hipMemcpyAsync(num_, old_num, sizeof(double) * blocks_ * cells, hipMemcpyDeviceToDevice, stream_));
-      CR_TRY(hipMemcpyAsync(den_, old_den, sizeof(double) * blocks_ * cells, hipMemcpyDeviceToDevice, stream_));
-    }
-    CR_TRY(hipStreamSynchronize(stream_));
-    if (old_num) (void)hipFree(old_num);
-    if (old_den) (void)hipFree(old_den);
-    cap_ = cap;
-    blocks_ = blocks;
+  bool launch(Slot& s, int T) override {
+    const Shape sh = launch_shape(T);
+    CountArgs ca{T, N_, G_, E_, GP_, sh.cpw, lpc_, s.leaf.d, s.node.d, s.gv.d, groups_, gpre_, cumB_, R_};
+    const size_t lds = call_lds_ * sh.cpw;
+    if (lds_pre_) hipLaunchKernelGGL(cr_count<true>, dim3(sh.grid), dim3(sh.lanes), lds, stream_, ca);
+    else hipLaunchKernelGGL(cr_count<false>, dim3(sh.grid), dim3(sh.lanes), lds, stream_, ca);
+    WALKER_TRY(hipGetLastError());
+    FoldArgs fa{T, E_, GP_, OA_, cumB_, R_, s.w.d, s.gv.d, s.block.d, oa_epoch_, pairs_, sub_, width_, num_, den_};
+    const int cells = E_ * GP_;
+    hipLaunchKernelGGL(cr_fold, dim3((cells + 63) / 64), dim3(64), 0, stream_, fa);
+    WALKER_TRY(hipGetLastError());
     return true;
   }
 
-  int device_ = 0, N_ = 0, G_ = 0, E_ = 0, GP_ = 0, OA_ = 0, max_calls_ = 1, lpc_ = 1, cpw_cap_ = 1;
+  int G_ = 0, E_ = 0, GP_ = 0, OA_ = 0;
   bool lds_pre_ = true;
   size_t call_lds_ = 0;
-  int wave_slots_ = 1;
-  CcBuffers buf_;
-  hipStream_t stream_ = nullptr;
-  Slot slot_[2];
-  int cur_ = 0;
   int* groups_ = nullptr;
   int* oa_epoch_ = nullptr;
   long long* pairs_ = nullptr;
@@ -352,8 +219,6 @@ class DeviceWalker final : public CoalRateWalker {
   int* cumB_ = nullptr;
   double* R_ = nullptr;
   unsigned short* gpre_ = nullptr;
-  double *num_ = nullptr, *den_ = nullptr;
-  int cap_ = 0, blocks_ = 0;
 };
 
 }  // namespace

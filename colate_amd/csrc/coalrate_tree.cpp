@@ -2,7 +2,7 @@
 //   * the preparation of a call (a tree checked and dated as Tree::GetCoordinates dates it);
 //   * the host twin of the device's sort, scan and epoch sums (coalrate_tree.h: the walk and the one summation order);
 //   * the C ABI over raw trees (colate_coalrate_tree_accumulate[_host]).
-// The driver is coalrate.cpp's run_tree.
+// The driver is coalrate.cpp's run_tree; the C ABI body runs on coalrate.h's BlockAccumulate.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -139,44 +139,29 @@ using colate::fail;
 int tree_accumulate(bool device, int N, int T, const int* parents, const double* branch_lengths, const double* weights,
                     const int* blocks, int num_blocks, const double* sample_ages, int E, const double* epochs, double* num,
                     double* denom) {
-  if (N < 2 || N > kMaxHaplotypes)
-    return fail(N < 2 ? COLATE_EINVAL : COLATE_ELIMIT, "coalrate tree: N = %d haplotypes (supported: 2 .. %d)", N, kMaxHaplotypes);
+  const colate_cr::BlockAccumulate a{"coalrate tree", device, N, T, weights, blocks, num_blocks, E, epochs};
+  if (const int rc = a.check_N()) return rc;
   if (T < 0 || num_blocks < 1 || E < 2 || E > 65535)
     return fail(COLATE_EINVAL, "coalrate tree: bad sizes (T %d, blocks %d, E %d)", T, num_blocks, E);
   if ((T && (!parents || !branch_lengths || !weights || !blocks)) || !epochs || !num || !denom)
     return fail(COLATE_EINVAL, "coalrate tree: NULL argument");
-  for (int e = 0; e < E; e++)
-    if ((e == 0 && epochs[0] != 0.0) || (e && !(epochs[e] > epochs[e - 1])))
-      return fail(COLATE_EINVAL, "coalrate tree: epochs must start at 0 and increase");
-  for (int t = 0; t < T; t++) {
-    if (blocks[t] < 0 || blocks[t] >= num_blocks) return fail(COLATE_EINVAL, "coalrate tree: tree %d in block %d", t, blocks[t]);
-    if (!std::isfinite(weights[t])) return fail(COLATE_EINVAL, "coalrate tree: tree %d has weight %g", t, weights[t]);
-  }
+  if (const int rc = a.check_trees([](int) { return COLATE_OK; })) return rc;
   if (sample_ages)
     for (int i = 0; i < N; i++)
       if (!(sample_ages[i] >= 0.0)) return fail(COLATE_EINVAL, "coalrate tree: sample %d has age %g", i, sample_ages[i]);
   const std::vector<double> ep(epochs, epochs + E);
-  if (device && colate_device_count() <= 0) return fail(COLATE_ENODEVICE, "coalrate tree: no usable HIP device");
-  const int chunk = std::max(1, std::min(std::max(T, 1), chunk_calls_for(N, E)));
-  int code = 0;
-  std::string err;
-  std::unique_ptr<CoalTreeWalker> w = device ? make_device_walker(-1, N, ep, chunk, err, &code) : make_host_walker(N, ep);
-  if (!w) return fail(code ? code : COLATE_EHIP, "coalrate tree: %s", err.c_str());
   const size_t nn = 2 * (size_t)N - 1;
-  CrtChunk c;
-  for (int t0 = 0; t0 < T; t0 += chunk) {
-    c.clear();
-    const int t1 = std::min(T, t0 + chunk);
-    for (int t = t0; t < t1; t++) {
-      const int k = c.append(N);
-      if (!prepare_times(N, sample_ages, ep, parents + t * nn, branch_lengths + t * nn, c.t.data() + k * nn, err))
-        return fail(COLATE_EINVAL, "coalrate tree: tree %d: %s", t, err.c_str());
-      c.w[k] = weights[t], c.block[k] = blocks[t];
-    }
-    if (!w->submit(c)) return fail(w->error_code() ? w->error_code() : COLATE_EHIP, "%s", w->error().c_str());
-  }
   CrSums sums;
-  if (!w->finish(sums)) return fail(w->error_code() ? w->error_code() : COLATE_EHIP, "%s", w->error().c_str());
+  const int rc = a.run<CrtChunk>(
+      chunk_calls_for(N, E),
+      [&](int chunk, std::string& err, int* code) { return device ? make_device_walker(-1, N, ep, chunk, err, code) : make_host_walker(N, ep); },
+      [&](int t, CrtChunk& c, std::string& err) {
+        const int k = c.append(N);
+        c.w[k] = weights[t], c.block[k] = blocks[t];
+        return prepare_times(N, sample_ages, ep, parents + t * nn, branch_lengths + t * nn, c.t.data() + k * nn, err);
+      },
+      sums);
+  if (rc) return rc;
   std::fill(num, num + (size_t)num_blocks * E, 0.0);
   std::fill(denom, denom + (size_t)num_blocks * E, 0.0);
   const size_t n = (size_t)std::min(num_blocks, sums.blocks) * E;

@@ -123,28 +123,8 @@ struct CrtChunk {
 bool prepare_times(int N, const double* ages, const std::vector<double>& epochs, const int* parent, const double* bl, float* t,
                    std::string& err);
 
-// One way to accumulate, as colate_cr::CoalRateWalker: chunks in, per-block sums [block][E] out, the same bits from both.
-class CoalTreeWalker {
- public:
-  virtual ~CoalTreeWalker() = default;
-  virtual bool submit(const CrtChunk& c) = 0;
-  virtual bool finish(CrSums& out) = 0;
-  const std::string& error() const { return err_; }
-  int error_code() const { return code_; }
-  double gpu_seconds() const { return gpu_s_; }  // kernel time by events (0 for the host twin)
-
- protected:
-  bool fail(const std::string& what, int code) {
-    err_ = what;
-    code_ = code;
-    return false;
-  }
-  double gpu_s_ = 0;
-
- private:
-  std::string err_;
-  int code_ = 0;
-};
+// chunks in, per-block sums [block][E] out, the same bits from the host twin and the device
+using CoalTreeWalker = colate_cr::BlockSumWalker<CrtChunk>;
 
 std::unique_ptr<CoalTreeWalker> make_host_walker(int N, const std::vector<double>& epochs);
 // Null, the reason in `why` and its COLATE_E code in *code, when there is no device or the run does not fit it (device -1:

@@ -11,24 +11,22 @@
 //     wave slots.  Out: count / den [call][E].
 //   * crt_fold: one lane per epoch adds the calls' addends into their blocks in call order; the per-block sums stay on the
 //     device until finish().
-// No atomics: every output word has one writer.
+// No atomics: every output word has one writer.  The walker around the two launches is coalrate_device.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 
+#include "coalrate_device.hpp"
 #include "coalrate_tree.h"
-#include "condcoal_device.hpp"
 
 namespace colate_crt {
 
 namespace {
 
-using colate_cc::CcBuffers;
-
-constexpr int kMaxLanes = 256;            // lanes per workgroup
-constexpr size_t kLdsBytes = 160 * 1024;  // the LDS of a CU, which one workgroup may have whole (the launch opts in)
-constexpr int kWavesPerCu = 8;            // resident waves per CU beyond which packing calls into a workgroup pays
+using colate::Staged;
+using colate_cr::kLdsBytes;
+using colate_cr::kMaxLanes;
 
 struct SortArgs {
   int T, N, P, E;
@@ -213,187 +211,67 @@ __global__ void __launch_bounds__(kMaxLanes) crt_fold(FoldArgs a) {
   }
 }
 
-#define CRT_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_), COLATE_EHIP); \
-  } while (0)
+struct CrtArrays {  // the calls of one launch
+  Staged<float> t;
+  Staged<double> w;
+  Staged<int> block;
+};
 
-class DeviceWalker final : public CoalTreeWalker {
+class DeviceWalker final : public colate_cr::BlockSumDeviceWalker<CrtChunk, CrtArrays> {
  public:
-  ~DeviceWalker() override {
-    if (stream_) (void)hipStreamSynchronize(stream_);  // (before the buffers go)
-    for (Slot& s : slot_)
-      for (hipEvent_t e : {s.ev0, s.ev1})
-        if (e) (void)hipEventDestroy(e);
-    if (stream_) (void)hipStreamDestroy(stream_);
-    if (num_) (void)hipFree(num_);
-    if (den_) (void)hipFree(den_);
-  }
+  DeviceWalker() : BlockSumDeviceWalker("coalrate tree") {}
 
   bool open(int device, int N, const std::vector<double>& epochs, int max_calls) {
-    colate::mark_device_touched();
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail("no HIP device", COLATE_EHIP);
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-    if (device >= n) return fail("no HIP device " + std::to_string(device), COLATE_EHIP);
-    device_ = device;
-    N_ = N, E_ = (int)epochs.size(), P_ = padded_keys(N);
+    if (!open_device(device)) return false;
+    E_ = (int)epochs.size(), P_ = padded_keys(N);
     if (E_ > kMaxDeviceEpochs)
       return fail(std::to_string(E_) + " epochs are more than the kernel keeps in LDS (" + std::to_string(kMaxDeviceEpochs) + ")",
                   COLATE_ELIMIT);
-    max_calls_ = std::max(1, max_calls);
     lpc_ = std::min(kMaxLanes, std::max(4, P_ / 2));
     lds_keys_ = P_ <= kLdsKeys;
     const int rl = crt_round_lanes(lpc_);
     call_lds_ = (lds_keys_ ? sizeof(unsigned long long) * P_ : 0) + (sizeof(double) + sizeof(int)) * rl +
                 sizeof(int) * ((size_t)lpc_ + E_);
     cpw_cap_ = (int)std::max<size_t>(1, std::min<size_t>(kMaxLanes / lpc_, (kLdsBytes - 8) / call_lds_));
-    CRT_TRY(hipSetDevice(device));
-    CRT_TRY(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    hipDeviceProp_t prop;
-    CRT_TRY(hipGetDeviceProperties(&prop, device));
-    wave_slots_ = std::max(1, prop.multiProcessorCount) * kWavesPerCu;
-    CRT_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&crt_sort<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-    CRT_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&crt_sort<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-    CRT_TRY(buf_.device(epochs_, epochs.size()));
-    CRT_TRY(hipMemcpy(epochs_, epochs.data(), sizeof(double) * epochs.size(), hipMemcpyHostToDevice));
+    if (!open_sums(N, max_calls, E_)) return false;
+    WALKER_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&crt_sort<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
+    WALKER_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&crt_sort<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
+    if (!upload(epochs_, epochs)) return false;
     const size_t T = max_calls_, nn = 2 * (size_t)N_ - 1;
-    for (Slot& s : slot_) {
-      CRT_TRY(buf_.pinned(s.h_t, T * nn));
-      CRT_TRY(buf_.pinned(s.h_w, T));
-      CRT_TRY(buf_.pinned(s.h_block, T));
-      CRT_TRY(buf_.device(s.t, T * nn));
-      CRT_TRY(buf_.device(s.w, T));
-      CRT_TRY(buf_.device(s.block, T));
-      CRT_TRY(hipEventCreate(&s.ev0));
-      CRT_TRY(hipEventCreate(&s.ev1));
-    }
-    // the kernels' intermediate results are used within the stream's order: one copy serves both slots
-    CRT_TRY(buf_.device(count_, T * E_));
-    CRT_TRY(buf_.device(cden_, T * E_));
-    if (!lds_keys_) CRT_TRY(buf_.device(gkeys_, T * P_));
-    return true;
-  }
-
-  bool submit(const CrtChunk& c) override {
-    if (c.T == 0) return true;
-    if (c.N != N_) return fail("coalrate tree: chunk of another N", COLATE_EINVAL);
-    CRT_TRY(hipSetDevice(device_));
-    int max_block = 0;
-    for (int k = 0; k < c.T; k++) max_block = std::max(max_block, c.block[k]);
-    if (!grow(max_block + 1)) return false;
-    const size_t nn = 2 * (size_t)N_ - 1;
-    for (int t0 = 0; t0 < c.T; t0 += max_calls_) {
-      const int T = std::min(c.T - t0, max_calls_);
-      Slot& s = slot_[cur_];
-      cur_ ^= 1;
-      if (s.busy && !wait(s)) return false;
-      std::memcpy(s.h_t, c.t.data() + t0 * nn, sizeof(float) * T * nn);
-      std::memcpy(s.h_w, c.w.data() + t0, sizeof(double) * T);
-      std::memcpy(s.h_block, c.block.data() + t0, sizeof(int) * T);
-      CRT_TRY(hipMemcpyAsync(s.t, s.h_t, sizeof(float) * T * nn, hipMemcpyHostToDevice, stream_));
-      CRT_TRY(hipMemcpyAsync(s.w, s.h_w, sizeof(double) * T, hipMemcpyHostToDevice, stream_));
-      CRT_TRY(hipMemcpyAsync(s.block, s.h_block, sizeof(int) * T, hipMemcpyHostToDevice, stream_));
-      CRT_TRY(hipEventRecord(s.ev0, stream_));
-      // calls per workgroup: one while every call finds a wave slot of its own on the chip, beyond that as many as fill
-      // the lanes and the LDS
-      const int waves_per_call = (lpc_ + 63) / 64;
-      const int cpw = std::max(1, std::min(cpw_cap_, (int)(((long long)T * waves_per_call + wave_slots_ - 1) / wave_slots_)));
-      SortArgs sa{T, N_, P_, E_, cpw, lpc_, s.t, epochs_, s.w, gkeys_, count_, cden_};
-      const int lanes = std::max(64, cpw * lpc_);
-      const int grid = (T + cpw - 1) / cpw;
-      const size_t lds = (call_lds_ * cpw + 7) / 8 * 8;
-      if (lds_keys_) hipLaunchKernelGGL(crt_sort<true>, dim3(grid), dim3(lanes), lds, stream_, sa);
-      else hipLaunchKernelGGL(crt_sort<false>, dim3(grid), dim3(lanes), lds, stream_, sa);
-      CRT_TRY(hipGetLastError());
-      FoldArgs fa{T, E_, count_, cden_, s.w, s.block, num_, den_};
-      hipLaunchKernelGGL(crt_fold, dim3((E_ + 63) / 64), dim3(64), 0, stream_, fa);
-      CRT_TRY(hipGetLastError());
-      CRT_TRY(hipEventRecord(s.ev1, stream_));
-      s.busy = true;
-    }
-    return true;
-  }
-
-  bool finish(CrSums& out) override {
-    CRT_TRY(hipSetDevice(device_));
     for (Slot& s : slot_)
-      if (s.busy && !wait(s)) return false;
-    CRT_TRY(hipStreamSynchronize(stream_));
-    const size_t n = (size_t)blocks_ * E_;
-    out.blocks = blocks_;
-    out.num.assign(n, 0.0);
-    out.den.assign(n, 0.0);
-    if (n) {
-      CRT_TRY(hipMemcpy(out.num.data(), num_, sizeof(double) * n, hipMemcpyDeviceToHost));
-      CRT_TRY(hipMemcpy(out.den.data(), den_, sizeof(double) * n, hipMemcpyDeviceToHost));
-    }
+      if (!make(s.t, T * nn) || !make(s.w, T) || !make(s.block, T)) return false;
+    // the kernels' intermediate results are used within the stream's order: one copy serves both slots
+    WALKER_TRY(buf_.device(count_, T * E_));
+    WALKER_TRY(buf_.device(cden_, T * E_));
+    if (!lds_keys_) WALKER_TRY(buf_.device(gkeys_, T * P_));
     return true;
   }
 
  private:
-  struct Slot {
-    float *h_t = nullptr, *t = nullptr;
-    double *h_w = nullptr, *w = nullptr;
-    int *h_block = nullptr, *block = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // kernels start / kernels end
-    bool busy = false;
-  };
-  bool wait(Slot& s) {
-    CRT_TRY(hipEventSynchronize(s.ev1));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s.ev0, s.ev1) == hipSuccess) gpu_s_ += ms * 1e-3;
-    s.busy = false;
-    return true;
+  bool stage(Slot& s, const CrtChunk& c, int t0, int T) override {
+    const size_t nn = 2 * (size_t)N_ - 1;
+    return send(s.t, c.t.data() + t0 * nn, T * nn) && send(s.w, c.w.data() + t0, T) && send(s.block, c.block.data() + t0, T);
   }
-  // the per-block sums for at least `blocks` blocks (new ones zero), in the stream's order
-  bool grow(int blocks) {
-    if (blocks <= cap_) {
-      blocks_ = std::max(blocks_, blocks);
-      return true;
-    }
-    const int cap = std::max(blocks, 2 * cap_);
-    double *num = nullptr, *den = nullptr;
-    CRT_TRY(hipMalloc((void**)&num, sizeof(double) * cap * E_));
-    if (hipMalloc((void**)&den, sizeof(double) * cap * E_) != hipSuccess) {
-      (void)hipFree(num);
-      return fail("hipMalloc of the per-block sums", COLATE_EHIP);
-    }
-    // the new pair is filled in the stream's order and takes the old one's place only once that has succeeded
-    hipError_t e = hipMemsetAsync(num, 0, sizeof(double) * cap * E_, stream_);
-    if (e == hipSuccess) e = hipMemsetAsync(den, 0, sizeof(double) * cap * E_, stream_);
-    if (e == hipSuccess && blocks_) e = hipMemcpyAsync(num, num_, sizeof(double) * blocks_ * E_, hipMemcpyDeviceToDevice, stream_);
-    if (e == hipSuccess && blocks_) e = hipMemcpyAsync(den, den_, sizeof(double) * blocks_ * E_, hipMemcpyDeviceToDevice, stream_);
-    const hipError_t synced = hipStreamSynchronize(stream_);  // (also after a failed call: nothing may still write to the pair)
-    if (e == hipSuccess) e = synced;
-    if (e != hipSuccess) {
-      (void)hipFree(num);
-      (void)hipFree(den);
-      return fail(std::string("growing the per-block sums: ") + hipGetErrorString(e), COLATE_EHIP);
-    }
-    if (num_) (void)hipFree(num_);
-    if (den_) (void)hipFree(den_);
-    num_ = num, den_ = den;
-    cap_ = cap;
-    blocks_ = blocks;
+  bool launch(Slot& s, int T) override {
+    const Shape sh = launch_shape(T);
+    SortArgs sa{T, N_, P_, E_, sh.cpw, lpc_, s.t.d, epochs_, s.w.d, gkeys_, count_, cden_};
+    const size_t lds = (call_lds_ * sh.cpw + 7) / 8 * 8;
+    if (lds_keys_) hipLaunchKernelGGL(crt_sort<true>, dim3(sh.grid), dim3(sh.lanes), lds, stream_, sa);
+    else hipLaunchKernelGGL(crt_sort<false>, dim3(sh.grid), dim3(sh.lanes), lds, stream_, sa);
+    WALKER_TRY(hipGetLastError());
+    FoldArgs fa{T, E_, count_, cden_, s.w.d, s.block.d, num_, den_};
+    hipLaunchKernelGGL(crt_fold, dim3((E_ + 63) / 64), dim3(64), 0, stream_, fa);
+    WALKER_TRY(hipGetLastError());
     return true;
   }
 
-  int device_ = 0, N_ = 0, E_ = 0, P_ = 0, max_calls_ = 1, lpc_ = 1, cpw_cap_ = 1;
+  int E_ = 0, P_ = 0;
   bool lds_keys_ = true;
   size_t call_lds_ = 0;
-  int wave_slots_ = 1;
-  CcBuffers buf_;
-  hipStream_t stream_ = nullptr;
-  Slot slot_[2];
-  int cur_ = 0;
   double* epochs_ = nullptr;
   int* count_ = nullptr;
   double* cden_ = nullptr;
   unsigned long long* gkeys_ = nullptr;
-  double *num_ = nullptr, *den_ = nullptr;
-  int cap_ = 0, blocks_ = 0;
 };
 
 }  // namespace

@@ -1,8 +1,8 @@
 // colate_amd/csrc/condcoal.cpp -- `Colate --mode CondCoalRates` (include/coal/coal.cpp:5001-5585): conditional pairwise
 // coalescence rates from Relate genealogies (.anc / .mut).
 //
-//   * readers: the .anc (plain or .gz; the NUM_HAPLOTYPES line with its optional N sample ages, mutations.cpp:536-590;
-//     the trees, anc.cpp:6-45), the .mut's pos / dist / tree_index (for_each_mut_row), the poplabels (sample.cpp:8-110),
+//   * readers: the .anc's tree lines (anc.cpp:6-45; its opening, its header and the pool that parses a chunk of lines are
+//     anc_stream.h's, shared with CoalRate), the .mut's pos / dist / tree_index (for_each_mut_row), the poplabels (sample.cpp:8-110),
 //     the fasta mask (read_fasta_mask);
 //   * per tree, what NextTree (mutations.cpp:616-670) and the driver's loop make of it: the weight
 //     num_bases_tree_persists, the 30 Mb genome block, the mask filter (cutoff 0.9), and the extra pass of the last tree
@@ -29,11 +29,11 @@
 #include <thread>
 #include <vector>
 
+#include "anc_stream.h"
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "condcoal.h"
 #include "condcoal_walk.hpp"
-#include "mut_feeder.h"
 
 namespace colate_cc {
 
@@ -718,38 +718,18 @@ int condcoal_tables(const Options& opt, const std::vector<CcJob>& jobs, bool pai
       std::cerr << "Error: " << base_name << ".mut has no SNPs." << std::endl;
       return 1;
     }
-    GzText anc;
-    if (!anc.open(base_name + ".anc") && !anc.open(base_name + ".anc.gz")) {
+    AncStream anc;
+    if (!anc.open(base_name)) {
       std::cerr << "Failed to open file " << base_name << ".anc(.gz)" << std::endl;
       return 1;
     }
+    if (!anc.read_header(err)) {
+      std::cerr << "Error: " << err << std::endl;
+      return 1;
+    }
+    const int n_chr = anc.N, num_trees = anc.num_trees;
+    const std::vector<double>& ages = anc.ages;
     std::string line;
-    int n_chr = 0, num_trees = 0;
-    std::vector<double> ages;
-    {  // mutations.cpp:555-581
-      anc.getline(line);
-      std::istringstream is(line);
-      std::string tmp;
-      is >> tmp >> n_chr;
-      if (n_chr >= 2) {
-        ages.resize(n_chr);
-        int i = 0;
-        while (i < n_chr && is >> ages[i]) i++;
-        if (i != n_chr) ages.clear();
-      }
-      anc.getline(line);
-      std::istringstream is2(line);
-      is2 >> tmp >> num_trees;
-    }
-    if (n_chr < 2 || n_chr > kMaxHaplotypes) {
-      std::cerr << "Error: " << base_name << ".anc: " << n_chr << " haplotypes (colate_amd supports 2 .. " << kMaxHaplotypes
-                << ")." << std::endl;
-      return 1;
-    }
-    if (num_trees < 1) {
-      std::cerr << "Error: " << base_name << ".anc has no trees." << std::endl;
-      return 1;
-    }
     if (chr == 0) {
       N = n_chr;
       base.N = N;
@@ -803,33 +783,20 @@ int condcoal_tables(const Options& opt, const std::vector<CcJob>& jobs, bool pai
       const double tp = now_s();
       c.clear();
       for (size_t k = 0; k < lines.size(); k++) c.append(N);
-      std::vector<std::string> errs(nthreads);
-      std::vector<std::thread> pool;
-      const size_t per = (lines.size() + nthreads - 1) / nthreads;
-      for (int w = 0; w < nthreads; w++) {
-        const size_t a = w * per, b = std::min(lines.size(), a + per);
-        if (a >= b) break;
-        pool.emplace_back([&, a, b, w] {
-          for (size_t k = a; k < b; k++) {
-            int* par = c.parent.data() + k * nn;
-            if (!parse_tree_line(lines[k], N, par, c.bl.data() + k * nn)) {
-              errs[w] = "cannot read tree " + std::to_string(which[k]);
-              return;
-            }
-            std::string e;
-            if (!prepare_tree(N, par, c.lo.data() + k * nn, c.hi.data() + k * nn, c.leaf.data() + k * N, e)) {
-              errs[w] = "tree " + std::to_string(which[k]) + ": " + e;
-              return;
-            }
-          }
-        });
-      }
-      for (auto& th : pool) th.join();
-      for (const std::string& e : errs)
-        if (!e.empty()) {
-          err = e;
+      const bool parsed = for_each_sliced((int)lines.size(), nthreads, [&](int, int k, std::string& e) {
+        int* par = c.parent.data() + (size_t)k * nn;
+        if (!parse_tree_line(lines[k], N, par, c.bl.data() + (size_t)k * nn)) {
+          e = "cannot read tree " + std::to_string(which[k]);
           return false;
         }
+        std::string why;
+        if (!prepare_tree(N, par, c.lo.data() + (size_t)k * nn, c.hi.data() + (size_t)k * nn, c.leaf.data() + (size_t)k * N, why)) {
+          e = "tree " + std::to_string(which[k]) + ": " + why;
+          return false;
+        }
+        return true;
+      }, err);
+      if (!parsed) return false;
       for (size_t k = 0; k < lines.size(); k++) {
         c.factor[k] = plan[which[k]].factor;
         c.block[k] = plan[which[k]].bin;

@@ -78,8 +78,8 @@ class SingleWalker final : public CcDeviceWalker {
     if (!upload(d_cond_, run.is_cond) || !upload(d_focal_, run.focal)) return false;
     sh_.is_cond = d_cond_;
     sh_.cond_empty = run.cond_empty ? 1 : 0;
-    CC_TRY(buf_.device(d_pre_, (size_t)grid_ * (run.G + 1) * (N_ + 1)));
-    CC_TRY(buf_.device(d_slab_, (size_t)grid_ * S_ * kBlock));
+    WALKER_TRY(buf_.device(d_pre_, (size_t)grid_ * (run.G + 1) * (N_ + 1)));
+    WALKER_TRY(buf_.device(d_slab_, (size_t)grid_ * S_ * kBlock));
     for (Result& r : res_)
       if (!make(r.out, (size_t)max_trees_ * S_)) return false;
     return true;
@@ -110,12 +110,12 @@ class SingleWalker final : public CcDeviceWalker {
     a.pre = d_pre_;
     a.slab = d_slab_;
     a.out = r.out.d;
-    CC_TRY(hipEventRecord(s.ev0, stream_));
+    WALKER_TRY(hipEventRecord(s.ev0, stream_));
     hipLaunchKernelGGL(condcoal_kernel, dim3(std::min(grid_, c.T)), dim3(kBlock), 0, stream_, a);
-    CC_TRY(hipGetLastError());
-    CC_TRY(hipEventRecord(s.evk, stream_));
-    CC_TRY(hipMemcpyAsync(r.out.h, r.out.d, sizeof(double) * c.T * S_, hipMemcpyDeviceToHost, stream_));
-    CC_TRY(hipEventRecord(s.ev1, stream_));
+    WALKER_TRY(hipGetLastError());
+    WALKER_TRY(hipEventRecord(s.evk, stream_));
+    WALKER_TRY(hipMemcpyAsync(r.out.h, r.out.d, sizeof(double) * c.T * S_, hipMemcpyDeviceToHost, stream_));
+    WALKER_TRY(hipEventRecord(s.ev1, stream_));
     s.busy = true;
     return true;
   }
@@ -141,7 +141,6 @@ class SingleWalker final : public CcDeviceWalker {
       const double* src = res_[k].out.h + (size_t)t * S_;
       for (int c = 0; c < S_; c++) dst[c] += src[c];
     }
-    s.busy = false;
     return true;
   }
 

@@ -149,13 +149,13 @@ class PairsWalker final : public CcDeviceWalker {
         !upload(d_pair_cond_, pair_cond) || !upload(d_unit_start_, unit_start))
       return false;
     const size_t T = max_trees_;
-    CC_TRY(buf_.device(d_pre_, T * G_ * (N + 1)));
-    CC_TRY(buf_.device(d_slab_, (size_t)grid_ * S_ * kBlock));
-    CC_TRY(buf_.device(d_out_, T * PS_));
-    CC_TRY(buf_.device(d_run_, PS_));
-    CC_TRY(hipMemset(d_run_, 0, sizeof(double) * PS_));
-    CC_TRY(buf_.device(d_closed_, kMaxCloses * PS_));
-    for (Result& r : res_) CC_TRY(buf_.pinned(r.h_closed, kMaxCloses * PS_));
+    WALKER_TRY(buf_.device(d_pre_, T * G_ * (N + 1)));
+    WALKER_TRY(buf_.device(d_slab_, (size_t)grid_ * S_ * kBlock));
+    WALKER_TRY(buf_.device(d_out_, T * PS_));
+    WALKER_TRY(buf_.device(d_run_, PS_));
+    WALKER_TRY(hipMemset(d_run_, 0, sizeof(double) * PS_));
+    WALKER_TRY(buf_.device(d_closed_, kMaxCloses * PS_));
+    for (Result& r : res_) WALKER_TRY(buf_.pinned(r.h_closed, kMaxCloses * PS_));
     return true;
   }
 
@@ -186,9 +186,9 @@ class PairsWalker final : public CcDeviceWalker {
       const int b = open_block_;
       if ((int)acc_.size() <= b) acc_.resize(b + 1);
       acc_[b].resize(PS_);
-      CC_TRY(hipSetDevice(device_));
-      CC_TRY(hipMemcpyAsync(acc_[b].data(), d_run_, sizeof(double) * PS_, hipMemcpyDeviceToHost, stream_));
-      CC_TRY(hipStreamSynchronize(stream_));
+      WALKER_TRY(hipSetDevice(device_));
+      WALKER_TRY(hipMemcpyAsync(acc_[b].data(), d_run_, sizeof(double) * PS_, hipMemcpyDeviceToHost, stream_));
+      WALKER_TRY(hipStreamSynchronize(stream_));
       open_block_ = -1;
     }
     acc.assign(P_, std::vector<std::vector<double>>(acc_.size()));
@@ -212,7 +212,6 @@ class PairsWalker final : public CcDeviceWalker {
       acc_[b].assign(r.h_closed + i * PS_, r.h_closed + (i + 1) * PS_);
     }
     r.closed.clear();
-    s.busy = false;
     return true;
   }
 
@@ -254,20 +253,20 @@ class PairsWalker final : public CcDeviceWalker {
     a.sh = sh_;
     a.slab = d_slab_;
     a.out = d_out_;
-    CC_TRY(hipEventRecord(s.ev0, stream_));
+    WALKER_TRY(hipEventRecord(s.ev0, stream_));
     hipLaunchKernelGGL(condcoal_pairs_prefix, dim3(std::min<size_t>(T, kMaxGrid)), dim3(kBlock), 0, stream_, (int)T, N_, G_,
                        sh_.group, (const int*)s.leaf.d, d_pre_);
-    CC_TRY(hipGetLastError());
+    WALKER_TRY(hipGetLastError());
     const int grid = (int)std::min<size_t>(grid_, T * U_);
     hipLaunchKernelGGL(condcoal_pairs_kernel, dim3(grid), dim3(kBlock), 0, stream_, a);
-    CC_TRY(hipGetLastError());
+    WALKER_TRY(hipGetLastError());
     hipLaunchKernelGGL(condcoal_pairs_blocks, dim3((unsigned)((PS_ + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream_, (int)T,
                        (long)PS_, (const int*)s.block.d, open_block_, (const double*)d_out_, d_run_, d_closed_);
-    CC_TRY(hipGetLastError());
-    CC_TRY(hipEventRecord(s.evk, stream_));
+    WALKER_TRY(hipGetLastError());
+    WALKER_TRY(hipEventRecord(s.evk, stream_));
     if (!r.closed.empty())
-      CC_TRY(hipMemcpyAsync(r.h_closed, d_closed_, sizeof(double) * r.closed.size() * PS_, hipMemcpyDeviceToHost, stream_));
-    CC_TRY(hipEventRecord(s.ev1, stream_));
+      WALKER_TRY(hipMemcpyAsync(r.h_closed, d_closed_, sizeof(double) * r.closed.size() * PS_, hipMemcpyDeviceToHost, stream_));
+    WALKER_TRY(hipEventRecord(s.ev1, stream_));
     open_block_ = open;
     s.busy = true;
     return true;

@@ -133,6 +133,25 @@ def random_input(rng, N, T, G, S, num_blocks, ancient, epochs):
     return parents, bl, weights, blocks, gv, groups, ages
 
 
+# 36 calls in nine blocks whose boundaries fall inside the chunks of four: chunk c ends in block min(c + 1, 8)
+GROW_BLOCKS = np.minimum((np.arange(36) + 2) // 4, 8).astype(np.int32)
+
+
+def sum_reallocations(blocks, cap):
+    """The capacity rule of the device walkers' per-block sums over chunks of `cap` calls (capacity 0 at first; a chunk
+    needs its largest block + 1; a larger need takes max(need, 2 * capacity)): (reallocations, those among them that copy
+    blocks which earlier chunks have added to)."""
+    capacity, reallocations, copying, seen = 0, 0, 0, False
+    for i in range(0, len(blocks), cap):
+        need = int(blocks[i:i + cap].max()) + 1
+        if need > capacity:
+            capacity = max(need, 2 * capacity)
+            reallocations += 1
+            copying += seen
+        seen = True
+    return reallocations, copying
+
+
 def accumulate_in_child(tmp_path, inp, epochs, device, timeout, chunk_trees=None):
     """coalrate_accumulate in a child process under its own time limit; inp = random_input's tuple plus (num_blocks, G).
     Returns (num, denom); raises on a child that fails (nothing is retried)."""

@@ -1,6 +1,7 @@
 """`CoalRate --mode local_ancestry` on the device (coalrate_kernel.hip): the CLI against the reference's .coal for every
 committed fixture, and the raw sums against the host twin bit for bit over small and large N, one and many groups, modern
-and ancient samples, chunk and block boundaries, calls that share a workgroup, and prefix counts that do not fit the LDS.
+and ancient samples, chunk and block boundaries, calls that share a workgroup, prefix counts that do not fit the LDS, and
+per-block sums that outgrow their device buffers.
 Every GPU step runs in a child process under a time limit of its own; a test stops at the first child that fails."""
 import os
 
@@ -35,6 +36,7 @@ SHAPES = [
     (2000, 2, 40, 2, 3, True, 16),
     (2000, 26, 24, 2, 3, False, 10),
     (4000, 26, 12, 2, 3, True, 5),      # 26 x 4001 prefix counts do not fit the LDS: the device-memory path
+    (8, 1, 36, 2, 9, False, 4),         # nine blocks in chunks of four: the per-block sums on the device grow four times
 ]
 
 
@@ -45,6 +47,11 @@ def test_device_equals_host_twin_bit_for_bit(N, G, T, S, nb, ancient, cap, tmp_p
     rng = np.random.default_rng(1000 * N + 10 * G + ancient)
     epochs = cl.bins_epochs(2.0, 6.0, 0.25)
     inp = cl.random_input(rng, N, T, G, S, nb, ancient, epochs) + (nb, G)
+    if nb == 9:
+        inp = inp[:3] + (cl.GROW_BLOCKS,) + inp[4:]
+        assert len(set(inp[3].tolist())) == nb and (inp[2] != 0).all()
+        reallocations, copying = cl.sum_reallocations(inp[3], cap)
+        assert reallocations >= 3 and copying >= 2      # the sums move to larger buffers with earlier blocks in them
     if cap:
         assert T > cap and len(set(inp[3][:cap].tolist())) + len(set(inp[3].tolist())) > 2  # chunks and blocks are crossed
     dnum, dden = cl.accumulate_in_child(tmp_path, inp, epochs, device=True, timeout=300, chunk_trees=cap)

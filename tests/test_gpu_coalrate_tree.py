@@ -1,7 +1,8 @@
 """`CoalRate --mode tree` on the device (coalrate_tree_kernel.hip): the CLI against the reference's .coal for every
 committed fixture, and the raw sums against the host twin bit for bit from three keys to the path beyond the LDS, with ties,
-node times on epoch boundaries, ancient samples, calls that share a workgroup, and chunk and block boundaries.  Every GPU
-step runs in a child process under a time limit of its own; a test stops at the first child that fails."""
+node times on epoch boundaries, ancient samples, calls that share a workgroup, chunk and block boundaries, and per-block
+sums that outgrow their device buffers.  Every GPU step runs in a child process under a time limit of its own; a test stops
+at the first child that fails."""
 import os
 
 import numpy as np
@@ -35,6 +36,7 @@ SHAPES = [
     (2000, 40, 3, True, None, 16),     # ancient samples; chunk cap 16
     (8192, 4, 2, False, None, None),   # the last N that sorts in LDS
     (12000, 6, 2, True, None, 4),      # the path beyond the LDS
+    (8, 36, 9, False, None, 4),        # nine blocks in chunks of four: the per-block sums on the device grow four times
 ]
 
 
@@ -43,7 +45,7 @@ def test_device_equals_host_twin_bit_for_bit(N, T, nb, ancient, quantum, cap, tm
     P = tl.padded_keys(N)
     if N == 2:
         assert 2 * N - 1 == 3
-    if N == 8:
+    if N == 8 and T == 9000:
         cpw = tl.calls_per_workgroup(cap, N)
         assert cap > tl.WAVE_SLOTS and cpw >= 2      # more calls in a chunk than wave slots: workgroups are shared
         assert cap % cpw != 0 and T > 2 * cap        # the last workgroup of a chunk is partly filled; a last chunk unpacked
@@ -57,6 +59,11 @@ def test_device_equals_host_twin_bit_for_bit(N, T, nb, ancient, quantum, cap, tm
     rng = np.random.default_rng(77 * N + ancient)
     epochs = tl.TIE_EPOCHS if quantum else cl.bins_epochs(2.0, 6.0, 0.25)
     inp = tl.random_input(rng, N, T, nb, ancient, epochs, quantum, Ne=300.0 if quantum is None and N >= 2000 else 2000.0)
+    if nb == 9:
+        inp = inp[:3] + (cl.GROW_BLOCKS,) + inp[4:]
+        assert len(set(inp[3].tolist())) == nb and (inp[2] != 0).all()
+        reallocations, copying = cl.sum_reallocations(inp[3], cap)
+        assert reallocations >= 3 and copying >= 2      # the sums move to larger buffers with earlier blocks in them
     if cap:
         assert T > cap and tl.chunk_straddles_blocks(inp[3], cap)   # chunks are crossed, and block boundaries inside them
     dnum, dden = tl.accumulate_in_child(tmp_path, inp, nb, epochs, device=True, timeout=300, chunk_trees=cap)
