@@ -64,6 +64,10 @@ SIGNATURES = {
     "colate_em_interval_batch": (c_int, [c_int] * 3 + [c_void_p] * 6 + [c_int, c_int, c_double, c_double] + [c_void_p] * 4),
     "colate_em_interval_batch_host": (c_int, [c_int] * 3 + [c_void_p] * 6 + [c_int, c_int, c_double, c_double] + [c_void_p] * 4 + [c_int]),
     "colate_em_interval_batch_waves": (c_int, [c_int]),
+    "colate_bootstrap_em_interval_batch": (c_int, [c_int] * 4 + [c_void_p] * 7 + [c_int, c_int, c_double, c_double] + [c_void_p] * 4),
+    "colate_bootstrap_em_interval_batch_host": (c_int, [c_int] * 4 + [c_void_p] * 7 + [c_int, c_int, c_double, c_double]
+                                                + [c_void_p] * 4 + [c_int]),
+    "colate_bootstrap_rows_host": (c_int, [c_int] * 3 + [c_void_p] * 3),
     "colate_age_grid": (c_int, [c_void_p, c_int]),
     "colate_epochs_from_bins": (c_int, [c_char_p, c_double, c_double, c_void_p, c_int, ip]),
     "colate_epochs_from_coal": (c_int, [c_char_p, c_double, c_void_p, c_void_p, c_int]),

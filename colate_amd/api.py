@@ -346,6 +346,43 @@ def em_interval_batch(kinds, age_begin, age_end, weights, epochs, init_rates=Non
     return rates, iters, ll, flags
 
 
+def bootstrap_rows(block_weights, tables):
+    """colate_bootstrap_rows_host: W[B][R] = block_weights[B][nb] x tables[nb][R], per element summed from 0.0 over the blocks
+    in ascending order, every product rounded and then added -- the host twin of the bootstrap kernel in front of the
+    interval-dated fit (bit for bit its sums)."""
+    bw, t = _f64(np.atleast_2d(block_weights)), _f64(np.atleast_2d(tables))
+    if bw.ndim != 2 or t.ndim != 2 or bw.shape[1] != t.shape[0]:
+        raise ValueError("block_weights must be [B][nb] and tables [nb][R]")
+    W = np.zeros((bw.shape[0], t.shape[1]))
+    check(lib.colate_bootstrap_rows_host(bw.shape[0], t.shape[0], t.shape[1], _p(bw), _p(t), _p(W)))
+    return W
+
+
+def bootstrap_em_interval_batch(kinds, age_begin, age_end, block_weights, tables, epochs, init_rates=None,
+                                max_iter=DEFAULT_MAX_ITER, min_iter=DEFAULT_MIN_ITER, rel_tol=DEFAULT_REL_TOL,
+                                rate_floor=DEFAULT_RATE_FLOOR, device=True, math=1):
+    """colate_bootstrap_em_interval_batch: the block bootstrap and the EM fit on interval-dated mutations in one call.
+    tables[nb][R] holds per genome block the weights of the R rows (kinds[r], age_begin[r], age_end[r]), block_weights[B][nb]
+    (1-D: B = 1) the replicates' block weights (bootstrap_weights); the fit runs on bootstrap_rows(block_weights, tables),
+    which on the device never leaves it.  Returns (rates[B][E], iters[B], loglik[B], flags[B]) -- em_interval_batch's on that
+    W, bit for bit.  device=False: the host twin (colate_bootstrap_em_interval_batch_host; math as for em_interval_batch)."""
+    k = np.ascontiguousarray(np.atleast_1d(kinds), dtype=np.int32)
+    a0, a1, ep = _f64(np.atleast_1d(age_begin)), _f64(np.atleast_1d(age_end)), _f64(epochs)
+    bw, t = _f64(np.atleast_2d(block_weights)), _f64(np.atleast_2d(tables))
+    R, E, B, nb = k.size, ep.size, bw.shape[0], t.shape[0]
+    if a0.shape != (R,) or a1.shape != (R,) or t.shape != (nb, R) or bw.shape != (B, nb):
+        raise ValueError("kinds, age_begin, age_end must have one entry per row, tables one row of them per block and "
+                         "block_weights one weight per block and replicate")
+    init = _f64(np.full(E, DEFAULT_INIT_RATE) if init_rates is None else init_rates)
+    if init.shape != (E,):
+        raise ValueError("init_rates must have one entry per epoch")
+    rates, iters, ll, flags = np.zeros((B, E)), np.zeros(B, dtype=np.int32), np.zeros(B), np.zeros(B, dtype=np.int32)
+    args = [B, nb, R, E, _p(k), _p(a0), _p(a1), _p(bw), _p(t), _p(ep), _p(init), int(max_iter), int(min_iter), float(rel_tol),
+            float(rate_floor), _p(rates), _p(iters), _p(ll), _p(flags)]
+    check(lib.colate_bootstrap_em_interval_batch(*args) if device else lib.colate_bootstrap_em_interval_batch_host(*args, int(math)))
+    return rates, iters, ll, flags
+
+
 def em_interval_batch_waves(E):
     """How many rows a workgroup of em_interval_batch calls at a time for E epochs."""
     return lib.colate_em_interval_batch_waves(int(E))

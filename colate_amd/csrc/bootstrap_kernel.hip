@@ -115,7 +115,42 @@ __global__ __launch_bounds__(COLATE_EM_MAX_A) void bootstrap_groups_kernel(
                       cnt_ns + (size_t)blockIdx.x * A, status);
 }
 
+// The block bootstrap in front of the interval-dated fit (colate_bootstrap_em_interval_batch): the weighted block sums
+// of row tables, W[b][r] = sum_k block_weights[b][k] * tables[k][r] (coal.cpp:3358-3390 with rows for age bins).  One
+// thread per (b, r), consecutive threads on consecutive r, so that every read of tables[k][.] and the write of W[b][.]
+// are coalesced and block_weights[b][k] is one address per workgroup.  The sum starts at 0.0 and runs over k ascending
+// with separate multiply and add: no atomics, no tree -- the order is the contract, and the host twin
+// (colate_bootstrap_rows_host, em_interval_host.cpp) forms the same doubles.  Block `blockIdx.x` = replicate
+// blockIdx.x / chunks, rows [chunk * 256, chunk * 256 + 256) with chunk = blockIdx.x % chunks.
+#define COLATE_BOOTSTRAP_ROWS_THREADS 256
+__global__ __launch_bounds__(COLATE_BOOTSTRAP_ROWS_THREADS) void bootstrap_rows_kernel(
+    int nb, int R, int chunks, const double* __restrict__ block_weights, const double* __restrict__ tables,
+    double* __restrict__ W) {
+  const int b = blockIdx.x / chunks;
+  const size_t r = (size_t)(blockIdx.x % chunks) * COLATE_BOOTSTRAP_ROWS_THREADS + threadIdx.x;
+  if (r >= (size_t)R) return;
+  const double* __restrict__ w = block_weights + (size_t)b * nb;
+  double acc = 0.0;
+#pragma unroll 8  // (eight loads in flight; the additions stay in order)
+  for (int k = 0; k < nb; k++) acc += w[k] * tables[(size_t)k * R + r];
+  W[(size_t)b * R + r] = acc;
+}
+
 }  // namespace
+
+hipError_t colate_bootstrap_rows_launch(int B, int nb, int R, const double* block_weights, const double* tables, double* W,
+                                        hipStream_t stream) {
+  if (B < 1 || nb < 1 || R < 1) return hipErrorInvalidValue;
+  const long long chunks = ((long long)R + COLATE_BOOTSTRAP_ROWS_THREADS - 1) / COLATE_BOOTSTRAP_ROWS_THREADS;
+  if (chunks * B > 0x7fffffffLL) return hipErrorInvalidValue;  // (the caller has checked: colate_bootstrap_rows_fits)
+  hipLaunchKernelGGL(bootstrap_rows_kernel, dim3((unsigned)(chunks * B)), dim3(COLATE_BOOTSTRAP_ROWS_THREADS), 0, stream, nb, R,
+                     (int)chunks, block_weights, tables, W);
+  return hipGetLastError();
+}
+
+bool colate_bootstrap_rows_fits(int B, int R) {
+  return ((long long)R + COLATE_BOOTSTRAP_ROWS_THREADS - 1) / COLATE_BOOTSTRAP_ROWS_THREADS * B <= 0x7fffffffLL;
+}
 
 hipError_t colate_bootstrap_groups_launch(int B, int row_lo, int rows, int group_first, int A, const double* age_grid,
                                           const int* group_nb, const long long* group_block_off,

@@ -682,6 +682,36 @@ int colate_em_interval_batch(int B, int R, int E, const int* kinds, const double
   return st.finish();
 }
 
+int colate_bootstrap_em_interval_batch(int B, int nb, int R, int E, const int* kinds, const double* age_begin,
+                                       const double* age_end, const double* block_weights, const double* tables,
+                                       const double* epochs, const double* init_rates, int max_iter, int min_iter,
+                                       double rel_tol, double rate_floor, double* out_rates, int* out_iters,
+                                       double* out_loglik, int* out_flags) {
+  if (int rc = check_bootstrap_interval_batch(B, nb, R, E, kinds, age_begin, age_end, block_weights, tables, epochs, init_rates,
+                                              max_iter, min_iter, rel_tol, rate_floor, out_rates, out_iters, out_loglik,
+                                              out_flags))
+    return rc;
+  if (!colate_bootstrap_rows_fits(B, R)) return fail(COLATE_ELIMIT, "B=%d x R=%d above the grid of the bootstrap kernel", B, R);
+  if (int rc = ensure_device()) return rc;
+  ProfRange range("colate_bootstrap_em_interval_batch: H2D + row bootstrap kernel + interval EM kernel + D2H");
+  const size_t nE = (size_t)E, nBE = (size_t)B * E;
+  Arena st(g_ws);
+  const int i_kind = st.in(kinds, R), i_a0 = st.in(age_begin, R), i_a1 = st.in(age_end, R);
+  const int i_bw = st.in(block_weights, (size_t)B * nb), i_tab = st.in(tables, (size_t)nb * R);
+  const int i_ep = st.in(epochs, nE), i_init = st.in(init_rates, nE);
+  const int s_w = st.scratch<double>((size_t)B * R);  // W[B][R]: written by the first kernel, read by the second, never copied
+  const int o_rates = st.out(out_rates, nBE), o_iters = st.out(out_iters, B), o_ll = st.out(out_loglik, B), o_flags = st.out(out_flags, B);
+  if (int rc = st.commit()) return rc;
+  hipError_t e = colate_bootstrap_rows_launch(B, nb, R, st.dev<double>(i_bw), st.dev<double>(i_tab), st.dev<double>(s_w), st.stream());
+  if (e != hipSuccess) return hip_fail(e, "row bootstrap kernel launch");
+  e = colate_em_interval_fit_launch(B, R, E, st.dev<int>(i_kind), st.dev<double>(i_a0), st.dev<double>(i_a1),
+                                    st.dev<double>(s_w), st.dev<double>(i_ep), st.dev<double>(i_init), max_iter, min_iter,
+                                    rel_tol, rate_floor, st.dev<double>(o_rates), st.dev<int>(o_iters), st.dev<double>(o_ll),
+                                    st.dev<int>(o_flags), st.stream());
+  if (e != hipSuccess) return hip_fail(e, "interval EM kernel launch");
+  return st.finish();
+}
+
 int colate_em_interval_batch_waves(int E) { return colate_em_interval_fit_waves(E); }
 
 }  // extern "C"

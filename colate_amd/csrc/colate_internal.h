@@ -22,6 +22,14 @@ int check_interval_batch(int B, int R, int E, const int* kinds, const double* ag
                          const double* weights, const double* epochs, const double* init_rates, int max_iter, int min_iter,
                          double rel_tol, double rate_floor, const double* out_rates, const int* out_iters,
                          const double* out_loglik, const int* out_flags);
+// the argument checks of colate_bootstrap_em_interval_batch[_host] (em_interval_host.cpp): those of check_interval_batch with
+// the block weights [B][nb] and the row tables [nb][R] for the weights: nb >= 1, every entry of both finite and >= 0, and no
+// weighted block sum W[b][r] that overflows to infinity
+int check_bootstrap_interval_batch(int B, int nb, int R, int E, const int* kinds, const double* age_begin,
+                                   const double* age_end, const double* block_weights, const double* tables,
+                                   const double* epochs, const double* init_rates, int max_iter, int min_iter,
+                                   double rel_tol, double rate_floor, const double* out_rates, const int* out_iters,
+                                   const double* out_loglik, const int* out_flags);
 // Set (process-wide, never cleared) by every entry point that makes this process talk to the HIP runtime.  A process
 // that has done so must not fork() children that use the GPU: `Colate --ranks N` (run_ranked, mut_driver.cpp) refuses
 // when it is set (colate_device_touched, include/colate_amd.h).

@@ -59,6 +59,13 @@ hipError_t colate_bootstrap_groups_launch(int B, int row_lo, int rows, int group
                                           const double* sh_emp_block, const double* ns_emp_block, double* cnt_sh,
                                           double* cnt_ns, int* status, hipStream_t stream);
 
+// the block bootstrap in front of the interval-dated fit (bootstrap_rows_kernel): W[B][R] = block_weights[B][nb] x
+// tables[nb][R], per element from 0.0 over k ascending, multiply and add apart.  Device pointers.  _fits: the launch
+// has a grid for this shape (B * ceil(R / 256) workgroups below 2^31)
+hipError_t colate_bootstrap_rows_launch(int B, int nb, int R, const double* block_weights, const double* tables, double* W,
+                                        hipStream_t stream);
+bool colate_bootstrap_rows_fits(int B, int R);
+
 // coal_EM::EM_shared / EM_notshared for R calls (kind, age_begin, age_end) against one (epochs[E], rates[E]), one
 // wavefront per call (em_interval_kernel.hip; the arithmetic is em_interval.hpp).  Device pointers; weights NULL = no
 // accumulated outputs.  The caller has validated the ages (colate::check_interval_calls).

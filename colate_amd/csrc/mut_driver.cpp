@@ -41,6 +41,7 @@
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "mut_feeder.h"
+#include "mut_interval.h"
 
 namespace colate_drv {
 
@@ -59,7 +60,8 @@ const char* const kValueOptions[] = {
     "target_table", "target_bam", "reference_bam", "target_tmp", "reference_tmp", "target_age",
     "reference_age", "ref_genome", "anc_genome", "mask", "mask_cutoff", "chr", "bins",
     "lineage_bin", "outgroup_tmrca", "years_per_gen", "coal", "seed", "num_bootstraps", "filters",
-    "groups", "poplabels", "map", "input", "output", "device", "devices", "ranks", "counts_out", "pairs"};
+    "groups", "poplabels", "map", "input", "output", "device", "devices", "ranks", "counts_out", "pairs",
+    "rows", "max_iter", "min_iter"};
 const char* const kBoolOptions[] = {"help", "strandfilter", "counts_only", "write_colate_mat"};
 
 bool parse_options(int argc, char** argv, Options& o, std::string& err) {
@@ -112,7 +114,7 @@ bool parse_options(int argc, char** argv, Options& o, std::string& err) {
 void print_help() {
   std::cout << "Usage:\n  Colate [OPTION...]\n\n"
             << "      --help                 Print help.\n"
-            << "      --mode arg             Choose which part of the algorithm to run (colate_amd: mut, make_tmp, CondCoalRates).\n"
+            << "      --mode arg             Choose which part of the algorithm to run (colate_amd: mut, mut_interval, make_tmp, CondCoalRates).\n"
             << "      --mut arg              Filename of file containing mut.\n"
             << "      --target_tmp arg       Filename of target tmp file\n"
             << "      --reference_tmp arg    Filename of reference tmp file\n"
@@ -147,6 +149,11 @@ void print_help() {
             << "      --mask arg             (--mode CondCoalRates) Fasta mask (per chromosome with --chr).\n"
             << "                             (--mode CondCoalRates) --pairs FILE: `FOCAL,CONDITIONAL OUTPUT` per line, in place of\n"
             << "                             --groups / --output; every table is its single run's, from one pass over the trees.\n"
+            << "      --rows arg             (--mode mut_interval) File of `block kind age_begin age_end weight` lines (plain or gzip):\n"
+            << "                             block a non-negative integer, kind shared|notshared, ages in generations; with --bins or\n"
+            << "                             --coal, --num_bootstraps, --seed, --years_per_gen; writes <output>.coal.\n"
+            << "      --max_iter arg         (--mode mut_interval) Iteration cap of the EM (default 100000).\n"
+            << "      --min_iter arg         (--mode mut_interval) Iterations before the stop rule applies (default 1000).\n"
             << "  -o, --output arg           Filename of output.\n"
             << std::endl;
 }
@@ -1550,6 +1557,14 @@ extern "C" int colate_mut_main(int argc, char** argv) {
       return 1;
     }
   }
+  if (mode == "mut_interval") {
+    try {
+      return run_mut_interval(opt);
+    } catch (const std::exception& e) {
+      std::cerr << "Error: " << e.what() << std::endl;
+      return 1;
+    }
+  }
   if (mode == "make_tmp") {
     try {
       return run_make_tmp(opt);
@@ -1567,7 +1582,7 @@ extern "C" int colate_mut_main(int argc, char** argv) {
     }
   }
   std::cout << "####### error #######" << std::endl;
-  std::cout << "colate_amd implements --mode mut, --mode make_tmp --target_table and --mode CondCoalRates (preprocess_mut, "
+  std::cout << "colate_amd implements --mode mut, --mode mut_interval, --mode make_tmp --target_table and --mode CondCoalRates (preprocess_mut, "
                "make_tmp from BCF/BAM, calc_depth, print_tmp stay with the reference build)."
             << std::endl;
   return 1;

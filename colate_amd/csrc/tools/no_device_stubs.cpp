@@ -47,6 +47,10 @@ int colate_em_batch_rows_sharded(int, const int*, int, int, int, const double*, 
 int colate_bootstrap_em_batch(int, int, int, int, const double*, double, const double*, const double*, const double*,
                               const double*, const double*, const double*, const double*, int, int, double, double, double*,
                               int*, double*, int*, double*, double*) { return nodev(); }
+int colate_bootstrap_em_interval_batch(int, int, int, int, const int*, const double*, const double*, const double*, const double*,
+                                       const double*, const double*, int, int, double, double, double*, int*, double*, int*) {
+  return nodev();
+}
 int colate_shard_bounds(int B, int nranks, int rank, int* lo, int* hi) {
   const int base = B / nranks, rem = B % nranks;
   *lo = rank * base + (rank < rem ? rank : rem);

@@ -13,7 +13,12 @@
  * Mutations dated to an interval (coal_EM with age_begin < age_end, which the
  * reference wrote and tested but never put a loop around) have the same two
  * levels: colate_em_interval_calls is one E-step over a list of calls,
- * colate_em_interval_batch the whole EM fit for a batch of replicates.
+ * colate_em_interval_batch the whole EM fit for a batch of replicates, and
+ * colate_bootstrap_em_interval_batch that fit with the block bootstrap in front
+ * of it: per-block row tables and block weights in, rates out (the weighted
+ * block sums run from 0.0 over the blocks in ascending order, multiply and add
+ * apart; its speed has not been measured).  `Colate --mode mut_interval` is the
+ * command line of the last one.
  * INTEGRATION.md shows the patch a maintainer would apply to coal.cpp.
  *
  * Conventions: plain pointers and sizes, row-major, IEEE double; caller owns
@@ -211,6 +216,33 @@ int colate_em_interval_batch_host(int B, int R, int E, const int* kinds, const d
                                   double* out_loglik, int* out_flags, int math);
 /* Diagnostic: how many rows a workgroup of colate_em_interval_batch calls at a time for this E (no device needed). */
 int colate_em_interval_batch_waves(int E);
+
+/* The block bootstrap in front of that fit: per genome block k a table of the R rows' weights, tables[nb][R], and per
+ * replicate the block weights block_weights[B][nb] (colate_bootstrap_weights draws them); the fit runs on
+ *   W[b][r] = sum_k block_weights[b][k] * tables[k][r]
+ * -- coal.cpp:3358-3390 with rows for age bins.  Summation order (the contract, on the device and on the host): per
+ * (b, r) the sum starts at 0.0 and runs over k ascending; every product is rounded, then added (no fused multiply-add,
+ * no atomics, no tree).  colate_bootstrap_em_interval_batch stages the inputs once, runs the bootstrap kernel
+ * (csrc/bootstrap_kernel.hip, one thread per (b, r)) and the fit kernel back to back on one stream -- W stays in device
+ * memory, nothing is copied back or waited for before the results -- and returns what colate_em_interval_batch returns
+ * on that W, bit for bit.  COLATE_ENODEVICE without a device, there is no fall-back.  _host: the same on the CPU (math
+ * as for colate_em_interval_batch_host; math = 1 is bit for bit the device).  colate_bootstrap_rows_host: W alone, the
+ * host twin of the bootstrap kernel.
+ * Refused (COLATE_EINVAL, before anything is staged; the outputs are not touched): everything colate_em_interval_batch
+ * refuses, nb < 1, a negative or non-finite block weight or table entry, a W entry that overflows to infinity.
+ * Speed: not measured on a device yet (tools/em_interval_bootstrap_bench.py is the measurement: this call against W
+ * formed on the host plus colate_em_interval_batch). */
+int colate_bootstrap_em_interval_batch(int B, int nb, int R, int E, const int* kinds, const double* age_begin,
+                                       const double* age_end, const double* block_weights, const double* tables,
+                                       const double* epochs, const double* init_rates, int max_iter, int min_iter,
+                                       double rel_tol, double rate_floor, double* out_rates, int* out_iters,
+                                       double* out_loglik, int* out_flags);
+int colate_bootstrap_em_interval_batch_host(int B, int nb, int R, int E, const int* kinds, const double* age_begin,
+                                            const double* age_end, const double* block_weights, const double* tables,
+                                            const double* epochs, const double* init_rates, int max_iter, int min_iter,
+                                            double rel_tol, double rate_floor, double* out_rates, int* out_iters,
+                                            double* out_loglik, int* out_flags, int math);
+int colate_bootstrap_rows_host(int B, int nb, int R, const double* block_weights, const double* tables, double* W);
 
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
@@ -430,7 +462,17 @@ int colate_coalrate_main(int argc, char** argv);
 
 /* The whole `Colate --mode mut` command line for the .colate.in / .colate_mat
  * inputs (Colate.cpp:6-116 -> coal.cpp:3071-3863): same option names, same
- * stderr progress lines, same .coal output.  Returns the process exit code. */
+ * stderr progress lines, same .coal output.  Returns the process exit code.
+ * `--mode mut_interval --rows FILE (--bins x,y,s | --coal FILE) -o OUT [--num_bootstraps B] [--seed S]
+ * [--years_per_gen Y] [--max_iter N] [--min_iter N]` (no reference counterpart) is colate_bootstrap_em_interval_batch
+ * on a text file: FILE (plain or gzip) has one line `block kind age_begin age_end weight` per observation -- block a
+ * non-negative integer, kind `shared` or `notshared`, ages in generations, weight finite and >= 0; blank lines and
+ * lines starting with `#` are skipped.  Distinct block ids, ascending, are the table rows 0 .. nb-1; distinct (kind,
+ * age_begin, age_end) triples (equal as parsed doubles), in order of first appearance, the R rows; repeated lines of
+ * one cell add up in file order.  Epochs and starting rates as for `mut` at age 0; block weights from
+ * colate_bootstrap_weights on std::mt19937(--seed).  Writes OUT.coal (colate_write_coal).  Without a device, or with
+ * COLATE_DEVICE_INTERVAL=0, the math = 1 host twin runs after one line on stderr and writes the same bytes.  A
+ * malformed line is an error that names its line number; nothing is written then. */
 int colate_mut_main(int argc, char** argv);
 
 #ifdef __cplusplus
