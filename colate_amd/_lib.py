@@ -68,6 +68,10 @@ SIGNATURES = {
     "colate_bootstrap_em_interval_batch_host": (c_int, [c_int] * 4 + [c_void_p] * 7 + [c_int, c_int, c_double, c_double]
                                                 + [c_void_p] * 4 + [c_int]),
     "colate_bootstrap_rows_host": (c_int, [c_int] * 3 + [c_void_p] * 3),
+    "colate_interval_bin_thresholds": (c_int, [c_void_p]),
+    "colate_interval_cells": (c_int, [ctypes.c_longlong, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 5),
+    "colate_interval_cells_host": (c_int, [ctypes.c_longlong, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 5),
+    "colate_interval_cells_tile": (c_int, []),
     "colate_age_grid": (c_int, [c_void_p, c_int]),
     "colate_epochs_from_bins": (c_int, [c_char_p, c_double, c_double, c_void_p, c_int, ip]),
     "colate_epochs_from_coal": (c_int, [c_char_p, c_double, c_void_p, c_void_p, c_int]),

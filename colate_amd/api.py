@@ -388,6 +388,47 @@ def em_interval_batch_waves(E):
     return lib.colate_em_interval_batch_waves(int(E))
 
 
+INTERVAL_BINS = 185
+INTERVAL_MAX_ROWS = INTERVAL_BINS * (INTERVAL_BINS + 1)
+INTERVAL_REC = np.dtype([("begin", np.float32), ("end", np.float32), ("w_sh", np.float64), ("w_ns", np.float64)])
+
+
+def interval_bin_thresholds():
+    """float32 [185]: entry n - 1 is the smallest float whose age bin (coal.cpp:2265 on the float widened to double) is
+    >= n, so that the bin of x is the number of entries <= x (colate_interval_bin_thresholds)."""
+    T = np.zeros(INTERVAL_BINS, dtype=np.float32)
+    check(lib.colate_interval_bin_thresholds(_p(T)))
+    return T
+
+
+def interval_cells_tile():
+    """Cells of the (bb, be) triangle per tile of the interval-cells kernel (diagnostic; no device needed)."""
+    return lib.colate_interval_cells_tile()
+
+
+def interval_cells(begin, end, w_sh, w_ns, block, nb, device=True, max_rows=None):
+    """The used SNPs of a pair -- float32 ages begin <= end, weights w_sh / w_ns, genome block per record (not decreasing,
+    in [0, nb)) -- as the rows and per-block tables of bootstrap_em_interval_batch (colate_interval_cells[_host]): ages
+    snapped to the age grid, per (block, kind, bin(begin), bin(end)) the weights summed from 0.0 in record order.
+    Returns (kinds [R], age_begin [R], age_end [R], tables [nb, R], dropped): the rows with a positive sum in at least one
+    block, ordered by kind, bin(begin), bin(end); dropped = records beyond the age grid.  device=False: the host twin
+    (the same doubles).  max_rows: the room given (default: always enough)."""
+    recs = np.zeros(np.asarray(begin).size, dtype=INTERVAL_REC)
+    recs["begin"], recs["end"], recs["w_sh"], recs["w_ns"] = np.ravel(begin), np.ravel(end), np.ravel(w_sh), np.ravel(w_ns)
+    block = np.ascontiguousarray(block, dtype=np.int32).ravel()
+    if block.size != recs.size:
+        raise ValueError("one block index per record")
+    nb = int(nb)
+    cap = min(INTERVAL_MAX_ROWS, 2 * recs.size) if max_rows is None else int(max_rows)
+    kinds = np.zeros(cap, dtype=np.int32)
+    a0, a1 = np.zeros(cap), np.zeros(cap)
+    tables = np.zeros(max(nb, 0) * cap)
+    dropped = ctypes.c_longlong(0)
+    fn = lib.colate_interval_cells if device else lib.colate_interval_cells_host
+    R = check(fn(recs.size, _p(recs), _p(block), nb, cap, _p(kinds), _p(a0), _p(a1), _p(tables), ctypes.addressof(dropped)))
+    return kinds[:R].copy(), a0[:R].copy(), a1[:R].copy(), tables[:nb * R].reshape(nb, R).copy(), int(dropped.value)
+
+
 def _stream_ptr(stream):
     if stream is None:
         import torch

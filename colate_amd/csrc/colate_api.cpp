@@ -20,6 +20,7 @@
 #include "colate_internal.h"
 #include "em_job.hpp"
 #include "em_kernels.h"
+#include "interval_cells.h"
 
 static_assert(COLATE_FLAG_NAN == 1 && COLATE_FLAG_NEG == 2 && COLATE_FLAG_MAXITER == 4 && COLATE_FLAG_UNRESOLVED == 8 &&
                   COLATE_UNRESOLVED_SHIFT == 8, "flags");
@@ -713,5 +714,35 @@ int colate_bootstrap_em_interval_batch(int B, int nb, int R, int E, const int* k
 }
 
 int colate_em_interval_batch_waves(int E) { return colate_em_interval_fit_waves(E); }
+
+int colate_interval_cells(long long n, const colate_interval_rec* recs, const int* block, int nb, int max_rows, int* kinds,
+                          double* age_begin, double* age_end, double* tables, long long* dropped) {
+  using namespace colate_ic;
+  if (int rc = check_cells_args(n, recs, block, nb, max_rows, kinds, age_begin, age_end, tables, dropped)) return rc;
+  float T[kBins];
+  if (int rc = build_thresholds(T)) return rc;
+  if (int rc = ensure_device()) return rc;
+  ProfRange range("colate_interval_cells: H2D + bin kernel + cell-sum kernel + D2H");
+  std::vector<long long> off((size_t)nb + 1);
+  block_ranges(n, block, nb, off.data());
+  std::vector<double> cells((size_t)nb * 2 * kCells);
+  std::vector<unsigned long long> nd((size_t)nb);
+  Arena st(g_ws);
+  const int i_recs = st.in(recs, (size_t)n), i_off = st.in(off.data(), off.size()), i_T = st.in(T, (size_t)kBins);
+  const int s_idx = st.scratch<int>((size_t)n);
+  const int o_cells = st.out(cells.data(), cells.size()), o_nd = st.out(nd.data(), nd.size());
+  if (int rc = st.commit()) return rc;
+  const hipError_t e = colate_interval_cells_launch(n, st.dev<IntervalRec>(i_recs), st.dev<long long>(i_off), nb, st.dev<float>(i_T),
+                                                    st.dev<int>(s_idx), st.dev<double>(o_cells),
+                                                    st.dev<unsigned long long>(o_nd), st.stream());
+  if (e != hipSuccess) return hip_fail(e, "interval cells kernel launch");
+  if (int rc = st.finish()) return rc;
+  const int R = compact_cells(nb, cells.data(), max_rows, kinds, age_begin, age_end, tables);
+  if (R < 0) return R;
+  unsigned long long total = 0;
+  for (unsigned long long d : nd) total += d;
+  *dropped = (long long)total;
+  return R;
+}
 
 }  // extern "C"

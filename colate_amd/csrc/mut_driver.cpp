@@ -61,7 +61,7 @@ const char* const kValueOptions[] = {
     "reference_age", "ref_genome", "anc_genome", "mask", "mask_cutoff", "chr", "bins",
     "lineage_bin", "outgroup_tmrca", "years_per_gen", "coal", "seed", "num_bootstraps", "filters",
     "groups", "poplabels", "map", "input", "output", "device", "devices", "ranks", "counts_out", "pairs",
-    "rows", "max_iter", "min_iter"};
+    "rows", "max_iter", "min_iter", "write_rows"};
 const char* const kBoolOptions[] = {"help", "strandfilter", "counts_only", "write_colate_mat"};
 
 bool parse_options(int argc, char** argv, Options& o, std::string& err) {
@@ -152,6 +152,9 @@ void print_help() {
             << "      --rows arg             (--mode mut_interval) File of `block kind age_begin age_end weight` lines (plain or gzip):\n"
             << "                             block a non-negative integer, kind shared|notshared, ages in generations; with --bins or\n"
             << "                             --coal, --num_bootstraps, --seed, --years_per_gen; writes <output>.coal.\n"
+            << "                             (--mode mut_interval) or --mut, --target_tmp, --reference_tmp [--chr, --target_mask,\n"
+            << "                             --reference_mask] as for --mode mut: every used SNP is one interval-dated observation.\n"
+            << "      --write_rows arg       (--mode mut_interval) Write the rows and per-block weights in the --rows format.\n"
             << "      --max_iter arg         (--mode mut_interval) Iteration cap of the EM (default 100000).\n"
             << "      --min_iter arg         (--mode mut_interval) Iterations before the stop rule applies (default 1000).\n"
             << "  -o, --output arg           Filename of output.\n"

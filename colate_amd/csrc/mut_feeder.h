@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 
+#include "colate_amd.h"
+
 namespace colate_drv {
 
 struct Options {
@@ -207,5 +209,13 @@ int run_condcoal(const Options& opt);  // "CPU Time spent: ...; Max Memory usage
 // error message.
 bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
                 const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& out);
+
+
+// mut_pairs.cpp: the engine's walk for `--mode mut_interval`.  The SNPs the pair uses -- use filter, block advance, masks and
+// the float rounding of the target genotype are those of fill_pairs, coal.cpp:2148-2244 -- as interval-dated observations
+// (interval_cells.h) in the walk's order: chromosome, then file order; blocks[i]: the genome block of record i, numbered
+// as fill_pairs numbers them; nb: the number of genome blocks.  Nothing is drawn.  False after an error message.
+bool collect_interval_records(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const PairSpec& pair,
+                              std::vector<colate_interval_rec>& recs, std::vector<int>& blocks, int& nb);
 
 }  // namespace colate_drv

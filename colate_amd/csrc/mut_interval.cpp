@@ -5,12 +5,16 @@
 // where the two overlap: epochs from --bins or --coal at age 0, the block weights of coal.cpp:3350-3357 from the run's
 // std::mt19937, the reference's iteration limits, the .coal writer.
 //
-// How a line of the file becomes a mutation's (kind, age_begin, age_end) is the caller's business: the mode takes rows.
+// The rows come from a file (--rows: how a line becomes a mutation's (kind, age_begin, age_end) is the caller's business),
+// or from the inputs of `--mode mut` (--mut, --target_tmp, --reference_tmp): every SNP the pair uses, snapped to the age
+// grid, is one observation of each kind (interval_cells.h), formed on the device by colate_interval_cells.
 #include <unistd.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <ctime>
 #include <iostream>
@@ -123,10 +127,88 @@ bool read_interval_rows(const std::string& path, double epoch0, IntervalRows& ou
   return true;
 }
 
+// The used SNPs of --mut / --target_tmp / --reference_tmp as rows and per-block tables (interval_cells.h): the engine's walk
+// (mut_pairs.cpp) gives the records, colate_interval_cells -- or its host twin after a line on stderr -- the cells.
+static bool rows_from_mut(const Options& opt, bool on_host, const std::string& host_why, IntervalRows& out) {
+  std::vector<std::string> names, mut_files;
+  PairSpec pair;
+  pair.target = opt.get("target_tmp"), pair.reference = opt.get("reference_tmp");
+  chromosome_files(opt, names, mut_files, &pair.target_masks, &pair.ref_masks);
+  std::vector<colate_interval_rec> recs;
+  std::vector<int> blocks;
+  int nb = 0;
+  if (!collect_interval_records(names, mut_files, pair, recs, blocks, nb)) {
+    std::cerr << "Error: the SNPs of the pair could not be walked." << std::endl;
+    return false;
+  }
+  if (nb < 1) {
+    std::cerr << "Error: no genome block (no chromosome was read)." << std::endl;
+    return false;
+  }
+  out = IntervalRows();
+  const int cap = (int)std::min<size_t>(COLATE_INTERVAL_MAX_ROWS, 2 * recs.size());
+  out.kinds.resize((size_t)cap), out.age_begin.resize((size_t)cap), out.age_end.resize((size_t)cap), out.tables.resize((size_t)nb * cap);
+  long long dropped = 0;
+  if (on_host) std::cerr << "interval cells on the host (" << host_why << ")" << std::endl;
+  const int R = (on_host ? colate_interval_cells_host : colate_interval_cells)(
+      (long long)recs.size(), recs.data(), blocks.data(), nb, cap, out.kinds.data(), out.age_begin.data(), out.age_end.data(),
+      out.tables.data(), &dropped);
+  if (R < 0) {
+    std::cerr << "Error: " << colate_last_error() << " (" << R << ")" << std::endl;
+    return false;
+  }
+  out.nb = nb, out.R = R;
+  out.kinds.resize((size_t)R), out.age_begin.resize((size_t)R), out.age_end.resize((size_t)R), out.tables.resize((size_t)nb * R);
+  for (int k = 0; k < nb; k++) out.block_ids.push_back(k);
+  std::cerr << "Number of blocks: " << nb << std::endl;
+  std::cerr << "Number of rows: " << R << std::endl;
+  std::cerr << "SNPs beyond the age grid: " << dropped << std::endl;
+  if (R == 0) {
+    std::cerr << "Error: the pair uses no SNP within the age grid." << std::endl;
+    return false;
+  }
+  return true;
+}
+
+// --write_rows: the rows in the --rows format, row by row and within a row the blocks ascending, one line per cell with a
+// positive weight, 17 significant digits.  A block without any positive cell gets a line of weight 0 on the first row, so
+// that reading the file back gives the same blocks, rows (in this order: first appearance) and tables.
+static bool write_interval_rows(const std::string& path, const IntervalRows& rows) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return false;
+  std::fprintf(f, "# block kind age_begin age_end weight\n");
+  std::vector<char> seen((size_t)rows.nb, 0);
+  for (int k = 0; k < rows.nb; k++)
+    for (int r = 0; r < rows.R && !seen[k]; r++) seen[k] = rows.tables[(size_t)k * rows.R + r] > 0.0;
+  for (int r = 0; r < rows.R; r++)
+    for (int k = 0; k < rows.nb; k++) {
+      const double w = rows.tables[(size_t)k * rows.R + r];
+      if (w > 0.0 || (r == 0 && !seen[k]))
+        std::fprintf(f, "%lld %s %.17g %.17g %.17g\n", rows.block_ids[k], rows.kinds[r] == 0 ? "shared" : "notshared", rows.age_begin[r],
+                     rows.age_end[r], w);
+    }
+  return std::fclose(f) == 0;
+}
+
 int run_mut_interval(const Options& opt) {
-  if (!opt.has("rows") || !opt.has("output") || (!opt.has("bins") && !opt.has("coal"))) {
-    std::cerr << "Error: --mode mut_interval needs --rows FILE, -o OUT and --bins x,y,stepsize or --coal FILE "
-                 "(optional: --num_bootstraps, --seed, --years_per_gen, --max_iter, --min_iter, --device)."
+  const bool from_mut = opt.has("mut") || opt.has("target_tmp") || opt.has("reference_tmp");
+  if (from_mut && opt.has("rows")) {
+    std::cerr << "Error: --rows cannot be combined with --mut, --target_tmp or --reference_tmp." << std::endl;
+    return 1;
+  }
+  if (from_mut && (opt.has("target_age") || opt.has("reference_age"))) {
+    std::cerr << "Error: --mode mut_interval takes modern samples only: --target_age and --reference_age are not supported." << std::endl;
+    return 1;
+  }
+  if (from_mut && opt.has("pairs")) {
+    std::cerr << "Error: --mode mut_interval does not take --pairs." << std::endl;
+    return 1;
+  }
+  const bool inputs_ok = from_mut ? opt.has("mut") && opt.has("target_tmp") && opt.has("reference_tmp") : opt.has("rows");
+  if (!inputs_ok || !opt.has("output") || (!opt.has("bins") && !opt.has("coal"))) {
+    std::cerr << "Error: --mode mut_interval needs --rows FILE (or --mut, --target_tmp and --reference_tmp), -o OUT and --bins "
+                 "x,y,stepsize or --coal FILE (optional: --chr, --target_mask, --reference_mask, --write_rows, --num_bootstraps, "
+                 "--seed, --years_per_gen, --max_iter, --min_iter, --device)."
               << std::endl;
     return 1;
   }
@@ -160,29 +242,37 @@ int run_mut_interval(const Options& opt) {
   }
   epochs.resize(E), init_rates.resize(E);
 
-  // ---- the rows and the per-block tables
-  IntervalRows rows;
-  std::string err;
-  if (!read_interval_rows(opt.get("rows"), epochs[0], rows, err)) {
-    std::cerr << "Error: " << err << std::endl;
-    return 1;
-  }
-  const int nb = rows.nb, R = rows.R;
-  std::cerr << "Number of blocks: " << nb << std::endl;
-  std::cerr << "Number of rows: " << R << std::endl;
-
-  // ---- block weights (coal.cpp:3350-3357)
-  std::mt19937 rng(seed);
-  std::vector<double> weights((size_t)B * nb);
-  if (int rc = colate_bootstrap_weights(&rng, B, nb, weights.data())) return api_error(rc);
-
-  // ---- device or host twin
+  // ---- device or host twin (the cells step and the fit alike)
   std::string host_why;
   if (const char* e = std::getenv("COLATE_DEVICE_INTERVAL"))
     if (std::string(e) == "0") host_why = "COLATE_DEVICE_INTERVAL=0";
   if (host_why.empty() && colate_device_count() <= 0) host_why = "no device";
   if (host_why.empty() && opt.has("device"))
     if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc);
+
+  // ---- the rows and the per-block tables
+  IntervalRows rows;
+  if (from_mut) {
+    if (!rows_from_mut(opt, !host_why.empty(), host_why, rows)) return 1;
+  } else {
+    std::string err;
+    if (!read_interval_rows(opt.get("rows"), epochs[0], rows, err)) {
+      std::cerr << "Error: " << err << std::endl;
+      return 1;
+    }
+    std::cerr << "Number of blocks: " << rows.nb << std::endl;
+    std::cerr << "Number of rows: " << rows.R << std::endl;
+  }
+  const int nb = rows.nb, R = rows.R;
+  if (opt.has("write_rows") && !write_interval_rows(opt.get("write_rows"), rows)) {
+    std::cerr << "Error: cannot write " << opt.get("write_rows") << std::endl;
+    return 1;
+  }
+
+  // ---- block weights (coal.cpp:3350-3357)
+  std::mt19937 rng(seed);
+  std::vector<double> weights((size_t)B * nb);
+  if (int rc = colate_bootstrap_weights(&rng, B, nb, weights.data())) return api_error(rc);
 
   std::cerr << "Maximising likelihood using EM.. " << std::endl;
   std::vector<double> rates((size_t)B * E), ll(B);

@@ -48,6 +48,7 @@
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "fill_device.h"
+#include "interval_cells.h"
 #include "mut_feeder.h"
 
 namespace colate_drv {
@@ -1102,12 +1103,16 @@ struct Engine {
   int A;
   double C;
   int num_bases_per_block;
-  SharedUniforms& stream;
-  const FastBin& fastbin;
+  SharedUniforms* stream;  // (null with `cells`: nothing is drawn)
+  const FastBin* fastbin;
   Pool& pool;
   BinSnpFn bin_snp = nullptr;  // the vector form of the 100 bins of a SNP where the CPU has one (and the table passed its self-check)
   AddSnpFn add_snp = nullptr;  // ... and of the additions
   DeviceSampler* dev = nullptr;  // not null: the sampling runs on the device
+  // not null: `--mode mut_interval`.  The same walk, but a used SNP is handed over as one interval-dated observation
+  // (interval_cells.h) with the number of its genome block: no uniform is taken, no table is filled.
+  std::vector<colate_ic::IntervalRec>* cells = nullptr;
+  std::vector<int>* cell_blocks = nullptr;
 
   // the 100 draws of every SNP of one genome-block segment, in order (coal.cpp:2260-2273, 2279-2295)
   void sample(PairFill& pf, Block& b, const std::vector<FillRec>& snps, uint64_t off) const {
@@ -1119,11 +1124,12 @@ struct Engine {
     double* ns = sh + A;
     const double age = 0;  // forced, coal.cpp:2074-2075
     double tmp[104];
+    const FastBin& fastbin = *this->fastbin;
     const double* const g_lo = fastbin.guard_lo();
     const double* const g_hi = fastbin.guard_hi();
     for (const FillRec& s : snps) {
       if (pf.redo.load(std::memory_order_relaxed)) return;
-      const double* u = stream.get100(off, tmp);
+      const double* u = stream->get100(off, tmp);
       const bool last_of_chunk = (off % SharedUniforms::kChunk) + 104 > SharedUniforms::kChunk;  // (the vector code reads 104 values)
       off += 100;
       const bool emp = s.begin <= 0;  // the F path (coal.cpp:2245-2275): not-shared weight only, no redraws
@@ -1203,7 +1209,7 @@ struct Engine {
     else flush(pf);
     pf.blk++;
     pf.num_blocks++;
-    if (pf.blk >= pf.blocks.size()) pf.blocks.emplace_back(new Block(A));
+    if (!cells && pf.blk >= pf.blocks.size()) pf.blocks.emplace_back(new Block(A));
   }
 
   // a SNP the pair uses (coal.cpp:2221-2297): its genome block, the row-0 entries of the F tables, and its 100 draws queued
@@ -1224,6 +1230,13 @@ struct Engine {
     f_AAF_target /= N_target / 2.0;
     f_DAF_target = std::round(f_DAF_target);
     f_AAF_target = std::round(f_AAF_target);
+    if (cells) {  // the weights as coal.cpp:2255-2256 writes them (no 1 / num_samples: the SNP is one observation)
+      cells->push_back(colate_ic::IntervalRec{(float)age_begin, m.age_end, f_DAF_target * DAF_ref / ((double)N_ref),
+                                              f_AAF_target * DAF_ref / ((double)N_ref)});
+      cell_blocks->push_back((int)pf.blk);
+      pf.used_snps++;
+      return;
+    }
     if (pf.recs.empty()) pf.recs_off = pf.off;
     double w_sh = 0.0;
     if (age_begin <= age) {  // coal.cpp:2245-2275
@@ -1250,7 +1263,7 @@ struct Engine {
     WorkSeconds::add(g_work.walk, now_s() - t_walk0 - (pf.inline_sample_s - sample0));
   }
   void walk_impl(PairFill& pf, uint64_t limit) const {
-    if (pf.blocks.empty()) pf.blocks.emplace_back(new Block(A));
+    if (!cells && pf.blocks.empty()) pf.blocks.emplace_back(new Block(A));
     while (pf.chr < rows.size()) {
       if (pf.redo.load(std::memory_order_relaxed)) break;
       if (!pf.chr_open) {
@@ -1280,8 +1293,9 @@ struct Engine {
     }
     flush(pf);
     pf.walked = true;
+    if (cells) return;
     pf.blocks.resize((size_t)pf.num_blocks);
-    if (!stream.state_at(pf.off, pf.rng_end)) pf.redo.store(true);
+    if (!stream->state_at(pf.off, pf.rng_end)) pf.redo.store(true);
   }
 
   // The rows of the pair's chromosome from pf.row on, through the two files' indices (WalkRows); false: stopped at `limit`.  The
@@ -1533,7 +1547,7 @@ bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const
 
   // ---- the pairs, window by window through the shared uniform stream
   DeviceSampler* dev = sampler.start(A, todo.size(), in.n_kept, W) ? &sampler : nullptr;
-  Engine eng{names, in.rows, A, C, num_bases_per_block, stream, fastbin, pool, fastbin.ok() ? pick_bin_snp() : nullptr,
+  Engine eng{names, in.rows, A, C, num_bases_per_block, &stream, &fastbin, pool, fastbin.ok() ? pick_bin_snp() : nullptr,
              fastbin.ok() ? pick_add_snp() : nullptr, dev};
   int windows = 0;
   for (uint64_t w = 0;; w++, windows++) {
@@ -1576,6 +1590,27 @@ bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const
   g_times.parse_mut = t1 - t0;
   g_times.table_fill = now_s() - t1;
   return true;
+}
+
+// (mut_feeder.h)
+bool collect_interval_records(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const PairSpec& pair,
+                              std::vector<colate_ic::IntervalRec>& recs, std::vector<int>& blocks, int& nb) {
+  const double t0 = now_s();
+  recs.clear(), blocks.clear();
+  Pool pool(pairs_threads());
+  const std::vector<PairSpec> pairs(1, pair);
+  const std::vector<size_t> todo(1, 0);
+  const char* e_idx = std::getenv("COLATE_INDEXED_WALK");
+  const Inputs in = load_inputs(pool, names, mut_files, pairs, todo, !(e_idx && std::atoi(e_idx) == 0));
+  Fills fills = open_pairs(in, pairs, todo);
+  const double t1 = now_s();
+  Engine eng{names, in.rows, 0, 10.0, (int)30e6, nullptr, nullptr, pool, nullptr, nullptr, nullptr, &recs, &blocks};
+  PairFill& pf = *fills[0];
+  eng.walk(pf, std::numeric_limits<uint64_t>::max());  // (on this thread: one pair, and the order of the records is the walk's)
+  nb = pf.num_blocks;
+  g_times.parse_mut = t1 - t0;
+  g_times.table_fill = now_s() - t1;
+  return pf.walked && !pf.redo.load();
 }
 
 }  // namespace colate_drv

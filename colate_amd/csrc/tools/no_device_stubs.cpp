@@ -51,6 +51,9 @@ int colate_bootstrap_em_interval_batch(int, int, int, int, const int*, const dou
                                        const double*, const double*, int, int, double, double, double*, int*, double*, int*) {
   return nodev();
 }
+int colate_interval_cells(long long, const colate_interval_rec*, const int*, int, int, int*, double*, double*, double*, long long*) {
+  return nodev();
+}
 int colate_shard_bounds(int B, int nranks, int rank, int* lo, int* hi) {
   const int base = B / nranks, rem = B % nranks;
   *lo = rank * base + (rank < rem ? rank : rem);

@@ -244,6 +244,50 @@ int colate_bootstrap_em_interval_batch_host(int B, int nb, int R, int E, const i
                                             double* out_loglik, int* out_flags, int math);
 int colate_bootstrap_rows_host(int B, int nb, int R, const double* block_weights, const double* tables, double* W);
 
+/* ---- from used SNPs to the rows and tables of that call (csrc/interval_cells.h) ----
+ * `--mode mut` spreads a used SNP's weight over 100 ages drawn uniformly on [age_begin, age_end] (coal.cpp:2245-2297);
+ * the interval fit treats that uniform distribution exactly, so here a used SNP is one observation of each kind and
+ * nothing is drawn.  A record is one used SNP: its float ages as the walk holds them (age_begin clamped to the sample
+ * age 0) and its weights f_DAF_target * DAF_ref / N_ref (shared) and the same with f_AAF_target (not shared).  Ages are
+ * snapped to the 185-point age grid: bb = bin(begin), be = bin(end), bin(x) = max(0, (int)round(log(10 x) * 10) + 1)
+ * (coal.cpp:2265) on the float widened to double; the cell (kind, bb, be) is the row age_begin = age_grid[bb], age_end =
+ * age_grid[be] of that kind (bb == be: a point row; begin <= 0, the reference's F path: an ordinary row from 0); a
+ * record with be >= 185 lies beyond the grid and is dropped.
+ * colate_interval_bin_thresholds: T185[n - 1], n = 1 .. 185, is the smallest float whose bin is >= n -- located by
+ * bisection over float bit patterns on the library expression and checked at both neighbouring floats (COLATE_EINVAL
+ * where it is not such a step) -- so that bin(x) = #{n : T[n - 1] <= x}.  Both calls below bin through this table.
+ * Summation order (the contract, on the device and on the host): per (genome block, kind, bb, be) the sum starts at 0.0
+ * and adds the records' weights in record order, every addition rounded (no floating-point atomics, no partial sums).
+ * block[n]: the genome block of every record, in [0, nb), not decreasing.  Out: the R rows are the cells with a positive
+ * sum in at least one block, ordered by kind (0 = shared first), bb, be: kinds / age_begin / age_end[R] and
+ * tables[nb][R] -- what colate_bootstrap_em_interval_batch takes --, *dropped the records beyond the grid.  Returns R
+ * (>= 0; n = 0 gives 0) or a negative code.  The caller gives room for max_rows rows (tables: nb * max_rows doubles,
+ * filled as [nb][R]); COLATE_INTERVAL_MAX_ROWS always suffices, R above max_rows is COLATE_EINVAL.
+ * Refused (COLATE_EINVAL, before anything is staged; the outputs are not touched): a NaN or negative age, begin > end,
+ * a negative or non-finite weight, a block index outside [0, nb) or out of order, nb < 1.  nb above
+ * COLATE_INTERVAL_MAX_BLOCKS: COLATE_ELIMIT.
+ * colate_interval_cells bins and sums on the calling thread's device (csrc/interval_cells_kernel.hip: a thread per
+ * record, then one wave per (block, tile of the (bb, be) triangle) that resolves equal cells in lane order through
+ * LDS); the rows are picked on the host after one copy.  COLATE_ENODEVICE without a device, there is no fall-back.
+ * _host: the host twin, the same doubles.  colate_interval_cells_tile: diagnostic, the cells per tile of the kernel
+ * (tile t covers the triangular indices be * (be + 1) / 2 + bb in [t * tile, (t + 1) * tile); no device needed).
+ * Speed (one MI355X, tools/interval_cells_bench.py, profiles/interval/interval_cells_bench.json): 8.8 M records in 110
+ * blocks take 0.035 s on the device (0.21 s for a process's first call) against 0.32 s for the host twin; 10 000 records
+ * take about half a millisecond either way. */
+#define COLATE_INTERVAL_BINS 185
+#define COLATE_INTERVAL_MAX_ROWS (COLATE_INTERVAL_BINS * (COLATE_INTERVAL_BINS + 1))
+#define COLATE_INTERVAL_MAX_BLOCKS 4096
+typedef struct colate_interval_rec {
+  float begin, end;
+  double w_sh, w_ns;
+} colate_interval_rec;
+int colate_interval_bin_thresholds(float* T185);
+int colate_interval_cells(long long n, const colate_interval_rec* recs, const int* block, int nb, int max_rows, int* kinds,
+                          double* age_begin, double* age_end, double* tables, long long* dropped);
+int colate_interval_cells_host(long long n, const colate_interval_rec* recs, const int* block, int nb, int max_rows,
+                               int* kinds, double* age_begin, double* age_end, double* tables, long long* dropped);
+int colate_interval_cells_tile(void);
+
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
 int colate_age_grid(double* age_grid, int cap);
@@ -472,7 +516,14 @@ int colate_coalrate_main(int argc, char** argv);
  * one cell add up in file order.  Epochs and starting rates as for `mut` at age 0; block weights from
  * colate_bootstrap_weights on std::mt19937(--seed).  Writes OUT.coal (colate_write_coal).  Without a device, or with
  * COLATE_DEVICE_INTERVAL=0, the math = 1 host twin runs after one line on stderr and writes the same bytes.  A
- * malformed line is an error that names its line number; nothing is written then. */
+ * malformed line is an error that names its line number; nothing is written then.
+ * `--mode mut_interval --mut P --target_tmp T --reference_tmp R [--chr FILE] [--target_mask PREFIX] [--reference_mask PREFIX]
+ * [--write_rows FILE]` with the same fit options takes the inputs of `--mode mut` instead of --rows (both together: an
+ * error; --target_age / --reference_age and --pairs are refused): the SNPs `--mode mut` uses become the rows and tables
+ * through colate_interval_cells (the host twin without a device or with COLATE_DEVICE_INTERVAL=0, after a line on stderr;
+ * same bytes), stderr shows `Number of blocks`, `Number of rows` and `SNPs beyond the age grid`, and --write_rows writes
+ * them in the --rows format (17 significant digits; a block without a positive cell keeps a line of weight 0), from which
+ * --rows gives the same OUT.coal. */
 int colate_mut_main(int argc, char** argv);
 
 #ifdef __cplusplus
