@@ -76,6 +76,13 @@ __device__ __forceinline__ double readlane_d(double v, int lane) {
   return __hiloint2double(hi, lo);
 }
 
+// the double of the lane at byte address `addr` (lane * 4), through the LDS crossbar
+__device__ __forceinline__ double bpermute_d(int addr, double v) {
+  const int lo = __builtin_amdgcn_ds_bpermute(addr, __double2loint(v));
+  const int hi = __builtin_amdgcn_ds_bpermute(addr, __double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
 // DPP move of a double.  Lanes whose source is out of range, or whose row is
 // not in ROW_MASK, keep `old` (BOUND == false) or read 0 (BOUND == true).
 template <int CTRL, int ROW_MASK = 0xf, bool BOUND = false>
@@ -289,7 +296,7 @@ constexpr int em_loop_pad(int mode, int nch, int erows, bool tput, int wpe) {
 #ifdef COLATE_LOOP_PAD
   return (COLATE_LOOP_PAD) & 7;
 #else
-  (void)erows, (void)wpe;
+  (void)erows, (void)wpe;  // (not read in every build)
   if (mode != 0) return 0;
   // measured on MI355X, kernel ms for pads 0..7, loop code of round 3 (gpurun_out/r03j/padsweep.txt -> profiles/r03_placement.txt).
   // The pad shifts everything behind it, the loops compiled per kind of wave included.
@@ -309,7 +316,12 @@ constexpr int em_loop_pad(int mode, int nch, int erows, bool tput, int wpe) {
   // E=23 B=100 0.880 0.876 0.870 0.871 0.871 0.881 0.874 0.871 (parent: 0.898 0.898 0.906 0.912 0.912 0.888 0.901 0.916)
   // (swept on the two-row instantiation, 17..32 epochs, only: the one- and the four-row instantiation of that build, whose loops
   // changed as well, take the same pad without a sweep of their own, as they always have)
-  return nch == 1 ? (wpe == 2 ? 2 : 6) : 2;
+  // ... and with role A's front scheduled by hand (em_role_a_front; the loops of role A's waves in that build changed and, compiled
+  // in one function with them, the order of a few instructions in role B's; profiles/role_a_front_ab.txt, one run per pad, the parent
+  // commit's library alternating with it on the same box):
+  // E=23 B=100 0.824 0.828 0.833 0.833 0.823 0.832 0.809 0.825 (parent: 0.880 0.882 0.873 0.874 0.870 0.880 0.879 0.875)
+  // (again the two-row instantiation only: it moves to pad 6, the other two stay where they were)
+  return nch == 1 ? (wpe == 2 ? (erows == 2 ? 6 : 2) : 6) : 2;
 #else
   (void)nch;
   if (!tput) return 6;  // latency variant, default build (not picked by colate_em_variant any more; COLATE_EM_VARIANT=latency)
@@ -342,6 +354,21 @@ constexpr bool em_affine_split(int nch, bool tput, int wpe) {
 #endif
 }
 
+// Role A's waves in front of barrier 2, scheduled by hand (see `kFront` in the iteration): the two-barrier build only, whose
+// iteration is as long as role A's waves take to reach that barrier.  The cs scan with exp(-cs_e) and the rate-only head of the bin
+// terms (exp(-lambda_k (age - t_k)), 1 / lambda_k, the two quotients) are two chains that only meet in the bin's normaliser: the
+// second one's instructions are written between the steps of the first, where the scan's DPP hazards and the wait for the exp
+// table otherwise cost issue slots.  Same operations on the same operands in either chain.  -DCOLATE_ROLE_A_FRONT=0 turns it off (A/B runs).
+constexpr bool em_role_a_front(int nch, bool tput, int wpe) {
+#if defined(COLATE_EXP_SERIES) || defined(COLATE_ABL)
+  (void)nch, (void)tput, (void)wpe;
+  return false;  // (the experiments' builds keep the compiler's schedule)
+#elif defined(COLATE_ROLE_A_FRONT)
+  return (COLATE_ROLE_A_FRONT) != 0 && !tput && nch == 1 && wpe == 2;
+#else
+  return !tput && nch == 1 && wpe == 2;
+#endif
+}
 // MODE 0: EM to convergence, 1: one E-step (num/den/ll out).  NCH = epochs per lane (1, 2, 4: up to 64, 128, 256 epochs);
 // EROWS = 16-lane rows that hold epochs (1, 2 or 4; 4 whenever NCH > 1).
 // TPUT = false: the latency variant described at the top (a wave per role and bin group, one workgroup per CU
@@ -719,6 +746,17 @@ __global__ __launch_bounds__(TPUT ? 2 * kWave : 2 * COLATE_EM_MAX_A, WPE ? WPE :
   const int p1b_wave = (kFree && NB >= 2) ? 3 : 1;
   const int nwave_live = 2 * NB;
   (void)nwave_live;
+  // Role A's front by hand (em_role_a_front, `kFront` in the iteration).  The rate of this lane's bin's epoch is fetched from the
+  // wave's own epoch lanes right behind the M-step that produced it -- at the end of the iteration before, in front of the first
+  // one by COLATE_STEADY -- so that it has arrived when the scan's first gap wants it; the lanes with data as a scalar mask.
+  constexpr bool kFrontBuild = kFree && em_role_a_front(NCH, TPUT, WPE);
+  double lk_carry = 0.0, x_carry = 0.0;
+  const int bp_k = kFrontBuild ? ((bs0.kb < E ? bs0.kb : 0) & 63) << 2 : 0;  // (ds_bpermute address of the lane that holds this bin's epoch)
+  unsigned long long live_mask = 0;
+  if constexpr (kFrontBuild) {
+    live_mask = ballot64(bs0.live);
+    asm volatile("" : "+s"(live_mask));  // (stays a scalar pair: as a per-lane flag it is turned back into the mask every iteration)
+  }
 
   int my_flags = 0;
   // bit l: the numerator of epoch l of the chunk was below kTinyNum (0 included) / was not 0 in some iteration
@@ -848,7 +886,93 @@ __global__ __launch_bounds__(TPUT ? 2 * kWave : 2 * COLATE_EM_MAX_A, WPE ? WPE :
     double q_e[NCH], p_e[NCH], beta_e[NCH], S_e[NCH], omS_e[NCH], cs_e[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; c++) q_e[c] = p_e[c] = beta_e[c] = S_e[c] = omS_e[c] = cs_e[c] = 0.0;
-    if ((P1A || P1B) && !COLATE_ABL_HAS(15)) {
+    // Role A's waves, steady-state loops of the two-barrier build (em_role_a_front): P1 and the rate-only head of the bin terms,
+    // written in the order they are to be issued.  Chain 1 is the cs scan, S_e = exp(-cs_e), the rows (leader) and the fetch of
+    // S_k, 1 - S_k; chain 2 the bin's exp(-lambda_k (age - t_k)), 1 / lambda_k and the two quotients (t_k + 1/lambda_k) lambda_k,
+    // (age + 1/lambda_k) lambda_k.  A scan step ends in an addition whose result the next step's DPP moves may read two issue slots
+    // later at the earliest, and each exp waits for its table entry: pieces of chain 2 stand in those places.  Every piece is
+    // held where it is written (its results pinned, a scheduling barrier behind it); inside a piece the compiler orders.  The
+    // operations are those of the code below and of bin_terms (em_exp_om_t, em_exp_t, em_rcp_ieee, em_div_known_rcp), on the same
+    // operands and in the same order within either chain.
+    constexpr bool kFront = kFrontBuild && kSteady && kNeedLL == 0 && kRole == 0;
+    double head_ik = 0.0, head_Xak = 0.0, head_Y = 0.0, head_Sk = 0.0, head_PWk = 0.0, head_qd = 0.0;
+    if constexpr (kFront) {
+      static_assert(NCH == 1, "one epoch per lane");
+#define COLATE_CUT() __builtin_amdgcn_sched_barrier(0);
+#define COLATE_PIN(x) asm volatile("" : "+v"(x));
+      const double lk = lk_carry;  // lambda_k, on its way since the M-step
+      double v = x_carry;  // lambda_e dt_e, the product taken behind the M-step like the fetch: the first DPP move has nothing to wait for
+      v += dpp_d<ROW_SHR1, 0xf, true>(0.0, v);
+      COLATE_CUT()
+      const double xc2 = em::max_c(-(lk * bs0.da), -1100.0);  // chain 2: the argument of exp(-lambda_k (age - t_k))
+      double zero15 = 0.0;  // (what the rows outside the cross-row step's mask add: set up here, not next to the move that reads it)
+      double y2 = em::em_rcp_ieee_seed(lk);  // 1 / lambda_k: the hardware's estimate
+      COLATE_PIN(zero15) COLATE_PIN(y2) COLATE_CUT()
+      v += dpp_d<ROW_SHR2, 0xf, true>(0.0, v);
+      COLATE_CUT()
+      em::ExpK k2 = em::em_exp_tab_k(xc2);
+      unsigned long long lpos_mask = __builtin_amdgcn_fcmp(lk, 0.0, 2 /* FCMP_OGT */);  // lambda_k > 0, for the select of 1 / lambda_k
+      COLATE_PIN(k2.kd) COLATE_PIN(k2.k) asm volatile("" : "+s"(lpos_mask)); COLATE_CUT()
+      v += dpp_d<ROW_SHR4, 0xf, true>(0.0, v);
+      COLATE_CUT()
+      const int ki2 = em::em_lo32(k2.kd);
+      int e2 = ki2 >> 5, j2 = 2 * (ki2 & 31);
+      double r2 = em::em_exp_tab_r(xc2, k2.k);
+      COLATE_PIN(e2) COLATE_PIN(j2) COLATE_PIN(r2) COLATE_CUT()
+      v += dpp_d<ROW_SHR8, 0xf, true>(0.0, v);
+      COLATE_CUT()
+      const double th2 = s_exptab[j2], tl2 = s_exptab[j2 + 1];  // (issued here, read behind chain 1's exp)
+      COLATE_CUT()
+      if (erows > 1) {
+        v += dpp_d<ROW_BCAST15, 0xa>(zero15, v);
+        COLATE_CUT()
+      }
+      double ik_all = em::em_rcp_ieee_refine(lk, y2);
+      COLATE_PIN(ik_all) COLATE_CUT()
+      if (erows > 2) {
+        head_ik = __builtin_amdgcn_inverse_ballot_w64(lpos_mask) ? ik_all : 0.0;  // (a rate of 0: see bin_terms)
+        COLATE_PIN(head_ik) COLATE_CUT()
+        v += dpp_d<ROW_BCAST31, 0xc>(0.0, v);
+        COLATE_CUT()
+      }
+      cs_e[0] = dpp_d<WAVE_SHR1, 0xf, true>(0.0, v);
+      COLATE_STAMP(8)
+      // chain 1: exp(-cs_e) up to the read of its table entry ...
+      const double xc1 = em::max_c_neg(cs_e[0], -1100.0);
+      COLATE_CUT()
+      if (erows <= 2) {  // (here: between the v_max_f64 above, written as asm, and the instruction that reads its result)
+        head_ik = __builtin_amdgcn_inverse_ballot_w64(lpos_mask) ? ik_all : 0.0;
+        COLATE_PIN(head_ik) COLATE_CUT()
+      }
+      em::ExpK k1 = em::em_exp_tab_k(xc1);
+      const int ki1 = em::em_lo32(k1.kd);
+      const int e1 = ki1 >> 5, j1 = 2 * (ki1 & 31);
+      double r1 = em::em_exp_tab_r(xc1, k1.k);
+      const double th1 = s_exptab[j1], tl1 = s_exptab[j1 + 1];
+      COLATE_CUT()
+      // ... and while that is on its way, the polynomials of both
+      double p1 = em::em_exp_tab_poly(r1);
+      double p2 = em::em_exp_tab_poly(r2);
+      COLATE_PIN(p1) COLATE_PIN(p2) COLATE_CUT()
+      S_e[0] = em::em_exp_tab_value_om(th1, tl1, p1, e1, &omS_e[0]);
+      if (LEADER) {  // (every wave of role A has them in registers; wave 0 writes the rows)
+        const int e = ep_of(0);
+        s_ep[G_CS * EPAD + e] = cs_e[0];
+        s_ep[G_S * EPAD + e] = S_e[0];
+        s_ep[G_PW * EPAD + e] = omS_e[0];
+      }
+      head_Sk = bpermute_d(bp_k, S_e[0]);
+      head_PWk = bpermute_d(bp_k, omS_e[0]);
+      COLATE_CUT()
+      // ... and while S_k is on its way, chain 2's quotients and the end of its exp
+      head_Xak = em::em_div_known_rcp(bs0.tk + head_ik, head_ik, lk);
+      head_Y = em::em_div_known_rcp(bs0.a_b + head_ik, head_ik, lk);
+      head_qd = em::em_exp_tab_value(th2, tl2, p2, e2);
+      COLATE_PIN(head_Xak) COLATE_PIN(head_Y) COLATE_CUT()
+#undef COLATE_PIN
+#undef COLATE_CUT
+    }
+    if constexpr (!kFront) if ((P1A || P1B) && !COLATE_ABL_HAS(15)) {
       double x_e[NCH];
 #pragma unroll
       for (int c = 0; c < NCH; c++) x_e[c] = lam_e[c] * dt_e[c];
@@ -958,7 +1082,7 @@ __global__ __launch_bounds__(TPUT ? 2 * kWave : 2 * COLATE_EM_MAX_A, WPE ? WPE :
     // the wait the barrier needs anyway) lets the bin's exp(-lambda_k (age - t_k)) start right behind the barrier instead
     // of behind the LDS gather of the other per-epoch values.  Same value, so nothing changes but the time.
     double lk_pre = 0.0;
-    if (!TPUT) {
+    if constexpr (!kFront) if (!TPUT) {
       const int kq = bs0.kb < E ? bs0.kb : 0;
 #pragma unroll
       for (int c = 0; c < NCH; c++) {
@@ -971,7 +1095,11 @@ __global__ __launch_bounds__(TPUT ? 2 * kWave : 2 * COLATE_EM_MAX_A, WPE ? WPE :
     // free: the bin's S_k, 1 - S_k out of this wave's own epoch lanes, and its exp(-lambda_k (age - t_k)) -- outside the
     // `live` branch of the bin terms, so that it shares a basic block with the scan and fills its stalls
     double Sk_pre = 0.0, PWk_pre = 0.0, qd_pre = 0.0;
-    if (kFree && ROLE == 0) {
+    if constexpr (kFront) {  // (all of it done above)
+      lk_pre = lk_carry;
+      Sk_pre = head_Sk, PWk_pre = head_PWk, qd_pre = head_qd;
+    }
+    if constexpr (!kFront) if (kFree && ROLE == 0) {
       const int kq = bs0.kb < E ? bs0.kb : 0;
       const int s_lo = __builtin_amdgcn_ds_bpermute((kq & 63) << 2, __double2loint(S_e[0]));
       const int s_hi = __builtin_amdgcn_ds_bpermute((kq & 63) << 2, __double2hiint(S_e[0]));
@@ -1013,7 +1141,33 @@ __global__ __launch_bounds__(TPUT ? 2 * kWave : 2 * COLATE_EM_MAX_A, WPE ? WPE :
       // v_cndmask and a v_cmp to get the mask back); `fail` itself is for the paths behind branches
       unsigned long long fail_direct = 0;
       bool have_fail_direct = false;
-      if (ROLE == 0 && !COLATE_ABL_HAS(12)) {
+      if constexpr (kFront) {
+        // ---- EM_shared as in the next block (crossed), what is left of it behind the front: 1 / lambda_k, the two quotients, S_k,
+        // 1 - S_k and exp(-lambda_k (age - t_k)) are there (the reciprocal was taken in every lane -- v_div_fixup copes with a rate
+        // of 0 -- and selected afterwards: no exec-masked branch around it).  The normaliser's test -- positive, normal or subnormal:
+        // what finite_pos asks -- goes straight into a scalar mask and meets the scalar mask of the lanes with data there; the select
+        // takes its condition from the masks.  (Through the bool the compiler turns the test into a per-lane 0 / 1 and compares
+        // that again to get the mask back: four issue slots.)
+        const double ik = head_ik, Sk = Sk_in, PWk = PWk_in, Xak = head_Xak, qd = qd_in, Y = head_Y;
+        const double Wp = Sk * (1.0 - qd);
+        const double X = Xak - Y * qd;
+        const double Vp = X * ik * Sk;
+        const double Sig = PWk + Wp;
+        unsigned long long fin_mask;
+        // (class mask 0x180: bit 7, positive subnormal, and bit 8, positive normal -- not zero, not infinite, not a NaN, not negative)
+        asm("v_cmp_class_f64 %0, %1, %2" : "=s"(fin_mask) : "v"(Sig), "v"(0x180));
+        const bool ok = __builtin_amdgcn_inverse_ballot_w64(live_mask & fin_mask);
+        const double r = ok ? em::em_rcp(Sig) : 0.0;
+        const double nk = Wp * r;
+        double dk = Vp * r + (-tk * nk);
+        dk = __builtin_fmax(dk, 0.0);
+        o_w = cnt * r;
+        o_N = cnt * nk;
+        o_D = cnt * dk;
+        fail_direct = live_mask & ~fin_mask;
+        have_fail_direct = true;
+        (void)a_b, (void)live, (void)lk_own;
+      } else if (ROLE == 0 && !COLATE_ABL_HAS(12)) {
         // ---- EM_shared, coal_EM.cpp:198-210, 263-287, WITHOUT exec-masked branches on `live` and `finite_pos(Sig)`: every lane
         // computes, the three results are selected at the end.  The two branches cost the wave 14 scalar / branch instructions per
         // iteration -- each an issue slot like an FP64 instruction -- against 6 v_cndmask here; a lane without data computes on
@@ -1641,6 +1795,11 @@ __global__ __launch_bounds__(TPUT ? 2 * kWave : 2 * COLATE_EM_MAX_A, WPE ? WPE :
         }
       }
     }
+    if constexpr (kFront) {  // (the next iteration's lambda_k and the first operand of its cs scan, see kFrontBuild)
+      x_carry = lam_e[0] * dt_e[0];
+      asm volatile("" : "+v"(x_carry));  // (or the compiler takes the product at the loop head again)
+      lk_carry = bpermute_d(bp_k, lam_e[0]);
+    }
     // (for the loop conditions, see `kFree`; as scalar arithmetic on the compare's lane mask -- written as a shift of the mask the
     // compiler made a per-lane value and an exec-masked loop of it: 14 instructions at the top of every iteration)
     if (kAssumeAbsorbing && kSteady) {
@@ -1676,6 +1835,7 @@ __global__ __launch_bounds__(TPUT ? 2 * kWave : 2 * COLATE_EM_MAX_A, WPE ? WPE :
 #define COLATE_STEADY(R, L, T, P)                             \
   {                                                           \
     lim = n_steady;                                           \
+    if constexpr (kFrontBuild && R::value == 0) x_carry = lam_e[0] * dt_e[0], lk_carry = bpermute_d(bp_k, lam_e[0]); \
     COLATE_LOOP_ANCHOR()                                      \
     do {                                                      \
       iteration(R{}, L{}, C0{}, T{}, C0{}, P{});              \

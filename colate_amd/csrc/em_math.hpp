@@ -31,6 +31,9 @@ EM_HD double fma_(double a, double b, double c) { return __builtin_fma(a, b, c);
 // copies c0 into the destination first (one v_mov_b64 per term: c0 stays live across the EM loop); spelling
 // the three-address v_fma_f64 out -- c1 from a scalar register pair, c0 from a loop-invariant vector pair --
 // drops those copies from the dependent chains of the kernel.  Same operation, same result.
+// (An instruction written as asm fills no hazard gap: LLVM's hazard recogniser does not count an inline-asm statement as a wait
+// state, so behind fma_cc / max_c / max_c_neg an s_nop appears in front of whatever reads a register written two issue slots
+// earlier -- their result included -- unless another, compiler-emitted instruction stands in between.)
 EM_HD double fma_cc(double c1, double x, double c0) {
 #if defined(__HIP_DEVICE_COMPILE__)
   double d;
@@ -184,6 +187,8 @@ struct ExpTab {
   double th, tl, p;  // exp(xc) = 2^e (th + (th p + tl)), p = expm1(r)
   int e;
 };
+// (em_exp_tab_k / _r / _poly below are this function cut into stages: a change of a constant or an operation here goes there as well;
+// tests/test_em_math_stages.py compares the two on the host, bit for bit)
 EM_HD ExpTab em_exp_tab_parts(double xc, const double* tab) {
   const double INVLN2N = 0x1.71547652b82fep+5;   // 32 / ln2
   const double LN2N_HI = 0x1.62e42fefa0000p-6;   // ln2/32, first 37 bits
@@ -208,6 +213,37 @@ EM_HD ExpTab em_exp_tab_parts(double xc, const double* tab) {
   o.p = fma_(r2, q, r);
   return o;
 }
+// em_exp_tab_parts in stages, for a caller that issues another chain's instructions between them (the EM loops scheduled by hand,
+// em_role_a_front in em_kernel_impl.hpp): the operations of em_exp_tab_parts one for one, on the same operands -- the same doubles.
+// `kd` carries k in its low mantissa bits (em_lo32), `k` is the same integer as a double.
+struct ExpK {
+  double kd, k;
+};
+EM_HD ExpK em_exp_tab_k(double xc) {
+  ExpK o;
+  o.kd = fma_(xc, 0x1.71547652b82fep+5, 0x1.8p52);
+  o.k = o.kd - 0x1.8p52;
+  return o;
+}
+EM_HD double em_exp_tab_r(double xc, double k) { return fma_(-k, 0x1.cf79abc9e0000p-45, fma_(-k, 0x1.62e42fefa0000p-6, xc)); }
+EM_HD double em_exp_tab_poly(double r) {
+  const double r2 = r * r;
+  const double a = fma_cc(0x1.5555555555555p-3, r, 0x1.0000000000000p-1);
+  const double b = fma_cc(0x1.1111111111111p-7, r, 0x1.5555555555555p-5);
+  const double c = fma_cc(0x1.a01a01a01a01ap-13, r, 0x1.6c16c16c16c17p-10);
+  const double r4 = r2 * r2;
+  const double q = fma_(c, r4, fma_(b, r2, a));
+  return fma_(r2, q, r);
+}
+// ... and what em_exp_t / em_exp_om_t make of the parts (th, tl: the table entry j = k & 31; e = k >> 5)
+EM_HD double em_exp_tab_value(double th, double tl, double p, int e) { return __builtin_ldexp(th + fma_(th, p, tl), e); }
+EM_HD double em_exp_tab_value_om(double th, double tl, double p, int e, double* one_minus) {
+  const double yh = __builtin_ldexp(th, e);
+  const double yl = __builtin_ldexp(fma_(th, p, tl), e);
+  *one_minus = (1.0 - yh) - yl;
+  return yh + yl;
+}
+
 // exp(x) for x <= 709 (any value down to -inf; a NaN is not propagated, as in em_exp)
 // (-DCOLATE_EXP_SERIES: experiments only -- the kernel then evaluates the series version through the same calls)
 EM_HD double em_exp_t(double x, const double* tab) {
@@ -256,6 +292,7 @@ EM_HD double em_rcp(double x) {
 // x = 0, inf, NaN -- minus the two v_div_scale and the scaling of v_div_fmas, which only act on operands beyond 2^+-768 or so: four
 // instructions fewer for the same bits on every rate the EM can hold (tests/test_gpu_em_math.py compares it with the device's own
 // division over the rates' range and beyond).  Host: the division itself.
+// (em_rcp_ieee_seed / _refine below are the same sequence in two stages: keep them in step)
 EM_HD double em_rcp_ieee(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   double y = __builtin_amdgcn_rcp(x);
@@ -268,6 +305,29 @@ EM_HD double em_rcp_ieee(double x) {
   return __builtin_amdgcn_div_fixup(q, x, 1.0);
 #else
   return 1.0 / x;
+#endif
+}
+
+// em_rcp_ieee in two stages (see em_exp_tab_k): the hardware's estimate, and everything behind it
+EM_HD double em_rcp_ieee_seed(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_rcp(x);
+#else
+  return 1.0 / x;
+#endif
+}
+EM_HD double em_rcp_ieee_refine(double x, double y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double e = fma_(-x, y, 1.0);
+  y = fma_(y, e, y);
+  e = fma_(-x, y, 1.0);
+  y = fma_(y, e, y);
+  const double r = fma_(-x, y, 1.0);
+  const double q = fma_(r, y, y);
+  return __builtin_amdgcn_div_fixup(q, x, 1.0);
+#else
+  (void)x;
+  return y;
 #endif
 }
 
