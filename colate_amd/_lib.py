@@ -72,6 +72,10 @@ SIGNATURES = {
     "colate_interval_cells": (c_int, [ctypes.c_longlong, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 5),
     "colate_interval_cells_host": (c_int, [ctypes.c_longlong, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 5),
     "colate_interval_cells_tile": (c_int, []),
+    "colate_interval_fit_groups": (c_int, [c_int] * 3 + [c_void_p] * 7 + [c_int, c_int, c_double, c_double] + [c_void_p] * 6),
+    "colate_interval_fit_groups_host": (c_int, [c_int] * 3 + [c_void_p] * 7 + [c_int, c_int, c_double, c_double] + [c_void_p] * 6
+                                        + [c_int]),
+    "colate_interval_fit_groups_kernel_seconds": (c_double, []),
     "colate_age_grid": (c_int, [c_void_p, c_int]),
     "colate_epochs_from_bins": (c_int, [c_char_p, c_double, c_double, c_void_p, c_int, ip]),
     "colate_epochs_from_coal": (c_int, [c_char_p, c_double, c_void_p, c_void_p, c_int]),

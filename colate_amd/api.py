@@ -429,6 +429,50 @@ def interval_cells(begin, end, w_sh, w_ns, block, nb, device=True, max_rows=None
     return kinds[:R].copy(), a0[:R].copy(), a1[:R].copy(), tables[:nb * R].reshape(nb, R).copy(), int(dropped.value)
 
 
+def interval_fit_groups(groups, epochs, init_rates=None, max_iter=DEFAULT_MAX_ITER, min_iter=DEFAULT_MIN_ITER,
+                        rel_tol=DEFAULT_REL_TOL, rate_floor=DEFAULT_RATE_FLOOR, device=True, math=1):
+    """colate_interval_fit_groups: for each group -- a tuple (begin, end, w_sh, w_ns, block, nb, block_weights[B][nb]), the
+    records as interval_cells takes them and the block weights of its B replicates -- interval_cells followed by
+    bootstrap_em_interval_batch, all groups in one call; on the device neither the cell sums nor W leave it.  epochs and
+    init_rates: [E] for all groups or [G][E].  Returns (R[G], dropped[G], rates[G][B][E], iters[G][B], loglik[G][B],
+    flags[G][B]): per group, bit for bit, what the two single calls return; a group without rows keeps its starting rates,
+    with iters, loglik and flags 0.  device=False: the host twin (colate_interval_fit_groups_host; math as for
+    em_interval_batch)."""
+    G = len(groups)
+    recs, blocks, nbs, bws, rec_off = [], [], [], [], [0]
+    B = None
+    for begin, end, w_sh, w_ns, block, nb, block_weights in groups:
+        r = np.zeros(np.asarray(begin).size, dtype=INTERVAL_REC)
+        r["begin"], r["end"], r["w_sh"], r["w_ns"] = np.ravel(begin), np.ravel(end), np.ravel(w_sh), np.ravel(w_ns)
+        blk = np.ascontiguousarray(block, dtype=np.int32).ravel()
+        bw = _f64(np.atleast_2d(block_weights))
+        if blk.size != r.size:
+            raise ValueError("one block index per record")
+        if bw.shape[1] != int(nb) or (B is not None and bw.shape[0] != B):
+            raise ValueError("block_weights must be [B][nb] with the same B in every group")
+        B = bw.shape[0]
+        recs.append(r), blocks.append(blk), nbs.append(int(nb)), bws.append(bw.ravel())
+        rec_off.append(rec_off[-1] + r.size)
+    B = 0 if B is None else B
+    ep = _f64(epochs)
+    E = ep.shape[-1]
+    ep = _f64(np.broadcast_to(ep, (G, E))) if ep.ndim == 1 else ep
+    init = _f64(np.full(E, DEFAULT_INIT_RATE) if init_rates is None else init_rates)
+    init = _f64(np.broadcast_to(init, (G, E))) if init.ndim == 1 else init
+    if ep.shape != (G, E) or init.shape != (G, E):
+        raise ValueError("epochs and init_rates must be [E] or [G][E]")
+    recs = np.concatenate(recs) if G else np.zeros(0, dtype=INTERVAL_REC)
+    blocks = np.ascontiguousarray(np.concatenate(blocks) if G else np.zeros(0), dtype=np.int32)
+    bws = _f64(np.concatenate(bws) if G else np.zeros(0))
+    rec_off, nbs = np.asarray(rec_off, dtype=np.int64), np.asarray(nbs, dtype=np.int32)
+    R, dropped = np.zeros(G, dtype=np.int32), np.zeros(G, dtype=np.int64)
+    rates, iters, ll, flags = np.zeros((G, B, E)), np.zeros((G, B), dtype=np.int32), np.zeros((G, B)), np.zeros((G, B), dtype=np.int32)
+    args = [G, B, E, _p(rec_off), _p(recs), _p(blocks), _p(nbs), _p(bws), _p(ep), _p(init), int(max_iter), int(min_iter),
+            float(rel_tol), float(rate_floor), _p(R), _p(dropped), _p(rates), _p(iters), _p(ll), _p(flags)]
+    check(lib.colate_interval_fit_groups(*args) if device else lib.colate_interval_fit_groups_host(*args, int(math)))
+    return R, dropped, rates, iters, ll, flags
+
+
 def _stream_ptr(stream):
     if stream is None:
         import torch

@@ -12,6 +12,7 @@
 // (colate_bootstrap_counts) and to the reference.
 #include <hip/hip_runtime.h>
 
+#include "colate_amd.h"
 #include "em_kernels.h"
 
 namespace {
@@ -136,7 +137,36 @@ __global__ __launch_bounds__(COLATE_BOOTSTRAP_ROWS_THREADS) void bootstrap_rows_
   W[(size_t)b * R + r] = acc;
 }
 
+// The same sums for the groups of a chunk of colate_interval_fit_groups, read out of the dense cell sums
+// cells[segment][2][17205] (interval_cells_kernel.hip) through each group's row list instead of compacted tables:
+// tables[k][r] of group j is cells[seg0 + k][cell_of_row[r]], the same double, so W_j[b][r] is the sum above operand for
+// operand.  blockIdx.z = the group, blockIdx.y = the replicate, blockIdx.x = the 256 rows; a group with fewer rows than
+// the chunk's largest leaves the blocks beyond its own idle.  Writes of W_j[b][.] are coalesced, reads of a block's cells
+// follow the row list (ascending within a kind).
+__global__ __launch_bounds__(COLATE_BOOTSTRAP_ROWS_THREADS) void bootstrap_rows_groups_kernel(
+    const ColateIntervalRowsJob* __restrict__ jobs, const double* __restrict__ cells, size_t cells_per_segment) {
+  const ColateIntervalRowsJob j = jobs[blockIdx.z];
+  const int b = blockIdx.y;
+  const size_t r = (size_t)blockIdx.x * COLATE_BOOTSTRAP_ROWS_THREADS + threadIdx.x;
+  if (r >= (size_t)j.R) return;
+  const double* __restrict__ w = j.block_weights + (size_t)b * j.nb;
+  const double* __restrict__ t = cells + (size_t)j.seg0 * cells_per_segment + j.cell_of_row[r];
+  double acc = 0.0;
+#pragma unroll 8  // (eight loads in flight; the additions stay in order)
+  for (int k = 0; k < j.nb; k++) acc += w[k] * t[(size_t)k * cells_per_segment];
+  j.W[(size_t)b * j.R + r] = acc;
+}
+
 }  // namespace
+
+hipError_t colate_bootstrap_rows_groups_launch(int groups, int B, int max_R, const ColateIntervalRowsJob* jobs,
+                                               const double* cells, hipStream_t stream) {
+  if (groups < 1 || groups > 65535 || B < 1 || B > 65535 || max_R < 1) return hipErrorInvalidValue;  // (gridDim.y, gridDim.z)
+  const unsigned chunks = (unsigned)((max_R + COLATE_BOOTSTRAP_ROWS_THREADS - 1) / COLATE_BOOTSTRAP_ROWS_THREADS);
+  hipLaunchKernelGGL(bootstrap_rows_groups_kernel, dim3(chunks, (unsigned)B, (unsigned)groups), dim3(COLATE_BOOTSTRAP_ROWS_THREADS), 0,
+                     stream, jobs, cells, (size_t)2 * COLATE_INTERVAL_BINS * (COLATE_INTERVAL_BINS + 1) / 2);
+  return hipGetLastError();
+}
 
 hipError_t colate_bootstrap_rows_launch(int B, int nb, int R, const double* block_weights, const double* tables, double* W,
                                         hipStream_t stream) {

@@ -20,7 +20,9 @@
 #include "colate_internal.h"
 #include "em_job.hpp"
 #include "em_kernels.h"
+#include "device_stage.hpp"
 #include "interval_cells.h"
+#include "interval_groups.h"
 
 static_assert(COLATE_FLAG_NAN == 1 && COLATE_FLAG_NEG == 2 && COLATE_FLAG_MAXITER == 4 && COLATE_FLAG_UNRESOLVED == 8 &&
                   COLATE_UNRESOLVED_SHIFT == 8, "flags");
@@ -743,6 +745,210 @@ int colate_interval_cells(long long n, const colate_interval_rec* recs, const in
   for (unsigned long long d : nd) total += d;
   *dropped = (long long)total;
   return R;
+}
+
+static thread_local double g_interval_groups_kernel_s = 0.0;
+double colate_interval_fit_groups_kernel_seconds(void) { return g_interval_groups_kernel_s; }
+
+// Many groups' cells, rows and fits in one pass (include/colate_amd.h).  One stream; the groups go through the cells, the row
+// pick and the row bootstrap in chunks whose dense cell sums fit a budget, and the only thing the host waits for before the
+// results is each chunk's R and dropped counts, which size the chunk's W; then one launch fits all groups.
+int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, const colate_interval_rec* recs, const int* block,
+                               const int* nb, const double* block_weights, const double* epochs, const double* init_rates,
+                               int max_iter, int min_iter, double rel_tol, double rate_floor, int* out_R, long long* out_dropped,
+                               double* out_rates, int* out_iters, double* out_loglik, int* out_flags) {
+  using namespace colate_ic;
+  float T[kBins];
+  if (int rc = build_thresholds(T)) return rc;
+  if (int rc = check_groups_args(G, B, E, rec_off, recs, block, nb, block_weights, epochs, init_rates, max_iter, min_iter, rel_tol,
+                                 rate_floor, T, out_R, out_dropped, out_rates, out_iters, out_loglik, out_flags))
+    return rc;
+  double grid[COLATE_MAX_AGE_BINS];
+  if (colate_age_grid(grid, COLATE_MAX_AGE_BINS) != kBins) return fail(COLATE_EINVAL, "the age grid has not %d points", kBins);
+  if (int rc = ensure_device()) return rc;
+  ProfRange range("colate_interval_fit_groups: per chunk H2D + cells + row pick + row bootstrap; one interval EM kernel + D2H");
+
+  // ---- the chunks: runs of consecutive groups whose segments (group, block) fit the budget; a larger group goes alone
+  constexpr size_t kSegBytes = sizeof(double) * 2 * kCells;
+  long long budget_mb = COLATE_INTERVAL_GROUPS_CELLS_MB_DEFAULT;
+  if (const char* e = std::getenv("COLATE_INTERVAL_GROUPS_CELLS_MB")) budget_mb = std::max(0LL, std::atoll(e));
+  const size_t budget_segs = std::max<size_t>(1, (size_t)budget_mb * (1u << 20) / kSegBytes);
+  struct Chunk {
+    int g0 = 0, g1 = 0;  // groups [g0, g1)
+    std::vector<long long> off;  // per segment: its records within the chunk's
+    std::vector<int> seg_off, cap;
+    std::vector<long long> row_off;
+    std::vector<int> R;
+    std::vector<long long> dropped;
+    std::vector<ColateIntervalRowsJob> jobs;
+  };
+  std::vector<Chunk> chunks;
+  size_t max_segs = 0, max_groups = 0;
+  long long max_recs = 0;
+  for (int g = 0; g < G;) {
+    Chunk c;
+    c.g0 = g;
+    size_t segs = 0;
+    do segs += (size_t)nb[g++];
+    while (g < G && g - c.g0 < 65535 && segs + (size_t)nb[g] <= budget_segs);
+    c.g1 = g;
+    max_segs = std::max(max_segs, segs), max_groups = std::max(max_groups, (size_t)(c.g1 - c.g0));
+    max_recs = std::max(max_recs, rec_off[c.g1] - rec_off[c.g0]);
+    chunks.push_back(std::move(c));
+  }
+
+  if (int rc = g_ws.reserve(256, 256)) return rc;  // (the workspace's stream)
+  hipStream_t stream = g_ws.stream;
+  struct SyncAtExit {  // nothing that the stream still reads or writes is freed before it is idle
+    hipStream_t s;
+    ~SyncAtExit() { (void)hipStreamSynchronize(s); }
+  };
+  DeviceBuffers buf;
+  struct Events {  // pairs of events around the kernels, for colate_interval_fit_groups_kernel_seconds
+    std::vector<hipEvent_t> ev;
+    ~Events() {
+      for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    hipError_t mark(hipStream_t s) {
+      hipEvent_t e;
+      if (hipError_t rc = hipEventCreate(&e)) return rc;
+      ev.push_back(e);
+      return hipEventRecord(e, s);
+    }
+  } events;
+  const SyncAtExit sync_at_exit{stream};
+  g_interval_groups_kernel_s = 0.0;
+  size_t bw_total = 0;
+  std::vector<size_t> bw_off((size_t)G);
+  for (int g = 0; g < G; g++) bw_off[(size_t)g] = bw_total, bw_total += (size_t)B * nb[g];
+  const size_t GB = (size_t)G * B, GE = (size_t)G * E;
+  // what lives for the whole call
+  float* d_T = nullptr;
+  double *d_grid = nullptr, *d_bw = nullptr, *d_ep = nullptr, *d_init = nullptr, *d_rates = nullptr, *d_ll = nullptr;
+  int *d_iters = nullptr, *d_flags = nullptr;
+  ColateIntervalGroup* d_desc = nullptr;
+  HIP_TRY(buf.device(d_T, kBins)); HIP_TRY(buf.device(d_grid, kBins)); HIP_TRY(buf.device(d_bw, bw_total));
+  HIP_TRY(buf.device(d_ep, GE)); HIP_TRY(buf.device(d_init, GE)); HIP_TRY(buf.device(d_desc, (size_t)G));
+  HIP_TRY(buf.device(d_rates, GB * E)); HIP_TRY(buf.device(d_ll, GB)); HIP_TRY(buf.device(d_iters, GB)); HIP_TRY(buf.device(d_flags, GB));
+  // the scratch of a chunk, sized for the largest and used by one chunk after the other in stream order
+  IntervalRec* d_recs = nullptr;
+  int *d_idx = nullptr, *d_seg_off = nullptr, *d_cap = nullptr, *d_R = nullptr;
+  long long *d_off = nullptr, *d_row_off = nullptr, *d_dropped = nullptr;
+  unsigned long long* d_seg_dropped = nullptr;
+  double* d_cells = nullptr;
+  unsigned char* d_flagbytes = nullptr;
+  ColateIntervalRowsJob* d_jobs = nullptr;
+  HIP_TRY(buf.device(d_recs, (size_t)max_recs)); HIP_TRY(buf.device(d_idx, (size_t)max_recs)); HIP_TRY(buf.device(d_off, max_segs + 1));
+  HIP_TRY(buf.device(d_cells, max_segs * 2 * kCells)); HIP_TRY(buf.device(d_seg_dropped, max_segs));
+  HIP_TRY(buf.device(d_seg_off, max_groups + 1)); HIP_TRY(buf.device(d_cap, max_groups)); HIP_TRY(buf.device(d_row_off, max_groups));
+  HIP_TRY(buf.device(d_R, max_groups)); HIP_TRY(buf.device(d_dropped, max_groups)); HIP_TRY(buf.device(d_jobs, max_groups));
+  HIP_TRY(buf.device(d_flagbytes, max_groups * 2 * kCells));
+  auto h2d = [stream](void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
+  };
+  HIP_TRY(h2d(d_T, T, sizeof(T))); HIP_TRY(h2d(d_grid, grid, sizeof(double) * kBins));
+  HIP_TRY(h2d(d_bw, block_weights, sizeof(double) * bw_total));
+  HIP_TRY(h2d(d_ep, epochs, sizeof(double) * GE)); HIP_TRY(h2d(d_init, init_rates, sizeof(double) * GE));
+
+  std::vector<ColateIntervalGroup> desc((size_t)G);
+  std::vector<int> R_all((size_t)G);
+  std::vector<long long> dropped_all((size_t)G);
+  bool any_rows = false;
+  for (Chunk& c : chunks) {
+    const int ng = c.g1 - c.g0;
+    const long long r0 = rec_off[c.g0], n = rec_off[c.g1] - r0;
+    c.seg_off.assign(1, 0), c.off.clear(), c.cap.resize((size_t)ng), c.row_off.resize((size_t)ng);
+    long long rows_cap = 0;
+    for (int j = 0; j < ng; j++) {
+      const int g = c.g0 + j;
+      const long long ng_recs = rec_off[g + 1] - rec_off[g];
+      std::vector<long long> off((size_t)nb[g] + 1);
+      block_ranges(ng_recs, ng_recs ? block + rec_off[g] : nullptr, nb[g], off.data());
+      for (int k = 0; k < nb[g]; k++) c.off.push_back(rec_off[g] - r0 + off[(size_t)k]);
+      c.seg_off.push_back(c.seg_off.back() + nb[g]);
+      c.cap[(size_t)j] = row_cap(ng_recs), c.row_off[(size_t)j] = rows_cap;
+      rows_cap += c.cap[(size_t)j];
+    }
+    c.off.push_back(n);
+    const int nseg = c.seg_off.back();
+    // the chunk's rows stay for the fit: room for every group's cap
+    int *d_cell_of_row = nullptr, *d_kinds = nullptr;
+    double *d_a0 = nullptr, *d_a1 = nullptr;
+    HIP_TRY(buf.device(d_cell_of_row, (size_t)rows_cap)); HIP_TRY(buf.device(d_kinds, (size_t)rows_cap));
+    HIP_TRY(buf.device(d_a0, (size_t)rows_cap)); HIP_TRY(buf.device(d_a1, (size_t)rows_cap));
+    HIP_TRY(h2d(d_recs, n ? recs + r0 : nullptr, sizeof(IntervalRec) * (size_t)n));
+    HIP_TRY(h2d(d_off, c.off.data(), sizeof(long long) * c.off.size()));
+    HIP_TRY(h2d(d_seg_off, c.seg_off.data(), sizeof(int) * c.seg_off.size()));
+    HIP_TRY(h2d(d_cap, c.cap.data(), sizeof(int) * (size_t)ng)); HIP_TRY(h2d(d_row_off, c.row_off.data(), sizeof(long long) * (size_t)ng));
+    HIP_TRY(events.mark(stream));
+    hipError_t e = colate_interval_cells_launch(n, d_recs, d_off, nseg, d_T, d_idx, d_cells, d_seg_dropped, stream);
+    if (e != hipSuccess) return hip_fail(e, "interval cells kernel launch");
+    e = colate_interval_rows_launch(ng, d_cells, d_seg_off, d_seg_dropped, d_grid, d_row_off, d_cap, d_flagbytes, d_cell_of_row, d_kinds,
+                                    d_a0, d_a1, d_R, d_dropped, stream);
+    if (e != hipSuccess) return hip_fail(e, "interval rows kernel launch");
+    HIP_TRY(events.mark(stream));
+    c.R.resize((size_t)ng), c.dropped.resize((size_t)ng);
+    HIP_TRY(hipMemcpyAsync(c.R.data(), d_R, sizeof(int) * (size_t)ng, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(c.dropped.data(), d_dropped, sizeof(long long) * (size_t)ng, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // the one wait of the chunk: R sizes its W
+    size_t w_total = 0;
+    int max_R = 0;
+    for (int j = 0; j < ng; j++) {
+      if (c.R[(size_t)j] < 0 || c.R[(size_t)j] > c.cap[(size_t)j])
+        return fail(COLATE_EHIP, "group %d: the row pick returned %d rows, room for %d", c.g0 + j, c.R[(size_t)j], c.cap[(size_t)j]);
+      w_total += (size_t)B * c.R[(size_t)j], max_R = std::max(max_R, c.R[(size_t)j]);
+    }
+    double* d_W = nullptr;
+    HIP_TRY(buf.device(d_W, w_total));
+    c.jobs.resize((size_t)ng);
+    size_t w_at = 0;
+    for (int j = 0; j < ng; j++) {
+      const int g = c.g0 + j, R = c.R[(size_t)j];
+      const long long ro = c.row_off[(size_t)j];
+      c.jobs[(size_t)j] = ColateIntervalRowsJob{c.seg_off[(size_t)j], nb[g], R, d_cell_of_row + ro, d_bw + bw_off[(size_t)g], d_W + w_at};
+      desc[(size_t)g] = ColateIntervalGroup{R, d_kinds + ro, d_a0 + ro, d_a1 + ro, d_W + w_at, d_ep + (size_t)g * E, d_init + (size_t)g * E};
+      R_all[(size_t)g] = R, dropped_all[(size_t)g] = c.dropped[(size_t)j];
+      w_at += (size_t)B * R;
+    }
+    if (max_R > 0) {
+      any_rows = true;
+      HIP_TRY(h2d(d_jobs, c.jobs.data(), sizeof(ColateIntervalRowsJob) * (size_t)ng));
+      HIP_TRY(events.mark(stream));
+      e = colate_bootstrap_rows_groups_launch(ng, B, max_R, d_jobs, d_cells, stream);
+      if (e != hipSuccess) return hip_fail(e, "grouped row bootstrap kernel launch");
+      HIP_TRY(events.mark(stream));
+    }
+  }
+
+  // ---- one fit launch for all groups; a group without rows keeps its starting rates
+  std::vector<double> rates(GB * E), ll(GB);
+  std::vector<int> iters(GB), flags(GB);
+  if (any_rows) {
+    HIP_TRY(h2d(d_desc, desc.data(), sizeof(ColateIntervalGroup) * (size_t)G));
+    HIP_TRY(events.mark(stream));
+    const hipError_t e = colate_em_interval_fit_groups_launch(G, B, E, d_desc, max_iter, min_iter, rel_tol, rate_floor, d_rates, d_iters,
+                                                              d_ll, d_flags, stream);
+    if (e != hipSuccess) return hip_fail(e, "grouped interval EM kernel launch");
+    HIP_TRY(events.mark(stream));
+    HIP_TRY(hipMemcpyAsync(rates.data(), d_rates, sizeof(double) * GB * E, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(ll.data(), d_ll, sizeof(double) * GB, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(iters.data(), d_iters, sizeof(int) * GB, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), d_flags, sizeof(int) * GB, hipMemcpyDeviceToHost, stream));
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (size_t i = 0; i + 1 < events.ev.size(); i += 2) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, events.ev[i], events.ev[i + 1]) == hipSuccess) g_interval_groups_kernel_s += ms * 1e-3;
+  }
+  for (int g = 0; g < G; g++) {
+    const size_t o = (size_t)g * B;
+    if (R_all[(size_t)g] == 0)
+      no_rows_results(B, E, init_rates + (size_t)g * E, rates.data() + o * E, iters.data() + o, ll.data() + o, flags.data() + o);
+  }
+  std::memcpy(out_R, R_all.data(), sizeof(int) * (size_t)G), std::memcpy(out_dropped, dropped_all.data(), sizeof(long long) * (size_t)G);
+  std::memcpy(out_rates, rates.data(), sizeof(double) * GB * E), std::memcpy(out_loglik, ll.data(), sizeof(double) * GB);
+  std::memcpy(out_iters, iters.data(), sizeof(int) * GB), std::memcpy(out_flags, flags.data(), sizeof(int) * GB);
+  return COLATE_OK;
 }
 
 }  // extern "C"

@@ -17,6 +17,10 @@
 // Control flow: every barrier is reached by every wave.  Trip counts depend on R, E, the weights of a group (every
 // thread reads the same WAVES values and skips a group in which none is > 0) and the verdict that all threads read
 // from LDS behind a barrier, so all threads leave the loop in the same iteration; max_iter bounds it.
+//
+// colate_interval_fit_groups launches the same body for G groups x B replicates at once (em_interval_fit_groups_kernel):
+// rows, R, weights, epochs and starting rates then differ between workgroups, but within a workgroup each is one value
+// that all threads read, so the above holds per workgroup.
 #include <hip/hip_runtime.h>
 
 #include "em_interval_fit.hpp"
@@ -27,15 +31,16 @@ namespace {
 
 using namespace em_interval;
 
+// The fit of one replicate by its workgroup: `wrow` = the replicate's R weights, `out_rates` = its E rates, `out_iters`,
+// `out_ll`, `out_flags` = its three scalars; `smem` = the workgroup's dynamic LDS.  Both kernels below are this body.
 // KOWN: epochs owned per thread (e = tid, tid + WAVES * 64, ...): WAVES * 64 * KOWN >= the largest E of the layout
 template <int WAVES, int KOWN>
-__global__ __launch_bounds__(WAVES * 64) void em_interval_fit_kernel(
-    int R, int E, const int* __restrict__ kinds, const double* __restrict__ age_begin, const double* __restrict__ age_end,
-    const double* __restrict__ weights, const double* __restrict__ epochs, const double* __restrict__ init_rates,
-    int max_iter, int min_iter, double rel_tol, double rate_floor, double* __restrict__ out_rates,
-    int* __restrict__ out_iters, double* __restrict__ out_ll, int* __restrict__ out_flags) {
+__device__ __forceinline__ void fit_replicate(
+    double* smem, int R, int E, const int* __restrict__ kinds, const double* __restrict__ age_begin,
+    const double* __restrict__ age_end, const double* __restrict__ wrow, const double* __restrict__ epochs,
+    const double* __restrict__ init_rates, int max_iter, int min_iter, double rel_tol, double rate_floor,
+    double* __restrict__ out_rates, int* __restrict__ out_iters, double* __restrict__ out_ll, int* __restrict__ out_flags) {
   constexpr int NT = WAVES * 64;
-  extern __shared__ double smem[];
   double* tab = smem;
   double* ep = tab + em::kExpTableDoubles;
   double* rt = ep + E;
@@ -45,7 +50,6 @@ __global__ __launch_bounds__(WAVES * 64) void em_interval_fit_kernel(
   double* ctl = first_wave + WAVES * wave_doubles(E);  // [0]: the verdict of the stop rule
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const WaveLds w = wave_lds(first_wave, E, wave);
-  const double* wrow = weights + (size_t)blockIdx.x * R;
 
   for (int i = tid; i < em::kExpTableDoubles; i += NT) tab[i] = em::kExpTableDevice[i];
   for (int e = tid; e < E; e += NT) ep[e] = epochs[e], rt[e] = init_rates[e];
@@ -137,17 +141,47 @@ __global__ __launch_bounds__(WAVES * 64) void em_interval_fit_kernel(
   }
 
   // ---- results: rates, "Total iterations", the last log-likelihood, the flags of all calls of all iterations
-  for (int e = tid; e < E; e += NT) out_rates[(size_t)blockIdx.x * E + e] = rt[e];
+  for (int e = tid; e < E; e += NT) out_rates[e] = rt[e];
   if (lane == 0) w.misc[0] = (double)flags;  // (wave_call's flags are the same in all lanes)
   __syncthreads();
   if (tid == 0) {
     int f = (iter == max_iter) ? COLATE_FLAG_MAXITER : 0;
 #pragma unroll
     for (int i = 0; i < WAVES; i++) f |= (int)wave_lds(first_wave, E, i).misc[0];
-    out_iters[blockIdx.x] = iter;
-    out_ll[blockIdx.x] = ll;
-    out_flags[blockIdx.x] = f;
+    *out_iters = iter;
+    *out_ll = ll;
+    *out_flags = f;
   }
+}
+
+// colate_em_interval_batch: workgroup b is replicate b of one set of rows
+template <int WAVES, int KOWN>
+__global__ __launch_bounds__(WAVES * 64) void em_interval_fit_kernel(
+    int R, int E, const int* __restrict__ kinds, const double* __restrict__ age_begin, const double* __restrict__ age_end,
+    const double* __restrict__ weights, const double* __restrict__ epochs, const double* __restrict__ init_rates,
+    int max_iter, int min_iter, double rel_tol, double rate_floor, double* __restrict__ out_rates,
+    int* __restrict__ out_iters, double* __restrict__ out_ll, int* __restrict__ out_flags) {
+  extern __shared__ double smem[];
+  const size_t b = blockIdx.x;
+  fit_replicate<WAVES, KOWN>(smem, R, E, kinds, age_begin, age_end, weights + b * R, epochs, init_rates, max_iter, min_iter,
+                             rel_tol, rate_floor, out_rates + b * E, out_iters + b, out_ll + b, out_flags + b);
+}
+
+// colate_interval_fit_groups: workgroup i is replicate i % B of group i / B, whose rows, weights, epochs and starting
+// rates it finds through the group's descriptor.  A group without rows is left to the host (its rates are its starting
+// rates): its workgroups return here, on a value all their threads read alike, before any barrier.
+template <int WAVES, int KOWN>
+__global__ __launch_bounds__(WAVES * 64) void em_interval_fit_groups_kernel(
+    int B, int E, const ColateIntervalGroup* __restrict__ groups, int max_iter, int min_iter, double rel_tol,
+    double rate_floor, double* __restrict__ out_rates, int* __restrict__ out_iters, double* __restrict__ out_ll,
+    int* __restrict__ out_flags) {
+  extern __shared__ double smem[];
+  const size_t i = blockIdx.x;
+  const ColateIntervalGroup g = groups[i / B];
+  if (g.R < 1) return;
+  const size_t b = i % B;
+  fit_replicate<WAVES, KOWN>(smem, g.R, E, g.kinds, g.age_begin, g.age_end, g.W + b * g.R, g.epochs, g.init_rates, max_iter,
+                             min_iter, rel_tol, rate_floor, out_rates + i * E, out_iters + i, out_ll + i, out_flags + i);
 }
 
 constexpr size_t fit_lds_bytes(int E, int waves) { return (lds_doubles(E, waves) + 2) * sizeof(double); }
@@ -174,6 +208,22 @@ hipError_t colate_em_interval_fit_launch(int B, int R, int E, const int* kinds, 
     em_interval_fit_kernel<1, 16><<<B, 64, fit_lds_bytes(E, 1), stream>>>(
         R, E, kinds, age_begin, age_end, weights, epochs, init_rates, max_iter, min_iter, rel_tol, rate_floor, out_rates,
         out_iters, out_ll, out_flags);
+  }
+  return hipGetLastError();
+}
+
+hipError_t colate_em_interval_fit_groups_launch(int G, int B, int E, const ColateIntervalGroup* groups, int max_iter,
+                                                int min_iter, double rel_tol, double rate_floor, double* out_rates,
+                                                int* out_iters, double* out_ll, int* out_flags, hipStream_t stream) {
+  if (G < 1 || B < 1 || (long long)G * B > 0x7fffffffLL || E < 1 || E > COLATE_EM_MAX_E) return hipErrorInvalidValue;
+  const unsigned grid = (unsigned)((long long)G * B);
+  if (E <= 256) {  // (the two instantiations and their LDS: colate_em_interval_fit_launch)
+    constexpr int W = COLATE_EM_INTERVAL_FIT_WAVES;
+    em_interval_fit_groups_kernel<W, 1><<<grid, W * 64, fit_lds_bytes(E, W), stream>>>(
+        B, E, groups, max_iter, min_iter, rel_tol, rate_floor, out_rates, out_iters, out_ll, out_flags);
+  } else {
+    em_interval_fit_groups_kernel<1, 16><<<grid, 64, fit_lds_bytes(E, 1), stream>>>(
+        B, E, groups, max_iter, min_iter, rel_tol, rate_floor, out_rates, out_iters, out_ll, out_flags);
   }
   return hipGetLastError();
 }

@@ -85,3 +85,40 @@ hipError_t colate_em_interval_fit_launch(int B, int R, int E, const int* kinds, 
                                          const double* init_rates, int max_iter, int min_iter, double rel_tol,
                                          double rate_floor, double* out_rates, int* out_iters, double* out_ll,
                                          int* out_flags, hipStream_t stream);
+
+// ---- colate_interval_fit_groups: many groups' cells, rows and fits in one pass (all device pointers) ----
+// What a workgroup of the grouped fit reads about its group: the group's R rows, W[B][R], epochs[E] and starting rates[E].
+struct ColateIntervalGroup {
+  int R;
+  const int* kinds;
+  const double *age_begin, *age_end;
+  const double* W;
+  const double *epochs, *init_rates;
+};
+// colate_em_interval_fit_launch for G groups x B replicates in one launch: workgroup i is replicate i % B of group
+// i / B and writes row i of the four outputs.  A group with R < 1 runs no loop and writes nothing (the caller fills in).
+hipError_t colate_em_interval_fit_groups_launch(int G, int B, int E, const ColateIntervalGroup* groups, int max_iter,
+                                                int min_iter, double rel_tol, double rate_floor, double* out_rates,
+                                                int* out_iters, double* out_ll, int* out_flags, hipStream_t stream);
+
+// The rows of a group picked on the device (interval_rows_kernel.hip).  cells: the dense sums of
+// colate_interval_cells_launch for the chunk's segments, [segments][2][17205]; group j of the chunk owns the segments
+// [seg_off[j], seg_off[j + 1]) and has room for row_cap[j] rows from row_off[j] on in cell_of_row / kinds / age_begin /
+// age_end.  flags: scratch, [groups][2 * 17205] bytes.  Out: the group's rows in row order (kind, bb, be) -- the cell
+// index kind * 17205 + be * (be + 1) / 2 + bb, the kind and the two ages from age_grid[185] --, R[j], and dropped[j] = the
+// sum of seg_dropped over the group's segments.
+hipError_t colate_interval_rows_launch(int groups, const double* cells, const int* seg_off, const unsigned long long* seg_dropped,
+                                       const double* age_grid, const long long* row_off, const int* row_cap,
+                                       unsigned char* flags, int* cell_of_row, int* kinds, double* age_begin, double* age_end,
+                                       int* R, long long* dropped, hipStream_t stream);
+
+// bootstrap_rows_kernel for the groups of a chunk, reading the dense sums through the groups' row lists:
+// W_j[b][r] = sum_k block_weights_j[b][k] * cells[seg0 + k][cell_of_row[r]], k ascending from 0.0, multiply and add apart.
+struct ColateIntervalRowsJob {
+  int seg0, nb, R;
+  const int* cell_of_row;       // [R]
+  const double* block_weights;  // [B][nb]
+  double* W;                    // [B][R]
+};
+hipError_t colate_bootstrap_rows_groups_launch(int groups, int B, int max_R, const ColateIntervalRowsJob* jobs,
+                                               const double* cells, hipStream_t stream);

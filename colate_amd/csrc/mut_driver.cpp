@@ -137,6 +137,8 @@ void print_help() {
             << "                             line may carry, in any order and mixed with the ages, target_mask=PREFIX,\n"
             << "                             reference_mask=PREFIX (expanded as --target_mask / --reference_mask are) and\n"
             << "                             coal=FILE (the pair's --coal warm start; --bins is then not needed for that line).\n"
+            << "                             (--mode mut_interval) --pairs FILE with --mut [--chr, --bins]: the same lines without ages;\n"
+            << "                             every pair's interval-dated fit in one pass, each <output>.coal that of its single run.\n"
             << "      --counts_out arg       Optional (colate_amd): write the bootstrap count tables (.colate_mat layout).\n"
             << "      --counts_only          Optional (colate_amd): stop after --counts_out (no GPU needed).\n"
             << "      --write_colate_mat     Optional (colate_amd): write <output>.colate_mat as the reference does for BCF/BAM inputs.\n"
@@ -745,11 +747,9 @@ void report_replicates(int pair, int B, int E, const int* iters, const int* flag
               << std::endl;
 }
 
-// "target reference output [target_age [reference_age]]" per line; after the three names, `key=value` tokens in any order and
-// mixed with the ages: target_mask=PREFIX, reference_mask=PREFIX (expanded as the single-pair CLI expands --target_mask /
-// --reference_mask: with --chr PREFIX_chr<name>.fa per chromosome, else PREFIX itself) and coal=FILE (the pair's warm start).
-// A token with '=' is a key, any other the next age.  An unknown, repeated or empty key, a third age or an age that is no
-// number is an error naming the file and the line.  A line of fewer than three tokens is skipped.
+}  // namespace
+
+// (mut_feeder.h)
 bool read_pair_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names, std::vector<PairSpec>& pairs) {
   std::ifstream is(path);
   if (!is) {
@@ -792,6 +792,7 @@ bool read_pair_list(const std::string& path, const Options& opt, const std::vect
       else if (key == "reference_mask") ps.ref_masks = mask_files(opt, chr_names, value);
       else ps.coal = value;
     }
+    ps.line = line_no, ps.ages_given = n_ages;
     pairs.push_back(ps);
   }
   if (pairs.empty()) {
@@ -800,8 +801,6 @@ bool read_pair_list(const std::string& path, const Options& opt, const std::vect
   }
   return true;
 }
-
-}  // namespace
 
 int run_mut(const Options& opt) {
   if (!opt.has("mut") || !opt.has("output")) {  // coal.cpp:3077-3087

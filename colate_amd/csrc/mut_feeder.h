@@ -182,6 +182,8 @@ struct PairSpec {
   double target_age = 0, ref_age = 0;
   std::vector<std::string> target_masks, ref_masks;  // one fasta per chromosome, or none
   std::string coal;                                   // --pairs `coal=FILE`: the pair's epochs and starting rates ("": --bins)
+  size_t line = 0;                                    // --pairs: the line of the list (1-based), and how many ages it carried
+  int ages_given = 0;
 };
 
 // coal.cpp:2071-2321 for one (target, reference) pair, on the calling thread in the reference's order: the sequential feeder.
@@ -217,5 +219,25 @@ bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const
 // as fill_pairs numbers them; nb: the number of genome blocks.  Nothing is drawn.  False after an error message.
 bool collect_interval_records(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const PairSpec& pair,
                               std::vector<colate_interval_rec>& recs, std::vector<int>& blocks, int& nb);
+// The same for a list of pairs (`--mode mut_interval --pairs`): every .mut file, .colate.in file and mask is read and decoded
+// once (the inputs of fill_pairs), the pairs are walked on the pool, and out[p] holds pair p's records and blocks in its
+// walk's order -- what collect_interval_records gives for that pair alone, which is this function on a list of one.
+// walked: false where the pair's walk did not finish.  False after an error message.
+struct PairRecords {
+  std::vector<colate_interval_rec> recs;
+  std::vector<int> blocks;
+  int nb = 0;
+  bool walked = false;
+};
+bool collect_interval_records_pairs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                                    const std::vector<PairSpec>& pairs, std::vector<PairRecords>& out);
+
+// mut_driver.cpp: the list of `--pairs`.  "target reference output [target_age [reference_age]]" per line; after the three
+// names, `key=value` tokens in any order and mixed with the ages: target_mask=PREFIX, reference_mask=PREFIX (expanded as the
+// single-pair CLI expands --target_mask / --reference_mask: with --chr PREFIX_chr<name>.fa per chromosome, else PREFIX itself)
+// and coal=FILE (the pair's warm start).  A token with '=' is a key, any other the next age.  An unknown, repeated or empty key,
+// a third age or an age that is no number is an error naming the file and the line.  A line of fewer than three tokens is
+// skipped.  PairSpec::line / ages_given: the pair's line in the file and how many age tokens it carried.
+bool read_pair_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names, std::vector<PairSpec>& pairs);
 
 }  // namespace colate_drv

@@ -8,6 +8,7 @@
 // The rows come from a file (--rows: how a line becomes a mutation's (kind, age_begin, age_end) is the caller's business),
 // or from the inputs of `--mode mut` (--mut, --target_tmp, --reference_tmp): every SNP the pair uses, snapped to the age
 // grid, is one observation of each kind (interval_cells.h), formed on the device by colate_interval_cells.
+// With --pairs LIST the second form runs for every line of the list in one pass (colate_interval_fit_groups).
 #include <unistd.h>
 
 #include <algorithm>
@@ -190,7 +191,186 @@ static bool write_interval_rows(const std::string& path, const IntervalRows& row
   return std::fclose(f) == 0;
 }
 
+// `--mode mut_interval --pairs LIST`: the single run above for every line of the list, in one pass.  Every input file is read
+// once and the pairs are walked on the pool (collect_interval_records_pairs); the pairs with the same number of epochs, in
+// order of first appearance, go through one colate_interval_fit_groups call -- cells, rows, block bootstrap and fit of all of
+// them on the device, or the host twin after a line on stderr.  Every pair draws its block weights from a generator of its
+// own on the run's seed, as its single run does, so OUTPUT.coal is that run's, byte for byte.
+static int run_mut_interval_pairs(const Options& opt) {
+  for (const char* o : {"target_tmp", "reference_tmp", "rows", "write_rows", "output", "ranks", "target_age", "reference_age"})
+    if (opt.has(o)) {
+      std::cerr << "Error: --" << o << " cannot be combined with --mode mut_interval --pairs." << std::endl;
+      return 1;
+    }
+  for (const char* o : {"target_mask", "reference_mask", "coal"})
+    if (opt.has(o)) {  // (the wording of `--mode mut --pairs`)
+      std::cerr << "Error: --" << o << " cannot be combined with --pairs (give it per line: " << o << "=...)." << std::endl;
+      return 1;
+    }
+  if (!opt.has("mut")) {
+    std::cerr << "Error: --pairs needs --mut (and optionally --chr, --bins, --num_bootstraps, --seed, --years_per_gen, --max_iter, "
+                 "--min_iter, --device)."
+              << std::endl;
+    return 1;
+  }
+  std::vector<std::string> names, mut_files;
+  chromosome_files(opt, names, mut_files);
+  std::vector<PairSpec> pairs;
+  if (!read_pair_list(opt.get("pairs"), opt, names, pairs)) return 1;
+  for (const PairSpec& ps : pairs)
+    if (ps.ages_given) {
+      std::cerr << "Error: " << opt.get("pairs") << ", line " << ps.line
+                << ": --mode mut_interval takes modern samples only: a line cannot carry sample ages." << std::endl;
+      return 1;
+    }
+  if (!opt.has("bins"))
+    for (size_t p = 0; p < pairs.size(); p++)
+      if (pairs[p].coal.empty()) {  // (a line with coal= takes its epochs from that file)
+        std::cerr << "Error: --pairs needs --bins for pair " << p + 1 << " (it names no coal= file)." << std::endl;
+        return 1;
+      }
+  const size_t P = pairs.size();
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating coalescence rates from interval-dated mutations for " << P << " pairs.." << std::endl;
+  double years_per_gen = 28.0;
+  int B = 1, max_iter = COLATE_DEFAULT_MAX_ITER, min_iter = COLATE_DEFAULT_MIN_ITER;
+  int seed = std::time(0) + getpid();  // coal.cpp:3158; one seed for the whole run
+  if (opt.has("years_per_gen")) years_per_gen = std::stof(opt.get("years_per_gen"));
+  if (opt.has("seed")) seed = std::stoi(opt.get("seed"));
+  if (opt.has("num_bootstraps")) B = std::stoi(opt.get("num_bootstraps"));
+  if (opt.has("max_iter")) max_iter = std::stoi(opt.get("max_iter"));
+  if (opt.has("min_iter")) min_iter = std::stoi(opt.get("min_iter"));
+  if (B < 1) {
+    std::cerr << "Error: --num_bootstraps must be at least 1." << std::endl;
+    return 1;
+  }
+  auto api_error = [](int rc) {
+    std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
+    return 1;
+  };
+
+  // ---- epochs and starting rates per pair, as the single run forms them
+  std::vector<std::vector<double>> epochs(P), init(P);
+  std::vector<int> ep_null(P, 0);
+  for (size_t p = 0; p < P; p++) {
+    epochs[p].assign(COLATE_MAX_EPOCHS, 0.0), init[p].assign(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
+    const int E = !pairs[p].coal.empty()
+                      ? colate_epochs_from_coal(pairs[p].coal.c_str(), 0.0, epochs[p].data(), init[p].data(), COLATE_MAX_EPOCHS)
+                      : colate_epochs_from_bins(opt.get("bins").c_str(), 0.0, years_per_gen, epochs[p].data(), COLATE_MAX_EPOCHS, &ep_null[p]);
+    if (E <= 0) {
+      std::cerr << "Error: pair " << p + 1 << ": " << colate_last_error() << std::endl;
+      return 1;
+    }
+    epochs[p].resize(E), init[p].resize(E);
+  }
+
+  // ---- device or host twin
+  std::string host_why;
+  if (const char* e = std::getenv("COLATE_DEVICE_INTERVAL"))
+    if (std::string(e) == "0") host_why = "COLATE_DEVICE_INTERVAL=0";
+  if (host_why.empty() && colate_device_count() <= 0) host_why = "no device";
+  if (host_why.empty() && opt.has("device"))
+    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc);
+
+  // ---- the records of all pairs
+  const double t_start = StageTimes::now();
+  std::vector<PairRecords> recs;
+  if (!collect_interval_records_pairs(names, mut_files, pairs, recs)) return 1;
+  const double t_fit = StageTimes::now();
+  double kernel_s = 0.0;
+  int status = 0;
+  std::vector<char> usable(P, 1);
+  for (size_t p = 0; p < P; p++) {
+    std::cerr << "Pair " << p + 1 << " / " << P << ": " << pairs[p].target << " x " << pairs[p].reference << ": Number of blocks: " << recs[p].nb
+              << std::endl;
+    if (!recs[p].walked || recs[p].nb < 1) {
+      std::cerr << "Error: pair " << p + 1 << " (" << pairs[p].target << " x " << pairs[p].reference << "): "
+                << (recs[p].walked ? "no genome block (no chromosome was read)." : "the SNPs of the pair could not be walked.") << std::endl;
+      usable[p] = 0, status = 1;
+    }
+  }
+
+  // ---- classes of pairs with the same number of epochs, in order of first appearance: one grouped call each
+  std::vector<std::vector<size_t>> classes;
+  for (size_t p = 0; p < P; p++) {
+    if (!usable[p]) continue;
+    size_t c = 0;
+    while (c < classes.size() && epochs[classes[c][0]].size() != epochs[p].size()) c++;
+    if (c == classes.size()) classes.emplace_back();
+    classes[c].push_back(p);
+  }
+  std::cerr << "Maximising likelihood using EM.. " << std::endl;
+  if (!host_why.empty()) std::cerr << "interval cells and fits on the host (" << host_why << ")" << std::endl;
+  for (const std::vector<size_t>& cls : classes) {
+    const int G = (int)cls.size(), E = (int)epochs[cls[0]].size();
+    std::vector<long long> rec_off(1, 0);
+    std::vector<int> nb;
+    std::vector<double> weights, g_ep, g_init;
+    for (size_t p : cls) {
+      rec_off.push_back(rec_off.back() + (long long)recs[p].recs.size());
+      nb.push_back(recs[p].nb);
+      std::mt19937 rng(seed);  // (coal.cpp:3350-3357: every pair from the run's seed, as its single run)
+      const size_t at = weights.size();
+      weights.resize(at + (size_t)B * recs[p].nb);
+      if (int rc = colate_bootstrap_weights(&rng, B, recs[p].nb, weights.data() + at)) return api_error(rc);
+      g_ep.insert(g_ep.end(), epochs[p].begin(), epochs[p].end());
+      g_init.insert(g_init.end(), init[p].begin(), init[p].end());
+    }
+    std::vector<colate_interval_rec> all_recs((size_t)rec_off.back());
+    std::vector<int> all_blocks((size_t)rec_off.back());
+    for (int g = 0; g < G; g++) {
+      PairRecords& pr = recs[cls[(size_t)g]];
+      std::copy(pr.recs.begin(), pr.recs.end(), all_recs.begin() + rec_off[(size_t)g]);
+      std::copy(pr.blocks.begin(), pr.blocks.end(), all_blocks.begin() + rec_off[(size_t)g]);
+      pr = PairRecords();  // (the pair's own copy is no longer needed)
+    }
+    const size_t GB = (size_t)G * B;
+    std::vector<int> R(G), iters(GB), flags(GB);
+    std::vector<long long> dropped(G);
+    std::vector<double> rates(GB * E), ll(GB);
+    const int rc = host_why.empty()
+                       ? colate_interval_fit_groups(G, B, E, rec_off.data(), all_recs.data(), all_blocks.data(), nb.data(), weights.data(),
+                                                    g_ep.data(), g_init.data(), max_iter, min_iter, COLATE_DEFAULT_REL_TOL,
+                                                    COLATE_DEFAULT_RATE_FLOOR, R.data(), dropped.data(), rates.data(), iters.data(),
+                                                    ll.data(), flags.data())
+                       : colate_interval_fit_groups_host(G, B, E, rec_off.data(), all_recs.data(), all_blocks.data(), nb.data(),
+                                                         weights.data(), g_ep.data(), g_init.data(), max_iter, min_iter,
+                                                         COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, R.data(), dropped.data(),
+                                                         rates.data(), iters.data(), ll.data(), flags.data(), 1);
+    if (rc) return api_error(rc);
+    if (host_why.empty()) kernel_s += colate_interval_fit_groups_kernel_seconds();
+    for (int g = 0; g < G; g++) {
+      const size_t p = cls[(size_t)g];
+      const std::string lead = "Pair " + std::to_string(p + 1) + " ";
+      std::cerr << lead << "Number of rows: " << R[g] << std::endl;
+      std::cerr << lead << "SNPs beyond the age grid: " << dropped[g] << std::endl;
+      if (R[g] == 0) {
+        std::cerr << "Error: pair " << p + 1 << " (" << pairs[p].target << " x " << pairs[p].reference
+                  << ") uses no SNP within the age grid; " << pairs[p].output << ".coal is not written." << std::endl;
+        status = 1;
+        continue;
+      }
+      for (int i = 0; i < B; i++) {
+        std::cerr << lead << "Bootstrap " << i + 1 << ": Total iterations " << iters[(size_t)g * B + i] << std::endl;
+        if (flags[(size_t)g * B + i] & (COLATE_FLAG_NAN | COLATE_FLAG_NEG))
+          std::cerr << "Warning: pair " << p + 1 << " bootstrap " << i + 1 << " produced NaN or negative sufficient statistics." << std::endl;
+      }
+      if (colate_write_coal((pairs[p].output + ".coal").c_str(), B, E, epochs[p].data(), rates.data() + (size_t)g * B * E, 0, ep_null[p])) {
+        std::cerr << "Error: " << colate_last_error() << std::endl;
+        status = 1;
+      }
+    }
+  }
+  if (g_times.on)
+    std::cerr << "Timing: interval pairs: inputs and walks " << t_fit - t_start << " s, cells, rows and fits " << StageTimes::now() - t_fit
+              << " s (device kernels " << kernel_s << " s)" << std::endl;
+  if (status) return status;
+  print_usage_footer();
+  return 0;
+}
+
 int run_mut_interval(const Options& opt) {
+  if (opt.has("pairs")) return run_mut_interval_pairs(opt);
   const bool from_mut = opt.has("mut") || opt.has("target_tmp") || opt.has("reference_tmp");
   if (from_mut && opt.has("rows")) {
     std::cerr << "Error: --rows cannot be combined with --mut, --target_tmp or --reference_tmp." << std::endl;
@@ -198,10 +378,6 @@ int run_mut_interval(const Options& opt) {
   }
   if (from_mut && (opt.has("target_age") || opt.has("reference_age"))) {
     std::cerr << "Error: --mode mut_interval takes modern samples only: --target_age and --reference_age are not supported." << std::endl;
-    return 1;
-  }
-  if (from_mut && opt.has("pairs")) {
-    std::cerr << "Error: --mode mut_interval does not take --pairs." << std::endl;
     return 1;
   }
   const bool inputs_ok = from_mut ? opt.has("mut") && opt.has("target_tmp") && opt.has("reference_tmp") : opt.has("rows");

@@ -1,6 +1,6 @@
 // colate_amd/csrc/mut_interval.h -- `Colate --mode mut_interval`: the rows file of interval-dated observations per genome
 // block -- or the SNPs a pair uses, through colate_interval_cells -- and the driver around colate_bootstrap_em_interval_batch
-// (mut_interval.cpp).
+// (mut_interval.cpp); with --pairs, the driver around colate_interval_fit_groups.
 #pragma once
 #include <string>
 #include <vector>

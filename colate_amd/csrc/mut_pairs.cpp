@@ -1593,24 +1593,45 @@ bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const
 }
 
 // (mut_feeder.h)
-bool collect_interval_records(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const PairSpec& pair,
-                              std::vector<colate_ic::IntervalRec>& recs, std::vector<int>& blocks, int& nb) {
+bool collect_interval_records_pairs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                                    const std::vector<PairSpec>& pairs, std::vector<PairRecords>& out) {
   const double t0 = now_s();
-  recs.clear(), blocks.clear();
+  out.assign(pairs.size(), PairRecords());
+  if (pairs.empty()) return true;
   Pool pool(pairs_threads());
-  const std::vector<PairSpec> pairs(1, pair);
-  const std::vector<size_t> todo(1, 0);
+  std::vector<size_t> todo(pairs.size());
+  for (size_t p = 0; p < todo.size(); p++) todo[p] = p;
   const char* e_idx = std::getenv("COLATE_INDEXED_WALK");
   const Inputs in = load_inputs(pool, names, mut_files, pairs, todo, !(e_idx && std::atoi(e_idx) == 0));
   Fills fills = open_pairs(in, pairs, todo);
   const double t1 = now_s();
-  Engine eng{names, in.rows, 0, 10.0, (int)30e6, nullptr, nullptr, pool, nullptr, nullptr, nullptr, &recs, &blocks};
-  PairFill& pf = *fills[0];
-  eng.walk(pf, std::numeric_limits<uint64_t>::max());  // (on this thread: one pair, and the order of the records is the walk's)
-  nb = pf.num_blocks;
+  // one walk per pair on the pool; a walk is sequential, so a pair's records are in the walk's order whatever the pool does
+  std::vector<Engine> engines;
+  engines.reserve(pairs.size());
+  for (size_t p = 0; p < pairs.size(); p++) {
+    engines.push_back(Engine{names, in.rows, 0, 10.0, (int)30e6, nullptr, nullptr, pool, nullptr, nullptr, nullptr, &out[p].recs, &out[p].blocks});
+    const Engine* eng = &engines.back();
+    PairFill* pf = fills[p].get();
+    pool.submit([eng, pf] { eng->walk(*pf, std::numeric_limits<uint64_t>::max()); });
+  }
+  pool.wait_idle();
+  for (size_t p = 0; p < pairs.size(); p++) {
+    out[p].nb = fills[p]->num_blocks;
+    out[p].walked = fills[p]->walked && !fills[p]->redo.load();
+  }
   g_times.parse_mut = t1 - t0;
   g_times.table_fill = now_s() - t1;
-  return pf.walked && !pf.redo.load();
+  return true;
+}
+
+bool collect_interval_records(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const PairSpec& pair,
+                              std::vector<colate_ic::IntervalRec>& recs, std::vector<int>& blocks, int& nb) {
+  std::vector<PairRecords> out;
+  recs.clear(), blocks.clear();
+  if (!collect_interval_records_pairs(names, mut_files, std::vector<PairSpec>(1, pair), out)) return false;
+  recs.swap(out[0].recs), blocks.swap(out[0].blocks);
+  nb = out[0].nb;
+  return out[0].walked;
 }
 
 }  // namespace colate_drv

@@ -54,6 +54,12 @@ int colate_bootstrap_em_interval_batch(int, int, int, int, const int*, const dou
 int colate_interval_cells(long long, const colate_interval_rec*, const int*, int, int, int*, double*, double*, double*, long long*) {
   return nodev();
 }
+int colate_interval_fit_groups(int, int, int, const long long*, const colate_interval_rec*, const int*, const int*, const double*,
+                               const double*, const double*, int, int, double, double, int*, long long*, double*, int*, double*,
+                               int*) {
+  return nodev();
+}
+double colate_interval_fit_groups_kernel_seconds(void) { return 0.0; }
 int colate_shard_bounds(int B, int nranks, int rank, int* lo, int* hi) {
   const int base = B / nranks, rem = B % nranks;
   *lo = rank * base + (rank < rem ? rank : rem);

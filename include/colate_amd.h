@@ -18,7 +18,8 @@
  * of it: per-block row tables and block weights in, rates out (the weighted
  * block sums run from 0.0 over the blocks in ascending order, multiply and add
  * apart; its speed has not been measured).  `Colate --mode mut_interval` is the
- * command line of the last one.
+ * command line of the last one; colate_interval_fit_groups does it for many pairs
+ * of samples in one pass, from their used SNPs to their rates.
  * INTEGRATION.md shows the patch a maintainer would apply to coal.cpp.
  *
  * Conventions: plain pointers and sizes, row-major, IEEE double; caller owns
@@ -288,6 +289,49 @@ int colate_interval_cells_host(long long n, const colate_interval_rec* recs, con
                                int* kinds, double* age_begin, double* age_end, double* tables, long long* dropped);
 int colate_interval_cells_tile(void);
 
+/* ---- many groups' cells, rows and fits in one pass ----
+ * colate_interval_fit_groups is, for each of G groups (a group: the used SNPs of one pair of samples),
+ * colate_interval_cells on the group's records followed by colate_bootstrap_em_interval_batch on the rows and tables of
+ * that call, with the group's block weights, epochs and starting rates -- in one call, without the dense cell sums or W
+ * ever reaching the host.  Group g owns the records [rec_off[g], rec_off[g + 1]) of recs / block; block[i] is the genome
+ * block of record i within its group, in [0, nb[g]), not decreasing within the group; block_weights holds the groups'
+ * [B][nb[g]] arrays one after the other; epochs and init_rates are [G][E].
+ * Contract, for every group g: out_R[g] and out_dropped[g] are what colate_interval_cells returns on the group's records;
+ * out_rates[g][B][E], out_iters / out_loglik / out_flags[g][B] are, in every bit, what
+ * colate_bootstrap_em_interval_batch returns on the rows and tables of that cells call -- the summation contracts above
+ * are unchanged: cells from 0.0 in record order, W[b][r] from 0.0 over the blocks ascending with every product rounded and
+ * then added, and the fit visits the rows with a positive weight in ascending r (kind, bb, be).  A group with no row
+ * (out_R[g] = 0: no records, or all beyond the grid or without weight) keeps its starting rates; its iters, loglik and
+ * flags are 0.
+ * On the device (COLATE_ENODEVICE without one, there is no fall-back), all on one stream: the groups pass through the
+ * cells kernels (csrc/interval_cells_kernel.hip, segments = (group, block)), the row pick (csrc/interval_rows_kernel.hip:
+ * a flag per cell, then the rank of every flagged cell in row order by an integer scan) and the grouped row bootstrap
+ * (csrc/bootstrap_kernel.hip, reading the dense sums through the row lists) in chunks -- runs of consecutive groups whose
+ * dense sums (275 KB per segment) fit COLATE_INTERVAL_GROUPS_CELLS_MB_DEFAULT megabytes, or what the environment
+ * variable COLATE_INTERVAL_GROUPS_CELLS_MB says; a larger group goes alone.  Per chunk the host waits once, for the
+ * chunk's R and dropped counts, which size its W.  Then one launch of G x B persistent workgroups fits all groups
+ * (csrc/em_interval_fit_kernel.hip: workgroup i is replicate i % B of group i / B; the body is that of
+ * colate_em_interval_batch).  The chunking changes no bit.
+ * _host: the host twin, group by group through colate_interval_cells_host and colate_bootstrap_em_interval_batch_host
+ * (math as there; math = 1 is bit for bit the device).
+ * Refused (COLATE_EINVAL, before anything is staged; the outputs are not touched; the message names the group): G < 1,
+ * B < 1, a decreasing rec_off, and per group whatever the two calls refuse.  COLATE_ELIMIT: E above 1024, nb[g] above
+ * COLATE_INTERVAL_MAX_BLOCKS, G x B at or above 2^31, B above 65535.
+ * Speed: not measured on a device yet (tools/interval_pairs_bench.py is the measurement). */
+#define COLATE_INTERVAL_GROUPS_CELLS_MB_DEFAULT 1024
+int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, const colate_interval_rec* recs, const int* block,
+                               const int* nb, const double* block_weights, const double* epochs, const double* init_rates,
+                               int max_iter, int min_iter, double rel_tol, double rate_floor, int* out_R, long long* out_dropped,
+                               double* out_rates, int* out_iters, double* out_loglik, int* out_flags);
+/* Diagnostic: the seconds the kernels of the calling thread's last colate_interval_fit_groups took on the device (hip events
+ * around the cells and row-pick kernels and the row bootstrap of every chunk, and around the fit; copies and waits excluded). */
+double colate_interval_fit_groups_kernel_seconds(void);
+int colate_interval_fit_groups_host(int G, int B, int E, const long long* rec_off, const colate_interval_rec* recs,
+                                    const int* block, const int* nb, const double* block_weights, const double* epochs,
+                                    const double* init_rates, int max_iter, int min_iter, double rel_tol, double rate_floor,
+                                    int* out_R, long long* out_dropped, double* out_rates, int* out_iters, double* out_loglik,
+                                    int* out_flags, int math);
+
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
 int colate_age_grid(double* age_grid, int cap);
@@ -519,11 +563,22 @@ int colate_coalrate_main(int argc, char** argv);
  * malformed line is an error that names its line number; nothing is written then.
  * `--mode mut_interval --mut P --target_tmp T --reference_tmp R [--chr FILE] [--target_mask PREFIX] [--reference_mask PREFIX]
  * [--write_rows FILE]` with the same fit options takes the inputs of `--mode mut` instead of --rows (both together: an
- * error; --target_age / --reference_age and --pairs are refused): the SNPs `--mode mut` uses become the rows and tables
+ * error; --target_age / --reference_age are refused): the SNPs `--mode mut` uses become the rows and tables
  * through colate_interval_cells (the host twin without a device or with COLATE_DEVICE_INTERVAL=0, after a line on stderr;
  * same bytes), stderr shows `Number of blocks`, `Number of rows` and `SNPs beyond the age grid`, and --write_rows writes
  * them in the --rows format (17 significant digits; a block without a positive cell keeps a line of weight 0), from which
- * --rows gives the same OUT.coal. */
+ * --rows gives the same OUT.coal.
+ * `--mode mut_interval --pairs LIST --mut P [--chr FILE] (--bins x,y,s and/or coal= per line)` with the same fit options is that
+ * run for every line `target.colate.in reference.colate.in output [target_mask=PREFIX] [reference_mask=PREFIX] [coal=FILE]`
+ * of LIST in one pass: every input file is read once, and the pairs with the same number of epochs, in order of first
+ * appearance, go through one colate_interval_fit_groups call (its host twin without a device or with
+ * COLATE_DEVICE_INTERVAL=0, after a line on stderr; same bytes).  Every pair draws its block weights from a std::mt19937 of its
+ * own on the run's seed, so OUTPUT.coal is, byte for byte, the single run's with the same options, masks, warm start and
+ * --seed.  An age token on a line is an error naming the line; --target_tmp, --reference_tmp, --rows, --write_rows, --output,
+ * --target_mask, --reference_mask, --coal, --ranks, --target_age and --reference_age are refused by name; a line without coal=
+ * needs --bins.  stderr: per pair `Pair i / P: T x R: Number of blocks: n`, then `Pair i ` in front of the single run's
+ * `Number of rows`, `SNPs beyond the age grid` and `Bootstrap k: Total iterations` lines.  A pair that uses no SNP within the
+ * age grid gets no file and an error line naming it; the others are written and the exit code is 1. */
 int colate_mut_main(int argc, char** argv);
 
 #ifdef __cplusplus
