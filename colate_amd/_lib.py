@@ -76,6 +76,18 @@ SIGNATURES = {
     "colate_interval_fit_groups_host": (c_int, [c_int] * 3 + [c_void_p] * 7 + [c_int, c_int, c_double, c_double] + [c_void_p] * 6
                                         + [c_int]),
     "colate_interval_fit_groups_kernel_seconds": (c_double, []),
+    "colate_interval_walk": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                     ctypes.c_longlong] + [c_void_p] * 4),
+    "colate_interval_walk_host": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                          ctypes.c_longlong] + [c_void_p] * 4),
+    "colate_interval_walk_tile": (c_int, []),
+    "colate_interval_fit_samples": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                            c_int, c_int, c_void_p, c_void_p, ctypes.c_uint, c_int, c_int, c_double, c_double]
+                                    + [c_void_p] * 8),
+    "colate_interval_fit_samples_host": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                 c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint, c_int, c_int, c_double,
+                                                 c_double] + [c_void_p] * 8 + [c_int]),
+    "colate_interval_fit_samples_kernel_seconds": (c_double, []),
     "colate_age_grid": (c_int, [c_void_p, c_int]),
     "colate_epochs_from_bins": (c_int, [c_char_p, c_double, c_double, c_void_p, c_int, ip]),
     "colate_epochs_from_coal": (c_int, [c_char_p, c_double, c_void_p, c_void_p, c_int]),

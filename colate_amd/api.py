@@ -473,6 +473,81 @@ def interval_fit_groups(groups, epochs, init_rates=None, max_iter=DEFAULT_MAX_IT
     return R, dropped, rates, iters, ll, flags
 
 
+WALK_ROW = np.dtype([("pos", np.int32), ("age_begin", np.float32), ("age_end", np.float32)])
+WALK_IDX = np.dtype([("prev_bp", np.int32), ("DAF", np.uint16), ("AAF", np.uint16)])
+WALK_PAIR = np.dtype([("target", np.int32), ("reference", np.int32), ("target_mask", np.int32), ("reference_mask", np.int32)])
+
+
+def interval_walk_tile():
+    """Rows of a chromosome a workgroup of the pair-walk kernel looks at per step (diagnostic; no device needed)."""
+    return lib.colate_interval_walk_tile()
+
+
+def _walk_inputs(row_off, rows, idx, masks, pairs):
+    row_off = np.ascontiguousarray(row_off, dtype=np.int64).ravel()
+    rows = np.ascontiguousarray(rows, dtype=WALK_ROW).ravel()
+    idx = np.ascontiguousarray(idx, dtype=WALK_IDX)
+    pairs = np.ascontiguousarray(pairs, dtype=WALK_PAIR).ravel()
+    masks = np.zeros((0, 0), dtype=np.uint64) if masks is None else np.ascontiguousarray(masks, dtype=np.uint64)
+    if idx.ndim != 2 or idx.shape[1] != rows.size:
+        raise ValueError("idx must be [S][rows]")
+    if masks.ndim != 2:
+        raise ValueError("masks must be [M][words]")
+    if row_off.size >= 2 and row_off[0] == 0 and (np.diff(row_off) >= 0).all():  # (else the library names what is wrong)
+        if row_off[-1] != rows.size:
+            raise ValueError("row_off[-1] must be the number of rows")
+        if masks.shape[0] and masks.shape[1] != int(((np.diff(row_off) + 63) // 64).sum()):
+            raise ValueError("a mask holds ceil(rows / 64) words per chromosome")
+    return [row_off.size - 1, _p(row_off), _p(rows), idx.shape[0], _p(idx), masks.shape[0], _p(masks), pairs.size, _p(pairs)], \
+        (row_off, rows, idx, masks, pairs)
+
+
+def interval_walk(row_off, rows, idx, masks, pairs, num_bases_per_block, device=True, cap=None):
+    """colate_interval_walk[_host]: the pair walk of `--mode mut_interval` for every pair of `pairs` over per-sample walk
+    indices.  row_off [C + 1]: the chromosomes' rows back to back in rows (WALK_ROW); idx [S][rows] (WALK_IDX); masks
+    [M][words] uint64 or None (one bit per row, each chromosome starting on a word); pairs (WALK_PAIR: sample ids, mask ids
+    or -1).  Returns (rec_off [P + 1], nb [P], recs (INTERVAL_REC), block): every pair's used SNPs and their genome blocks
+    back to back.  cap: the room given (default: every row of every pair).  device=False: the host twin, the same bytes."""
+    args, keep = _walk_inputs(row_off, rows, idx, masks, pairs)
+    P = keep[4].size
+    cap = P * keep[1].size if cap is None else int(cap)
+    rec_off, nb = np.zeros(P + 1, dtype=np.int64), np.zeros(P, dtype=np.int32)
+    recs, block = np.zeros(max(cap, 0), dtype=INTERVAL_REC), np.zeros(max(cap, 0), dtype=np.int32)
+    fn = lib.colate_interval_walk if device else lib.colate_interval_walk_host
+    check(fn(*args, int(num_bases_per_block), cap, _p(rec_off), _p(nb), _p(recs), _p(block)))
+    n = int(rec_off[-1])
+    return rec_off, nb, recs[:n].copy(), block[:n].copy()
+
+
+def interval_fit_samples(row_off, rows, idx, masks, pairs, num_bases_per_block, num_bootstrap, epochs, seed, init_rates=None,
+                         max_iter=DEFAULT_MAX_ITER, min_iter=DEFAULT_MIN_ITER, rel_tol=DEFAULT_REL_TOL,
+                         rate_floor=DEFAULT_RATE_FLOOR, device=True, math=1):
+    """colate_interval_fit_samples[_host]: interval_walk followed by interval_fit_groups on its records (group p = pair p),
+    the records never leaving the device; every pair's block weights [B][nb] are drawn by the call from a fresh mt19937 on
+    `seed` (bootstrap_weights).  epochs / init_rates: [E] for all pairs.  Returns (nb[P], used[P], R[P], dropped[P],
+    rates[P][B][E], iters[P][B], loglik[P][B], flags[P][B]).  device=False: the host twin (math as for em_interval_batch)."""
+    args, keep = _walk_inputs(row_off, rows, idx, masks, pairs)
+    P, B = keep[4].size, int(num_bootstrap)
+    ep = _f64(epochs).ravel()
+    E = ep.size
+    init = _f64(np.full(E, DEFAULT_INIT_RATE) if init_rates is None else init_rates).ravel()
+    if init.size != E:
+        raise ValueError("init_rates must be [E]")
+    Bn = max(B, 0)
+    nb, used = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int64)
+    R, dropped = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int64)
+    rates, iters, ll, flags = np.zeros((P, Bn, E)), np.zeros((P, Bn), dtype=np.int32), np.zeros((P, Bn)), np.zeros((P, Bn), dtype=np.int32)
+    full = args + [int(num_bases_per_block), B, E, _p(ep), _p(init), int(seed) & 0xffffffff, int(max_iter), int(min_iter),
+                   float(rel_tol), float(rate_floor), _p(nb), _p(used), _p(R), _p(dropped), _p(rates), _p(iters), _p(ll), _p(flags)]
+    check(lib.colate_interval_fit_samples(*full) if device else lib.colate_interval_fit_samples_host(*full, int(math)))
+    return nb, used, R, dropped, rates, iters, ll, flags
+
+
+def interval_fit_samples_kernel_seconds():
+    """Seconds the kernels of this thread's last interval_fit_samples(device=True) took on the device, the walk included."""
+    return lib.colate_interval_fit_samples_kernel_seconds()
+
+
 def _stream_ptr(stream):
     if stream is None:
         import torch

@@ -12,6 +12,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
+#include <limits>
 #include <memory>
 #include <string>
 #include <vector>
@@ -23,6 +25,7 @@
 #include "device_stage.hpp"
 #include "interval_cells.h"
 #include "interval_groups.h"
+#include "interval_walk.h"
 
 static_assert(COLATE_FLAG_NAN == 1 && COLATE_FLAG_NEG == 2 && COLATE_FLAG_MAXITER == 4 && COLATE_FLAG_UNRESOLVED == 8 &&
                   COLATE_UNRESOLVED_SHIFT == 8, "flags");
@@ -750,23 +753,59 @@ int colate_interval_cells(long long n, const colate_interval_rec* recs, const in
 static thread_local double g_interval_groups_kernel_s = 0.0;
 double colate_interval_fit_groups_kernel_seconds(void) { return g_interval_groups_kernel_s; }
 
-// Many groups' cells, rows and fits in one pass (include/colate_amd.h).  One stream; the groups go through the cells, the row
-// pick and the row bootstrap in chunks whose dense cell sums fit a budget, and the only thing the host waits for before the
-// results is each chunk's R and dropped counts, which size the chunk's W; then one launch fits all groups.
-int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, const colate_interval_rec* recs, const int* block,
-                               const int* nb, const double* block_weights, const double* epochs, const double* init_rates,
-                               int max_iter, int min_iter, double rel_tol, double rate_floor, int* out_R, long long* out_dropped,
-                               double* out_rates, int* out_iters, double* out_loglik, int* out_flags) {
+}  // extern "C"
+
+namespace {
+
+// Where the records of a chunk of groups come from: the caller's host arrays (colate_interval_fit_groups) or the write
+// pass of the pair walk (colate_interval_fit_samples).
+struct GroupRecords {
+  virtual ~GroupRecords() = default;
+  // the staging is kernels, to be timed with the chunk's other kernels (not copies)
+  virtual bool kernels() const = 0;
+  // On `stream`: the records of groups [g0, g1) at d_recs and, for the chunk's segments (group, block) in order, the nseg + 1
+  // record ranges at d_off (seg_off[j]: the first segment of group g0 + j; n: the chunk's records).
+  virtual int stage(int g0, int g1, const std::vector<int>& seg_off, long long n, colate_ic::IntervalRec* d_recs, long long* d_off,
+                    hipStream_t stream) = 0;
+};
+
+struct HostGroupRecords : GroupRecords {
+  const long long* rec_off;
+  const colate_interval_rec* recs;
+  const int *block, *nb;
+  std::deque<std::vector<long long>> offs;  // per chunk, alive until the call ends: its copy is asynchronous
+  HostGroupRecords(const long long* ro, const colate_interval_rec* r, const int* b, const int* n) : rec_off(ro), recs(r), block(b), nb(n) {}
+  bool kernels() const override { return false; }
+  int stage(int g0, int g1, const std::vector<int>&, long long n, colate_ic::IntervalRec* d_recs, long long* d_off,
+            hipStream_t stream) override {
+    using namespace colate_ic;
+    const long long r0 = rec_off[g0];
+    offs.emplace_back();
+    std::vector<long long>& coff = offs.back();
+    for (int g = g0; g < g1; g++) {
+      const long long ng_recs = rec_off[g + 1] - rec_off[g];
+      std::vector<long long> off((size_t)nb[g] + 1);
+      block_ranges(ng_recs, ng_recs ? block + rec_off[g] : nullptr, nb[g], off.data());
+      for (int k = 0; k < nb[g]; k++) coff.push_back(rec_off[g] - r0 + off[(size_t)k]);
+    }
+    coff.push_back(n);
+    if (n) HIP_TRY(hipMemcpyAsync(d_recs, recs + r0, sizeof(IntervalRec) * (size_t)n, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_off, coff.data(), sizeof(long long) * coff.size(), hipMemcpyHostToDevice, stream));
+    return COLATE_OK;
+  }
+};
+
+// Many groups' cells, rows and fits in one pass (include/colate_amd.h), after the checks.  One stream (the workspace's); the groups
+// go through the cells, the row pick and the row bootstrap in chunks whose dense cell sums fit a budget (and whose records fit
+// max_chunk_recs), and the only thing the host waits for before the results is each chunk's R and dropped counts, which size the
+// chunk's W; then one launch fits all groups.  epochs / init_rates: [G][E].  Adds the kernels' seconds to g_interval_groups_kernel_s.
+int fit_groups_core(int G, int B, int E, const long long* rec_off, const int* nb, const double* block_weights, const double* epochs,
+                    const double* init_rates, int max_iter, int min_iter, double rel_tol, double rate_floor, long long max_chunk_recs,
+                    GroupRecords& src, const float* T, int* out_R, long long* out_dropped, double* out_rates, int* out_iters,
+                    double* out_loglik, int* out_flags) {
   using namespace colate_ic;
-  float T[kBins];
-  if (int rc = build_thresholds(T)) return rc;
-  if (int rc = check_groups_args(G, B, E, rec_off, recs, block, nb, block_weights, epochs, init_rates, max_iter, min_iter, rel_tol,
-                                 rate_floor, T, out_R, out_dropped, out_rates, out_iters, out_loglik, out_flags))
-    return rc;
   double grid[COLATE_MAX_AGE_BINS];
   if (colate_age_grid(grid, COLATE_MAX_AGE_BINS) != kBins) return fail(COLATE_EINVAL, "the age grid has not %d points", kBins);
-  if (int rc = ensure_device()) return rc;
-  ProfRange range("colate_interval_fit_groups: per chunk H2D + cells + row pick + row bootstrap; one interval EM kernel + D2H");
 
   // ---- the chunks: runs of consecutive groups whose segments (group, block) fit the budget; a larger group goes alone
   constexpr size_t kSegBytes = sizeof(double) * 2 * kCells;
@@ -775,7 +814,6 @@ int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, co
   const size_t budget_segs = std::max<size_t>(1, (size_t)budget_mb * (1u << 20) / kSegBytes);
   struct Chunk {
     int g0 = 0, g1 = 0;  // groups [g0, g1)
-    std::vector<long long> off;  // per segment: its records within the chunk's
     std::vector<int> seg_off, cap;
     std::vector<long long> row_off;
     std::vector<int> R;
@@ -790,7 +828,7 @@ int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, co
     c.g0 = g;
     size_t segs = 0;
     do segs += (size_t)nb[g++];
-    while (g < G && g - c.g0 < 65535 && segs + (size_t)nb[g] <= budget_segs);
+    while (g < G && g - c.g0 < 65535 && segs + (size_t)nb[g] <= budget_segs && rec_off[g + 1] - rec_off[c.g0] <= max_chunk_recs);
     c.g1 = g;
     max_segs = std::max(max_segs, segs), max_groups = std::max(max_groups, (size_t)(c.g1 - c.g0));
     max_recs = std::max(max_recs, rec_off[c.g1] - rec_off[c.g0]);
@@ -817,7 +855,6 @@ int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, co
     }
   } events;
   const SyncAtExit sync_at_exit{stream};
-  g_interval_groups_kernel_s = 0.0;
   size_t bw_total = 0;
   std::vector<size_t> bw_off((size_t)G);
   for (int g = 0; g < G; g++) bw_off[(size_t)g] = bw_total, bw_total += (size_t)B * nb[g];
@@ -846,7 +883,7 @@ int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, co
   auto h2d = [stream](void* dst, const void* src, size_t bytes) {
     return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
   };
-  HIP_TRY(h2d(d_T, T, sizeof(T))); HIP_TRY(h2d(d_grid, grid, sizeof(double) * kBins));
+  HIP_TRY(h2d(d_T, T, sizeof(float) * kBins)); HIP_TRY(h2d(d_grid, grid, sizeof(double) * kBins));
   HIP_TRY(h2d(d_bw, block_weights, sizeof(double) * bw_total));
   HIP_TRY(h2d(d_ep, epochs, sizeof(double) * GE)); HIP_TRY(h2d(d_init, init_rates, sizeof(double) * GE));
 
@@ -856,31 +893,27 @@ int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, co
   bool any_rows = false;
   for (Chunk& c : chunks) {
     const int ng = c.g1 - c.g0;
-    const long long r0 = rec_off[c.g0], n = rec_off[c.g1] - r0;
-    c.seg_off.assign(1, 0), c.off.clear(), c.cap.resize((size_t)ng), c.row_off.resize((size_t)ng);
+    const long long n = rec_off[c.g1] - rec_off[c.g0];
+    c.seg_off.assign(1, 0), c.cap.resize((size_t)ng), c.row_off.resize((size_t)ng);
     long long rows_cap = 0;
     for (int j = 0; j < ng; j++) {
       const int g = c.g0 + j;
       const long long ng_recs = rec_off[g + 1] - rec_off[g];
-      std::vector<long long> off((size_t)nb[g] + 1);
-      block_ranges(ng_recs, ng_recs ? block + rec_off[g] : nullptr, nb[g], off.data());
-      for (int k = 0; k < nb[g]; k++) c.off.push_back(rec_off[g] - r0 + off[(size_t)k]);
       c.seg_off.push_back(c.seg_off.back() + nb[g]);
       c.cap[(size_t)j] = row_cap(ng_recs), c.row_off[(size_t)j] = rows_cap;
       rows_cap += c.cap[(size_t)j];
     }
-    c.off.push_back(n);
     const int nseg = c.seg_off.back();
     // the chunk's rows stay for the fit: room for every group's cap
     int *d_cell_of_row = nullptr, *d_kinds = nullptr;
     double *d_a0 = nullptr, *d_a1 = nullptr;
     HIP_TRY(buf.device(d_cell_of_row, (size_t)rows_cap)); HIP_TRY(buf.device(d_kinds, (size_t)rows_cap));
     HIP_TRY(buf.device(d_a0, (size_t)rows_cap)); HIP_TRY(buf.device(d_a1, (size_t)rows_cap));
-    HIP_TRY(h2d(d_recs, n ? recs + r0 : nullptr, sizeof(IntervalRec) * (size_t)n));
-    HIP_TRY(h2d(d_off, c.off.data(), sizeof(long long) * c.off.size()));
     HIP_TRY(h2d(d_seg_off, c.seg_off.data(), sizeof(int) * c.seg_off.size()));
     HIP_TRY(h2d(d_cap, c.cap.data(), sizeof(int) * (size_t)ng)); HIP_TRY(h2d(d_row_off, c.row_off.data(), sizeof(long long) * (size_t)ng));
-    HIP_TRY(events.mark(stream));
+    if (src.kernels()) HIP_TRY(events.mark(stream));
+    if (int rc = src.stage(c.g0, c.g1, c.seg_off, n, d_recs, d_off, stream)) return rc;
+    if (!src.kernels()) HIP_TRY(events.mark(stream));
     hipError_t e = colate_interval_cells_launch(n, d_recs, d_off, nseg, d_T, d_idx, d_cells, d_seg_dropped, stream);
     if (e != hipSuccess) return hip_fail(e, "interval cells kernel launch");
     e = colate_interval_rows_launch(ng, d_cells, d_seg_off, d_seg_dropped, d_grid, d_row_off, d_cap, d_flagbytes, d_cell_of_row, d_kinds,
@@ -951,4 +984,222 @@ int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, co
   return COLATE_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, const colate_interval_rec* recs, const int* block,
+                               const int* nb, const double* block_weights, const double* epochs, const double* init_rates,
+                               int max_iter, int min_iter, double rel_tol, double rate_floor, int* out_R, long long* out_dropped,
+                               double* out_rates, int* out_iters, double* out_loglik, int* out_flags) {
+  using namespace colate_ic;
+  float T[kBins];
+  if (int rc = build_thresholds(T)) return rc;
+  if (int rc = check_groups_args(G, B, E, rec_off, recs, block, nb, block_weights, epochs, init_rates, max_iter, min_iter, rel_tol,
+                                 rate_floor, T, out_R, out_dropped, out_rates, out_iters, out_loglik, out_flags))
+    return rc;
+  if (int rc = ensure_device()) return rc;
+  ProfRange range("colate_interval_fit_groups: per chunk H2D + cells + row pick + row bootstrap; one interval EM kernel + D2H");
+  g_interval_groups_kernel_s = 0.0;
+  HostGroupRecords src(rec_off, recs, block, nb);
+  return fit_groups_core(G, B, E, rec_off, nb, block_weights, epochs, init_rates, max_iter, min_iter, rel_tol, rate_floor,
+                         std::numeric_limits<long long>::max(), src, T, out_R, out_dropped, out_rates, out_iters, out_loglik, out_flags);
+}
+
+double colate_interval_fit_samples_kernel_seconds(void) { return g_interval_groups_kernel_s; }
+
 }  // extern "C"
+
+// ---- the pair walk on the device (interval_walk.h)
+namespace colate_iw {
+
+namespace {
+
+// The inputs of a view, resident on the device: uploaded once per call, chromosome by chromosome from where they lie.
+struct Resident {
+  DeviceBuffers buf;
+  DeviceInputs in;
+  std::vector<long long> word_off;
+  int upload(const View& v, hipStream_t stream) {
+    const int C = v.C;
+    in.C = C, in.S = v.S, in.M = v.M, in.P = v.P, in.nbpb = v.nbpb, in.n = v.row_off[C];
+    word_off.resize((size_t)C + 1);
+    in.words = mask_words(C, v.row_off, word_off.data());
+    long long *d_row_off = nullptr, *d_word_off = nullptr;
+    Row* d_rows = nullptr;
+    Idx* d_idx = nullptr;
+    unsigned long long* d_masks = nullptr;
+    Pair* d_pairs = nullptr;
+    HIP_TRY(buf.device(d_row_off, (size_t)C + 1)); HIP_TRY(buf.device(d_word_off, (size_t)C + 1));
+    HIP_TRY(buf.device(d_rows, (size_t)in.n)); HIP_TRY(buf.device(d_idx, (size_t)v.S * in.n));
+    HIP_TRY(buf.device(d_masks, (size_t)v.M * in.words)); HIP_TRY(buf.device(d_pairs, (size_t)v.P));
+    auto h2d = [stream](void* dst, const void* src, size_t bytes) {
+      return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
+    };
+    HIP_TRY(h2d(d_row_off, v.row_off, sizeof(long long) * ((size_t)C + 1)));
+    HIP_TRY(h2d(d_word_off, word_off.data(), sizeof(long long) * ((size_t)C + 1)));
+    HIP_TRY(h2d(d_pairs, v.pairs, sizeof(Pair) * (size_t)v.P));
+    for (int c = 0; c < C; c++) {
+      const size_t nc = (size_t)(v.row_off[c + 1] - v.row_off[c]), wc = (size_t)(word_off[(size_t)c + 1] - word_off[(size_t)c]);
+      HIP_TRY(h2d(d_rows + v.row_off[c], v.rows[c], sizeof(Row) * nc));
+      for (int s = 0; s < v.S; s++) HIP_TRY(h2d(d_idx + (size_t)s * in.n + v.row_off[c], v.idx[(size_t)s * C + c], sizeof(Idx) * nc));
+      for (int m = 0; m < v.M; m++)
+        HIP_TRY(h2d(d_masks + (size_t)m * in.words + word_off[(size_t)c], v.masks[(size_t)m * C + c], sizeof(unsigned long long) * wc));
+    }
+    in.row_off = d_row_off, in.word_off = d_word_off, in.rows = d_rows, in.idx = d_idx, in.masks = d_masks, in.pairs = d_pairs;
+    return COLATE_OK;
+  }
+};
+
+struct StreamSync {  // nothing that the stream still reads or writes is freed before it is idle
+  hipStream_t s;
+  ~StreamSync() { (void)hipStreamSynchronize(s); }
+};
+
+// seconds between two events recorded on a stream that is idle by now
+double seconds_between(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.f;
+  return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1e-3 : 0.0;
+}
+
+// The count pass for all pairs and the one host wait: cnt / last_block [P][C] on the host.
+int count_pass(const Resident& res, hipStream_t stream, std::vector<int>& cnt, std::vector<int>& last, DeviceBuffers& buf, double* seconds) {
+  const size_t PC = (size_t)res.in.P * res.in.C;
+  int *d_cnt = nullptr, *d_last = nullptr;
+  HIP_TRY(buf.device(d_cnt, PC)); HIP_TRY(buf.device(d_last, PC));
+  hipEvent_t e0, e1;
+  HIP_TRY(hipEventCreate(&e0));
+  HIP_TRY(hipEventCreate(&e1));
+  struct Ev {
+    hipEvent_t a, b;
+    ~Ev() { (void)hipEventDestroy(a), (void)hipEventDestroy(b); }
+  } ev{e0, e1};
+  HIP_TRY(hipEventRecord(e0, stream));
+  if (hipError_t e = count_launch(res.in, 0, res.in.P, d_cnt, d_last, stream)) return hip_fail(e, "interval walk count kernel launch");
+  HIP_TRY(hipEventRecord(e1, stream));
+  cnt.resize(PC), last.resize(PC);
+  HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * PC, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(last.data(), d_last, sizeof(int) * PC, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (seconds) *seconds += seconds_between(e0, e1);
+  return COLATE_OK;
+}
+
+// the records of a chunk of pairs straight from the write pass
+struct WalkGroupRecords : GroupRecords {
+  const Resident& res;
+  const long long* rec_off;
+  const std::vector<int>&cnt, &blk0;
+  long long* d_rec0;
+  int *d_blk0, *d_seg0;
+  struct Host {
+    std::vector<long long> rec0;
+    std::vector<int> seg0;
+  };
+  std::deque<Host> hosts;  // per chunk, alive until the call ends: their copies are asynchronous
+  WalkGroupRecords(const Resident& r, const long long* ro, const std::vector<int>& c, const std::vector<int>& b, long long* dr, int* db, int* ds)
+      : res(r), rec_off(ro), cnt(c), blk0(b), d_rec0(dr), d_blk0(db), d_seg0(ds) {}
+  bool kernels() const override { return true; }
+  int stage(int g0, int g1, const std::vector<int>& seg_off, long long n, colate_ic::IntervalRec* d_recs, long long* d_off,
+            hipStream_t stream) override {
+    const int C = res.in.C;
+    const size_t k0 = (size_t)g0 * C, nk = (size_t)(g1 - g0) * C;
+    hosts.emplace_back();
+    Host& h = hosts.back();
+    h.rec0.resize(nk), h.seg0.resize(nk);
+    long long at = 0;
+    for (size_t k = 0; k < nk; k++) {
+      h.rec0[k] = at, at += cnt[k0 + k];
+      h.seg0[k] = seg_off[k / (size_t)C] + blk0[k0 + k];
+    }
+    if (at != n) return fail(COLATE_EHIP, "the walk's counts do not add up to the chunk's records (%lld, %lld)", at, n);
+    HIP_TRY(hipMemcpyAsync(d_rec0, h.rec0.data(), sizeof(long long) * nk, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_seg0, h.seg0.data(), sizeof(int) * nk, hipMemcpyHostToDevice, stream));
+    if (hipError_t e = write_launch(res.in, g0, g1, d_rec0, d_blk0 + k0, d_seg0, d_recs, nullptr, d_off, seg_off.back(), n, stream))
+      return hip_fail(e, "interval walk write kernel launch");
+    return COLATE_OK;
+  }
+};
+
+}  // namespace
+
+int walk_view_device(const View& v, long long cap, long long* rec_off, int* nb, colate_ic::IntervalRec* recs, int* block) {
+  if (int rc = check_walk_outputs(cap, rec_off, nb, recs, block)) return rc;
+  if (int rc = check_view(v)) return rc;
+  if (int rc = ensure_device()) return rc;
+  ProfRange range("colate_interval_walk: H2D + count pass + write pass + D2H");
+  if (int rc = g_ws.reserve(256, 256)) return rc;  // (the workspace's stream)
+  hipStream_t stream = g_ws.stream;
+  Resident res;
+  DeviceBuffers buf;
+  const StreamSync sync_at_exit{stream};
+  if (int rc = res.upload(v, stream)) return rc;
+  std::vector<int> cnt, last;
+  if (int rc = count_pass(res, stream, cnt, last, buf, nullptr)) return rc;
+  const size_t PC = (size_t)v.P * v.C;
+  std::vector<int> blk0(PC), nbs((size_t)v.P);
+  std::vector<long long> off((size_t)v.P + 1), rec0(PC);
+  if (int rc = finish_counts(v.P, v.C, cnt.data(), last.data(), blk0.data(), nbs.data(), off.data())) return rc;
+  const long long total = off[(size_t)v.P];
+  if (int rc = check_capacity(total, cap)) return rc;
+  long long at = 0;
+  for (size_t k = 0; k < PC; k++) rec0[k] = at, at += cnt[k];
+  long long* d_rec0 = nullptr;
+  int *d_blk0 = nullptr, *d_block = nullptr;
+  colate_ic::IntervalRec* d_recs = nullptr;
+  HIP_TRY(buf.device(d_rec0, PC)); HIP_TRY(buf.device(d_blk0, PC)); HIP_TRY(buf.device(d_recs, (size_t)total)); HIP_TRY(buf.device(d_block, (size_t)total));
+  HIP_TRY(hipMemcpyAsync(d_rec0, rec0.data(), sizeof(long long) * PC, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(d_blk0, blk0.data(), sizeof(int) * PC, hipMemcpyHostToDevice, stream));
+  if (hipError_t e = write_launch(res.in, 0, v.P, d_rec0, d_blk0, nullptr, d_recs, d_block, nullptr, 0, total, stream))
+    return hip_fail(e, "interval walk write kernel launch");
+  if (total) {
+    HIP_TRY(hipMemcpyAsync(recs, d_recs, sizeof(colate_ic::IntervalRec) * (size_t)total, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(block, d_block, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, stream));
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  std::memcpy(rec_off, off.data(), sizeof(long long) * off.size()), std::memcpy(nb, nbs.data(), sizeof(int) * nbs.size());
+  return COLATE_OK;
+}
+
+int fit_samples_view_device(const View& v, const FitArgs& a) {
+  if (int rc = check_fit_args(v, a)) return rc;
+  float T[colate_ic::kBins];
+  if (int rc = colate_ic::build_thresholds(T)) return rc;
+  if (int rc = ensure_device()) return rc;
+  ProfRange range("colate_interval_fit_samples: H2D + walk count pass; per chunk walk write pass + cells + row pick + row bootstrap; one interval EM kernel + D2H");
+  if (int rc = g_ws.reserve(256, 256)) return rc;  // (the workspace's stream)
+  hipStream_t stream = g_ws.stream;
+  Resident res;
+  DeviceBuffers buf;
+  const StreamSync sync_at_exit{stream};
+  g_interval_groups_kernel_s = 0.0;
+  if (int rc = res.upload(v, stream)) return rc;
+  std::vector<int> cnt, last;
+  if (int rc = count_pass(res, stream, cnt, last, buf, &g_interval_groups_kernel_s)) return rc;
+  const int P = v.P, C = v.C;
+  const size_t PC = (size_t)P * C;
+  std::vector<int> blk0(PC), nb((size_t)P);
+  std::vector<long long> off((size_t)P + 1);
+  if (int rc = finish_counts(P, C, cnt.data(), last.data(), blk0.data(), nb.data(), off.data())) return rc;
+  std::vector<double> weights;
+  if (int rc = draw_pair_weights(a.seed, a.B, P, nb.data(), weights)) return rc;
+  long long budget_mb = COLATE_INTERVAL_WALK_RECS_MB_DEFAULT;
+  if (const char* e = std::getenv("COLATE_INTERVAL_WALK_RECS_MB")) budget_mb = std::max(0LL, std::atoll(e));
+  const long long max_chunk_recs = std::max<long long>(1, budget_mb * (1LL << 20) / (long long)(sizeof(colate_ic::IntervalRec) + sizeof(int)));
+  long long* d_rec0 = nullptr;
+  int *d_blk0 = nullptr, *d_seg0 = nullptr;
+  HIP_TRY(buf.device(d_rec0, PC)); HIP_TRY(buf.device(d_blk0, PC)); HIP_TRY(buf.device(d_seg0, PC));
+  HIP_TRY(hipMemcpyAsync(d_blk0, blk0.data(), sizeof(int) * PC, hipMemcpyHostToDevice, stream));
+  WalkGroupRecords src(res, off.data(), cnt, blk0, d_rec0, d_blk0, d_seg0);
+  std::vector<double> ep((size_t)P * a.E), init((size_t)P * a.E);
+  for (int p = 0; p < P; p++)
+    std::memcpy(&ep[(size_t)p * a.E], a.epochs, sizeof(double) * a.E), std::memcpy(&init[(size_t)p * a.E], a.init_rates, sizeof(double) * a.E);
+  if (int rc = fit_groups_core(P, a.B, a.E, off.data(), nb.data(), weights.data(), ep.data(), init.data(), a.max_iter, a.min_iter, a.rel_tol,
+                               a.rate_floor, max_chunk_recs, src, T, a.out_R, a.out_dropped, a.out_rates, a.out_iters, a.out_loglik,
+                               a.out_flags))
+    return rc;
+  for (int p = 0; p < P; p++) a.out_nb[p] = nb[(size_t)p], a.out_used[p] = off[(size_t)p + 1] - off[(size_t)p];
+  return COLATE_OK;
+}
+
+}  // namespace colate_iw

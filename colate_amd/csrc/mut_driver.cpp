@@ -61,7 +61,7 @@ const char* const kValueOptions[] = {
     "reference_age", "ref_genome", "anc_genome", "mask", "mask_cutoff", "chr", "bins",
     "lineage_bin", "outgroup_tmrca", "years_per_gen", "coal", "seed", "num_bootstraps", "filters",
     "groups", "poplabels", "map", "input", "output", "device", "devices", "ranks", "counts_out", "pairs",
-    "rows", "max_iter", "min_iter", "write_rows"};
+    "rows", "max_iter", "min_iter", "write_rows", "samples"};
 const char* const kBoolOptions[] = {"help", "strandfilter", "counts_only", "write_colate_mat"};
 
 bool parse_options(int argc, char** argv, Options& o, std::string& err) {
@@ -139,6 +139,10 @@ void print_help() {
             << "                             coal=FILE (the pair's --coal warm start; --bins is then not needed for that line).\n"
             << "                             (--mode mut_interval) --pairs FILE with --mut [--chr, --bins]: the same lines without ages;\n"
             << "                             every pair's interval-dated fit in one pass, each <output>.coal that of its single run.\n"
+            << "      --samples arg          (--mode mut_interval) file of `NAME FILE.colate.in [mask=PREFIX] [role=target|reference]`\n"
+            << "                             lines; with --mut, -o PREFIX [--chr] and --bins or --coal every target x reference pair of\n"
+            << "                             different lines is fitted, the pairs walked on the GPU; writes PREFIX_<target>_<reference>.coal,\n"
+            << "                             each the file `--pairs` writes for that pair.\n"
             << "      --counts_out arg       Optional (colate_amd): write the bootstrap count tables (.colate_mat layout).\n"
             << "      --counts_only          Optional (colate_amd): stop after --counts_out (no GPU needed).\n"
             << "      --write_colate_mat     Optional (colate_amd): write <output>.colate_mat as the reference does for BCF/BAM inputs.\n"

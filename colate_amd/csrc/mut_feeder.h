@@ -11,6 +11,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <random>
 #include <sstream>
 #include <string>
@@ -231,6 +232,32 @@ struct PairRecords {
 };
 bool collect_interval_records_pairs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
                                     const std::vector<PairSpec>& pairs, std::vector<PairRecords>& out);
+
+// mut_pairs.cpp: the inputs of a list of pairs as the pair walk over walk indices takes them (`--mode mut_interval --samples`;
+// csrc/interval_walk.h): every .mut file, .colate.in file and mask read, decoded and indexed once by the loader of fill_pairs.
+// indexed: every file has a walk index -- only then are the arrays below filled.  The rows of all chromosomes back to back;
+// per (sample, chromosome) the file's index where it lies, per (mask, chromosome) the mask's bits; samples are the distinct
+// .colate.in paths, masks the distinct lists of mask files, both in the order of their names.  The object owns what it points to.
+constexpr int kIntervalBasesPerBlock = (int)30e6;  // the genome block of `--mode mut_interval` (coal.cpp: num_bases_per_block)
+struct WalkInputs {
+  struct Loaded;
+  std::unique_ptr<Loaded> loaded;
+  bool indexed = false;
+  std::vector<long long> row_off;
+  std::vector<colate_walk_row> rows;
+  std::vector<const colate_walk_row*> row_ptrs;            // [C]
+  std::vector<const colate_walk_idx*> idx_ptrs;            // [S][C]
+  std::vector<const unsigned long long*> mask_ptrs;        // [M][C]
+  std::vector<colate_walk_pair> pairs;
+  int S = 0, M = 0;
+  WalkInputs();
+  ~WalkInputs();
+};
+bool load_walk_inputs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const std::vector<PairSpec>& pairs,
+                      WalkInputs& out);
+// collect_interval_records_pairs on inputs loaded before (the path `--samples` takes where a file has no walk index)
+bool collect_interval_records_loaded(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& pairs,
+                                     std::vector<PairRecords>& out);
 
 // mut_driver.cpp: the list of `--pairs`.  "target reference output [target_age [reference_age]]" per line; after the three
 // names, `key=value` tokens in any order and mixed with the ages: target_mask=PREFIX, reference_mask=PREFIX (expanded as the

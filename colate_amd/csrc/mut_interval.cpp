@@ -8,7 +8,9 @@
 // The rows come from a file (--rows: how a line becomes a mutation's (kind, age_begin, age_end) is the caller's business),
 // or from the inputs of `--mode mut` (--mut, --target_tmp, --reference_tmp): every SNP the pair uses, snapped to the age
 // grid, is one observation of each kind (interval_cells.h), formed on the device by colate_interval_cells.
-// With --pairs LIST the second form runs for every line of the list in one pass (colate_interval_fit_groups).
+// With --pairs LIST the second form runs for every line of the list in one pass (colate_interval_fit_groups); with
+// --samples LIST for every target x reference pair of a sample list, the pairs walked on the device
+// (colate_interval_fit_samples).
 #include <unistd.h>
 
 #include <algorithm>
@@ -18,14 +20,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <ctime>
+#include <fstream>
 #include <iostream>
 #include <map>
 #include <random>
+#include <sstream>
 #include <string>
 #include <tuple>
 #include <vector>
 
 #include "colate_amd.h"
+#include "interval_walk.h"
 #include "mut_interval.h"
 
 namespace colate_drv {
@@ -191,72 +196,88 @@ static bool write_interval_rows(const std::string& path, const IntervalRows& row
   return std::fclose(f) == 0;
 }
 
-// `--mode mut_interval --pairs LIST`: the single run above for every line of the list, in one pass.  Every input file is read
-// once and the pairs are walked on the pool (collect_interval_records_pairs); the pairs with the same number of epochs, in
-// order of first appearance, go through one colate_interval_fit_groups call -- cells, rows, block bootstrap and fit of all of
-// them on the device, or the host twin after a line on stderr.  Every pair draws its block weights from a generator of its
-// own on the run's seed, as its single run does, so OUTPUT.coal is that run's, byte for byte.
-static int run_mut_interval_pairs(const Options& opt) {
-  for (const char* o : {"target_tmp", "reference_tmp", "rows", "write_rows", "output", "ranks", "target_age", "reference_age"})
-    if (opt.has(o)) {
-      std::cerr << "Error: --" << o << " cannot be combined with --mode mut_interval --pairs." << std::endl;
-      return 1;
-    }
-  for (const char* o : {"target_mask", "reference_mask", "coal"})
-    if (opt.has(o)) {  // (the wording of `--mode mut --pairs`)
-      std::cerr << "Error: --" << o << " cannot be combined with --pairs (give it per line: " << o << "=...)." << std::endl;
-      return 1;
-    }
-  if (!opt.has("mut")) {
-    std::cerr << "Error: --pairs needs --mut (and optionally --chr, --bins, --num_bootstraps, --seed, --years_per_gen, --max_iter, "
-                 "--min_iter, --device)."
-              << std::endl;
-    return 1;
-  }
-  std::vector<std::string> names, mut_files;
-  chromosome_files(opt, names, mut_files);
-  std::vector<PairSpec> pairs;
-  if (!read_pair_list(opt.get("pairs"), opt, names, pairs)) return 1;
-  for (const PairSpec& ps : pairs)
-    if (ps.ages_given) {
-      std::cerr << "Error: " << opt.get("pairs") << ", line " << ps.line
-                << ": --mode mut_interval takes modern samples only: a line cannot carry sample ages." << std::endl;
-      return 1;
-    }
-  if (!opt.has("bins"))
-    for (size_t p = 0; p < pairs.size(); p++)
-      if (pairs[p].coal.empty()) {  // (a line with coal= takes its epochs from that file)
-        std::cerr << "Error: --pairs needs --bins for pair " << p + 1 << " (it names no coal= file)." << std::endl;
-        return 1;
-      }
-  const size_t P = pairs.size();
-  std::cerr << "---------------------------------------------------------" << std::endl;
-  std::cerr << "Calculating coalescence rates from interval-dated mutations for " << P << " pairs.." << std::endl;
+// What the list forms of `--mode mut_interval` share: the fit options, the choice between device and host twin, and what is
+// said and written per pair.
+struct ListRun {
   double years_per_gen = 28.0;
   int B = 1, max_iter = COLATE_DEFAULT_MAX_ITER, min_iter = COLATE_DEFAULT_MIN_ITER;
-  int seed = std::time(0) + getpid();  // coal.cpp:3158; one seed for the whole run
-  if (opt.has("years_per_gen")) years_per_gen = std::stof(opt.get("years_per_gen"));
-  if (opt.has("seed")) seed = std::stoi(opt.get("seed"));
-  if (opt.has("num_bootstraps")) B = std::stoi(opt.get("num_bootstraps"));
-  if (opt.has("max_iter")) max_iter = std::stoi(opt.get("max_iter"));
-  if (opt.has("min_iter")) min_iter = std::stoi(opt.get("min_iter"));
-  if (B < 1) {
+  int seed = 0;
+  std::string host_why;  // not empty: the host twins run
+  int status = 0;
+};
+static int api_error(int rc) {
+  std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
+  return 1;
+}
+static bool list_run_options(const Options& opt, ListRun& run) {
+  run.seed = std::time(0) + getpid();  // coal.cpp:3158; one seed for the whole run
+  if (opt.has("years_per_gen")) run.years_per_gen = std::stof(opt.get("years_per_gen"));
+  if (opt.has("seed")) run.seed = std::stoi(opt.get("seed"));
+  if (opt.has("num_bootstraps")) run.B = std::stoi(opt.get("num_bootstraps"));
+  if (opt.has("max_iter")) run.max_iter = std::stoi(opt.get("max_iter"));
+  if (opt.has("min_iter")) run.min_iter = std::stoi(opt.get("min_iter"));
+  if (run.B < 1) {
     std::cerr << "Error: --num_bootstraps must be at least 1." << std::endl;
-    return 1;
+    return false;
   }
-  auto api_error = [](int rc) {
-    std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-    return 1;
-  };
+  return true;
+}
+// device or host twin (false after an error message)
+static bool list_run_device(const Options& opt, ListRun& run) {
+  if (const char* e = std::getenv("COLATE_DEVICE_INTERVAL"))
+    if (std::string(e) == "0") run.host_why = "COLATE_DEVICE_INTERVAL=0";
+  if (run.host_why.empty() && colate_device_count() <= 0) run.host_why = "no device";
+  if (run.host_why.empty() && opt.has("device"))
+    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc), false;
+  return true;
+}
+static void say_blocks(size_t p, size_t P, const PairSpec& ps, int nb) {
+  std::cerr << "Pair " << p + 1 << " / " << P << ": " << ps.target << " x " << ps.reference << ": Number of blocks: " << nb << std::endl;
+}
+// the lines of pair p after its fit, and its .coal (rates: [B][E] of the pair)
+static void report_pair(ListRun& run, size_t p, const PairSpec& ps, int R, long long dropped, int E, const double* epochs, int ep_null,
+                        const double* rates, const int* iters, const int* flags) {
+  const std::string lead = "Pair " + std::to_string(p + 1) + " ";
+  std::cerr << lead << "Number of rows: " << R << std::endl;
+  std::cerr << lead << "SNPs beyond the age grid: " << dropped << std::endl;
+  if (R == 0) {
+    std::cerr << "Error: pair " << p + 1 << " (" << ps.target << " x " << ps.reference << ") uses no SNP within the age grid; " << ps.output
+              << ".coal is not written." << std::endl;
+    run.status = 1;
+    return;
+  }
+  for (int i = 0; i < run.B; i++) {
+    std::cerr << lead << "Bootstrap " << i + 1 << ": Total iterations " << iters[i] << std::endl;
+    if (flags[i] & (COLATE_FLAG_NAN | COLATE_FLAG_NEG))
+      std::cerr << "Warning: pair " << p + 1 << " bootstrap " << i + 1 << " produced NaN or negative sufficient statistics." << std::endl;
+  }
+  if (colate_write_coal((ps.output + ".coal").c_str(), run.B, E, epochs, rates, 0, ep_null)) {
+    std::cerr << "Error: " << colate_last_error() << std::endl;
+    run.status = 1;
+  }
+}
+
+// The pairs of a list (`--pairs`, or the expanded list of `--samples` where its pairs cannot be walked over indices): every
+// input file is read once and the pairs are walked on the pool (collect_interval_records_pairs; loaded: inputs read before);
+// the pairs with the same number of epochs, in order of first appearance, go through one colate_interval_fit_groups call --
+// cells, rows, block bootstrap and fit of all of them on the device, or the host twin after a line on stderr.  Every pair
+// draws its block weights from a generator of its own on the run's seed, as its single run does, so OUTPUT.coal is that
+// run's, byte for byte.
+static int fit_pair_list(const Options& opt, ListRun& run, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                         const std::vector<PairSpec>& pairs, const WalkInputs* loaded) {
+  const size_t P = pairs.size();
+  const int B = run.B, max_iter = run.max_iter, min_iter = run.min_iter, seed = run.seed;
+  const std::string& host_why = run.host_why;
+  int& status = run.status;
 
   // ---- epochs and starting rates per pair, as the single run forms them
   std::vector<std::vector<double>> epochs(P), init(P);
   std::vector<int> ep_null(P, 0);
   for (size_t p = 0; p < P; p++) {
     epochs[p].assign(COLATE_MAX_EPOCHS, 0.0), init[p].assign(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
-    const int E = !pairs[p].coal.empty()
-                      ? colate_epochs_from_coal(pairs[p].coal.c_str(), 0.0, epochs[p].data(), init[p].data(), COLATE_MAX_EPOCHS)
-                      : colate_epochs_from_bins(opt.get("bins").c_str(), 0.0, years_per_gen, epochs[p].data(), COLATE_MAX_EPOCHS, &ep_null[p]);
+    const std::string& coal = !pairs[p].coal.empty() ? pairs[p].coal : !opt.has("bins") && opt.has("coal") ? opt.get("coal") : pairs[p].coal;
+    const int E = !coal.empty() ? colate_epochs_from_coal(coal.c_str(), 0.0, epochs[p].data(), init[p].data(), COLATE_MAX_EPOCHS)
+                                : colate_epochs_from_bins(opt.get("bins").c_str(), 0.0, run.years_per_gen, epochs[p].data(), COLATE_MAX_EPOCHS, &ep_null[p]);
     if (E <= 0) {
       std::cerr << "Error: pair " << p + 1 << ": " << colate_last_error() << std::endl;
       return 1;
@@ -264,25 +285,18 @@ static int run_mut_interval_pairs(const Options& opt) {
     epochs[p].resize(E), init[p].resize(E);
   }
 
-  // ---- device or host twin
-  std::string host_why;
-  if (const char* e = std::getenv("COLATE_DEVICE_INTERVAL"))
-    if (std::string(e) == "0") host_why = "COLATE_DEVICE_INTERVAL=0";
-  if (host_why.empty() && colate_device_count() <= 0) host_why = "no device";
-  if (host_why.empty() && opt.has("device"))
-    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc);
-
   // ---- the records of all pairs
   const double t_start = StageTimes::now();
   std::vector<PairRecords> recs;
-  if (!collect_interval_records_pairs(names, mut_files, pairs, recs)) return 1;
+  if (!(loaded ? collect_interval_records_loaded(*loaded, names, pairs, recs) : collect_interval_records_pairs(names, mut_files, pairs, recs)))
+    return 1;
   const double t_fit = StageTimes::now();
   double kernel_s = 0.0;
-  int status = 0;
+  long long total_recs = 0;
+  for (const PairRecords& pr : recs) total_recs += (long long)pr.recs.size();
   std::vector<char> usable(P, 1);
   for (size_t p = 0; p < P; p++) {
-    std::cerr << "Pair " << p + 1 << " / " << P << ": " << pairs[p].target << " x " << pairs[p].reference << ": Number of blocks: " << recs[p].nb
-              << std::endl;
+    say_blocks(p, P, pairs[p], recs[p].nb);
     if (!recs[p].walked || recs[p].nb < 1) {
       std::cerr << "Error: pair " << p + 1 << " (" << pairs[p].target << " x " << pairs[p].reference << "): "
                 << (recs[p].walked ? "no genome block (no chromosome was read)." : "the SNPs of the pair could not be walked.") << std::endl;
@@ -341,35 +355,217 @@ static int run_mut_interval_pairs(const Options& opt) {
     if (host_why.empty()) kernel_s += colate_interval_fit_groups_kernel_seconds();
     for (int g = 0; g < G; g++) {
       const size_t p = cls[(size_t)g];
-      const std::string lead = "Pair " + std::to_string(p + 1) + " ";
-      std::cerr << lead << "Number of rows: " << R[g] << std::endl;
-      std::cerr << lead << "SNPs beyond the age grid: " << dropped[g] << std::endl;
-      if (R[g] == 0) {
-        std::cerr << "Error: pair " << p + 1 << " (" << pairs[p].target << " x " << pairs[p].reference
-                  << ") uses no SNP within the age grid; " << pairs[p].output << ".coal is not written." << std::endl;
-        status = 1;
-        continue;
-      }
-      for (int i = 0; i < B; i++) {
-        std::cerr << lead << "Bootstrap " << i + 1 << ": Total iterations " << iters[(size_t)g * B + i] << std::endl;
-        if (flags[(size_t)g * B + i] & (COLATE_FLAG_NAN | COLATE_FLAG_NEG))
-          std::cerr << "Warning: pair " << p + 1 << " bootstrap " << i + 1 << " produced NaN or negative sufficient statistics." << std::endl;
-      }
-      if (colate_write_coal((pairs[p].output + ".coal").c_str(), B, E, epochs[p].data(), rates.data() + (size_t)g * B * E, 0, ep_null[p])) {
-        std::cerr << "Error: " << colate_last_error() << std::endl;
-        status = 1;
-      }
+      report_pair(run, p, pairs[p], R[g], dropped[g], E, epochs[p].data(), ep_null[p], rates.data() + (size_t)g * B * E,
+                  iters.data() + (size_t)g * B, flags.data() + (size_t)g * B);
     }
   }
   if (g_times.on)
     std::cerr << "Timing: interval pairs: inputs and walks " << t_fit - t_start << " s, cells, rows and fits " << StageTimes::now() - t_fit
-              << " s (device kernels " << kernel_s << " s)" << std::endl;
+              << " s (device kernels " << kernel_s << " s); " << total_recs << " records uploaded" << std::endl;
   if (status) return status;
   print_usage_footer();
   return 0;
 }
 
+// `--mode mut_interval --pairs LIST`: the single run above for every line of the list, in one pass (fit_pair_list).
+static int run_mut_interval_pairs(const Options& opt) {
+  for (const char* o : {"target_tmp", "reference_tmp", "rows", "write_rows", "output", "ranks", "target_age", "reference_age"})
+    if (opt.has(o)) {
+      std::cerr << "Error: --" << o << " cannot be combined with --mode mut_interval --pairs." << std::endl;
+      return 1;
+    }
+  for (const char* o : {"target_mask", "reference_mask", "coal"})
+    if (opt.has(o)) {  // (the wording of `--mode mut --pairs`)
+      std::cerr << "Error: --" << o << " cannot be combined with --pairs (give it per line: " << o << "=...)." << std::endl;
+      return 1;
+    }
+  if (!opt.has("mut")) {
+    std::cerr << "Error: --pairs needs --mut (and optionally --chr, --bins, --num_bootstraps, --seed, --years_per_gen, --max_iter, "
+                 "--min_iter, --device)."
+              << std::endl;
+    return 1;
+  }
+  std::vector<std::string> names, mut_files;
+  chromosome_files(opt, names, mut_files);
+  std::vector<PairSpec> pairs;
+  if (!read_pair_list(opt.get("pairs"), opt, names, pairs)) return 1;
+  for (const PairSpec& ps : pairs)
+    if (ps.ages_given) {
+      std::cerr << "Error: " << opt.get("pairs") << ", line " << ps.line
+                << ": --mode mut_interval takes modern samples only: a line cannot carry sample ages." << std::endl;
+      return 1;
+    }
+  if (!opt.has("bins"))
+    for (size_t p = 0; p < pairs.size(); p++)
+      if (pairs[p].coal.empty()) {  // (a line with coal= takes its epochs from that file)
+        std::cerr << "Error: --pairs needs --bins for pair " << p + 1 << " (it names no coal= file)." << std::endl;
+        return 1;
+      }
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating coalescence rates from interval-dated mutations for " << pairs.size() << " pairs.." << std::endl;
+  ListRun run;
+  if (!list_run_options(opt, run)) return 1;
+  if (!list_run_device(opt, run)) return 1;
+  return fit_pair_list(opt, run, names, mut_files, pairs, nullptr);
+}
+
+// ------------------------------------------------------------------ `--mode mut_interval --samples LIST`
+// The list: `NAME FILE.colate.in` per line, then in any order mask=PREFIX (expanded as --target_mask is) and
+// role=target|reference (default: both).  Blank lines are skipped.  Every error names the line.
+struct SampleLine {
+  std::string name, file;
+  std::vector<std::string> masks;
+  bool target = true, reference = true;
+  size_t line = 0;
+};
+static bool read_sample_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names,
+                             std::vector<SampleLine>& samples) {
+  std::ifstream is(path);
+  if (!is) {
+    std::cerr << "Error while opening file " << path << std::endl;
+    return false;
+  }
+  std::string line;
+  for (size_t line_no = 1; std::getline(is, line); line_no++) {
+    auto fail = [&](const std::string& what) {
+      std::cerr << "Error: " << path << ", line " << line_no << ": " << what << std::endl;
+      return false;
+    };
+    std::istringstream ss(line);
+    SampleLine sl;
+    sl.line = line_no;
+    if (!(ss >> sl.name)) continue;  // a blank line
+    if (sl.name.find('=') != std::string::npos) return fail("the line starts with '" + sl.name + "': the sample's NAME is missing or empty");
+    if (sl.name.find('/') != std::string::npos) return fail("the NAME '" + sl.name + "' contains '/'");
+    if (!(ss >> sl.file) || sl.file.find('=') != std::string::npos) return fail("expected `NAME FILE.colate.in [mask=PREFIX] [role=target|reference]`");
+    for (const SampleLine& other : samples)
+      if (other.name == sl.name) return fail("the NAME '" + sl.name + "' is given twice (first on line " + std::to_string(other.line) + ")");
+    bool seen_mask = false, seen_role = false;
+    for (std::string tok; ss >> tok;) {
+      const size_t eq = tok.find('=');
+      if (eq == std::string::npos) return fail("'" + tok + "' is no key=value token (--mode mut_interval takes modern samples only: a line cannot carry sample ages)");
+      const std::string key = tok.substr(0, eq), value = tok.substr(eq + 1);
+      bool* seen = key == "mask" ? &seen_mask : key == "role" ? &seen_role : nullptr;
+      if (!seen) return fail("unknown key '" + key + "' (known: mask, role)");
+      if (*seen) return fail("the key '" + key + "' is given twice");
+      if (value.empty()) return fail("the key '" + key + "' has no value");
+      *seen = true;
+      if (key == "mask") sl.masks = mask_files(opt, chr_names, value);
+      else if (value == "target") sl.reference = false;
+      else if (value == "reference") sl.target = false;
+      else return fail("unknown role '" + value + "' (known: target, reference)");
+    }
+    samples.push_back(sl);
+  }
+  bool any_t = false, any_r = false;
+  for (const SampleLine& sl : samples) any_t = any_t || sl.target, any_r = any_r || sl.reference;
+  if (!any_t || !any_r) {
+    std::cerr << "Error: " << path << ": the list names no " << (!any_t ? "target" : "reference") << " sample." << std::endl;
+    return false;
+  }
+  return true;
+}
+
+// Every (target line, reference line) of the list with different lines, targets outermost; each pair's PREFIX_<target>_<reference>.coal
+// is, byte for byte, what `--pairs` writes for it given the expanded list.  Where every file has a walk index the pairs are not
+// walked on the host at all: N index arrays and the rows go to the device once and colate_interval_fit_samples forms every pair's
+// records where the cells kernel reads them (its host twin without a device or with COLATE_DEVICE_INTERVAL=0).  Otherwise, or with
+// COLATE_DEVICE_INTERVAL_WALK=0, the expanded list takes the path of `--pairs` after one line on stderr.
+static int run_mut_interval_samples(const Options& opt) {
+  for (const char* o : {"pairs", "rows", "target_tmp", "reference_tmp", "write_rows", "target_mask", "reference_mask", "ranks", "target_age",
+                        "reference_age"})
+    if (opt.has(o)) {
+      std::cerr << "Error: --" << o << " cannot be combined with --mode mut_interval --samples." << std::endl;
+      return 1;
+    }
+  if (!opt.has("mut") || !opt.has("output") || (!opt.has("bins") && !opt.has("coal"))) {
+    std::cerr << "Error: --samples needs --mut, -o PREFIX and --bins x,y,stepsize or --coal FILE (optional: --chr, --num_bootstraps, --seed, "
+                 "--years_per_gen, --max_iter, --min_iter, --device)."
+              << std::endl;
+    return 1;
+  }
+  std::vector<std::string> names, mut_files;
+  chromosome_files(opt, names, mut_files);
+  std::vector<SampleLine> samples;
+  if (!read_sample_list(opt.get("samples"), opt, names, samples)) return 1;
+  std::vector<PairSpec> pairs;
+  for (const SampleLine& t : samples)
+    for (const SampleLine& r : samples) {
+      if (!t.target || !r.reference || &t == &r) continue;
+      PairSpec ps;
+      ps.target = t.file, ps.reference = r.file, ps.output = opt.get("output") + "_" + t.name + "_" + r.name;
+      ps.target_masks = t.masks, ps.ref_masks = r.masks, ps.line = t.line;
+      pairs.push_back(ps);
+    }
+  if (pairs.empty()) {
+    std::cerr << "Error: " << opt.get("samples") << ": no pair of a target and a reference on different lines." << std::endl;
+    return 1;
+  }
+  const size_t P = pairs.size();
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating coalescence rates from interval-dated mutations for " << P << " pairs.." << std::endl;
+  ListRun run;
+  if (!list_run_options(opt, run)) return 1;
+  if (!list_run_device(opt, run)) return 1;
+  if (const char* e = std::getenv("COLATE_DEVICE_INTERVAL_WALK"))
+    if (std::string(e) == "0") {
+      std::cerr << "pairs walked on the host through the engine (COLATE_DEVICE_INTERVAL_WALK=0)" << std::endl;
+      return fit_pair_list(opt, run, names, mut_files, pairs, nullptr);
+    }
+  const double t_start = StageTimes::now();
+  WalkInputs in;
+  if (!load_walk_inputs(names, mut_files, pairs, in)) return 1;
+  if (!in.indexed) {
+    std::cerr << "pairs walked on the host through the engine (a sample has no walk index)" << std::endl;
+    return fit_pair_list(opt, run, names, mut_files, pairs, &in);
+  }
+
+  // ---- one set of epochs and starting rates for all pairs, as the single run forms them
+  std::vector<double> epochs(COLATE_MAX_EPOCHS, 0.0), init(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
+  int ep_null = 0;
+  const int E = opt.has("bins") ? colate_epochs_from_bins(opt.get("bins").c_str(), 0.0, run.years_per_gen, epochs.data(), COLATE_MAX_EPOCHS, &ep_null)
+                                : colate_epochs_from_coal(opt.get("coal").c_str(), 0.0, epochs.data(), init.data(), COLATE_MAX_EPOCHS);
+  if (E <= 0) {
+    std::cerr << "Error: " << colate_last_error() << std::endl;
+    return 1;
+  }
+  epochs.resize(E), init.resize(E);
+
+  const bool on_host = !run.host_why.empty();
+  std::cerr << in.S << " samples and " << in.M << " masks staged, " << P << " pairs walked on the " << (on_host ? "host" : "device")
+            << std::endl;
+  std::cerr << "Maximising likelihood using EM.. " << std::endl;
+  if (on_host) std::cerr << "interval cells and fits on the host (" << run.host_why << ")" << std::endl;
+  colate_iw::View v;
+  v.C = (int)names.size(), v.row_off = in.row_off.data(), v.rows = in.row_ptrs.data(), v.S = in.S, v.idx = in.idx_ptrs.data(), v.M = in.M;
+  v.masks = in.mask_ptrs.data(), v.P = (int)P, v.pairs = in.pairs.data(), v.nbpb = kIntervalBasesPerBlock;
+  const size_t PB = P * (size_t)run.B;
+  std::vector<int> nb(P), R(P), iters(PB), flags(PB);
+  std::vector<long long> used(P), dropped(P);
+  std::vector<double> rates(PB * E), ll(PB);
+  const colate_iw::FitArgs args{run.B,        E,           epochs.data(), init.data(),   (unsigned)run.seed, run.max_iter, run.min_iter,
+                                COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, nb.data(), used.data(), R.data(), dropped.data(),
+                                rates.data(), iters.data(), ll.data(), flags.data()};
+  const double t_fit = StageTimes::now();
+  if (int rc = on_host ? colate_iw::fit_samples_view_host(v, args, 1) : colate_iw::fit_samples_view_device(v, args)) return api_error(rc);
+  long long total_recs = 0;
+  for (size_t p = 0; p < P; p++) {
+    total_recs += used[p];
+    say_blocks(p, P, pairs[p], nb[p]);
+    report_pair(run, p, pairs[p], R[p], dropped[p], E, epochs.data(), ep_null, rates.data() + p * run.B * E, iters.data() + p * run.B,
+                flags.data() + p * run.B);
+  }
+  if (g_times.on)
+    std::cerr << "Timing: interval samples: inputs " << t_fit - t_start << " s, walks, cells, rows and fits " << StageTimes::now() - t_fit
+              << " s (device kernels " << (on_host ? 0.0 : colate_interval_fit_samples_kernel_seconds()) << " s); " << in.row_off.back()
+              << " rows, " << in.S << " index arrays and " << in.M << " masks staged, " << total_recs << " records formed" << std::endl;
+  if (run.status) return run.status;
+  print_usage_footer();
+  return 0;
+}
+
 int run_mut_interval(const Options& opt) {
+  if (opt.has("samples")) return run_mut_interval_samples(opt);
   if (opt.has("pairs")) return run_mut_interval_pairs(opt);
   const bool from_mut = opt.has("mut") || opt.has("target_tmp") || opt.has("reference_tmp");
   if (from_mut && opt.has("rows")) {

@@ -1592,24 +1592,19 @@ bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const
   return true;
 }
 
-// (mut_feeder.h)
-bool collect_interval_records_pairs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
-                                    const std::vector<PairSpec>& pairs, std::vector<PairRecords>& out) {
-  const double t0 = now_s();
-  out.assign(pairs.size(), PairRecords());
-  if (pairs.empty()) return true;
-  Pool pool(pairs_threads());
+namespace {
+
+// the pairs of a list, each walked on the pool through the engine; out[p]: pair p's records and blocks in its walk's order
+void walk_pairs_for_records(Pool& pool, const Inputs& in, const std::vector<std::string>& names, const std::vector<PairSpec>& pairs,
+                            std::vector<PairRecords>& out) {
   std::vector<size_t> todo(pairs.size());
   for (size_t p = 0; p < todo.size(); p++) todo[p] = p;
-  const char* e_idx = std::getenv("COLATE_INDEXED_WALK");
-  const Inputs in = load_inputs(pool, names, mut_files, pairs, todo, !(e_idx && std::atoi(e_idx) == 0));
   Fills fills = open_pairs(in, pairs, todo);
-  const double t1 = now_s();
   // one walk per pair on the pool; a walk is sequential, so a pair's records are in the walk's order whatever the pool does
   std::vector<Engine> engines;
   engines.reserve(pairs.size());
   for (size_t p = 0; p < pairs.size(); p++) {
-    engines.push_back(Engine{names, in.rows, 0, 10.0, (int)30e6, nullptr, nullptr, pool, nullptr, nullptr, nullptr, &out[p].recs, &out[p].blocks});
+    engines.push_back(Engine{names, in.rows, 0, 10.0, kIntervalBasesPerBlock, nullptr, nullptr, pool, nullptr, nullptr, nullptr, &out[p].recs, &out[p].blocks});
     const Engine* eng = &engines.back();
     PairFill* pf = fills[p].get();
     pool.submit([eng, pf] { eng->walk(*pf, std::numeric_limits<uint64_t>::max()); });
@@ -1619,7 +1614,92 @@ bool collect_interval_records_pairs(const std::vector<std::string>& names, const
     out[p].nb = fills[p]->num_blocks;
     out[p].walked = fills[p]->walked && !fills[p]->redo.load();
   }
+}
+
+Inputs load_all(Pool& pool, const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const std::vector<PairSpec>& pairs) {
+  std::vector<size_t> todo(pairs.size());
+  for (size_t p = 0; p < todo.size(); p++) todo[p] = p;
+  const char* e_idx = std::getenv("COLATE_INDEXED_WALK");
+  return load_inputs(pool, names, mut_files, pairs, todo, !(e_idx && std::atoi(e_idx) == 0));
+}
+
+}  // namespace
+
+// (mut_feeder.h)
+bool collect_interval_records_pairs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                                    const std::vector<PairSpec>& pairs, std::vector<PairRecords>& out) {
+  const double t0 = now_s();
+  out.assign(pairs.size(), PairRecords());
+  if (pairs.empty()) return true;
+  Pool pool(pairs_threads());
+  const Inputs in = load_all(pool, names, mut_files, pairs);
+  const double t1 = now_s();
+  walk_pairs_for_records(pool, in, names, pairs, out);
   g_times.parse_mut = t1 - t0;
+  g_times.table_fill = now_s() - t1;
+  return true;
+}
+
+// (mut_feeder.h)
+struct WalkInputs::Loaded {
+  Inputs in;
+};
+WalkInputs::WalkInputs() = default;
+WalkInputs::~WalkInputs() = default;
+
+static_assert(sizeof(TmpFile::RowIdx) == sizeof(colate_walk_idx) && offsetof(TmpFile::RowIdx, DAF) == offsetof(colate_walk_idx, DAF) &&
+                  offsetof(TmpFile::RowIdx, AAF) == offsetof(colate_walk_idx, AAF),
+              "a file's walk index is handed to the pair walk as it lies");
+static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "mask words");
+
+bool load_walk_inputs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const std::vector<PairSpec>& pairs,
+                      WalkInputs& out) {
+  const double t0 = now_s();
+  out.loaded.reset(new WalkInputs::Loaded);
+  Pool pool(pairs_threads());
+  out.loaded->in = load_all(pool, names, mut_files, pairs);
+  const Inputs& in = out.loaded->in;
+  g_times.parse_mut = now_s() - t0;
+  const size_t C = in.rows.size();
+  out.indexed = true;
+  for (const auto& kv : in.tmp_files) out.indexed = out.indexed && kv.second->indexed;
+  if (!out.indexed) return true;
+  // the rows as the walk reads them, the samples and masks in the order of their names, the pairs by their ids
+  out.row_off.assign(1, 0);
+  for (size_t c = 0; c < C; c++) out.row_off.push_back(out.row_off.back() + (long long)in.rows[c].size());
+  out.rows.resize((size_t)out.row_off.back());
+  out.row_ptrs.resize(C);
+  for (size_t c = 0; c < C; c++) {
+    colate_walk_row* dst = out.rows.data() + out.row_off[c];
+    for (size_t i = 0; i < in.rows[c].size(); i++) dst[i] = colate_walk_row{in.rows[c][i].pos, in.rows[c][i].age_begin, in.rows[c][i].age_end};
+    out.row_ptrs[c] = dst;
+  }
+  std::map<std::string, int> sample_id;
+  for (const auto& kv : in.tmp_files) {
+    sample_id[kv.first] = (int)sample_id.size();
+    for (size_t c = 0; c < C; c++) out.idx_ptrs.push_back(reinterpret_cast<const colate_walk_idx*>(kv.second->idx[c].data()));
+  }
+  std::map<std::vector<std::string>, int> mask_id;
+  for (const auto& kv : in.masks) {
+    mask_id[kv.first] = (int)mask_id.size();
+    for (size_t c = 0; c < C; c++) out.mask_ptrs.push_back(reinterpret_cast<const unsigned long long*>(kv.second->pass[c].data()));
+  }
+  out.S = (int)sample_id.size(), out.M = (int)mask_id.size();
+  out.pairs.clear();
+  for (const PairSpec& ps : pairs)
+    out.pairs.push_back(colate_walk_pair{sample_id.at(ps.target), sample_id.at(ps.reference),
+                                         ps.target_masks.empty() ? -1 : mask_id.at(ps.target_masks),
+                                         ps.ref_masks.empty() ? -1 : mask_id.at(ps.ref_masks)});
+  return true;
+}
+
+bool collect_interval_records_loaded(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& pairs,
+                                     std::vector<PairRecords>& out) {
+  const double t1 = now_s();
+  out.assign(pairs.size(), PairRecords());
+  if (pairs.empty() || !loaded.loaded) return !loaded.loaded ? false : true;
+  Pool pool(pairs_threads());
+  walk_pairs_for_records(pool, loaded.loaded->in, names, pairs, out);
   g_times.table_fill = now_s() - t1;
   return true;
 }

@@ -60,6 +60,7 @@ int colate_interval_fit_groups(int, int, int, const long long*, const colate_int
   return nodev();
 }
 double colate_interval_fit_groups_kernel_seconds(void) { return 0.0; }
+double colate_interval_fit_samples_kernel_seconds(void) { return 0.0; }
 int colate_shard_bounds(int B, int nranks, int rank, int* lo, int* hi) {
   const int base = B / nranks, rem = B % nranks;
   *lo = rank * base + (rank < rem ? rank : rem);
@@ -82,6 +83,13 @@ int colate_bootstrap_em_batch_allgather(void*, int, int, int, int, const double*
                                         const double*, const double*, const double*, const double*, const double*, int, int,
                                         double, double, double*, int*, double*, int*) { return nodev(); }
 }
+
+// the pair walk on the device (interval_walk.h; colate_interval_walk and colate_interval_fit_samples end here): none in this build
+#include "interval_walk.h"
+namespace colate_iw {
+int walk_view_device(const View&, long long, long long*, int*, colate_ic::IntervalRec*, int*) { return nodev(); }
+int fit_samples_view_device(const View&, const FitArgs&) { return nodev(); }
+}  // namespace colate_iw
 
 // the age sampling on the device (fill_device.h): there is none in this build, the host code samples
 #include "fill_device.h"

@@ -332,6 +332,85 @@ int colate_interval_fit_groups_host(int G, int B, int E, const long long* rec_of
                                     int* out_R, long long* out_dropped, double* out_rates, int* out_iters, double* out_loglik,
                                     int* out_flags, int math);
 
+/* ---- the pair walk over per-sample walk indices: every pair of a sample list (csrc/interval_walk.h) ----
+ * What a pair's walk needs of a sample is one 8-byte entry per .mut row (colate_walk_idx: the position of the sample's
+ * record in front of the row's lower bound, -2 for none, and the lower bound's counts where position and alleles match,
+ * else 0, 0), so N samples need N such arrays, not N^2 arrays of records.  Inputs: the rows of C chromosomes back to
+ * back, chromosome c owning rows [row_off[c], row_off[c + 1]), row_off[0] = 0, positions not negative and not
+ * descending within a chromosome; idx[S][n], n = row_off[C]; masks[M][words], one bit per row (set: the row passes), each
+ * chromosome starting on a 64-bit word (words = the sum over c of ceil(rows of c / 64); bit i & 63 of word i >> 6 of the
+ * chromosome is its row i); pairs[P] of sample ids and mask ids (-1: no mask).
+ * The walk, per pair and chromosome, rows in order, states searched = ref_pass = -1, pos(-1) = -1: a row whose bit is
+ * clear in the target's or the reference's mask changes nothing; otherwise ref_from = searched, searched = i, and with
+ * r = idx[reference][i] the row is skipped if r.DAF == 0 or r.prev_bp < pos(ref_from); otherwise tgt_from = ref_pass,
+ * ref_pass = i, and with t = idx[target][i] it is skipped if (t.DAF | t.AAF) == 0 or t.prev_bp < pos(tgt_from);
+ * otherwise it is used.  A used row is one colate_interval_rec: begin = (float)max(age_begin, 0), end = age_end,
+ * f = roundf((float)((double)(float)t.DAF / ((t.DAF + t.AAF) / 2.0))), w_sh = (double)(f * (float)r.DAF) /
+ * (double)(r.DAF + r.AAF), w_ns the same from t.AAF.  Its block within the chromosome is k(pos) = (pos - 1) /
+ * num_bases_per_block (0 for pos <= 0); a chromosome has k(pos of its last used row) + 1 blocks, or 1 without a used
+ * row; block[] numbers them through the pair's chromosomes, nb[p] is their number.  Records are ordered by chromosome,
+ * then row.  This is, byte for byte, what the engine's walk of `--mode mut_interval` collects for the pair.
+ * Out: rec_off[P + 1] (rec_off[0] = 0), nb[P], and the pairs' records and blocks back to back in recs / block, which
+ * have room for cap records.  A total above cap is COLATE_ELIMIT with the needed total in colate_last_error(); nothing
+ * is written then.
+ * colate_interval_walk runs two passes on one stream of the calling thread's device (csrc/interval_walk_kernel.hip: one
+ * workgroup per (pair, chromosome) walks colate_interval_walk_tile() rows at a time; a count pass, the offsets formed on
+ * the host, a write pass); COLATE_ENODEVICE without a device, there is no fall-back.  _host: the host twin, a plain loop,
+ * the same bytes.
+ * Refused (COLATE_EINVAL, before anything is staged): NULL pointers, C, S or P < 1, M < 0, a sample or mask id out of
+ * range, decreasing offsets, num_bases_per_block < 1, a position at or above 2^31 - num_bases_per_block, a negative or
+ * descending position.
+ * Speed: tools/interval_samples_bench.py is the measurement (README). */
+typedef struct colate_walk_row {
+  int pos;
+  float age_begin, age_end;
+} colate_walk_row;
+typedef struct colate_walk_idx {
+  int prev_bp;
+  unsigned short DAF, AAF;
+} colate_walk_idx;
+typedef struct colate_walk_pair {
+  int target, reference;           /* sample ids */
+  int target_mask, reference_mask; /* mask ids, -1: none */
+} colate_walk_pair;
+int colate_interval_walk(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx, int M,
+                         const unsigned long long* masks, int P, const colate_walk_pair* pairs, int num_bases_per_block, long long cap,
+                         long long* rec_off, int* nb, colate_interval_rec* recs, int* block);
+int colate_interval_walk_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx, int M,
+                              const unsigned long long* masks, int P, const colate_walk_pair* pairs, int num_bases_per_block,
+                              long long cap, long long* rec_off, int* nb, colate_interval_rec* recs, int* block);
+int colate_interval_walk_tile(void); /* diagnostic: rows per step of a workgroup of the walk kernel (no device needed) */
+
+/* The walk, then colate_interval_fit_groups on its records (group p = pair p), with the records never leaving the device:
+ * per chunk of pairs the write pass of the walk puts the records and the per-(pair, block) record ranges where the cells
+ * kernel reads them.  epochs[E] and init_rates[E] serve all pairs.  The call draws every pair's block weights itself, as
+ * the command line does: pair p's [B][nb[p]] from a fresh std::mt19937 on `seed` through colate_bootstrap_weights, once
+ * nb is known -- one host wait after the count pass, which also sizes the chunks: runs of consecutive pairs whose dense
+ * cell sums fit COLATE_INTERVAL_GROUPS_CELLS_MB and whose records (28 bytes each with the cell index) fit
+ * COLATE_INTERVAL_WALK_RECS_MB megabytes (default COLATE_INTERVAL_WALK_RECS_MB_DEFAULT); a larger pair goes alone.
+ * Out, per pair: out_nb, out_used (its records), and out_R, out_dropped, out_rates[P][B][E], out_iters / out_loglik /
+ * out_flags[P][B] -- in every bit what colate_interval_fit_groups returns on the records of colate_interval_walk with
+ * those weights.  _host: colate_interval_walk_host followed by colate_interval_fit_groups_host (math as there).
+ * Refused: what colate_interval_walk refuses; B or E < 1, epochs, starting rates and iteration limits as
+ * colate_bootstrap_em_interval_batch refuses them (epochs[0] must not lie behind the first point of the age grid);
+ * COLATE_ELIMIT: E above 1024, B above 65535, P x B at or above 2^31, a pair with more than COLATE_INTERVAL_MAX_BLOCKS
+ * blocks.  The library forms the records itself (weights in [0, 2], blocks not decreasing), so the sums are bounded
+ * analytically and no record is scanned on the host.
+ * colate_interval_fit_samples_kernel_seconds: as colate_interval_fit_groups_kernel_seconds, with both walk passes. */
+#define COLATE_INTERVAL_WALK_RECS_MB_DEFAULT 4096
+int colate_interval_fit_samples(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx, int M,
+                                const unsigned long long* masks, int P, const colate_walk_pair* pairs, int num_bases_per_block, int B,
+                                int E, const double* epochs, const double* init_rates, unsigned int seed, int max_iter, int min_iter,
+                                double rel_tol, double rate_floor, int* out_nb, long long* out_used, int* out_R, long long* out_dropped,
+                                double* out_rates, int* out_iters, double* out_loglik, int* out_flags);
+int colate_interval_fit_samples_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                                     int M, const unsigned long long* masks, int P, const colate_walk_pair* pairs,
+                                     int num_bases_per_block, int B, int E, const double* epochs, const double* init_rates,
+                                     unsigned int seed, int max_iter, int min_iter, double rel_tol, double rate_floor, int* out_nb,
+                                     long long* out_used, int* out_R, long long* out_dropped, double* out_rates, int* out_iters,
+                                     double* out_loglik, int* out_flags, int math);
+double colate_interval_fit_samples_kernel_seconds(void);
+
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
 int colate_age_grid(double* age_grid, int cap);
@@ -578,7 +657,17 @@ int colate_coalrate_main(int argc, char** argv);
  * --target_mask, --reference_mask, --coal, --ranks, --target_age and --reference_age are refused by name; a line without coal=
  * needs --bins.  stderr: per pair `Pair i / P: T x R: Number of blocks: n`, then `Pair i ` in front of the single run's
  * `Number of rows`, `SNPs beyond the age grid` and `Bootstrap k: Total iterations` lines.  A pair that uses no SNP within the
- * age grid gets no file and an error line naming it; the others are written and the exit code is 1. */
+ * age grid gets no file and an error line naming it; the others are written and the exit code is 1.
+ * `--mode mut_interval --samples LIST --mut P -o PREFIX [--chr FILE] (--bins x,y,s | --coal FILE)` with the same fit options: LIST
+ * has `NAME FILE.colate.in [mask=PREFIX] [role=target|reference]` lines (default role: both; blank lines skipped); every (target
+ * line, reference line) of different lines, targets outermost, is fitted and written to PREFIX_<target NAME>_<reference NAME>.coal,
+ * byte for byte the file `--pairs` writes for that pair given the expanded list.  The pairs are walked on the device over the
+ * files' walk indices (colate_interval_fit_samples; its host twin without a device or with COLATE_DEVICE_INTERVAL=0); where a
+ * sample has no walk index, or with COLATE_DEVICE_INTERVAL_WALK=0, the expanded list takes the `--pairs` path after one line on
+ * stderr.  A repeated or missing NAME, a NAME with '/', an unknown key or role, an age token and a list without a target or
+ * without a reference are errors naming the line; --pairs, --rows, --target_tmp, --reference_tmp, --write_rows, --target_mask,
+ * --reference_mask, --ranks, --target_age and --reference_age are refused by name.  stderr: the `Pair i ...` lines of `--pairs`
+ * and `S samples and M masks staged, P pairs walked on the device`. */
 int colate_mut_main(int argc, char** argv);
 
 #ifdef __cplusplus
