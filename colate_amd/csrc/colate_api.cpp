@@ -12,8 +12,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
-#include <limits>
 #include <memory>
 #include <string>
 #include <vector>
@@ -22,10 +20,7 @@
 #include "colate_internal.h"
 #include "em_job.hpp"
 #include "em_kernels.h"
-#include "device_stage.hpp"
 #include "interval_cells.h"
-#include "interval_groups.h"
-#include "interval_walk.h"
 
 static_assert(COLATE_FLAG_NAN == 1 && COLATE_FLAG_NEG == 2 && COLATE_FLAG_MAXITER == 4 && COLATE_FLAG_UNRESOLVED == 8 &&
                   COLATE_UNRESOLVED_SHIFT == 8, "flags");
@@ -175,7 +170,7 @@ struct WorkspaceOwner {
   }
 };
 static thread_local WorkspaceOwner g_ws_owner;
-#define g_ws (g_ws_owner.ws)
+ArenaStore& thread_workspace() { return g_ws_owner.ws; }
 
 int Arena::commit() {
   auto round_up = [](size_t b) { return (b + 255) & ~size_t(255); };
@@ -349,7 +344,7 @@ static int run_here(const EmJob& job, const char* range_name) {
   if (int rc = ensure_device()) return rc;
   if (job.R == 0) return COLATE_OK;
   ProfRange range(range_name);
-  Arena arena(g_ws);
+  Arena arena(thread_workspace());
   int status = 0;
   if (int rc = enqueue_rows(job, 0, job.R, arena, &status)) return rc;
   return finish_rows(arena, status);
@@ -530,7 +525,7 @@ int colate_em_batch_rows_sharded(int num_devices, const int* devices, int B, int
 }
 
 int colate_release_workspace(void) {
-  g_ws.release();
+  thread_workspace().release();
   return COLATE_OK;
 }
 
@@ -621,7 +616,7 @@ int colate_em_estep(int B, int E, int A, const double* age_grid, const double* c
   if (int rc = ensure_device()) return rc;
   if (B == 0) return COLATE_OK;
   const size_t nBA = (size_t)B * A, nBE = (size_t)B * E;
-  Arena st(g_ws);
+  Arena st(thread_workspace());
   const int i_grid = st.in(age_grid, A), i_sh = st.in(cnt_shared, nBA), i_ns = st.in(cnt_notshared, nBA);
   const int i_ep = st.in(epochs, E), i_rates = st.in(rates, nBE);
   const int o_num = st.out(num_acc, nBE), o_den = st.out(den_acc, nBE), o_ll = st.out(loglik, B), o_flags = st.out(flags, B);
@@ -648,7 +643,7 @@ int colate_em_interval_calls(int R, int E, const int* kinds, const double* age_b
     return COLATE_OK;
   }
   ProfRange range("colate_em_interval_calls: H2D + interval E-step kernel + D2H");
-  Arena st(g_ws);
+  Arena st(thread_workspace());
   const int i_kind = st.in(kinds, R), i_a0 = st.in(age_begin, R), i_a1 = st.in(age_end, R);
   const int i_ep = st.in(epochs, nE), i_rates = st.in(rates, nE), i_w = st.in(weights, weights ? (size_t)R : 0);
   const int o_num = st.out(out_num, nRE), o_den = st.out(out_den, nRE), o_ll = st.out(out_logl, R), o_flags = st.out(out_flags, R);
@@ -674,7 +669,7 @@ int colate_em_interval_batch(int B, int R, int E, const int* kinds, const double
   if (int rc = ensure_device()) return rc;
   ProfRange range("colate_em_interval_batch: H2D + interval EM kernel + D2H");
   const size_t nE = (size_t)E, nBE = (size_t)B * E;
-  Arena st(g_ws);
+  Arena st(thread_workspace());
   const int i_kind = st.in(kinds, R), i_a0 = st.in(age_begin, R), i_a1 = st.in(age_end, R);
   const int i_w = st.in(weights, (size_t)B * R), i_ep = st.in(epochs, nE), i_init = st.in(init_rates, nE);
   const int o_rates = st.out(out_rates, nBE), o_iters = st.out(out_iters, B), o_ll = st.out(out_loglik, B), o_flags = st.out(out_flags, B);
@@ -701,7 +696,7 @@ int colate_bootstrap_em_interval_batch(int B, int nb, int R, int E, const int* k
   if (int rc = ensure_device()) return rc;
   ProfRange range("colate_bootstrap_em_interval_batch: H2D + row bootstrap kernel + interval EM kernel + D2H");
   const size_t nE = (size_t)E, nBE = (size_t)B * E;
-  Arena st(g_ws);
+  Arena st(thread_workspace());
   const int i_kind = st.in(kinds, R), i_a0 = st.in(age_begin, R), i_a1 = st.in(age_end, R);
   const int i_bw = st.in(block_weights, (size_t)B * nb), i_tab = st.in(tables, (size_t)nb * R);
   const int i_ep = st.in(epochs, nE), i_init = st.in(init_rates, nE);
@@ -732,7 +727,7 @@ int colate_interval_cells(long long n, const colate_interval_rec* recs, const in
   block_ranges(n, block, nb, off.data());
   std::vector<double> cells((size_t)nb * 2 * kCells);
   std::vector<unsigned long long> nd((size_t)nb);
-  Arena st(g_ws);
+  Arena st(thread_workspace());
   const int i_recs = st.in(recs, (size_t)n), i_off = st.in(off.data(), off.size()), i_T = st.in(T, (size_t)kBins);
   const int s_idx = st.scratch<int>((size_t)n);
   const int o_cells = st.out(cells.data(), cells.size()), o_nd = st.out(nd.data(), nd.size());
@@ -750,456 +745,4 @@ int colate_interval_cells(long long n, const colate_interval_rec* recs, const in
   return R;
 }
 
-static thread_local double g_interval_groups_kernel_s = 0.0;
-double colate_interval_fit_groups_kernel_seconds(void) { return g_interval_groups_kernel_s; }
-
 }  // extern "C"
-
-namespace {
-
-// Where the records of a chunk of groups come from: the caller's host arrays (colate_interval_fit_groups) or the write
-// pass of the pair walk (colate_interval_fit_samples).
-struct GroupRecords {
-  virtual ~GroupRecords() = default;
-  // the staging is kernels, to be timed with the chunk's other kernels (not copies)
-  virtual bool kernels() const = 0;
-  // On `stream`: the records of groups [g0, g1) at d_recs and, for the chunk's segments (group, block) in order, the nseg + 1
-  // record ranges at d_off (seg_off[j]: the first segment of group g0 + j; n: the chunk's records).
-  virtual int stage(int g0, int g1, const std::vector<int>& seg_off, long long n, colate_ic::IntervalRec* d_recs, long long* d_off,
-                    hipStream_t stream) = 0;
-};
-
-struct HostGroupRecords : GroupRecords {
-  const long long* rec_off;
-  const colate_interval_rec* recs;
-  const int *block, *nb;
-  std::deque<std::vector<long long>> offs;  // per chunk, alive until the call ends: its copy is asynchronous
-  HostGroupRecords(const long long* ro, const colate_interval_rec* r, const int* b, const int* n) : rec_off(ro), recs(r), block(b), nb(n) {}
-  bool kernels() const override { return false; }
-  int stage(int g0, int g1, const std::vector<int>&, long long n, colate_ic::IntervalRec* d_recs, long long* d_off,
-            hipStream_t stream) override {
-    using namespace colate_ic;
-    const long long r0 = rec_off[g0];
-    offs.emplace_back();
-    std::vector<long long>& coff = offs.back();
-    for (int g = g0; g < g1; g++) {
-      const long long ng_recs = rec_off[g + 1] - rec_off[g];
-      std::vector<long long> off((size_t)nb[g] + 1);
-      block_ranges(ng_recs, ng_recs ? block + rec_off[g] : nullptr, nb[g], off.data());
-      for (int k = 0; k < nb[g]; k++) coff.push_back(rec_off[g] - r0 + off[(size_t)k]);
-    }
-    coff.push_back(n);
-    if (n) HIP_TRY(hipMemcpyAsync(d_recs, recs + r0, sizeof(IntervalRec) * (size_t)n, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_off, coff.data(), sizeof(long long) * coff.size(), hipMemcpyHostToDevice, stream));
-    return COLATE_OK;
-  }
-};
-
-// Many groups' cells, rows and fits in one pass (include/colate_amd.h), after the checks.  One stream (the workspace's); the groups
-// go through the cells, the row pick and the row bootstrap in chunks whose dense cell sums fit a budget (and whose records fit
-// max_chunk_recs), and the only thing the host waits for before the results is each chunk's R and dropped counts, which size the
-// chunk's W; then one launch fits all groups.  epochs / init_rates: [G][E].  Adds the kernels' seconds to g_interval_groups_kernel_s.
-int fit_groups_core(int G, int B, int E, const long long* rec_off, const int* nb, const double* block_weights, const double* epochs,
-                    const double* init_rates, int max_iter, int min_iter, double rel_tol, double rate_floor, long long max_chunk_recs,
-                    GroupRecords& src, const float* T, int* out_R, long long* out_dropped, double* out_rates, int* out_iters,
-                    double* out_loglik, int* out_flags) {
-  using namespace colate_ic;
-  double grid[COLATE_MAX_AGE_BINS];
-  if (colate_age_grid(grid, COLATE_MAX_AGE_BINS) != kBins) return fail(COLATE_EINVAL, "the age grid has not %d points", kBins);
-
-  // ---- the chunks: runs of consecutive groups whose segments (group, block) fit the budget; a larger group goes alone
-  constexpr size_t kSegBytes = sizeof(double) * 2 * kCells;
-  long long budget_mb = COLATE_INTERVAL_GROUPS_CELLS_MB_DEFAULT;
-  if (const char* e = std::getenv("COLATE_INTERVAL_GROUPS_CELLS_MB")) budget_mb = std::max(0LL, std::atoll(e));
-  const size_t budget_segs = std::max<size_t>(1, (size_t)budget_mb * (1u << 20) / kSegBytes);
-  struct Chunk {
-    int g0 = 0, g1 = 0;  // groups [g0, g1)
-    std::vector<int> seg_off, cap;
-    std::vector<long long> row_off;
-    std::vector<int> R;
-    std::vector<long long> dropped;
-    std::vector<ColateIntervalRowsJob> jobs;
-  };
-  std::vector<Chunk> chunks;
-  size_t max_segs = 0, max_groups = 0;
-  long long max_recs = 0;
-  for (int g = 0; g < G;) {
-    Chunk c;
-    c.g0 = g;
-    size_t segs = 0;
-    do segs += (size_t)nb[g++];
-    while (g < G && g - c.g0 < 65535 && segs + (size_t)nb[g] <= budget_segs && rec_off[g + 1] - rec_off[c.g0] <= max_chunk_recs);
-    c.g1 = g;
-    max_segs = std::max(max_segs, segs), max_groups = std::max(max_groups, (size_t)(c.g1 - c.g0));
-    max_recs = std::max(max_recs, rec_off[c.g1] - rec_off[c.g0]);
-    chunks.push_back(std::move(c));
-  }
-
-  if (int rc = g_ws.reserve(256, 256)) return rc;  // (the workspace's stream)
-  hipStream_t stream = g_ws.stream;
-  struct SyncAtExit {  // nothing that the stream still reads or writes is freed before it is idle
-    hipStream_t s;
-    ~SyncAtExit() { (void)hipStreamSynchronize(s); }
-  };
-  DeviceBuffers buf;
-  struct Events {  // pairs of events around the kernels, for colate_interval_fit_groups_kernel_seconds
-    std::vector<hipEvent_t> ev;
-    ~Events() {
-      for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    hipError_t mark(hipStream_t s) {
-      hipEvent_t e;
-      if (hipError_t rc = hipEventCreate(&e)) return rc;
-      ev.push_back(e);
-      return hipEventRecord(e, s);
-    }
-  } events;
-  const SyncAtExit sync_at_exit{stream};
-  size_t bw_total = 0;
-  std::vector<size_t> bw_off((size_t)G);
-  for (int g = 0; g < G; g++) bw_off[(size_t)g] = bw_total, bw_total += (size_t)B * nb[g];
-  const size_t GB = (size_t)G * B, GE = (size_t)G * E;
-  // what lives for the whole call
-  float* d_T = nullptr;
-  double *d_grid = nullptr, *d_bw = nullptr, *d_ep = nullptr, *d_init = nullptr, *d_rates = nullptr, *d_ll = nullptr;
-  int *d_iters = nullptr, *d_flags = nullptr;
-  ColateIntervalGroup* d_desc = nullptr;
-  HIP_TRY(buf.device(d_T, kBins)); HIP_TRY(buf.device(d_grid, kBins)); HIP_TRY(buf.device(d_bw, bw_total));
-  HIP_TRY(buf.device(d_ep, GE)); HIP_TRY(buf.device(d_init, GE)); HIP_TRY(buf.device(d_desc, (size_t)G));
-  HIP_TRY(buf.device(d_rates, GB * E)); HIP_TRY(buf.device(d_ll, GB)); HIP_TRY(buf.device(d_iters, GB)); HIP_TRY(buf.device(d_flags, GB));
-  // the scratch of a chunk, sized for the largest and used by one chunk after the other in stream order
-  IntervalRec* d_recs = nullptr;
-  int *d_idx = nullptr, *d_seg_off = nullptr, *d_cap = nullptr, *d_R = nullptr;
-  long long *d_off = nullptr, *d_row_off = nullptr, *d_dropped = nullptr;
-  unsigned long long* d_seg_dropped = nullptr;
-  double* d_cells = nullptr;
-  unsigned char* d_flagbytes = nullptr;
-  ColateIntervalRowsJob* d_jobs = nullptr;
-  HIP_TRY(buf.device(d_recs, (size_t)max_recs)); HIP_TRY(buf.device(d_idx, (size_t)max_recs)); HIP_TRY(buf.device(d_off, max_segs + 1));
-  HIP_TRY(buf.device(d_cells, max_segs * 2 * kCells)); HIP_TRY(buf.device(d_seg_dropped, max_segs));
-  HIP_TRY(buf.device(d_seg_off, max_groups + 1)); HIP_TRY(buf.device(d_cap, max_groups)); HIP_TRY(buf.device(d_row_off, max_groups));
-  HIP_TRY(buf.device(d_R, max_groups)); HIP_TRY(buf.device(d_dropped, max_groups)); HIP_TRY(buf.device(d_jobs, max_groups));
-  HIP_TRY(buf.device(d_flagbytes, max_groups * 2 * kCells));
-  auto h2d = [stream](void* dst, const void* src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
-  };
-  HIP_TRY(h2d(d_T, T, sizeof(float) * kBins)); HIP_TRY(h2d(d_grid, grid, sizeof(double) * kBins));
-  HIP_TRY(h2d(d_bw, block_weights, sizeof(double) * bw_total));
-  HIP_TRY(h2d(d_ep, epochs, sizeof(double) * GE)); HIP_TRY(h2d(d_init, init_rates, sizeof(double) * GE));
-
-  std::vector<ColateIntervalGroup> desc((size_t)G);
-  std::vector<int> R_all((size_t)G);
-  std::vector<long long> dropped_all((size_t)G);
-  bool any_rows = false;
-  for (Chunk& c : chunks) {
-    const int ng = c.g1 - c.g0;
-    const long long n = rec_off[c.g1] - rec_off[c.g0];
-    c.seg_off.assign(1, 0), c.cap.resize((size_t)ng), c.row_off.resize((size_t)ng);
-    long long rows_cap = 0;
-    for (int j = 0; j < ng; j++) {
-      const int g = c.g0 + j;
-      const long long ng_recs = rec_off[g + 1] - rec_off[g];
-      c.seg_off.push_back(c.seg_off.back() + nb[g]);
-      c.cap[(size_t)j] = row_cap(ng_recs), c.row_off[(size_t)j] = rows_cap;
-      rows_cap += c.cap[(size_t)j];
-    }
-    const int nseg = c.seg_off.back();
-    // the chunk's rows stay for the fit: room for every group's cap
-    int *d_cell_of_row = nullptr, *d_kinds = nullptr;
-    double *d_a0 = nullptr, *d_a1 = nullptr;
-    HIP_TRY(buf.device(d_cell_of_row, (size_t)rows_cap)); HIP_TRY(buf.device(d_kinds, (size_t)rows_cap));
-    HIP_TRY(buf.device(d_a0, (size_t)rows_cap)); HIP_TRY(buf.device(d_a1, (size_t)rows_cap));
-    HIP_TRY(h2d(d_seg_off, c.seg_off.data(), sizeof(int) * c.seg_off.size()));
-    HIP_TRY(h2d(d_cap, c.cap.data(), sizeof(int) * (size_t)ng)); HIP_TRY(h2d(d_row_off, c.row_off.data(), sizeof(long long) * (size_t)ng));
-    if (src.kernels()) HIP_TRY(events.mark(stream));
-    if (int rc = src.stage(c.g0, c.g1, c.seg_off, n, d_recs, d_off, stream)) return rc;
-    if (!src.kernels()) HIP_TRY(events.mark(stream));
-    hipError_t e = colate_interval_cells_launch(n, d_recs, d_off, nseg, d_T, d_idx, d_cells, d_seg_dropped, stream);
-    if (e != hipSuccess) return hip_fail(e, "interval cells kernel launch");
-    e = colate_interval_rows_launch(ng, d_cells, d_seg_off, d_seg_dropped, d_grid, d_row_off, d_cap, d_flagbytes, d_cell_of_row, d_kinds,
-                                    d_a0, d_a1, d_R, d_dropped, stream);
-    if (e != hipSuccess) return hip_fail(e, "interval rows kernel launch");
-    HIP_TRY(events.mark(stream));
-    c.R.resize((size_t)ng), c.dropped.resize((size_t)ng);
-    HIP_TRY(hipMemcpyAsync(c.R.data(), d_R, sizeof(int) * (size_t)ng, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(c.dropped.data(), d_dropped, sizeof(long long) * (size_t)ng, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));  // the one wait of the chunk: R sizes its W
-    size_t w_total = 0;
-    int max_R = 0;
-    for (int j = 0; j < ng; j++) {
-      if (c.R[(size_t)j] < 0 || c.R[(size_t)j] > c.cap[(size_t)j])
-        return fail(COLATE_EHIP, "group %d: the row pick returned %d rows, room for %d", c.g0 + j, c.R[(size_t)j], c.cap[(size_t)j]);
-      w_total += (size_t)B * c.R[(size_t)j], max_R = std::max(max_R, c.R[(size_t)j]);
-    }
-    double* d_W = nullptr;
-    HIP_TRY(buf.device(d_W, w_total));
-    c.jobs.resize((size_t)ng);
-    size_t w_at = 0;
-    for (int j = 0; j < ng; j++) {
-      const int g = c.g0 + j, R = c.R[(size_t)j];
-      const long long ro = c.row_off[(size_t)j];
-      c.jobs[(size_t)j] = ColateIntervalRowsJob{c.seg_off[(size_t)j], nb[g], R, d_cell_of_row + ro, d_bw + bw_off[(size_t)g], d_W + w_at};
-      desc[(size_t)g] = ColateIntervalGroup{R, d_kinds + ro, d_a0 + ro, d_a1 + ro, d_W + w_at, d_ep + (size_t)g * E, d_init + (size_t)g * E};
-      R_all[(size_t)g] = R, dropped_all[(size_t)g] = c.dropped[(size_t)j];
-      w_at += (size_t)B * R;
-    }
-    if (max_R > 0) {
-      any_rows = true;
-      HIP_TRY(h2d(d_jobs, c.jobs.data(), sizeof(ColateIntervalRowsJob) * (size_t)ng));
-      HIP_TRY(events.mark(stream));
-      e = colate_bootstrap_rows_groups_launch(ng, B, max_R, d_jobs, d_cells, stream);
-      if (e != hipSuccess) return hip_fail(e, "grouped row bootstrap kernel launch");
-      HIP_TRY(events.mark(stream));
-    }
-  }
-
-  // ---- one fit launch for all groups; a group without rows keeps its starting rates
-  std::vector<double> rates(GB * E), ll(GB);
-  std::vector<int> iters(GB), flags(GB);
-  if (any_rows) {
-    HIP_TRY(h2d(d_desc, desc.data(), sizeof(ColateIntervalGroup) * (size_t)G));
-    HIP_TRY(events.mark(stream));
-    const hipError_t e = colate_em_interval_fit_groups_launch(G, B, E, d_desc, max_iter, min_iter, rel_tol, rate_floor, d_rates, d_iters,
-                                                              d_ll, d_flags, stream);
-    if (e != hipSuccess) return hip_fail(e, "grouped interval EM kernel launch");
-    HIP_TRY(events.mark(stream));
-    HIP_TRY(hipMemcpyAsync(rates.data(), d_rates, sizeof(double) * GB * E, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(ll.data(), d_ll, sizeof(double) * GB, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(iters.data(), d_iters, sizeof(int) * GB, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), d_flags, sizeof(int) * GB, hipMemcpyDeviceToHost, stream));
-  }
-  HIP_TRY(hipStreamSynchronize(stream));
-  for (size_t i = 0; i + 1 < events.ev.size(); i += 2) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, events.ev[i], events.ev[i + 1]) == hipSuccess) g_interval_groups_kernel_s += ms * 1e-3;
-  }
-  for (int g = 0; g < G; g++) {
-    const size_t o = (size_t)g * B;
-    if (R_all[(size_t)g] == 0)
-      no_rows_results(B, E, init_rates + (size_t)g * E, rates.data() + o * E, iters.data() + o, ll.data() + o, flags.data() + o);
-  }
-  std::memcpy(out_R, R_all.data(), sizeof(int) * (size_t)G), std::memcpy(out_dropped, dropped_all.data(), sizeof(long long) * (size_t)G);
-  std::memcpy(out_rates, rates.data(), sizeof(double) * GB * E), std::memcpy(out_loglik, ll.data(), sizeof(double) * GB);
-  std::memcpy(out_iters, iters.data(), sizeof(int) * GB), std::memcpy(out_flags, flags.data(), sizeof(int) * GB);
-  return COLATE_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int colate_interval_fit_groups(int G, int B, int E, const long long* rec_off, const colate_interval_rec* recs, const int* block,
-                               const int* nb, const double* block_weights, const double* epochs, const double* init_rates,
-                               int max_iter, int min_iter, double rel_tol, double rate_floor, int* out_R, long long* out_dropped,
-                               double* out_rates, int* out_iters, double* out_loglik, int* out_flags) {
-  using namespace colate_ic;
-  float T[kBins];
-  if (int rc = build_thresholds(T)) return rc;
-  if (int rc = check_groups_args(G, B, E, rec_off, recs, block, nb, block_weights, epochs, init_rates, max_iter, min_iter, rel_tol,
-                                 rate_floor, T, out_R, out_dropped, out_rates, out_iters, out_loglik, out_flags))
-    return rc;
-  if (int rc = ensure_device()) return rc;
-  ProfRange range("colate_interval_fit_groups: per chunk H2D + cells + row pick + row bootstrap; one interval EM kernel + D2H");
-  g_interval_groups_kernel_s = 0.0;
-  HostGroupRecords src(rec_off, recs, block, nb);
-  return fit_groups_core(G, B, E, rec_off, nb, block_weights, epochs, init_rates, max_iter, min_iter, rel_tol, rate_floor,
-                         std::numeric_limits<long long>::max(), src, T, out_R, out_dropped, out_rates, out_iters, out_loglik, out_flags);
-}
-
-double colate_interval_fit_samples_kernel_seconds(void) { return g_interval_groups_kernel_s; }
-
-}  // extern "C"
-
-// ---- the pair walk on the device (interval_walk.h)
-namespace colate_iw {
-
-namespace {
-
-// The inputs of a view, resident on the device: uploaded once per call, chromosome by chromosome from where they lie.
-struct Resident {
-  DeviceBuffers buf;
-  DeviceInputs in;
-  std::vector<long long> word_off;
-  int upload(const View& v, hipStream_t stream) {
-    const int C = v.C;
-    in.C = C, in.S = v.S, in.M = v.M, in.P = v.P, in.nbpb = v.nbpb, in.n = v.row_off[C];
-    word_off.resize((size_t)C + 1);
-    in.words = mask_words(C, v.row_off, word_off.data());
-    long long *d_row_off = nullptr, *d_word_off = nullptr;
-    Row* d_rows = nullptr;
-    Idx* d_idx = nullptr;
-    unsigned long long* d_masks = nullptr;
-    Pair* d_pairs = nullptr;
-    HIP_TRY(buf.device(d_row_off, (size_t)C + 1)); HIP_TRY(buf.device(d_word_off, (size_t)C + 1));
-    HIP_TRY(buf.device(d_rows, (size_t)in.n)); HIP_TRY(buf.device(d_idx, (size_t)v.S * in.n));
-    HIP_TRY(buf.device(d_masks, (size_t)v.M * in.words)); HIP_TRY(buf.device(d_pairs, (size_t)v.P));
-    auto h2d = [stream](void* dst, const void* src, size_t bytes) {
-      return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
-    };
-    HIP_TRY(h2d(d_row_off, v.row_off, sizeof(long long) * ((size_t)C + 1)));
-    HIP_TRY(h2d(d_word_off, word_off.data(), sizeof(long long) * ((size_t)C + 1)));
-    HIP_TRY(h2d(d_pairs, v.pairs, sizeof(Pair) * (size_t)v.P));
-    for (int c = 0; c < C; c++) {
-      const size_t nc = (size_t)(v.row_off[c + 1] - v.row_off[c]), wc = (size_t)(word_off[(size_t)c + 1] - word_off[(size_t)c]);
-      HIP_TRY(h2d(d_rows + v.row_off[c], v.rows[c], sizeof(Row) * nc));
-      for (int s = 0; s < v.S; s++) HIP_TRY(h2d(d_idx + (size_t)s * in.n + v.row_off[c], v.idx[(size_t)s * C + c], sizeof(Idx) * nc));
-      for (int m = 0; m < v.M; m++)
-        HIP_TRY(h2d(d_masks + (size_t)m * in.words + word_off[(size_t)c], v.masks[(size_t)m * C + c], sizeof(unsigned long long) * wc));
-    }
-    in.row_off = d_row_off, in.word_off = d_word_off, in.rows = d_rows, in.idx = d_idx, in.masks = d_masks, in.pairs = d_pairs;
-    return COLATE_OK;
-  }
-};
-
-struct StreamSync {  // nothing that the stream still reads or writes is freed before it is idle
-  hipStream_t s;
-  ~StreamSync() { (void)hipStreamSynchronize(s); }
-};
-
-// seconds between two events recorded on a stream that is idle by now
-double seconds_between(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.f;
-  return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms * 1e-3 : 0.0;
-}
-
-// The count pass for all pairs and the one host wait: cnt / last_block [P][C] on the host.
-int count_pass(const Resident& res, hipStream_t stream, std::vector<int>& cnt, std::vector<int>& last, DeviceBuffers& buf, double* seconds) {
-  const size_t PC = (size_t)res.in.P * res.in.C;
-  int *d_cnt = nullptr, *d_last = nullptr;
-  HIP_TRY(buf.device(d_cnt, PC)); HIP_TRY(buf.device(d_last, PC));
-  hipEvent_t e0, e1;
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  struct Ev {
-    hipEvent_t a, b;
-    ~Ev() { (void)hipEventDestroy(a), (void)hipEventDestroy(b); }
-  } ev{e0, e1};
-  HIP_TRY(hipEventRecord(e0, stream));
-  if (hipError_t e = count_launch(res.in, 0, res.in.P, d_cnt, d_last, stream)) return hip_fail(e, "interval walk count kernel launch");
-  HIP_TRY(hipEventRecord(e1, stream));
-  cnt.resize(PC), last.resize(PC);
-  HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * PC, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(last.data(), d_last, sizeof(int) * PC, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (seconds) *seconds += seconds_between(e0, e1);
-  return COLATE_OK;
-}
-
-// the records of a chunk of pairs straight from the write pass
-struct WalkGroupRecords : GroupRecords {
-  const Resident& res;
-  const long long* rec_off;
-  const std::vector<int>&cnt, &blk0;
-  long long* d_rec0;
-  int *d_blk0, *d_seg0;
-  struct Host {
-    std::vector<long long> rec0;
-    std::vector<int> seg0;
-  };
-  std::deque<Host> hosts;  // per chunk, alive until the call ends: their copies are asynchronous
-  WalkGroupRecords(const Resident& r, const long long* ro, const std::vector<int>& c, const std::vector<int>& b, long long* dr, int* db, int* ds)
-      : res(r), rec_off(ro), cnt(c), blk0(b), d_rec0(dr), d_blk0(db), d_seg0(ds) {}
-  bool kernels() const override { return true; }
-  int stage(int g0, int g1, const std::vector<int>& seg_off, long long n, colate_ic::IntervalRec* d_recs, long long* d_off,
-            hipStream_t stream) override {
-    const int C = res.in.C;
-    const size_t k0 = (size_t)g0 * C, nk = (size_t)(g1 - g0) * C;
-    hosts.emplace_back();
-    Host& h = hosts.back();
-    h.rec0.resize(nk), h.seg0.resize(nk);
-    long long at = 0;
-    for (size_t k = 0; k < nk; k++) {
-      h.rec0[k] = at, at += cnt[k0 + k];
-      h.seg0[k] = seg_off[k / (size_t)C] + blk0[k0 + k];
-    }
-    if (at != n) return fail(COLATE_EHIP, "the walk's counts do not add up to the chunk's records (%lld, %lld)", at, n);
-    HIP_TRY(hipMemcpyAsync(d_rec0, h.rec0.data(), sizeof(long long) * nk, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_seg0, h.seg0.data(), sizeof(int) * nk, hipMemcpyHostToDevice, stream));
-    if (hipError_t e = write_launch(res.in, g0, g1, d_rec0, d_blk0 + k0, d_seg0, d_recs, nullptr, d_off, seg_off.back(), n, stream))
-      return hip_fail(e, "interval walk write kernel launch");
-    return COLATE_OK;
-  }
-};
-
-}  // namespace
-
-int walk_view_device(const View& v, long long cap, long long* rec_off, int* nb, colate_ic::IntervalRec* recs, int* block) {
-  if (int rc = check_walk_outputs(cap, rec_off, nb, recs, block)) return rc;
-  if (int rc = check_view(v)) return rc;
-  if (int rc = ensure_device()) return rc;
-  ProfRange range("colate_interval_walk: H2D + count pass + write pass + D2H");
-  if (int rc = g_ws.reserve(256, 256)) return rc;  // (the workspace's stream)
-  hipStream_t stream = g_ws.stream;
-  Resident res;
-  DeviceBuffers buf;
-  const StreamSync sync_at_exit{stream};
-  if (int rc = res.upload(v, stream)) return rc;
-  std::vector<int> cnt, last;
-  if (int rc = count_pass(res, stream, cnt, last, buf, nullptr)) return rc;
-  const size_t PC = (size_t)v.P * v.C;
-  std::vector<int> blk0(PC), nbs((size_t)v.P);
-  std::vector<long long> off((size_t)v.P + 1), rec0(PC);
-  if (int rc = finish_counts(v.P, v.C, cnt.data(), last.data(), blk0.data(), nbs.data(), off.data())) return rc;
-  const long long total = off[(size_t)v.P];
-  if (int rc = check_capacity(total, cap)) return rc;
-  long long at = 0;
-  for (size_t k = 0; k < PC; k++) rec0[k] = at, at += cnt[k];
-  long long* d_rec0 = nullptr;
-  int *d_blk0 = nullptr, *d_block = nullptr;
-  colate_ic::IntervalRec* d_recs = nullptr;
-  HIP_TRY(buf.device(d_rec0, PC)); HIP_TRY(buf.device(d_blk0, PC)); HIP_TRY(buf.device(d_recs, (size_t)total)); HIP_TRY(buf.device(d_block, (size_t)total));
-  HIP_TRY(hipMemcpyAsync(d_rec0, rec0.data(), sizeof(long long) * PC, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_blk0, blk0.data(), sizeof(int) * PC, hipMemcpyHostToDevice, stream));
-  if (hipError_t e = write_launch(res.in, 0, v.P, d_rec0, d_blk0, nullptr, d_recs, d_block, nullptr, 0, total, stream))
-    return hip_fail(e, "interval walk write kernel launch");
-  if (total) {
-    HIP_TRY(hipMemcpyAsync(recs, d_recs, sizeof(colate_ic::IntervalRec) * (size_t)total, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(block, d_block, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, stream));
-  }
-  HIP_TRY(hipStreamSynchronize(stream));
-  std::memcpy(rec_off, off.data(), sizeof(long long) * off.size()), std::memcpy(nb, nbs.data(), sizeof(int) * nbs.size());
-  return COLATE_OK;
-}
-
-int fit_samples_view_device(const View& v, const FitArgs& a) {
-  if (int rc = check_fit_args(v, a)) return rc;
-  float T[colate_ic::kBins];
-  if (int rc = colate_ic::build_thresholds(T)) return rc;
-  if (int rc = ensure_device()) return rc;
-  ProfRange range("colate_interval_fit_samples: H2D + walk count pass; per chunk walk write pass + cells + row pick + row bootstrap; one interval EM kernel + D2H");
-  if (int rc = g_ws.reserve(256, 256)) return rc;  // (the workspace's stream)
-  hipStream_t stream = g_ws.stream;
-  Resident res;
-  DeviceBuffers buf;
-  const StreamSync sync_at_exit{stream};
-  g_interval_groups_kernel_s = 0.0;
-  if (int rc = res.upload(v, stream)) return rc;
-  std::vector<int> cnt, last;
-  if (int rc = count_pass(res, stream, cnt, last, buf, &g_interval_groups_kernel_s)) return rc;
-  const int P = v.P, C = v.C;
-  const size_t PC = (size_t)P * C;
-  std::vector<int> blk0(PC), nb((size_t)P);
-  std::vector<long long> off((size_t)P + 1);
-  if (int rc = finish_counts(P, C, cnt.data(), last.data(), blk0.data(), nb.data(), off.data())) return rc;
-  std::vector<double> weights;
-  if (int rc = draw_pair_weights(a.seed, a.B, P, nb.data(), weights)) return rc;
-  long long budget_mb = COLATE_INTERVAL_WALK_RECS_MB_DEFAULT;
-  if (const char* e = std::getenv("COLATE_INTERVAL_WALK_RECS_MB")) budget_mb = std::max(0LL, std::atoll(e));
-  const long long max_chunk_recs = std::max<long long>(1, budget_mb * (1LL << 20) / (long long)(sizeof(colate_ic::IntervalRec) + sizeof(int)));
-  long long* d_rec0 = nullptr;
-  int *d_blk0 = nullptr, *d_seg0 = nullptr;
-  HIP_TRY(buf.device(d_rec0, PC)); HIP_TRY(buf.device(d_blk0, PC)); HIP_TRY(buf.device(d_seg0, PC));
-  HIP_TRY(hipMemcpyAsync(d_blk0, blk0.data(), sizeof(int) * PC, hipMemcpyHostToDevice, stream));
-  WalkGroupRecords src(res, off.data(), cnt, blk0, d_rec0, d_blk0, d_seg0);
-  std::vector<double> ep((size_t)P * a.E), init((size_t)P * a.E);
-  for (int p = 0; p < P; p++)
-    std::memcpy(&ep[(size_t)p * a.E], a.epochs, sizeof(double) * a.E), std::memcpy(&init[(size_t)p * a.E], a.init_rates, sizeof(double) * a.E);
-  if (int rc = fit_groups_core(P, a.B, a.E, off.data(), nb.data(), weights.data(), ep.data(), init.data(), a.max_iter, a.min_iter, a.rel_tol,
-                               a.rate_floor, max_chunk_recs, src, T, a.out_R, a.out_dropped, a.out_rates, a.out_iters, a.out_loglik,
-                               a.out_flags))
-    return rc;
-  for (int p = 0; p < P; p++) a.out_nb[p] = nb[(size_t)p], a.out_used[p] = off[(size_t)p + 1] - off[(size_t)p];
-  return COLATE_OK;
-}
-
-}  // namespace colate_iw

@@ -110,6 +110,8 @@ struct ArenaStore {
   int reserve(size_t dbytes, size_t hbytes);  // on the current device; a store that lived on another one starts over
   void release();                             // on the owning device; the caller's current device is restored
 };
+// the calling thread's workspace (colate_api.cpp): kept between calls, freed by colate_release_workspace or with the thread
+ArenaStore& thread_workspace();
 
 // One staged call on a store: declare what goes in, what stays on the device and what comes out, commit() (one H2D
 // copy), launch on stream(), finish() (one D2H copy, one synchronise, scatter to the caller).

@@ -2,6 +2,7 @@
 // both forms run before anything is staged, and the host twin, which walks the groups through the host twins of the two
 // calls it stands for (colate_interval_cells_host, colate_bootstrap_em_interval_batch_host).
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <string>
@@ -44,6 +45,24 @@ int group_fail(int rc, int g) {
 }
 
 }  // namespace
+
+std::vector<std::pair<int, int>> plan_chunks(int G, const int* nb, const long long* rec_off, size_t budget_segs, long long max_chunk_recs) {
+  budget_segs = std::max<size_t>(1, budget_segs);
+  std::vector<std::pair<int, int>> chunks;
+  for (int g = 0; g < G;) {
+    const int g0 = g;
+    size_t segs = 0;
+    do segs += (size_t)nb[g++];
+    while (g < G && g - g0 < 65535 && segs + (size_t)nb[g] <= budget_segs && rec_off[g + 1] - rec_off[g0] <= max_chunk_recs);
+    chunks.emplace_back(g0, g);
+  }
+  return chunks;
+}
+
+long long env_budget_mb(const char* name, long long default_mb) {
+  const char* e = std::getenv(name);
+  return e ? std::max(0LL, std::atoll(e)) : default_mb;
+}
 
 void no_rows_results(int B, int E, const double* init_rates, double* rates, int* iters, double* loglik, int* flags) {
   for (int b = 0; b < B; b++) {

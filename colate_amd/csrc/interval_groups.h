@@ -1,6 +1,10 @@
 // colate_amd/csrc/interval_groups.h -- what the two forms of colate_interval_fit_groups share (internal to libcolate_amd.so):
 // the argument checks that run before anything is staged, and the host twin's pieces (interval_groups.cpp).
 #pragma once
+#include <cstddef>
+#include <utility>
+#include <vector>
+
 #include "colate_amd.h"
 #include "interval_cells.h"
 
@@ -22,6 +26,20 @@ int check_groups_args(int G, int B, int E, const long long* rec_off, const Inter
 
 // room for the rows of a group of n records: a record flags at most one cell of each kind
 inline int row_cap(long long n) { return (int)(2 * n < COLATE_INTERVAL_MAX_ROWS ? 2 * n : COLATE_INTERVAL_MAX_ROWS); }
+
+// The chunks of a grouped device call: runs [g0, g1) of consecutive groups that share device scratch, covering [0, G) in order.
+// A chunk holds at most 65535 groups (a grid dimension), at most budget_segs segments (nb summed; clamped to at least 1) and at
+// most max_chunk_recs records (rec_off[g1] - rec_off[g0]); a group that exceeds a budget goes alone.
+std::vector<std::pair<int, int>> plan_chunks(int G, const int* nb, const long long* rec_off, size_t budget_segs, long long max_chunk_recs);
+// a budget in MB from the environment variable `name` (negative: 0), or default_mb where it is not set
+long long env_budget_mb(const char* name, long long default_mb);
+
+// row[E] repeated to [G][E]: one set of epochs or starting rates for all groups, as the grouped fit takes them
+inline std::vector<double> repeat_rows(const double* row, int E, int G) {
+  std::vector<double> out;
+  for (int g = 0; g < G; g++) out.insert(out.end(), row, row + E);
+  return out;
+}
 
 // the results of a group without rows: its starting rates, and zeros
 void no_rows_results(int B, int E, const double* init_rates, double* rates, int* iters, double* loglik, int* flags);

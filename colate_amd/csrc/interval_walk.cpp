@@ -10,6 +10,7 @@
 
 #include "colate_amd.h"
 #include "colate_internal.h"
+#include "interval_groups.h"
 #include "interval_walk.h"
 
 using colate::fail;
@@ -221,9 +222,7 @@ int fit_samples_view_host(const View& v, const FitArgs& a, int math) {
   std::vector<colate_ic::IntervalRec> recs((size_t)off[(size_t)v.P]);
   std::vector<int> block(recs.size());
   for (int p = 0; p < v.P; p++) host_write(v, p, blk0.data() + (size_t)p * v.C, recs.data() + off[(size_t)p], block.data() + off[(size_t)p]);
-  std::vector<double> ep((size_t)v.P * a.E), init((size_t)v.P * a.E);
-  for (int p = 0; p < v.P; p++)
-    std::memcpy(&ep[(size_t)p * a.E], a.epochs, sizeof(double) * a.E), std::memcpy(&init[(size_t)p * a.E], a.init_rates, sizeof(double) * a.E);
+  const std::vector<double> ep = colate_ic::repeat_rows(a.epochs, a.E, v.P), init = colate_ic::repeat_rows(a.init_rates, a.E, v.P);
   if (int rc = colate_interval_fit_groups_host(v.P, a.B, a.E, off.data(), recs.data(), block.data(), nb.data(), weights.data(), ep.data(),
                                                init.data(), a.max_iter, a.min_iter, a.rel_tol, a.rate_floor, a.out_R, a.out_dropped,
                                                a.out_rates, a.out_iters, a.out_loglik, a.out_flags, math))

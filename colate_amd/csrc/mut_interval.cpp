@@ -133,6 +133,11 @@ bool read_interval_rows(const std::string& path, double epoch0, IntervalRows& ou
   return true;
 }
 
+static int api_error(int rc) {
+  std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
+  return 1;
+}
+
 // The used SNPs of --mut / --target_tmp / --reference_tmp as rows and per-block tables (interval_cells.h): the engine's walk
 // (mut_pairs.cpp) gives the records, colate_interval_cells -- or its host twin after a line on stderr -- the cells.
 static bool rows_from_mut(const Options& opt, bool on_host, const std::string& host_why, IntervalRows& out) {
@@ -159,10 +164,7 @@ static bool rows_from_mut(const Options& opt, bool on_host, const std::string& h
   const int R = (on_host ? colate_interval_cells_host : colate_interval_cells)(
       (long long)recs.size(), recs.data(), blocks.data(), nb, cap, out.kinds.data(), out.age_begin.data(), out.age_end.data(),
       out.tables.data(), &dropped);
-  if (R < 0) {
-    std::cerr << "Error: " << colate_last_error() << " (" << R << ")" << std::endl;
-    return false;
-  }
+  if (R < 0) return api_error(R), false;
   out.nb = nb, out.R = R;
   out.kinds.resize((size_t)R), out.age_begin.resize((size_t)R), out.age_end.resize((size_t)R), out.tables.resize((size_t)nb * R);
   for (int k = 0; k < nb; k++) out.block_ids.push_back(k);
@@ -196,20 +198,16 @@ static bool write_interval_rows(const std::string& path, const IntervalRows& row
   return std::fclose(f) == 0;
 }
 
-// What the list forms of `--mode mut_interval` share: the fit options, the choice between device and host twin, and what is
-// said and written per pair.
-struct ListRun {
+// What the runs of `--mode mut_interval` share (one pair, --pairs, --samples): the fit options, the choice between device and
+// host twin, epochs and starting rates, and what is said per bootstrap and written per pair.
+struct FitRun {
   double years_per_gen = 28.0;
   int B = 1, max_iter = COLATE_DEFAULT_MAX_ITER, min_iter = COLATE_DEFAULT_MIN_ITER;
   int seed = 0;
   std::string host_why;  // not empty: the host twins run
   int status = 0;
 };
-static int api_error(int rc) {
-  std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-  return 1;
-}
-static bool list_run_options(const Options& opt, ListRun& run) {
+static bool fit_run_options(const Options& opt, FitRun& run) {
   run.seed = std::time(0) + getpid();  // coal.cpp:3158; one seed for the whole run
   if (opt.has("years_per_gen")) run.years_per_gen = std::stof(opt.get("years_per_gen"));
   if (opt.has("seed")) run.seed = std::stoi(opt.get("seed"));
@@ -223,7 +221,7 @@ static bool list_run_options(const Options& opt, ListRun& run) {
   return true;
 }
 // device or host twin (false after an error message)
-static bool list_run_device(const Options& opt, ListRun& run) {
+static bool fit_run_device(const Options& opt, FitRun& run) {
   if (const char* e = std::getenv("COLATE_DEVICE_INTERVAL"))
     if (std::string(e) == "0") run.host_why = "COLATE_DEVICE_INTERVAL=0";
   if (run.host_why.empty() && colate_device_count() <= 0) run.host_why = "no device";
@@ -231,11 +229,34 @@ static bool list_run_device(const Options& opt, ListRun& run) {
     if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc), false;
   return true;
 }
+// Epochs and starting rates at age 0, as for `mut` with a modern sample (coal.cpp:3501-3646): those of the .coal file where one
+// is given, else --bins with the default starting rate.  False after `lead` and the library's message on stderr.
+static bool fit_run_epochs(const Options& opt, const FitRun& run, const std::string* coal, const std::string& lead, std::vector<double>& epochs,
+                           std::vector<double>& init, int& ep_null) {
+  epochs.assign(COLATE_MAX_EPOCHS, 0.0), init.assign(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
+  ep_null = 0;
+  const int E = coal ? colate_epochs_from_coal(coal->c_str(), 0.0, epochs.data(), init.data(), COLATE_MAX_EPOCHS)
+                     : colate_epochs_from_bins(opt.get("bins").c_str(), 0.0, run.years_per_gen, epochs.data(), COLATE_MAX_EPOCHS, &ep_null);
+  if (E <= 0) {
+    std::cerr << lead << colate_last_error() << std::endl;
+    return false;
+  }
+  epochs.resize(E), init.resize(E);
+  return true;
+}
+// the lines of a fit's B bootstraps: `lead` in front of each, `who` in front of "bootstrap" in a warning
+static void say_bootstraps(const std::string& lead, const std::string& who, int B, const int* iters, const int* flags) {
+  for (int i = 0; i < B; i++) {
+    std::cerr << lead << "Bootstrap " << i + 1 << ": Total iterations " << iters[i] << std::endl;
+    if (flags[i] & (COLATE_FLAG_NAN | COLATE_FLAG_NEG))
+      std::cerr << "Warning: " << who << "bootstrap " << i + 1 << " produced NaN or negative sufficient statistics." << std::endl;
+  }
+}
 static void say_blocks(size_t p, size_t P, const PairSpec& ps, int nb) {
   std::cerr << "Pair " << p + 1 << " / " << P << ": " << ps.target << " x " << ps.reference << ": Number of blocks: " << nb << std::endl;
 }
 // the lines of pair p after its fit, and its .coal (rates: [B][E] of the pair)
-static void report_pair(ListRun& run, size_t p, const PairSpec& ps, int R, long long dropped, int E, const double* epochs, int ep_null,
+static void report_pair(FitRun& run, size_t p, const PairSpec& ps, int R, long long dropped, int E, const double* epochs, int ep_null,
                         const double* rates, const int* iters, const int* flags) {
   const std::string lead = "Pair " + std::to_string(p + 1) + " ";
   std::cerr << lead << "Number of rows: " << R << std::endl;
@@ -246,11 +267,7 @@ static void report_pair(ListRun& run, size_t p, const PairSpec& ps, int R, long 
     run.status = 1;
     return;
   }
-  for (int i = 0; i < run.B; i++) {
-    std::cerr << lead << "Bootstrap " << i + 1 << ": Total iterations " << iters[i] << std::endl;
-    if (flags[i] & (COLATE_FLAG_NAN | COLATE_FLAG_NEG))
-      std::cerr << "Warning: pair " << p + 1 << " bootstrap " << i + 1 << " produced NaN or negative sufficient statistics." << std::endl;
-  }
+  say_bootstraps(lead, "pair " + std::to_string(p + 1) + " ", run.B, iters, flags);
   if (colate_write_coal((ps.output + ".coal").c_str(), run.B, E, epochs, rates, 0, ep_null)) {
     std::cerr << "Error: " << colate_last_error() << std::endl;
     run.status = 1;
@@ -263,26 +280,18 @@ static void report_pair(ListRun& run, size_t p, const PairSpec& ps, int R, long 
 // cells, rows, block bootstrap and fit of all of them on the device, or the host twin after a line on stderr.  Every pair
 // draws its block weights from a generator of its own on the run's seed, as its single run does, so OUTPUT.coal is that
 // run's, byte for byte.
-static int fit_pair_list(const Options& opt, ListRun& run, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+static int fit_pair_list(const Options& opt, FitRun& run, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
                          const std::vector<PairSpec>& pairs, const WalkInputs* loaded) {
   const size_t P = pairs.size();
-  const int B = run.B, max_iter = run.max_iter, min_iter = run.min_iter, seed = run.seed;
-  const std::string& host_why = run.host_why;
-  int& status = run.status;
+  const int B = run.B;
 
-  // ---- epochs and starting rates per pair, as the single run forms them
+  // ---- epochs and starting rates per pair: the line's coal=, else --bins, else --coal
   std::vector<std::vector<double>> epochs(P), init(P);
   std::vector<int> ep_null(P, 0);
   for (size_t p = 0; p < P; p++) {
-    epochs[p].assign(COLATE_MAX_EPOCHS, 0.0), init[p].assign(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
-    const std::string& coal = !pairs[p].coal.empty() ? pairs[p].coal : !opt.has("bins") && opt.has("coal") ? opt.get("coal") : pairs[p].coal;
-    const int E = !coal.empty() ? colate_epochs_from_coal(coal.c_str(), 0.0, epochs[p].data(), init[p].data(), COLATE_MAX_EPOCHS)
-                                : colate_epochs_from_bins(opt.get("bins").c_str(), 0.0, run.years_per_gen, epochs[p].data(), COLATE_MAX_EPOCHS, &ep_null[p]);
-    if (E <= 0) {
-      std::cerr << "Error: pair " << p + 1 << ": " << colate_last_error() << std::endl;
-      return 1;
-    }
-    epochs[p].resize(E), init[p].resize(E);
+    const std::string* coal = !pairs[p].coal.empty() ? &pairs[p].coal : nullptr;
+    if (!coal && !opt.has("bins") && opt.has("coal") && !opt.get("coal").empty()) coal = &opt.get("coal");
+    if (!fit_run_epochs(opt, run, coal, "Error: pair " + std::to_string(p + 1) + ": ", epochs[p], init[p], ep_null[p])) return 1;
   }
 
   // ---- the records of all pairs
@@ -300,7 +309,7 @@ static int fit_pair_list(const Options& opt, ListRun& run, const std::vector<std
     if (!recs[p].walked || recs[p].nb < 1) {
       std::cerr << "Error: pair " << p + 1 << " (" << pairs[p].target << " x " << pairs[p].reference << "): "
                 << (recs[p].walked ? "no genome block (no chromosome was read)." : "the SNPs of the pair could not be walked.") << std::endl;
-      usable[p] = 0, status = 1;
+      usable[p] = 0, run.status = 1;
     }
   }
 
@@ -314,7 +323,7 @@ static int fit_pair_list(const Options& opt, ListRun& run, const std::vector<std
     classes[c].push_back(p);
   }
   std::cerr << "Maximising likelihood using EM.. " << std::endl;
-  if (!host_why.empty()) std::cerr << "interval cells and fits on the host (" << host_why << ")" << std::endl;
+  if (!run.host_why.empty()) std::cerr << "interval cells and fits on the host (" << run.host_why << ")" << std::endl;
   for (const std::vector<size_t>& cls : classes) {
     const int G = (int)cls.size(), E = (int)epochs[cls[0]].size();
     std::vector<long long> rec_off(1, 0);
@@ -323,7 +332,7 @@ static int fit_pair_list(const Options& opt, ListRun& run, const std::vector<std
     for (size_t p : cls) {
       rec_off.push_back(rec_off.back() + (long long)recs[p].recs.size());
       nb.push_back(recs[p].nb);
-      std::mt19937 rng(seed);  // (coal.cpp:3350-3357: every pair from the run's seed, as its single run)
+      std::mt19937 rng(run.seed);  // (coal.cpp:3350-3357: every pair from the run's seed, as its single run)
       const size_t at = weights.size();
       weights.resize(at + (size_t)B * recs[p].nb);
       if (int rc = colate_bootstrap_weights(&rng, B, recs[p].nb, weights.data() + at)) return api_error(rc);
@@ -342,17 +351,17 @@ static int fit_pair_list(const Options& opt, ListRun& run, const std::vector<std
     std::vector<int> R(G), iters(GB), flags(GB);
     std::vector<long long> dropped(G);
     std::vector<double> rates(GB * E), ll(GB);
-    const int rc = host_why.empty()
+    const int rc = run.host_why.empty()
                        ? colate_interval_fit_groups(G, B, E, rec_off.data(), all_recs.data(), all_blocks.data(), nb.data(), weights.data(),
-                                                    g_ep.data(), g_init.data(), max_iter, min_iter, COLATE_DEFAULT_REL_TOL,
+                                                    g_ep.data(), g_init.data(), run.max_iter, run.min_iter, COLATE_DEFAULT_REL_TOL,
                                                     COLATE_DEFAULT_RATE_FLOOR, R.data(), dropped.data(), rates.data(), iters.data(),
                                                     ll.data(), flags.data())
                        : colate_interval_fit_groups_host(G, B, E, rec_off.data(), all_recs.data(), all_blocks.data(), nb.data(),
-                                                         weights.data(), g_ep.data(), g_init.data(), max_iter, min_iter,
+                                                         weights.data(), g_ep.data(), g_init.data(), run.max_iter, run.min_iter,
                                                          COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, R.data(), dropped.data(),
                                                          rates.data(), iters.data(), ll.data(), flags.data(), 1);
     if (rc) return api_error(rc);
-    if (host_why.empty()) kernel_s += colate_interval_fit_groups_kernel_seconds();
+    if (run.host_why.empty()) kernel_s += colate_interval_fit_groups_kernel_seconds();
     for (int g = 0; g < G; g++) {
       const size_t p = cls[(size_t)g];
       report_pair(run, p, pairs[p], R[g], dropped[g], E, epochs[p].data(), ep_null[p], rates.data() + (size_t)g * B * E,
@@ -362,7 +371,7 @@ static int fit_pair_list(const Options& opt, ListRun& run, const std::vector<std
   if (g_times.on)
     std::cerr << "Timing: interval pairs: inputs and walks " << t_fit - t_start << " s, cells, rows and fits " << StageTimes::now() - t_fit
               << " s (device kernels " << kernel_s << " s); " << total_recs << " records uploaded" << std::endl;
-  if (status) return status;
+  if (run.status) return run.status;
   print_usage_footer();
   return 0;
 }
@@ -403,9 +412,9 @@ static int run_mut_interval_pairs(const Options& opt) {
       }
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating coalescence rates from interval-dated mutations for " << pairs.size() << " pairs.." << std::endl;
-  ListRun run;
-  if (!list_run_options(opt, run)) return 1;
-  if (!list_run_device(opt, run)) return 1;
+  FitRun run;
+  if (!fit_run_options(opt, run)) return 1;
+  if (!fit_run_device(opt, run)) return 1;
   return fit_pair_list(opt, run, names, mut_files, pairs, nullptr);
 }
 
@@ -504,9 +513,9 @@ static int run_mut_interval_samples(const Options& opt) {
   const size_t P = pairs.size();
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating coalescence rates from interval-dated mutations for " << P << " pairs.." << std::endl;
-  ListRun run;
-  if (!list_run_options(opt, run)) return 1;
-  if (!list_run_device(opt, run)) return 1;
+  FitRun run;
+  if (!fit_run_options(opt, run)) return 1;
+  if (!fit_run_device(opt, run)) return 1;
   if (const char* e = std::getenv("COLATE_DEVICE_INTERVAL_WALK"))
     if (std::string(e) == "0") {
       std::cerr << "pairs walked on the host through the engine (COLATE_DEVICE_INTERVAL_WALK=0)" << std::endl;
@@ -520,16 +529,11 @@ static int run_mut_interval_samples(const Options& opt) {
     return fit_pair_list(opt, run, names, mut_files, pairs, &in);
   }
 
-  // ---- one set of epochs and starting rates for all pairs, as the single run forms them
-  std::vector<double> epochs(COLATE_MAX_EPOCHS, 0.0), init(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
+  // ---- one set of epochs and starting rates for all pairs: --bins, else --coal
+  std::vector<double> epochs, init;
   int ep_null = 0;
-  const int E = opt.has("bins") ? colate_epochs_from_bins(opt.get("bins").c_str(), 0.0, run.years_per_gen, epochs.data(), COLATE_MAX_EPOCHS, &ep_null)
-                                : colate_epochs_from_coal(opt.get("coal").c_str(), 0.0, epochs.data(), init.data(), COLATE_MAX_EPOCHS);
-  if (E <= 0) {
-    std::cerr << "Error: " << colate_last_error() << std::endl;
-    return 1;
-  }
-  epochs.resize(E), init.resize(E);
+  if (!fit_run_epochs(opt, run, opt.has("bins") ? nullptr : &opt.get("coal"), "Error: ", epochs, init, ep_null)) return 1;
+  const int E = (int)epochs.size();
 
   const bool on_host = !run.host_why.empty();
   std::cerr << in.S << " samples and " << in.M << " masks staged, " << P << " pairs walked on the " << (on_host ? "host" : "device")
@@ -586,41 +590,16 @@ int run_mut_interval(const Options& opt) {
   }
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating coalescence rates from interval-dated mutations.." << std::endl;
-  double years_per_gen = 28.0;
-  int B = 1, max_iter = COLATE_DEFAULT_MAX_ITER, min_iter = COLATE_DEFAULT_MIN_ITER;
-  int seed = std::time(0) + getpid();  // coal.cpp:3158
-  if (opt.has("years_per_gen")) years_per_gen = std::stof(opt.get("years_per_gen"));
-  if (opt.has("seed")) seed = std::stoi(opt.get("seed"));
-  if (opt.has("num_bootstraps")) B = std::stoi(opt.get("num_bootstraps"));
-  if (opt.has("max_iter")) max_iter = std::stoi(opt.get("max_iter"));
-  if (opt.has("min_iter")) min_iter = std::stoi(opt.get("min_iter"));
-  if (B < 1) {
-    std::cerr << "Error: --num_bootstraps must be at least 1." << std::endl;
-    return 1;
-  }
-  auto api_error = [](int rc) {
-    std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-    return 1;
-  };
-
-  // ---- epochs and starting rates, as for `mut` with a modern sample (coal.cpp:3501-3646)
-  std::vector<double> epochs(COLATE_MAX_EPOCHS, 0.0), init_rates(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
+  FitRun run;
+  if (!fit_run_options(opt, run)) return 1;
+  // ---- epochs and starting rates (--coal, else --bins; the library's message without a lead), then device or host twin
+  std::vector<double> epochs, init_rates;
   int ep_null = 0;
-  const int E = opt.has("coal") ? colate_epochs_from_coal(opt.get("coal").c_str(), 0.0, epochs.data(), init_rates.data(), COLATE_MAX_EPOCHS)
-                                : colate_epochs_from_bins(opt.get("bins").c_str(), 0.0, years_per_gen, epochs.data(), COLATE_MAX_EPOCHS, &ep_null);
-  if (E <= 0) {
-    std::cerr << colate_last_error() << std::endl;
-    return 1;
-  }
-  epochs.resize(E), init_rates.resize(E);
-
-  // ---- device or host twin (the cells step and the fit alike)
-  std::string host_why;
-  if (const char* e = std::getenv("COLATE_DEVICE_INTERVAL"))
-    if (std::string(e) == "0") host_why = "COLATE_DEVICE_INTERVAL=0";
-  if (host_why.empty() && colate_device_count() <= 0) host_why = "no device";
-  if (host_why.empty() && opt.has("device"))
-    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc);
+  if (!fit_run_epochs(opt, run, opt.has("coal") ? &opt.get("coal") : nullptr, "", epochs, init_rates, ep_null)) return 1;
+  const int E = (int)epochs.size();
+  if (!fit_run_device(opt, run)) return 1;
+  const int B = run.B, max_iter = run.max_iter, min_iter = run.min_iter;
+  const std::string& host_why = run.host_why;
 
   // ---- the rows and the per-block tables
   IntervalRows rows;
@@ -642,32 +621,25 @@ int run_mut_interval(const Options& opt) {
   }
 
   // ---- block weights (coal.cpp:3350-3357)
-  std::mt19937 rng(seed);
+  std::mt19937 rng(run.seed);
   std::vector<double> weights((size_t)B * nb);
   if (int rc = colate_bootstrap_weights(&rng, B, nb, weights.data())) return api_error(rc);
 
   std::cerr << "Maximising likelihood using EM.. " << std::endl;
   std::vector<double> rates((size_t)B * E), ll(B);
   std::vector<int> iters(B), flags(B);
-  int rc;
-  if (host_why.empty()) {
-    rc = colate_bootstrap_em_interval_batch(B, nb, R, E, rows.kinds.data(), rows.age_begin.data(), rows.age_end.data(),
-                                            weights.data(), rows.tables.data(), epochs.data(), init_rates.data(), max_iter,
-                                            min_iter, COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, rates.data(),
-                                            iters.data(), ll.data(), flags.data());
-  } else {
-    std::cerr << "interval fit on the host (" << host_why << ")" << std::endl;
-    rc = colate_bootstrap_em_interval_batch_host(B, nb, R, E, rows.kinds.data(), rows.age_begin.data(), rows.age_end.data(),
-                                                 weights.data(), rows.tables.data(), epochs.data(), init_rates.data(), max_iter,
-                                                 min_iter, COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, rates.data(),
-                                                 iters.data(), ll.data(), flags.data(), 1);
-  }
+  if (!host_why.empty()) std::cerr << "interval fit on the host (" << host_why << ")" << std::endl;
+  const int rc = host_why.empty()
+                     ? colate_bootstrap_em_interval_batch(B, nb, R, E, rows.kinds.data(), rows.age_begin.data(), rows.age_end.data(),
+                                                          weights.data(), rows.tables.data(), epochs.data(), init_rates.data(), max_iter,
+                                                          min_iter, COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR, rates.data(),
+                                                          iters.data(), ll.data(), flags.data())
+                     : colate_bootstrap_em_interval_batch_host(B, nb, R, E, rows.kinds.data(), rows.age_begin.data(), rows.age_end.data(),
+                                                               weights.data(), rows.tables.data(), epochs.data(), init_rates.data(),
+                                                               max_iter, min_iter, COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR,
+                                                               rates.data(), iters.data(), ll.data(), flags.data(), 1);
   if (rc) return api_error(rc);
-  for (int i = 0; i < B; i++) {
-    std::cerr << "Bootstrap " << i + 1 << ": Total iterations " << iters[i] << std::endl;
-    if (flags[i] & (COLATE_FLAG_NAN | COLATE_FLAG_NEG))
-      std::cerr << "Warning: bootstrap " << i + 1 << " produced NaN or negative sufficient statistics." << std::endl;
-  }
+  say_bootstraps("", "", B, iters.data(), flags.data());
   if (colate_write_coal((opt.get("output") + ".coal").c_str(), B, E, epochs.data(), rates.data(), 0, ep_null)) {
     std::cerr << "Error: " << colate_last_error() << std::endl;
     return 1;

@@ -7,7 +7,10 @@
 //     COLATE_EINVAL, name the group, and leave every output alone;
 //   * collect_interval_records_pairs over small synthetic inputs written here (two chromosomes of three genome blocks, two
 //     targets, one reference; a pair listed twice): every pair's records, blocks and block count are those of
-//     collect_interval_records for the pair alone, and the grouped host twin runs on them.
+//     collect_interval_records for the pair alone, and the grouped host twin runs on them;
+//   * plan_chunks, the rule by which the device form cuts the groups into chunks that share scratch: the cases the GPU tests
+//     assume (a segment budget of 3 over 1,3,5,2,1 and 1,1,1,3,1 blocks; budget 0), a record budget, the cap of 65535 groups per
+//     chunk, and random inputs against the rule's properties.
 // For the host sanitizer build (`make asan`: bin/interval_groups_check_asan, linked with tools/no_device_stubs.cpp); prints
 // "ok" and exits 0 when everything agrees.  Usage: interval_groups_check_asan DIR (an existing, writable directory).
 #include <algorithm>
@@ -20,6 +23,7 @@
 #include <vector>
 
 #include "colate_amd.h"
+#include "interval_groups.h"
 #include "mut_feeder.h"
 
 namespace {
@@ -142,6 +146,61 @@ bool write_inputs(const std::string& dir, const std::vector<std::string>& chroms
   return std::fclose(ta) == 0 && std::fclose(tb) == 0 && std::fclose(ra) == 0;
 }
 
+// ---- plan_chunks
+using Chunks = std::vector<std::pair<int, int>>;
+const size_t kNoSegLimit = ~(size_t)0 / 2;
+const long long kNoRecLimit = 0x7fffffffffffffffLL;
+
+// `per_group` records in every group
+std::vector<long long> even_rec_off(size_t G, long long per_group) {
+  std::vector<long long> off(G + 1);
+  for (size_t g = 0; g <= G; g++) off[g] = (long long)g * per_group;
+  return off;
+}
+int expect_chunks(const char* what, const std::vector<int>& nb, long long per_group, size_t budget_segs, long long max_recs, const Chunks& want) {
+  const std::vector<long long> off = even_rec_off(nb.size(), per_group);
+  const Chunks got = colate_ic::plan_chunks((int)nb.size(), nb.data(), off.data(), budget_segs, max_recs);
+  if (got == want) return 0;
+  std::fprintf(stderr, "plan_chunks %s:", what);
+  for (const auto& c : got) std::fprintf(stderr, " [%d, %d)", c.first, c.second);
+  std::fprintf(stderr, ", expected %zu chunks\n", want.size());
+  return 1;
+}
+// in order and without gaps over [0, G); a chunk of more than one group within both budgets and the cap
+int check_partition(const Chunks& ch, const std::vector<int>& nb, const std::vector<long long>& off, size_t budget_segs, long long max_recs) {
+  int at = 0, bad = 0;
+  for (const auto& c : ch) {
+    bad += c.first != at || c.second <= c.first;
+    at = c.second;
+    size_t segs = 0;
+    for (int g = c.first; g < c.second && g < (int)nb.size(); g++) segs += (size_t)nb[(size_t)g];
+    if (c.second - c.first > 1 && c.second <= (int)nb.size())
+      bad += segs > std::max<size_t>(1, budget_segs) || off[(size_t)c.second] - off[(size_t)c.first] > max_recs || c.second - c.first > 65535;
+  }
+  return bad + (at != (int)nb.size());
+}
+int check_plan_chunks() {
+  int bad = 0;
+  const std::vector<int> nb_a = {1, 3, 5, 2, 1}, nb_c = {1, 1, 1, 3, 1};
+  bad += expect_chunks("(a)", nb_a, 10, 3, kNoRecLimit, {{0, 1}, {1, 2}, {2, 3}, {3, 5}});
+  bad += expect_chunks("(b)", nb_a, 10, 0, kNoRecLimit, {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}});
+  bad += expect_chunks("(c)", nb_c, 10, 3, kNoRecLimit, {{0, 3}, {3, 4}, {4, 5}});
+  bad += expect_chunks("(d)", nb_c, 15000, kNoSegLimit, (1 << 20) / 28, {{0, 2}, {2, 4}, {4, 5}});
+  bad += expect_chunks("(e)", std::vector<int>(65536, 1), 0, kNoSegLimit, kNoRecLimit, {{0, 65535}, {65535, 65536}});
+  for (int trial = 0; trial < 200; trial++) {  // (f)
+    const size_t G = 1 + next() % 40;
+    std::vector<int> nb(G);
+    std::vector<long long> off(G + 1, (long long)(next() % 5));
+    for (size_t g = 0; g < G; g++) nb[g] = 1 + (int)(next() % 9), off[g + 1] = off[g] + (next() % 4 ? (long long)(next() % 1000) : 0);
+    const size_t budget_segs = next() % 4 ? next() % 30 : kNoSegLimit;
+    const long long max_recs = next() % 4 ? (long long)(next() % 3000) : kNoRecLimit;
+    const int b = check_partition(colate_ic::plan_chunks((int)G, nb.data(), off.data(), budget_segs, max_recs), nb, off, budget_segs, max_recs);
+    if (b) std::fprintf(stderr, "plan_chunks (f), trial %d: %d violations\n", trial, b);
+    bad += b;
+  }
+  return bad;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -149,7 +208,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "usage: %s DIR\n", argv[0]);
     return 2;
   }
-  int bad = 0;
+  int bad = check_plan_chunks();
   const int B = 3;
   std::vector<double> ep1(COLATE_MAX_EPOCHS);
   int ep_null = 0;
