@@ -88,6 +88,12 @@ SIGNATURES = {
                                                  c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint, c_int, c_int, c_double,
                                                  c_double] + [c_void_p] * 8 + [c_int]),
     "colate_interval_fit_samples_kernel_seconds": (c_double, []),
+    "colate_fill_samples": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                    ctypes.c_uint, ctypes.c_longlong] + [c_void_p] * 5),
+    "colate_fill_samples_host": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                         ctypes.c_uint, ctypes.c_longlong] + [c_void_p] * 6),
+    "colate_fill_samples_chunks": (c_int, []),
+    "colate_fill_samples_kernel_seconds": (c_double, []),
     "colate_age_grid": (c_int, [c_void_p, c_int]),
     "colate_epochs_from_bins": (c_int, [c_char_p, c_double, c_double, c_void_p, c_int, ip]),
     "colate_epochs_from_coal": (c_int, [c_char_p, c_double, c_void_p, c_void_p, c_int]),

@@ -548,6 +548,43 @@ def interval_fit_samples_kernel_seconds():
     return lib.colate_interval_fit_samples_kernel_seconds()
 
 
+def fill_samples(row_off, rows, idx, masks, pairs, num_bases_per_block, seed, A=185, device=True, cap_blocks=None):
+    """colate_fill_samples[_host]: the table fill of `--mode mut` for every pair of `pairs` over per-sample walk indices (the
+    inputs of interval_walk).  Returns a dict: nb [P], used [P], tables (a list of [nb[p]][4][A] arrays: shared, not shared,
+    shared row 0, not-shared row 0 per block), words [P] (32-bit words each pair's mt19937 on `seed` has given out at the end
+    of its fill), handed_back [P], and with device=False near_band [P] (None otherwise).  cap_blocks: the room given for
+    tables (default: every block the positions allow).  device=False: the host twin, the same bytes."""
+    args, keep = _walk_inputs(row_off, rows, idx, masks, pairs)
+    row_off_, rows_ = keep[0], keep[1]
+    P, A = keep[4].size, int(A)
+    nbpb = int(num_bases_per_block)
+    if cap_blocks is None:  # per chromosome at most the block of its last position, plus one
+        cap_blocks = 0
+        for c in range(row_off_.size - 1):
+            seg = rows_["pos"][row_off_[c]:row_off_[c + 1]]
+            cap_blocks += 1 + (max(int(seg.max()) - 1, 0) // max(nbpb, 1) if seg.size else 0)
+        cap_blocks *= P
+    cap_blocks = int(cap_blocks)
+    nb, used = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int64)
+    tables = np.zeros((max(cap_blocks, 0), 4, max(A, 0)))
+    words, handed, near = np.zeros(P, dtype=np.uint64), np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int32)
+    full = args + [nbpb, A, int(seed) & 0xffffffff, cap_blocks, _p(nb), _p(used), _p(tables), _p(words), _p(handed)]
+    check(lib.colate_fill_samples(*full) if device else lib.colate_fill_samples_host(*full, _p(near)))
+    off = np.concatenate([[0], np.cumsum(nb)])
+    return dict(nb=nb, used=used, tables=[tables[off[p]:off[p + 1]].copy() for p in range(P)], words=words, handed_back=handed,
+                near_band=None if device else near)
+
+
+def fill_samples_chunks():
+    """Chunks of the write pass in this thread's last fill_samples(device=True) (diagnostic)."""
+    return lib.colate_fill_samples_chunks()
+
+
+def fill_samples_kernel_seconds():
+    """Seconds the kernels of this thread's last fill_samples(device=True) took on the device."""
+    return lib.colate_fill_samples_kernel_seconds()
+
+
 def _stream_ptr(stream):
     if stream is None:
         import torch

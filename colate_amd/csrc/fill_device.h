@@ -91,3 +91,14 @@ class DeviceFill {
 };
 
 }  // namespace colate_drv
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+namespace colate_drv {
+// The same kernel on jobs and records that already lie on the device (csrc/fill_samples_kernel.hip forms them there): device
+// pointers throughout; U: the seed's uniform stream; g_lo / g_hi [A + 2]: the guard bands; tables [njobs][2][A] and flags [njobs]
+// are zeroed by the caller.  Asynchronous on `stream`.
+hipError_t fill_sample_launch(const FillJob* jobs, int njobs, const FillRec* recs, const double* U, const double* g_lo,
+                              const double* g_hi, int A, double* tables, int* flags, hipStream_t stream);
+}  // namespace colate_drv
+#endif

@@ -1,5 +1,7 @@
 // colate_amd/csrc/fill_kernel.hip -- the age sampling of the table fill on the GPU: see fill_device.h.
 // Reference: include/coal/coal.cpp:2260-2273 (age_begin <= sample age: the F path), 2279-2295 (the 100 draws of a SNP).
+// Two ways in: DeviceFill (records and jobs staged from the host: `--pairs`) and fill_sample_launch (records and jobs formed on
+// the device by the pair walk: `--samples`, fill_samples_kernel.hip).  One kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -143,6 +145,15 @@ __global__ __launch_bounds__(kJobsPerBlock* kWave) void fill_sample_kernel(const
 }
 
 }  // namespace
+
+hipError_t fill_sample_launch(const FillJob* jobs, int njobs, const FillRec* recs, const double* U, const double* g_lo,
+                              const double* g_hi, int A, double* tables, int* flags, hipStream_t stream) {
+  if (njobs < 1) return hipSuccess;
+  if (A < 1 || A > kSlots * kWave) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fill_sample_kernel, dim3((njobs + kJobsPerBlock - 1) / kJobsPerBlock), dim3(kJobsPerBlock * kWave), 0, stream, jobs,
+                     njobs, recs, U, g_lo, g_hi, A, tables, flags);
+  return hipGetLastError();
+}
 
 bool DeviceFill::fail(const char* what, int code) {
   char buf[256];

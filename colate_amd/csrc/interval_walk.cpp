@@ -135,6 +135,17 @@ void host_write(const View& v, int p, const int* blk0, colate_ic::IntervalRec* r
     });
 }
 
+void host_write_fill(const View& v, int p, const int* blk0, colate_drv::FillRec* recs, FillSide* side, int* block) {
+  long long at = 0;
+  for (int c = 0; c < v.C; c++)
+    walk_chromosome(v, p, c, [&](long long i, const Idx& t, const Idx& r) {
+      const Row& m = v.rows[c][i];
+      recs[at] = make_fill_rec(m, t, r, side[at]);
+      block[at] = blk0[c] + block_of_pos(m.pos, v.nbpb);
+      at++;
+    });
+}
+
 int finish_counts(int P, int C, const int* cnt, const int* last_block, int* blk0, int* nb, long long* rec_off) {
   std::vector<long long> nb64((size_t)P);
   offsets_from_counts(P, C, cnt, last_block, blk0, nb64.data(), rec_off);

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "colate_amd.h"
+#include "fill_device.h"
 #include "interval_cells.h"
 
 namespace colate_iw {
@@ -50,6 +51,31 @@ COLATE_IC_HD inline colate_ic::IntervalRec make_rec(const Row& m, const Idx& t, 
   f_AAF_target = roundf(f_AAF_target);
   const float p_sh = f_DAF_target * (float)DAF_ref, p_ns = f_AAF_target * (float)DAF_ref;
   return colate_ic::IntervalRec{(float)age_begin, m.age_end, (double)p_sh / (double)N_ref, (double)p_ns / (double)N_ref};
+}
+
+// The same used row as `--mode mut` samples it (Engine::use_snp, the table branch; coal.cpp:2221-2297 with age = ref_age = 0):
+// the record of fill_sample_kernel -- a hundredth of the weights, w_sh = +0.0 on the F path (age_begin <= 0) -- and, in `side`,
+// the un-divided pair that the F path adds to row 0 of the reference's A x A tables.  Every product, conversion and division is
+// a rounding of its own, as there.
+struct FillSide {
+  double e_sh, e_ns;
+};
+static_assert(sizeof(FillSide) == 16, "FillSide");
+COLATE_IC_HD inline colate_drv::FillRec make_fill_rec(const Row& m, const Idx& t, const Idx& r, FillSide& side) {
+  const int tgt_DAF = t.DAF, tgt_AAF = t.AAF, DAF_ref = r.DAF, N_ref = (int)r.DAF + (int)r.AAF;
+  const int N_target = tgt_DAF + tgt_AAF;
+  double age_begin = m.age_begin;
+  if (age_begin < 0.0) age_begin = 0.0;
+  float f_DAF_target = (float)tgt_DAF, f_AAF_target = (float)tgt_AAF;
+  f_DAF_target = (float)((double)f_DAF_target / (N_target / 2.0));
+  f_AAF_target = (float)((double)f_AAF_target / (N_target / 2.0));
+  f_DAF_target = roundf(f_DAF_target);
+  f_AAF_target = roundf(f_AAF_target);
+  const float p_sh = f_DAF_target * (float)DAF_ref, p_ns = f_AAF_target * (float)DAF_ref;
+  side.e_sh = (double)p_sh / (double)N_ref, side.e_ns = (double)p_ns / (double)N_ref;
+  const double hundredth = (double)N_ref * 100.0;
+  const double w_sh = age_begin <= 0.0 ? 0.0 : (double)p_sh / hundredth;
+  return colate_drv::FillRec{(float)age_begin, m.age_end, w_sh, (double)p_ns / hundredth};
 }
 
 // The inputs as both stages read them: chromosome c's rows are rows[c][0 .. row_off[c + 1] - row_off[c]); sample s's index
@@ -83,6 +109,8 @@ void offsets_from_counts(int P, int C, const int* cnt, const int* last_block, in
 int finish_counts(int P, int C, const int* cnt, const int* last_block, int* blk0, int* nb, long long* rec_off);
 // The host twin's write pass of pair p: its records and pair-relative blocks at recs / block (room for the pair's count).
 void host_write(const View& v, int p, const int* blk0, colate_ic::IntervalRec* recs, int* block);
+// ... with the records of the table fill (make_fill_rec): recs / side / block have room for the pair's count
+void host_write_fill(const View& v, int p, const int* blk0, colate_drv::FillRec* recs, FillSide* side, int* block);
 
 // colate_interval_walk[_host] on a view: rec_off[P + 1], nb[P], records and blocks back to back, room for cap records
 // (COLATE_ELIMIT with the needed total in the message where they do not fit).
@@ -141,5 +169,9 @@ hipError_t count_launch(const DeviceInputs& in, int p0, int p1, int* cnt, int* l
 hipError_t write_launch(const DeviceInputs& in, int p0, int p1, const long long* rec0, const int* blk0, const int* seg0,
                         colate_ic::IntervalRec* recs, int* block, long long* off, long long off_end, long long rec_end,
                         hipStream_t stream);
+// The same pass writing the records of the table fill and their side array (make_fill_rec); `off` as above.
+hipError_t write_fill_launch(const DeviceInputs& in, int p0, int p1, const long long* rec0, const int* blk0, const int* seg0,
+                             colate_drv::FillRec* recs, FillSide* side, long long* off, long long off_end, long long rec_end,
+                             hipStream_t stream);
 }  // namespace colate_iw
 #endif

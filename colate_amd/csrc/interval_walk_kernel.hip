@@ -17,6 +17,8 @@
 // The count pass keeps the number of used rows and the block of the last one; the write pass repeats the walk and writes
 // record, block id and the block ranges at offsets the host formed from the counts between the two launches.  Integers
 // only decide where anything goes; a workgroup reads nothing another workgroup of the same launch writes.
+// The write pass has two forms of the same walk: the interval fit's record (make_rec), and for `--mode mut --samples` the record
+// of the age-sampling kernel with its row-0 weights beside it (make_fill_rec; fill_samples_kernel.hip drives it).
 #include <hip/hip_runtime.h>
 
 #include "interval_walk.h"
@@ -25,6 +27,21 @@ using namespace colate_iw;
 using colate_ic::IntervalRec;
 
 namespace {
+
+// where a used row goes in the write pass: the interval fit's record, or the table fill's record and its side entry
+struct IntervalOut {
+  IntervalRec* recs;
+  __device__ __forceinline__ void put(long long at, const Row& m, const Idx& t, const Idx& r) const { recs[at] = make_rec(m, t, r); }
+};
+struct FillOut {
+  colate_drv::FillRec* recs;
+  FillSide* side;
+  __device__ __forceinline__ void put(long long at, const Row& m, const Idx& t, const Idx& r) const {
+    FillSide s;
+    recs[at] = make_fill_rec(m, t, r, s);
+    side[at] = s;
+  }
+};
 
 struct Shared {
   int last[3][kWaves];  // per step and wave: the highest flagged row of the wave in this tile (-1: none)
@@ -49,11 +66,11 @@ __device__ __forceinline__ int latest_in_front(unsigned long long mask, int base
   return from;
 }
 
-template <bool Masked, bool Write>
+template <bool Masked, bool Write, class Out>
 __device__ __forceinline__ void walk(Shared& s, int n, const Row* __restrict__ rows, const Idx* __restrict__ TI,
                                      const Idx* __restrict__ RI, const unsigned long long* __restrict__ tmask,
                                      const unsigned long long* __restrict__ rmask, int nbpb, int& out_count, int& out_last,
-                                     long long rec0, int blk0, IntervalRec* __restrict__ recs, int* __restrict__ block,
+                                     long long rec0, int blk0, const Out out, int* __restrict__ block,
                                      long long* __restrict__ off_seg) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   int searched = -1, ref_pass = -1, last_used = -1, count = 0;
@@ -101,7 +118,7 @@ __device__ __forceinline__ void walk(Shared& s, int n, const Row* __restrict__ r
       const Row m = rows[i];
       const long long at = rec0 + count + before + __popcll(umask & ((1ull << lane) - 1ull));
       const int k = block_of_pos(m.pos, nbpb);
-      recs[at] = make_rec(m, t, r);
+      out.put(at, m, t, r);
       if (block) block[at] = blk0 + k;
       if (off_seg) {  // the blocks this row opens: those behind the block of the used row in front of it, up to its own
         const int k_from = used_from < 0 ? -1 : block_of_pos(rows[used_from].pos, nbpb);
@@ -114,11 +131,11 @@ __device__ __forceinline__ void walk(Shared& s, int n, const Row* __restrict__ r
   out_last = last_used;
 }
 
-template <bool Write>
+template <bool Write, class Out>
 __global__ __launch_bounds__(kTile) void interval_walk_kernel(DeviceInputs in, int p0, int* __restrict__ cnt,
                                                              int* __restrict__ last_block, const long long* __restrict__ rec0,
                                                              const int* __restrict__ blk0, const int* __restrict__ seg0,
-                                                             IntervalRec* __restrict__ recs, int* __restrict__ block,
+                                                             const Out out, int* __restrict__ block,
                                                              long long* __restrict__ off, long long off_end, long long rec_end) {
   __shared__ Shared s;
   const int c = blockIdx.x % in.C, j = blockIdx.x / in.C;  // (pair p0 + j, chromosome c)
@@ -139,8 +156,8 @@ __global__ __launch_bounds__(kTile) void interval_walk_kernel(DeviceInputs in, i
     if (off) off_seg = off + seg0[slot];
   }
   int count = 0, last = -1;
-  if (tmask || rmask) walk<true, Write>(s, n, rows, TI, RI, tmask, rmask, in.nbpb, count, last, my_rec0, my_blk0, recs, block, off_seg);
-  else walk<false, Write>(s, n, rows, TI, RI, tmask, rmask, in.nbpb, count, last, my_rec0, my_blk0, recs, block, off_seg);
+  if (tmask || rmask) walk<true, Write>(s, n, rows, TI, RI, tmask, rmask, in.nbpb, count, last, my_rec0, my_blk0, out, block, off_seg);
+  else walk<false, Write>(s, n, rows, TI, RI, tmask, rmask, in.nbpb, count, last, my_rec0, my_blk0, out, block, off_seg);
   if (threadIdx.x == 0) {
     if (!Write) {
       cnt[slot] = count;
@@ -152,18 +169,19 @@ __global__ __launch_bounds__(kTile) void interval_walk_kernel(DeviceInputs in, i
   }
 }
 
+template <class Out>
 hipError_t launch(bool write, const DeviceInputs& in, int p0, int p1, int* cnt, int* last_block, const long long* rec0,
-                  const int* blk0, const int* seg0, IntervalRec* recs, int* block, long long* off, long long off_end,
+                  const int* blk0, const int* seg0, const Out out, int* block, long long* off, long long off_end,
                   long long rec_end, hipStream_t stream) {
   if (p1 <= p0 || in.C < 1) return hipSuccess;
   const long long grid = (long long)(p1 - p0) * in.C;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
   if (write)
-    hipLaunchKernelGGL(interval_walk_kernel<true>, dim3((unsigned)grid), dim3(kTile), 0, stream, in, p0, cnt, last_block, rec0, blk0,
-                       seg0, recs, block, off, off_end, rec_end);
-  else
-    hipLaunchKernelGGL(interval_walk_kernel<false>, dim3((unsigned)grid), dim3(kTile), 0, stream, in, p0, cnt, last_block, rec0, blk0,
-                       seg0, recs, block, off, off_end, rec_end);
+    hipLaunchKernelGGL((interval_walk_kernel<true, Out>), dim3((unsigned)grid), dim3(kTile), 0, stream, in, p0, cnt, last_block, rec0,
+                       blk0, seg0, out, block, off, off_end, rec_end);
+  else  // (the count pass writes no record: one instantiation serves both record forms)
+    hipLaunchKernelGGL((interval_walk_kernel<false, IntervalOut>), dim3((unsigned)grid), dim3(kTile), 0, stream, in, p0, cnt, last_block,
+                       rec0, blk0, seg0, IntervalOut{nullptr}, block, off, off_end, rec_end);
   return hipGetLastError();
 }
 
@@ -172,12 +190,18 @@ hipError_t launch(bool write, const DeviceInputs& in, int p0, int p1, int* cnt, 
 namespace colate_iw {
 
 hipError_t count_launch(const DeviceInputs& in, int p0, int p1, int* cnt, int* last_block, hipStream_t stream) {
-  return launch(false, in, p0, p1, cnt, last_block, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, stream);
+  return launch(false, in, p0, p1, cnt, last_block, nullptr, nullptr, nullptr, IntervalOut{nullptr}, nullptr, nullptr, 0, 0, stream);
 }
 
 hipError_t write_launch(const DeviceInputs& in, int p0, int p1, const long long* rec0, const int* blk0, const int* seg0,
                         IntervalRec* recs, int* block, long long* off, long long off_end, long long rec_end, hipStream_t stream) {
-  return launch(true, in, p0, p1, nullptr, nullptr, rec0, blk0, seg0, recs, block, off, off_end, rec_end, stream);
+  return launch(true, in, p0, p1, nullptr, nullptr, rec0, blk0, seg0, IntervalOut{recs}, block, off, off_end, rec_end, stream);
+}
+
+hipError_t write_fill_launch(const DeviceInputs& in, int p0, int p1, const long long* rec0, const int* blk0, const int* seg0,
+                             colate_drv::FillRec* recs, FillSide* side, long long* off, long long off_end, long long rec_end,
+                             hipStream_t stream) {
+  return launch(true, in, p0, p1, nullptr, nullptr, rec0, blk0, seg0, FillOut{recs, side}, nullptr, off, off_end, rec_end, stream);
 }
 
 }  // namespace colate_iw

@@ -4,8 +4,10 @@
 // feeder that turns two .colate.in streams and the .mut files into per-block
 // age-bin tables (include/coal/coal.cpp:2071-2321 with include/src/mutations.cpp:56-283
 // and include/src/data.cpp:213-235), and the mut() driver (include/coal/coal.cpp:3071-3863)
-// around the GPU EM (colate_em_batch), for one pair (run_mut) and for a `--pairs` list
-// (run_mut_pairs; the tables of both come from the engine of mut_pairs.cpp).
+// around the GPU EM (colate_em_batch), for one pair (run_mut), for a `--pairs` list
+// (run_mut_pairs; the tables of both come from the engine of mut_pairs.cpp) and for the
+// pairs of a `--samples` list (run_mut_samples; the tables come from the walk and fill on
+// the device, fill_samples.h).  The two lists share run_pair_list, everything behind the fill.
 //
 // Everything here runs once per invocation on the host; the per-replicate EM,
 // which is where the reference spends its time, is the HIP kernel.
@@ -40,6 +42,8 @@
 
 #include "colate_amd.h"
 #include "colate_internal.h"
+#include "fill_samples.h"
+#include "interval_walk.h"
 #include "mut_feeder.h"
 #include "mut_interval.h"
 
@@ -143,6 +147,8 @@ void print_help() {
             << "                             lines; with --mut, -o PREFIX [--chr] and --bins or --coal every target x reference pair of\n"
             << "                             different lines is fitted, the pairs walked on the GPU; writes PREFIX_<target>_<reference>.coal,\n"
             << "                             each the file `--pairs` writes for that pair.\n"
+            << "                             (--mode mut) the same list, a line may add age=YEARS; the pairs are walked and their tables\n"
+            << "                             filled on the GPU; PREFIX_<target>_<reference>.coal (and .counts) as `--mode mut --pairs` writes them.\n"
             << "      --counts_out arg       Optional (colate_amd): write the bootstrap count tables (.colate_mat layout).\n"
             << "      --counts_only          Optional (colate_amd): stop after --counts_out (no GPU needed).\n"
             << "      --write_colate_mat     Optional (colate_amd): write <output>.colate_mat as the reference does for BCF/BAM inputs.\n"
@@ -806,6 +812,70 @@ bool read_pair_list(const std::string& path, const Options& opt, const std::vect
   return true;
 }
 
+// (mut_feeder.h)
+bool read_sample_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names, bool with_ages,
+                      std::vector<SampleLine>& samples) {
+  std::ifstream is(path);
+  if (!is) {
+    std::cerr << "Error while opening file " << path << std::endl;
+    return false;
+  }
+  std::string line;
+  for (size_t line_no = 1; std::getline(is, line); line_no++) {
+    auto fail = [&](const std::string& what) {
+      std::cerr << "Error: " << path << ", line " << line_no << ": " << what << std::endl;
+      return false;
+    };
+    std::istringstream ss(line);
+    SampleLine sl;
+    sl.line = line_no;
+    if (!(ss >> sl.name)) continue;  // a blank line
+    if (sl.name.find('=') != std::string::npos) return fail("the line starts with '" + sl.name + "': the sample's NAME is missing or empty");
+    if (sl.name.find('/') != std::string::npos) return fail("the NAME '" + sl.name + "' contains '/'");
+    if (!(ss >> sl.file) || sl.file.find('=') != std::string::npos)
+      return fail(with_ages ? "expected `NAME FILE.colate.in [mask=PREFIX] [role=target|reference] [age=YEARS]`"
+                            : "expected `NAME FILE.colate.in [mask=PREFIX] [role=target|reference]`");
+    for (const SampleLine& other : samples)
+      if (other.name == sl.name) return fail("the NAME '" + sl.name + "' is given twice (first on line " + std::to_string(other.line) + ")");
+    bool seen_mask = false, seen_role = false, seen_age = false;
+    for (std::string tok; ss >> tok;) {
+      const size_t eq = tok.find('=');
+      if (eq == std::string::npos)
+        return fail("'" + tok + "' is no key=value token (" +
+                    (with_ages ? "a sample's age is given as age=YEARS)" : "--mode mut_interval takes modern samples only: a line cannot carry sample ages)"));
+      const std::string key = tok.substr(0, eq), value = tok.substr(eq + 1);
+      bool* seen = key == "mask" ? &seen_mask : key == "role" ? &seen_role : (with_ages && key == "age") ? &seen_age : nullptr;
+      if (!seen) return fail("unknown key '" + key + (with_ages ? "' (known: mask, role, age)" : "' (known: mask, role)"));
+      if (*seen) return fail("the key '" + key + "' is given twice");
+      if (value.empty()) return fail("the key '" + key + "' has no value");
+      *seen = true;
+      if (key == "mask") sl.masks = mask_files(opt, chr_names, value);
+      else if (key == "age") {  // (read as the ages of a `--pairs` line are)
+        float v = 0;
+        size_t used = 0;
+        try {
+          v = std::stof(value, &used);
+        } catch (...) {
+          used = 0;
+        }
+        if (used == 0 || used != value.size() || !(v == v)) return fail("the age '" + value + "' is not a number");
+        if (v < 0) return fail("the age '" + value + "' is negative");
+        sl.age = v;
+      } else if (value == "target") sl.reference = false;
+      else if (value == "reference") sl.target = false;
+      else return fail("unknown role '" + value + "' (known: target, reference)");
+    }
+    samples.push_back(sl);
+  }
+  bool any_t = false, any_r = false;
+  for (const SampleLine& sl : samples) any_t = any_t || sl.target, any_r = any_r || sl.reference;
+  if (!any_t || !any_r) {
+    std::cerr << "Error: " << path << ": the list names no " << (!any_t ? "target" : "reference") << " sample." << std::endl;
+    return false;
+  }
+  return true;
+}
+
 int run_mut(const Options& opt) {
   if (!opt.has("mut") || !opt.has("output")) {  // coal.cpp:3077-3087
     std::cout << "Not enough arguments supplied." << std::endl;
@@ -1009,6 +1079,12 @@ int run_mut(const Options& opt) {
   return 0;
 }
 
+// Everything of a run over a list of pairs but the list and the table fill: epochs per pair, classes by number of epochs,
+// bootstrap weights from each pair's generator, counts, the EM launches and the writers.  fill(todo, seed, A, tabs): the tables
+// of the pairs listed in `todo` and each one's generator after its fill, as fill_pairs leaves them.
+using PairListFill = std::function<bool(const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& tabs)>;
+int run_pair_list(const Options& opt, const std::vector<PairSpec>& pairs, const PairListFill& fill);
+
 int run_mut_pairs(const Options& opt) {
   if (!opt.has("mut")) {
     std::cerr << "Error: --pairs needs --mut (and optionally --chr, --bins, --num_bootstraps, --seed)." << std::endl;
@@ -1029,6 +1105,12 @@ int run_mut_pairs(const Options& opt) {
         std::cerr << "Error: --pairs needs --bins for pair " << p + 1 << " (it names no coal= file)." << std::endl;
         return 1;
       }
+  return run_pair_list(opt, pairs, [&](const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& tabs) {
+    return fill_pairs(opt, chr_names, mut_files, pairs, todo, seed, A, tabs);
+  });
+}
+
+int run_pair_list(const Options& opt, const std::vector<PairSpec>& pairs, const PairListFill& fill) {
   const bool talk = g_rank.rank == 0;
   if (talk) {
     std::cerr << "---------------------------------------------------------" << std::endl;
@@ -1086,7 +1168,7 @@ int run_mut_pairs(const Options& opt) {
   std::sort(todo.begin(), todo.end());
 
   std::vector<PairTables> tabs;
-  if (!fill_pairs(opt, chr_names, mut_files, pairs, todo, run.seed, A, tabs)) return 1;
+  if (!fill(todo, run.seed, A, tabs)) return 1;
   for (size_t p : todo) {
     if (talk) std::cerr << "Pair " << p + 1 << " / " << P << ": " << pairs[p].target << " x " << pairs[p].reference << ": Number of blocks: " << tabs[p].nb << std::endl;
     if (tabs[p].nb < 1) {
@@ -1196,6 +1278,98 @@ int run_mut_pairs(const Options& opt) {
   if (status || !talk) return status;
   print_usage_footer();
   return 0;
+}
+
+// `Colate --mode mut --samples LIST`: every (target line, reference line) of the list, each pair's files byte for byte what
+// `--pairs` writes for the expanded list.  Where there is a device and every sample has a walk index, no pair is walked on the
+// host: N index arrays and the rows go to the device once, and colate_fill_samples' device form walks, forms the records and
+// fills the tables there (fill_samples.h).  Otherwise one line on stderr says why, and the expanded list goes through fill_pairs.
+int run_mut_samples(const Options& opt) {
+  for (const char* o : {"pairs", "target_tmp", "reference_tmp", "target_mask", "reference_mask", "target_age", "reference_age", "ranks"})
+    if (opt.has(o)) {
+      std::cerr << "Error: --" << o << " cannot be combined with --mode mut --samples." << std::endl;
+      return 1;
+    }
+  if (!opt.has("mut") || !opt.has("output") || (!opt.has("bins") && !opt.has("coal"))) {
+    std::cerr << "Error: --samples needs --mut, -o PREFIX and --bins x,y,stepsize or --coal FILE (optional: --chr, --num_bootstraps, --seed, "
+                 "--years_per_gen, --counts_out, --counts_only, --device, --devices)."
+              << std::endl;
+    return 1;
+  }
+  std::vector<std::string> chr_names, mut_files;
+  chromosome_files(opt, chr_names, mut_files);
+  std::vector<SampleLine> samples;
+  if (!read_sample_list(opt.get("samples"), opt, chr_names, true, samples)) return 1;
+  std::vector<PairSpec> pairs;
+  for (const SampleLine& t : samples)
+    for (const SampleLine& r : samples) {
+      if (!t.target || !r.reference || &t == &r) continue;
+      PairSpec ps;
+      ps.target = t.file, ps.reference = r.file, ps.output = opt.get("output") + "_" + t.name + "_" + r.name;
+      ps.target_age = t.age, ps.ref_age = r.age, ps.target_masks = t.masks, ps.ref_masks = r.masks, ps.line = t.line;
+      if (!opt.has("bins")) ps.coal = opt.get("coal");
+      pairs.push_back(ps);
+    }
+  if (pairs.empty()) {
+    std::cerr << "Error: " << opt.get("samples") << ": no pair of a target and a reference on different lines." << std::endl;
+    return 1;
+  }
+  const auto fill = [&](const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& tabs) -> bool {
+    const auto through_engine = [&](const char* why) {
+      std::cerr << "pairs walked and filled through the engine of --pairs (" << why << ")" << std::endl;
+      return fill_pairs(opt, chr_names, mut_files, pairs, todo, seed, A, tabs);
+    };
+    for (const char* name : {"COLATE_DEVICE_FILL", "COLATE_DEVICE_FILL_WALK"})
+      if (const char* e = std::getenv(name))
+        if (std::atoi(e) == 0) return through_engine((std::string(name) + "=0").c_str());
+    if (colate_device_count() < 1) return through_engine("no device");
+    if (opt.has("device"))
+      if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc) == 0;
+    const double t0 = StageTimes::now();
+    std::vector<PairSpec> mine;
+    for (size_t p : todo) mine.push_back(pairs[p]);
+    WalkInputs in;
+    if (!load_walk_inputs(chr_names, mut_files, mine, in)) return false;
+    if (!in.indexed) return through_engine("a sample has no walk index");
+    colate_iw::View v;
+    v.C = (int)chr_names.size(), v.row_off = in.row_off.data(), v.rows = in.row_ptrs.data(), v.S = in.S, v.idx = in.idx_ptrs.data(), v.M = in.M;
+    v.masks = in.mask_ptrs.data(), v.P = (int)mine.size(), v.pairs = in.pairs.data(), v.nbpb = kIntervalBasesPerBlock;
+    const double t1 = StageTimes::now();
+    colate_fs::Result res;
+    if (int rc = colate_fs::fill_view_device(v, A, (unsigned)seed, res)) return api_error(rc) == 0;
+    // the pairs' generators after their fills: one sweep through the seed's stream, in the order of the words taken
+    tabs.assign(pairs.size(), PairTables());
+    std::vector<size_t> order(mine.size());
+    for (size_t j = 0; j < order.size(); j++) order[j] = j;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return res.words[a] < res.words[b]; });
+    std::mt19937 g0((unsigned)seed);
+    BulkMt19937 bulk;
+    if (!bulk.load(g0)) return false;
+    unsigned long long at = 0;
+    int handed_back = 0;
+    for (size_t j : order) {
+      PairTables& pt = tabs[todo[j]];
+      bulk.skip(res.words[j] - at), at = res.words[j];
+      if (!bulk.store(pt.rng)) return false;
+      pt.nb = res.nb[j];
+      std::vector<double>* const tab[4] = {&pt.sh, &pt.ns, &pt.she, &pt.nse};  // (the order of Block::t)
+      const double* src = res.tables.data() + res.table_off[j];
+      for (int k = 0; k < 4; k++) {
+        tab[k]->resize((size_t)pt.nb * A);
+        for (int b = 0; b < pt.nb; b++) std::copy_n(src + ((size_t)b * 4 + k) * A, A, tab[k]->begin() + (size_t)b * A);
+      }
+      handed_back += res.handed_back[j];
+    }
+    std::cerr << in.S << " samples and " << in.M << " masks staged, " << mine.size() << " pairs walked and filled on the device ("
+              << handed_back << " handed back to the host)" << std::endl;
+    g_times.parse_mut = t1 - t0, g_times.table_fill = StageTimes::now() - t1;
+    if (g_times.on)
+      std::cerr << "Timing: samples fill: inputs " << t1 - t0 << " s, walks and fills " << g_times.table_fill << " s (device kernels "
+                << res.kernel_s << " s, " << res.chunks << " chunk(s)); " << in.row_off.back() << " rows, " << in.S << " index arrays and "
+                << in.M << " masks staged, " << 100 * *std::max_element(res.used.begin(), res.used.end()) << " uniforms uploaded" << std::endl;
+    return true;
+  };
+  return run_pair_list(opt, pairs, fill);
 }
 
 void write_counts_file(const std::string& path, int B, int A, const std::vector<double>& grid,
@@ -1548,6 +1722,7 @@ extern "C" int colate_mut_main(int argc, char** argv) {
       return 0;
     }
     try {
+      if (opt.has("samples")) return run_mut_samples(opt);  // (refuses --ranks by name)
       if (opt.has("ranks")) {
         const int nranks = std::stoi(opt.get("ranks"));
         if (nranks < 1 || nranks > 64) {

@@ -141,6 +141,14 @@ class BulkMt19937 {
       out += k, n -= k, p_ += (uint32_t)k;
     }
   }
+  // the same position as discard(n), without forming the outputs on the way (tempering is no part of the state)
+  void skip(unsigned long long n) {
+    while (n) {
+      if (p_ >= 624) twist();
+      const unsigned long long k = std::min<unsigned long long>(n, 624 - p_);
+      p_ += (uint32_t)k, n -= k;
+    }
+  }
   void discard(unsigned long long n) {
     uint32_t tmp[624];
     while (n) {
@@ -266,5 +274,21 @@ bool collect_interval_records_loaded(const WalkInputs& loaded, const std::vector
 // a third age or an age that is no number is an error naming the file and the line.  A line of fewer than three tokens is
 // skipped.  PairSpec::line / ages_given: the pair's line in the file and how many age tokens it carried.
 bool read_pair_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names, std::vector<PairSpec>& pairs);
+
+// mut_driver.cpp: the list of `--samples` (both `--mode mut` and `--mode mut_interval`).  `NAME FILE.colate.in` per line, then
+// in any order mask=PREFIX (expanded as --target_mask is), role=target|reference (default: both) and -- with_ages only, which
+// `--mode mut` passes -- age=YEARS, the sample's age (default 0; a number, not negative).  Blank lines are skipped.  Every error
+// names the line.  The pairs of a list are every (target line, reference line) of different lines, targets outermost.
+struct SampleLine {
+  std::string name, file;
+  std::vector<std::string> masks;
+  bool target = true, reference = true;
+  double age = 0;
+  size_t line = 0;
+};
+bool read_sample_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names, bool with_ages,
+                      std::vector<SampleLine>& samples);
+// mut_driver.cpp: `Colate --mode mut --samples LIST`
+int run_mut_samples(const Options& opt);
 
 }  // namespace colate_drv

@@ -419,62 +419,7 @@ static int run_mut_interval_pairs(const Options& opt) {
 }
 
 // ------------------------------------------------------------------ `--mode mut_interval --samples LIST`
-// The list: `NAME FILE.colate.in` per line, then in any order mask=PREFIX (expanded as --target_mask is) and
-// role=target|reference (default: both).  Blank lines are skipped.  Every error names the line.
-struct SampleLine {
-  std::string name, file;
-  std::vector<std::string> masks;
-  bool target = true, reference = true;
-  size_t line = 0;
-};
-static bool read_sample_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names,
-                             std::vector<SampleLine>& samples) {
-  std::ifstream is(path);
-  if (!is) {
-    std::cerr << "Error while opening file " << path << std::endl;
-    return false;
-  }
-  std::string line;
-  for (size_t line_no = 1; std::getline(is, line); line_no++) {
-    auto fail = [&](const std::string& what) {
-      std::cerr << "Error: " << path << ", line " << line_no << ": " << what << std::endl;
-      return false;
-    };
-    std::istringstream ss(line);
-    SampleLine sl;
-    sl.line = line_no;
-    if (!(ss >> sl.name)) continue;  // a blank line
-    if (sl.name.find('=') != std::string::npos) return fail("the line starts with '" + sl.name + "': the sample's NAME is missing or empty");
-    if (sl.name.find('/') != std::string::npos) return fail("the NAME '" + sl.name + "' contains '/'");
-    if (!(ss >> sl.file) || sl.file.find('=') != std::string::npos) return fail("expected `NAME FILE.colate.in [mask=PREFIX] [role=target|reference]`");
-    for (const SampleLine& other : samples)
-      if (other.name == sl.name) return fail("the NAME '" + sl.name + "' is given twice (first on line " + std::to_string(other.line) + ")");
-    bool seen_mask = false, seen_role = false;
-    for (std::string tok; ss >> tok;) {
-      const size_t eq = tok.find('=');
-      if (eq == std::string::npos) return fail("'" + tok + "' is no key=value token (--mode mut_interval takes modern samples only: a line cannot carry sample ages)");
-      const std::string key = tok.substr(0, eq), value = tok.substr(eq + 1);
-      bool* seen = key == "mask" ? &seen_mask : key == "role" ? &seen_role : nullptr;
-      if (!seen) return fail("unknown key '" + key + "' (known: mask, role)");
-      if (*seen) return fail("the key '" + key + "' is given twice");
-      if (value.empty()) return fail("the key '" + key + "' has no value");
-      *seen = true;
-      if (key == "mask") sl.masks = mask_files(opt, chr_names, value);
-      else if (value == "target") sl.reference = false;
-      else if (value == "reference") sl.target = false;
-      else return fail("unknown role '" + value + "' (known: target, reference)");
-    }
-    samples.push_back(sl);
-  }
-  bool any_t = false, any_r = false;
-  for (const SampleLine& sl : samples) any_t = any_t || sl.target, any_r = any_r || sl.reference;
-  if (!any_t || !any_r) {
-    std::cerr << "Error: " << path << ": the list names no " << (!any_t ? "target" : "reference") << " sample." << std::endl;
-    return false;
-  }
-  return true;
-}
-
+// (the list: read_sample_list, mut_feeder.h; no ages here)
 // Every (target line, reference line) of the list with different lines, targets outermost; each pair's PREFIX_<target>_<reference>.coal
 // is, byte for byte, what `--pairs` writes for it given the expanded list.  Where every file has a walk index the pairs are not
 // walked on the host at all: N index arrays and the rows go to the device once and colate_interval_fit_samples forms every pair's
@@ -496,7 +441,7 @@ static int run_mut_interval_samples(const Options& opt) {
   std::vector<std::string> names, mut_files;
   chromosome_files(opt, names, mut_files);
   std::vector<SampleLine> samples;
-  if (!read_sample_list(opt.get("samples"), opt, names, samples)) return 1;
+  if (!read_sample_list(opt.get("samples"), opt, names, false, samples)) return 1;
   std::vector<PairSpec> pairs;
   for (const SampleLine& t : samples)
     for (const SampleLine& r : samples) {

@@ -48,6 +48,7 @@
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "fill_device.h"
+#include "fill_samples.h"
 #include "interval_cells.h"
 #include "mut_feeder.h"
 
@@ -1503,6 +1504,17 @@ bool collect(const PairFill& pf, int A, PairTables& pt) {
 }
 
 }  // namespace
+
+// (fill_samples.h)
+struct AgeBins::Impl {
+  FastBin fb;
+};
+AgeBins::AgeBins(int A) : impl_(new Impl{FastBin(A, 10.0)}) {}
+AgeBins::~AgeBins() = default;
+bool AgeBins::ok() const { return impl_->fb.ok(); }
+const double* AgeBins::guard_lo() const { return impl_->fb.guard_lo(); }
+const double* AgeBins::guard_hi() const { return impl_->fb.guard_hi(); }
+bool fill_bulk_stream_ok(unsigned seed) { return bulk_stream_ok(seed); }
 
 // (mut_feeder.h)
 bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,

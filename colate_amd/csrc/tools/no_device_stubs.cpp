@@ -91,6 +91,12 @@ int walk_view_device(const View&, long long, long long*, int*, colate_ic::Interv
 int fit_samples_view_device(const View&, const FitArgs&) { return nodev(); }
 }  // namespace colate_iw
 
+// the table fill over walk indices on the device (fill_samples.h; colate_fill_samples ends here): none in this build
+#include "fill_samples.h"
+namespace colate_fs {
+int fill_view_device(const colate_iw::View&, int, unsigned, Result&) { return nodev(); }
+}  // namespace colate_fs
+
 // the age sampling on the device (fill_device.h): there is none in this build, the host code samples
 #include "fill_device.h"
 namespace colate_drv {

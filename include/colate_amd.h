@@ -411,6 +411,52 @@ int colate_interval_fit_samples_host(int C, const long long* row_off, const cola
                                      double* out_loglik, int* out_flags, int math);
 double colate_interval_fit_samples_kernel_seconds(void);
 
+/* ---- the table fill of `--mode mut` for every pair of a sample list, over the same walk indices (csrc/fill_samples.h) ----
+ * Inputs and refusals are those of colate_interval_walk; A must be the 185 of colate_age_grid (COLATE_EINVAL otherwise).
+ * Per pair the walk above picks the used rows and their genome blocks; the fill is coal.cpp:2221-2297 with age = ref_age
+ * = 0 (coal.cpp:2074-2075): the pair owns a std::mt19937 on `seed` and draws uniform_real_distribution<double>(0, 1)
+ * from it, row after row.  With begin = (float)max(age_begin, 0), end = age_end, f as above,
+ * e = (double)(f * (float)r.DAF) / (double)(r.DAF + r.AAF) and w = (double)(f * (float)r.DAF) / ((double)(r.DAF + r.AAF)
+ * * 100.0), each for the shared (t.DAF) and the not-shared (t.AAF) kind, and bin(x) = max(0, (int)round(log(10 x) * 10) +
+ * 1): a row with begin <= 0 (the F path) adds e to the two row-0 tables at bin(end) where that is below A, then makes
+ * 100 draws x = u * (end - begin) + begin (a separate multiply and add), clamps x at 0 and adds w of the not-shared kind
+ * at bin(x) where that is below A; any other row makes draws until 100 of them have x >= 0 and bin(x) < A, each of
+ * those adding both w at bin(x).  Every sum starts at 0.0 and adds in the order of the draws, each addition rounded.
+ * Out, per pair p: out_nb[p], out_used[p] (its used rows); its tables [nb[p]][4][A] -- shared, not shared, shared row 0,
+ * not-shared row 0 per block, the order of the engine's Block::t -- back to back in out_tables, which has room for
+ * cap_blocks blocks (a total above it is COLATE_ELIMIT with the needed total in colate_last_error(); nothing is written
+ * then); out_words[p]: the 32-bit words the pair's generator has given out when its fill ends (std::mt19937 g(seed);
+ * g.discard(out_words[p]) is the run's generator there: two words per draw, 200 per used row unless a draw was repeated);
+ * out_handed_back[p]: 1 where the device form had the host twin fill the pair (always 0 from _host).
+ * _host: the host twin, a plain loop per pair with the library's generator, distribution and log(): right for every
+ * input.  (Where no draw can ever be accepted the reference does not end; the twin stops after 100 x 100 x (rows + 1)
+ * draws.)  out_near_band[p]: 1 where a draw of the pair lies inside a guard band of the located bin steps (64 ulps either
+ * side, csrc/mut_pairs.cpp FastBin) or a draw was repeated -- the documented reasons for which the device hands a pair
+ * back.
+ * colate_fill_samples, all on one stream of the calling thread's device (COLATE_ENODEVICE without one): the inputs and the
+ * count pass of the walk once; one host wait for the counts; the seed's uniforms [0, 100 x the largest out_used) uploaded
+ * once for all pairs (record k of a pair reads them at 100 k); then chunks -- runs of consecutive pairs whose records (40
+ * bytes each with the row-0 weights) fit COLATE_FILL_SAMPLES_RECS_MB megabytes (default
+ * COLATE_FILL_SAMPLES_RECS_MB_DEFAULT), a larger pair alone, scratch allocated once for the largest --: the walk's write
+ * pass forms the records in HBM, one wave per (pair, block) sums the row-0 tables in record order (thresholds of
+ * colate_interval_bin_thresholds in LDS, no log, no floating-point atomics), one thread per (pair, block) writes the job of
+ * the age-sampling kernel (csrc/fill_kernel.hip, the kernel of `--pairs`), that kernel runs, and tables, row-0 tables and
+ * flags come back in one wait.  A pair with a flagged block is filled by the twin on the same inputs, so the results equal
+ * _host's in every bit, whatever the chunking.  Where the located steps fail their self-check or the bulk generator does
+ * not reproduce this machine's std::mt19937, every pair is handed back.
+ * colate_fill_samples_chunks / _kernel_seconds: diagnostics of the calling thread's last call (0 from _host). */
+#define COLATE_FILL_SAMPLES_RECS_MB_DEFAULT 4096
+int colate_fill_samples(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx, int M,
+                        const unsigned long long* masks, int P, const colate_walk_pair* pairs, int num_bases_per_block, int A,
+                        unsigned int seed, long long cap_blocks, int* out_nb, long long* out_used, double* out_tables,
+                        unsigned long long* out_words, int* out_handed_back);
+int colate_fill_samples_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx, int M,
+                             const unsigned long long* masks, int P, const colate_walk_pair* pairs, int num_bases_per_block, int A,
+                             unsigned int seed, long long cap_blocks, int* out_nb, long long* out_used, double* out_tables,
+                             unsigned long long* out_words, int* out_handed_back, int* out_near_band);
+int colate_fill_samples_chunks(void);
+double colate_fill_samples_kernel_seconds(void);
+
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
 int colate_age_grid(double* age_grid, int cap);
