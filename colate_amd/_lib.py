@@ -108,6 +108,10 @@ SIGNATURES = {
     "colate_bootstrap_em_batch_groups": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 10
                                          + [c_int, c_int, c_double, c_double] + [c_void_p] * 6),
     "colate_bootstrap_counts_groups_device": (c_int, [c_int] * 6 + [c_void_p] * 14),
+    "colate_bootstrap_em_batch_sharded": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_double]
+                                          + [c_void_p] * 7 + [c_int, c_int, c_double, c_double] + [c_void_p] * 6),
+    "colate_bootstrap_em_batch_groups_sharded": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 10
+                                                 + [c_int, c_int, c_double, c_double] + [c_void_p] * 6),
     "colate_bootstrap_em_batch_groups_allgather": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 10
                                                    + [c_int, c_int, c_double, c_double] + [c_void_p] * 4),
     "colate_release_workspace": (c_int, []),

@@ -141,10 +141,16 @@ def bootstrap_counts_from_weights(age_grid_, age, weights, sh_block, ns_block, s
     return csh, cns
 
 
-def bootstrap_em_batch(age_grid_, age, weights, sh_block, ns_block, sh_emp_block, ns_emp_block, epochs, init_rates=None,
-                       max_iter=DEFAULT_MAX_ITER, min_iter=DEFAULT_MIN_ITER, rel_tol=DEFAULT_REL_TOL,
-                       rate_floor=DEFAULT_RATE_FLOOR, want_counts=False):
-    """colate_bootstrap_em_batch: block tables [nb][A] + weights [B][nb] -> (rates, iters, loglik, flags[, csh, cns])."""
+def _lead(devices):
+    """The (num_devices, devices) arguments in front of a *_sharded call; none for the one-device call."""
+    if devices is None:
+        return ()
+    dev = np.ascontiguousarray(devices, dtype=np.int32)
+    return dev.size, _p(dev), dev  # (the array itself rides along so that it outlives the call)
+
+
+def _bootstrap_em_batch(devices, age_grid_, age, weights, sh_block, ns_block, sh_emp_block, ns_emp_block, epochs, init_rates,
+                        max_iter, min_iter, rel_tol, rate_floor, want_counts):
     g, w, ep = _f64(age_grid_), _f64(np.atleast_2d(weights)), _f64(epochs)
     t = [_f64(x) for x in (sh_block, ns_block, sh_emp_block, ns_emp_block)]
     nb, A = t[0].shape
@@ -152,18 +158,33 @@ def bootstrap_em_batch(age_grid_, age, weights, sh_block, ns_block, sh_emp_block
     init = _f64(np.full(E, DEFAULT_INIT_RATE) if init_rates is None else init_rates)
     rates, iters, ll, flags = np.zeros((B, E)), np.zeros(B, dtype=np.int32), np.zeros(B), np.zeros(B, dtype=np.int32)
     csh, cns = (np.zeros((B, A)), np.zeros((B, A))) if want_counts else (None, None)
-    check(lib.colate_bootstrap_em_batch(B, nb, E, A, _p(g), float(age), _p(w), _p(t[0]), _p(t[1]), _p(t[2]), _p(t[3]), _p(ep),
-                                        _p(init), max_iter, min_iter, rel_tol, rate_floor, _p(rates), _p(iters), _p(ll),
-                                        _p(flags), _p(csh) if want_counts else None, _p(cns) if want_counts else None))
+    lead = _lead(devices)
+    f = lib.colate_bootstrap_em_batch if devices is None else lib.colate_bootstrap_em_batch_sharded
+    check(f(*lead[:2], B, nb, E, A, _p(g), float(age), _p(w), _p(t[0]), _p(t[1]), _p(t[2]), _p(t[3]), _p(ep), _p(init), max_iter,
+            min_iter, rel_tol, rate_floor, _p(rates), _p(iters), _p(ll), _p(flags), _p(csh) if want_counts else None,
+            _p(cns) if want_counts else None))
     return (rates, iters, ll, flags, csh, cns) if want_counts else (rates, iters, ll, flags)
 
 
-def bootstrap_em_batch_groups(age_grid_, ages, weights, tables, epochs, init_rates=None, max_iter=DEFAULT_MAX_ITER,
-                              min_iter=DEFAULT_MIN_ITER, rel_tol=DEFAULT_REL_TOL, rate_floor=DEFAULT_RATE_FLOOR,
-                              want_counts=False):
-    """colate_bootstrap_em_batch_groups (batched all-pairs): per group g a sample age ages[g], weights[g] = [B][nb_g],
-    tables[g] = (sh, ns, sh_emp, ns_emp) each [nb_g][A], epochs[g] = [E].  Row g * B + i of the outputs = replicate i
-    of group g."""
+def bootstrap_em_batch(age_grid_, age, weights, sh_block, ns_block, sh_emp_block, ns_emp_block, epochs, init_rates=None,
+                       max_iter=DEFAULT_MAX_ITER, min_iter=DEFAULT_MIN_ITER, rel_tol=DEFAULT_REL_TOL,
+                       rate_floor=DEFAULT_RATE_FLOOR, want_counts=False):
+    """colate_bootstrap_em_batch: block tables [nb][A] + weights [B][nb] -> (rates, iters, loglik, flags[, csh, cns])."""
+    return _bootstrap_em_batch(None, age_grid_, age, weights, sh_block, ns_block, sh_emp_block, ns_emp_block, epochs, init_rates,
+                               max_iter, min_iter, rel_tol, rate_floor, want_counts)
+
+
+def bootstrap_em_batch_sharded(devices, age_grid_, age, weights, sh_block, ns_block, sh_emp_block, ns_emp_block, epochs,
+                               init_rates=None, max_iter=DEFAULT_MAX_ITER, min_iter=DEFAULT_MIN_ITER, rel_tol=DEFAULT_REL_TOL,
+                               rate_floor=DEFAULT_RATE_FLOOR, want_counts=False):
+    """colate_bootstrap_em_batch_sharded: bootstrap_em_batch with the replicates sharded over the GPUs listed in `devices`
+    (ordinals may repeat)."""
+    return _bootstrap_em_batch(devices, age_grid_, age, weights, sh_block, ns_block, sh_emp_block, ns_emp_block, epochs,
+                               init_rates, max_iter, min_iter, rel_tol, rate_floor, want_counts)
+
+
+def _bootstrap_em_batch_groups(devices, age_grid_, ages, weights, tables, epochs, init_rates, max_iter, min_iter, rel_tol,
+                               rate_floor, want_counts):
     g = _f64(age_grid_)
     G = len(weights)
     ws = [_f64(np.atleast_2d(w)) for w in weights]
@@ -181,11 +202,31 @@ def bootstrap_em_batch_groups(age_grid_, ages, weights, tables, epochs, init_rat
     R = G * B
     rates, iters, ll, flags = np.zeros((R, E)), np.zeros(R, dtype=np.int32), np.zeros(R), np.zeros(R, dtype=np.int32)
     csh, cns = (np.zeros((R, A)), np.zeros((R, A))) if want_counts else (None, None)
-    check(lib.colate_bootstrap_em_batch_groups(G, B, E, A, _p(g), _p(nb), _p(a), _p(w_all), _p(t_all[0]), _p(t_all[1]),
-                                               _p(t_all[2]), _p(t_all[3]), _p(ep), _p(init), max_iter, min_iter, rel_tol,
-                                               rate_floor, _p(rates), _p(iters), _p(ll), _p(flags),
-                                               _p(csh) if want_counts else None, _p(cns) if want_counts else None))
+    lead = _lead(devices)
+    f = lib.colate_bootstrap_em_batch_groups if devices is None else lib.colate_bootstrap_em_batch_groups_sharded
+    check(f(*lead[:2], G, B, E, A, _p(g), _p(nb), _p(a), _p(w_all), _p(t_all[0]), _p(t_all[1]), _p(t_all[2]), _p(t_all[3]), _p(ep),
+            _p(init), max_iter, min_iter, rel_tol, rate_floor, _p(rates), _p(iters), _p(ll), _p(flags),
+            _p(csh) if want_counts else None, _p(cns) if want_counts else None))
     return (rates, iters, ll, flags, csh, cns) if want_counts else (rates, iters, ll, flags)
+
+
+def bootstrap_em_batch_groups(age_grid_, ages, weights, tables, epochs, init_rates=None, max_iter=DEFAULT_MAX_ITER,
+                              min_iter=DEFAULT_MIN_ITER, rel_tol=DEFAULT_REL_TOL, rate_floor=DEFAULT_RATE_FLOOR,
+                              want_counts=False):
+    """colate_bootstrap_em_batch_groups (batched all-pairs): per group g a sample age ages[g], weights[g] = [B][nb_g],
+    tables[g] = (sh, ns, sh_emp, ns_emp) each [nb_g][A], epochs[g] = [E].  Row g * B + i of the outputs = replicate i
+    of group g."""
+    return _bootstrap_em_batch_groups(None, age_grid_, ages, weights, tables, epochs, init_rates, max_iter, min_iter, rel_tol,
+                                      rate_floor, want_counts)
+
+
+def bootstrap_em_batch_groups_sharded(devices, age_grid_, ages, weights, tables, epochs, init_rates=None,
+                                      max_iter=DEFAULT_MAX_ITER, min_iter=DEFAULT_MIN_ITER, rel_tol=DEFAULT_REL_TOL,
+                                      rate_floor=DEFAULT_RATE_FLOOR, want_counts=False):
+    """colate_bootstrap_em_batch_groups_sharded: bootstrap_em_batch_groups with the G * B rows sharded over the GPUs listed
+    in `devices` (ordinals may repeat; a shard may begin and end inside a group)."""
+    return _bootstrap_em_batch_groups(devices, age_grid_, ages, weights, tables, epochs, init_rates, max_iter, min_iter,
+                                      rel_tol, rate_floor, want_counts)
 
 
 def bootstrap_counts_groups_device(G, B, group_first, row_lo, row_hi, age_grid_, group_nb, group_block_off, group_weight_off, group_age,

@@ -524,6 +524,36 @@ int colate_em_batch_rows_sharded(int num_devices, const int* devices, int B, int
                         num_devices, devices);
 }
 
+int colate_bootstrap_em_batch_sharded(int num_devices, const int* devices, int B, int nb, int E, int A,
+                                      const double* age_grid, double age, const double* weights,
+                                      const double* sh_block, const double* ns_block, const double* sh_emp_block,
+                                      const double* ns_emp_block, const double* epochs, const double* init_rates,
+                                      int max_iter, int min_iter, double rel_tol, double rate_floor,
+                                      double* out_rates, int* out_iters, double* out_loglik, int* out_flags,
+                                      double* out_cnt_shared, double* out_cnt_notshared) {
+  EmJob j = genome_job(B, nb, E, A, age_grid, age, weights, sh_block, ns_block, sh_emp_block, ns_emp_block, epochs,
+                       init_rates, max_iter, min_iter, rel_tol, rate_floor, out_rates, out_iters, out_loglik, out_flags);
+  j.out_cnt_shared = out_cnt_shared, j.out_cnt_notshared = out_cnt_notshared;
+  return run_on_devices(j, num_devices, devices);
+}
+
+int colate_bootstrap_em_batch_groups_sharded(int num_devices, const int* devices, int G, int B, int E, int A,
+                                             const double* age_grid, const int* group_nb, const double* group_age,
+                                             const double* weights, const double* sh_block, const double* ns_block,
+                                             const double* sh_emp_block, const double* ns_emp_block,
+                                             const double* epochs, const double* init_rates, int max_iter,
+                                             int min_iter, double rel_tol, double rate_floor, double* out_rates,
+                                             int* out_iters, double* out_loglik, int* out_flags,
+                                             double* out_cnt_shared, double* out_cnt_notshared) {
+  if (G < 0 || B < 1) return fail(COLATE_EINVAL, "bad sizes G=%d B=%d", G, B);
+  if ((long long)G * B > 0x7fffffffLL) return fail(COLATE_ELIMIT, "G x B = %lld rows", (long long)G * B);
+  EmJob j = groups_job(G, B, 0, G, E, A, age_grid, group_nb, group_age, weights, sh_block, ns_block, sh_emp_block,
+                       ns_emp_block, epochs, init_rates, max_iter, min_iter, rel_tol, rate_floor, out_rates, out_iters,
+                       out_loglik, out_flags);
+  j.out_cnt_shared = out_cnt_shared, j.out_cnt_notshared = out_cnt_notshared;
+  return run_on_devices(j, num_devices, devices);
+}
+
 int colate_release_workspace(void) {
   thread_workspace().release();
   return COLATE_OK;

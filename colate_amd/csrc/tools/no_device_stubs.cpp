@@ -44,6 +44,13 @@ int colate_em_batch_sharded(int, const int*, int, int, int, const double*, const
                             const double*, int, int, double, double, double*, int*, double*, int*) { return nodev(); }
 int colate_em_batch_rows_sharded(int, const int*, int, int, int, const double*, const double*, const double*, const double*,
                                  const double*, int, int, double, double, double*, int*, double*, int*) { return nodev(); }
+int colate_bootstrap_em_batch_sharded(int, const int*, int, int, int, int, const double*, double, const double*, const double*,
+                                      const double*, const double*, const double*, const double*, const double*, int, int, double,
+                                      double, double*, int*, double*, int*, double*, double*) { return nodev(); }
+int colate_bootstrap_em_batch_groups_sharded(int, const int*, int, int, int, int, const double*, const int*, const double*,
+                                             const double*, const double*, const double*, const double*, const double*,
+                                             const double*, const double*, int, int, double, double, double*, int*, double*, int*,
+                                             double*, double*) { return nodev(); }
 int colate_bootstrap_em_batch(int, int, int, int, const double*, double, const double*, const double*, const double*,
                               const double*, const double*, const double*, const double*, int, int, double, double, double*,
                               int*, double*, int*, double*, double*) { return nodev(); }

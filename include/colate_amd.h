@@ -155,6 +155,28 @@ int colate_em_batch_rows_sharded(int num_devices, const int* devices, int B, int
                                  double rate_floor, double* out_rates, int* out_iters,
                                  double* out_loglik, int* out_flags);
 
+/* The same sharding for the two calls that bootstrap on the device: the arguments after `devices` are those of
+ * colate_bootstrap_em_batch / colate_bootstrap_em_batch_groups below.  Every shard uploads only what its rows read
+ * (its replicates' weights; in the groups form the tables, weights, ages and epochs of the groups its rows belong
+ * to -- a shard may begin and end inside a group), runs the bootstrap kernel and the EM kernel on its device, and
+ * the outputs (out_cnt_* included, may be NULL) come back in row order, bit-identical to the one-device call.  A
+ * sample age outside the age grid in any shard fails the whole call (COLATE_EINVAL). */
+int colate_bootstrap_em_batch_sharded(int num_devices, const int* devices, int B, int nb, int E, int A,
+                                      const double* age_grid, double age, const double* weights,
+                                      const double* sh_block, const double* ns_block, const double* sh_emp_block,
+                                      const double* ns_emp_block, const double* epochs, const double* init_rates,
+                                      int max_iter, int min_iter, double rel_tol, double rate_floor,
+                                      double* out_rates, int* out_iters, double* out_loglik, int* out_flags,
+                                      double* out_cnt_shared, double* out_cnt_notshared);
+int colate_bootstrap_em_batch_groups_sharded(int num_devices, const int* devices, int G, int B, int E, int A,
+                                             const double* age_grid, const int* group_nb, const double* group_age,
+                                             const double* weights, const double* sh_block, const double* ns_block,
+                                             const double* sh_emp_block, const double* ns_emp_block,
+                                             const double* epochs, const double* init_rates, int max_iter,
+                                             int min_iter, double rel_tol, double rate_floor, double* out_rates,
+                                             int* out_iters, double* out_loglik, int* out_flags,
+                                             double* out_cnt_shared, double* out_cnt_notshared);
+
 /* One E-step = one pass of coal.cpp:3698-3733 for each of B replicates with the
  * rates given per replicate: rates[B][E] -> num_acc[B][E], den_acc[B][E]
  * (coal_rates_num / coal_rates_denom), loglik[B], flags[B]. */

@@ -55,6 +55,22 @@ def test_sharded_entry_point_on_two_devices(ca):
         assert np.array_equal(r, r1) and np.array_equal(ll, ll1) and (it == it1).all() and (fl == fl1).all()
 
 
+def test_bootstrap_groups_sharded_on_two_devices(ca):
+    """colate_bootstrap_em_batch_groups_sharded on distinct GPUs: 6 groups x 5 replicates, two and three shards (the
+    three cut inside groups); every output, count tables included, bit-identical to the one-device call and the counts
+    to the plain model (tests/test_gpu_bootstrap_counts.py runs the same with repeated ordinals on one GPU)."""
+    _two(ca)
+    import bootstrap_counts_lib as bl
+
+    p = bl.groups_problem("ref185", 5)
+    kw = dict(want_counts=True, max_iter=40, min_iter=10)
+    one = ca.bootstrap_em_batch_groups(p.grid, p.ages, p.weights, p.tabs, p.epochs(), **kw)
+    assert np.array_equal(one[4], p.csh) and np.array_equal(one[5], p.cns)
+    for devs in ([0, 1], [1, 0, 1]):
+        got = ca.bootstrap_em_batch_groups_sharded(devs, p.grid, p.ages, p.weights, p.tabs, p.epochs(), **kw)
+        assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(got, one)), devs
+
+
 @pytest.mark.parametrize("how", ["--devices", "--ranks"])
 def test_cli_two_gpus_equal_one(ca, how, tmp_path):
     """`Colate --devices 2` (one process, two GPUs) and `Colate --ranks 2` (two processes, one RCCL all-gather):
