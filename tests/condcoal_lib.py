@@ -158,8 +158,9 @@ def assert_close(a, b, rel=1e-12):
         assert r.max() <= rel, r.max()
 
 
-def accumulate_in_child(tmpdir, inp, epochs, efocal, device, timeout):
-    """colate_amd.condcoal_accumulate in a child process under a time limit (the GPU steps of the tests): (num, denom)."""
+def accumulate_in_child(tmpdir, inp, epochs, efocal, device, timeout, env=None):
+    """colate_amd.condcoal_accumulate in a child process under a time limit (the GPU steps of the tests): (num, denom).
+    env: variables added to the child's environment (COLATE_CONDCOAL_CHUNK_TREES, say)."""
     import sys
     tag = f"{os.getpid()}_{random.getrandbits(32)}"
     src = os.path.join(str(tmpdir), f"in_{tag}.npz")
@@ -167,7 +168,7 @@ def accumulate_in_child(tmpdir, inp, epochs, efocal, device, timeout):
     arrays = {k: np.asarray(v) for k, v in inp.items() if v is not None}
     np.savez(src, epochs=epochs, efocal=efocal, **arrays)
     r = subprocess.run([sys.executable, os.path.abspath(__file__), src, dst, "1" if device else "0"], capture_output=True,
-                       text=True, timeout=timeout)
+                       text=True, timeout=timeout, env=dict(os.environ, **(env or {})))
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     out = np.load(dst)
     return out["num"], out["denom"]

@@ -30,8 +30,15 @@ def _leaves(parent, N):
     return members, children
 
 
-def tree_accumulators(parent, bl, factor, group_of_hap, G, focal, cond, epochs, efocal, ages=None):
-    """num, denom [EF][E][G] (float64) of one tree.  cond: conditional haplotypes ([] = the empty group, [-1])."""
+def _hit(events, key, n=1):
+    if events is not None:
+        events[key] = events.get(key, 0) + n
+
+
+def tree_accumulators(parent, bl, factor, group_of_hap, G, focal, cond, epochs, efocal, ages=None, events=None):
+    """num, denom [EF][E][G] (float64) of one tree.  cond: conditional haplotypes ([] = the empty group, [-1]).
+    events: an optional dict that counts, per key, how often the walk met an edge (a coordinate on a boundary, a search
+    that ran off its vector, ...): what an input exercises, counted where it happens.  The sums do not depend on it."""
     N = (len(parent) + 1) // 2
     nn = 2 * N - 1
     E, EF = len(epochs), len(efocal)
@@ -44,6 +51,7 @@ def tree_accumulators(parent, bl, factor, group_of_hap, G, focal, cond, epochs, 
     conds = list(cond) if len(cond) else [-1]
     ancient = ages is not None
     for f in focal:
+        joins = {}  # ancestor at which a conditional joins f's lineage -> how many do (the walk's class weight m)
         for c in conds:
             if f == c:
                 continue
@@ -59,12 +67,17 @@ def tree_accumulators(parent, bl, factor, group_of_hap, G, focal, cond, epochs, 
                     if c in members[node]:
                         coal_age = coord
                         use = True
+                        joins[node] = joins.get(node, 0) + 1
+                        if coal_age in efocal[1:]:
+                            _hit(events, "ancient_coal_age_on_focal_boundary" if ancient else "modern_coal_age_on_focal_boundary")
                     s = 0
                     if ancient:
                         if efocal[s] < coord:
                             while efocal[s] < coord:
                                 s += 1
                                 if s == EF:
+                                    if use:
+                                        _hit(events, "focal_search_hits_EF")
                                     break
                             s -= 1
                     else:
@@ -72,6 +85,8 @@ def tree_accumulators(parent, bl, factor, group_of_hap, G, focal, cond, epochs, 
                             while efocal[s] <= coal_age:
                                 s += 1
                                 if s == EF:
+                                    if use:
+                                        _hit(events, "focal_search_hits_EF")
                                     break
                             if s > 0:
                                 s -= 1
@@ -83,7 +98,18 @@ def tree_accumulators(parent, bl, factor, group_of_hap, G, focal, cond, epochs, 
                     if coal_age > epochs[0]:
                         while ep_init < E and coal_age > epochs[ep_init]:
                             ep_init += 1
+                        if ep_init == E:
+                            _hit(events, "epoch_search_hits_E")
                         ep_init -= 1
+                    if events is not None:
+                        if coord in epochs[1:E]:
+                            _hit(events, "coord_on_epoch_boundary")
+                        if coal_age in epochs[1:E]:
+                            _hit(events, "coal_age_on_epoch_boundary")
+                        if float(bl[node]) == 0.0:
+                            _hit(events, "zero_branch_on_used_step")
+                        if not ancient:
+                            _hit(events, "modern_sibling_smaller_than_G" if len(members[sib]) < G else "modern_sibling_at_least_G")
                     for x in members[sib]:
                         g = group_of_hap[x]
                         if ancient:
@@ -95,24 +121,40 @@ def tree_accumulators(parent, bl, factor, group_of_hap, G, focal, cond, epochs, 
                                     while efocal[s] < lower:
                                         s += 1
                                         if s == EF:
+                                            _hit(events, "focal_search_hits_EF")
                                             break
                                     s -= 1
                                 if epochs[ep] < lower:
                                     while epochs[ep] < lower:
                                         ep += 1
                                         if ep == E:
+                                            _hit(events, "epoch_search_hits_E")
                                             break
                                     ep -= 1
+                                if events is not None:
+                                    tag = "empty_cond" if c == -1 else "nonempty_cond"
+                                    _hit(events, f"ancient_lower_above_coal_age_{tag}")
+                                    if s != ep_coal:
+                                        _hit(events, f"ancient_lower_advances_s_{tag}")
+                                    if ep != ep_init:
+                                        _hit(events, f"ancient_lower_advances_ep_{tag}")
+                                    if lower in efocal[1:]:
+                                        _hit(events, "ancient_lower_on_focal_boundary")
+                                    if lower in epochs[1:E]:
+                                        _hit(events, "ancient_lower_on_epoch_boundary")
                         else:
                             lower, s, ep = coal_age, ep_coal, ep_init
                         while coord > epochs[ep + 1]:
                             den[s, ep, g] += float(factor * f32(epochs[ep + 1] - lower))
                             ep += 1
                             lower = epochs[ep]
+                        if ep + 1 == E:
+                            _hit(events, "epoch_past_the_end_read_as_inf")
                         den[s, ep, g] += float(factor * f32(coord - lower))
                         num[s, ep, g] += float(factor)
                 node = p
                 if node == nn - 1:
                     break
                 p = parent[node]
+        _hit(events, "class_weight_above_one", sum(1 for m in joins.values() if m > 1))
     return num, den
