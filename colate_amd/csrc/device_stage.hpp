@@ -1,7 +1,8 @@
 // colate_amd/csrc/device_stage.hpp -- what every device walker of the tree-based estimators owns, whatever it walks
 // (condcoal_device.hpp: CondCoalRates; coalrate_device.hpp: the two CoalRate modes): the opened device, one stream, its
 // events, device and pinned memory that goes with the walker, and arrays staged through a pinned copy.  Nothing here
-// knows about trees.
+// knows about trees: the table fill's DeviceFill (fill_kernel.hip), which runs several streams of its own, takes
+// DeviceBuffers and WALKER_TRY from here.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -12,9 +12,14 @@
 //     different bins and different (pair, block) tables are independent: a wave per (pair, block), its bins in its lanes (the tables
 //     live in registers), the counts of a SNP's samples per bin from an LDS histogram (integers: no order), then as many additions
 //     as the fullest bin got, every lane on its own bins.
+// Two ways in, one kernel (fill_kernel.hip): DeviceFill, for records and jobs staged from the host (the engine of `--pairs`,
+// mut_pairs.cpp), and fill_sample_launch, for records and jobs the pair walk formed on the device (`--samples`,
+// fill_samples_kernel.hip).  The guard bands come from FastBin (age_bins.hpp), the uniforms from uniform_stream.hpp.  No HIP type
+// outside the __HIPCC__ part: host-only translation units include this.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -33,62 +38,49 @@ struct FillJob {        // the SNPs of one (pair, genome block), in file order
   uint32_t table;       // which [2][A] table (shared | not shared) on the device
 };
 
+// The device side of the engine's fill (`--pairs` and a single pair): records and jobs staged from the host, batch by batch.
+// Two page-locked staging buffers on the host (one is filled while the other is copied) and four record buffers on the device,
+// each with a stream of its own, so that several launches run at the same time; the uniforms go up on a copy stream beside them.
+// The implementation is in fill_kernel.hip; a build without device code defines the two free functions below to say so.
 class DeviceFill {
  public:
-  static bool available();  // a HIP device is there
-  // null (and a reason in `why`) when there is no device to use
-  static DeviceFill* create(int device, int A, const double* guard_lo, const double* guard_hi, size_t max_tables, size_t batch_recs, std::string& why);
+  virtual ~DeviceFill() = default;
   // the two page-locked record buffers and their device copies (the slow part of the set-up -- gigabytes to lock --: callable from
   // another thread while uniforms are uploaded; before the first staging() / submit())
-  bool alloc_staging();
+  virtual bool alloc_staging() = 0;
   // room for the uniform stream (known once the inputs have been read: a pair takes at most 100 per row)
-  bool alloc_uniforms(uint64_t max_uniforms);
-  ~DeviceFill();
-  FillRec* staging() { return stage_[cur_]; }  // pinned: where the next batch's records go
-  size_t staging_capacity() const { return batch_recs_; }
+  virtual bool alloc_uniforms(uint64_t max_uniforms) = 0;
+  virtual FillRec* staging() = 0;  // pinned: where the next batch's records go
+  virtual size_t staging_capacity() const = 0;
   // page-locks a host buffer the uniforms will be uploaded from (the ring of the stream's producer): pageable memory goes through
   // a staging copy at a few GB/s, 6 GB of uniforms are then seconds of wall time.  Failure is not an error (the upload works either way).
-  void pin(void* p, size_t bytes);
+  virtual void pin(void* p, size_t bytes) = 0;
   // uniforms [off, off + n) of the stream: the copy is enqueued (launches submitted later wait for it on the device); the source may
   // be reused after sync_uploads()
-  bool upload_uniforms(uint64_t off, const double* src, size_t n);
-  bool sync_uploads();
+  virtual bool upload_uniforms(uint64_t off, const double* src, size_t n) = 0;
+  virtual bool sync_uploads() = 0;
   // records staging()[0 .. nrecs) and the jobs that refer to them: copied and launched asynchronously; staging() is another buffer afterwards
-  bool submit(const std::vector<FillJob>& jobs, size_t nrecs);
+  virtual bool submit(const std::vector<FillJob>& jobs, size_t nrecs) = 0;
   // waits for everything; tables [max_tables][2][A]; flags per table: 1 = a sample needs the host (guard band, redraw, range): redo the pair
-  bool finish(std::vector<double>& tables, std::vector<int>& flags);
+  virtual bool finish(std::vector<double>& tables, std::vector<int>& flags) = 0;
   const std::string& error() const { return err_; }
   double gpu_seconds() const { return gpu_s_; }
 
- private:
-  DeviceFill() = default;
-  int device_ = 0, A_ = 0, cur_ = 0;
-  uint64_t max_uniforms_ = 0;
-  size_t max_tables_ = 0, batch_recs_ = 0, max_jobs_ = 0;
-  double *d_u_ = nullptr, *d_lo_ = nullptr, *d_hi_ = nullptr, *d_tables_ = nullptr;
-  int* d_flags_ = nullptr;
-  // Two page-locked staging buffers on the host (one is filled while the other is copied), kDev record buffers on the device: a
-  // staging buffer is free again when its copy has completed, a device buffer when its kernel has -- so up to kDev launches run at
-  // the same time (a launch of ~1200 jobs is about one wave per SIMD, each waiting most of the time: they interleave).
-  static constexpr int kDev = 4;
-  FillRec* stage_[2] = {nullptr, nullptr};
-  FillJob* h_jobs_[2] = {nullptr, nullptr};
-  void* ev_h2d_[2] = {nullptr, nullptr};
-  bool copied_[2] = {false, false};
-  FillRec* d_recs_[kDev] = {nullptr, nullptr, nullptr, nullptr};
-  FillJob* d_jobs_[kDev] = {nullptr, nullptr, nullptr, nullptr};
-  void* stream_[kDev] = {nullptr, nullptr, nullptr, nullptr};
-  void* ev_[kDev][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};  // per device buffer: start / end of its latest kernel
-  bool launched_[kDev] = {false, false, false, false};
-  int dcur_ = 0;
-  void* copy_stream_ = nullptr;
-  void* upload_ev_ = nullptr;
-  bool uploads_pending_ = false;
+ protected:
+  bool fail(const std::string& what, int) {
+    err_ = what;
+    return false;
+  }
   double gpu_s_ = 0;
-  std::vector<void*> pinned_;
+
+ private:
   std::string err_;
-  bool fail(const char* what, int code);
 };
+
+bool fill_device_available();  // a HIP device is there
+// null (and a reason in `why`) when there is no device to use
+std::unique_ptr<DeviceFill> make_device_fill(int device, int A, const double* guard_lo, const double* guard_hi, size_t max_tables,
+                                             size_t batch_recs, std::string& why);
 
 }  // namespace colate_drv
 

@@ -4,9 +4,12 @@
 // the device by the pair walk: `--samples`, fill_samples_kernel.hip).  One kernel.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
 
+#include "device_stage.hpp"
 #include "fill_device.h"
 
 namespace colate_drv {
@@ -155,33 +158,197 @@ hipError_t fill_sample_launch(const FillJob* jobs, int njobs, const FillRec* rec
   return hipGetLastError();
 }
 
-bool DeviceFill::fail(const char* what, int code) {
-  char buf[256];
-  std::snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString((hipError_t)code));
-  err_ = buf;
-  return false;
-}
+namespace {
 
-#define FILL_TRY(call)                                     \
-  do {                                                     \
-    const hipError_t e_ = (call);                          \
-    if (e_ != hipSuccess) return fail(#call, (int)e_);     \
-  } while (0)
+// DeviceFill on a HIP device.  Two page-locked staging buffers on the host (one is filled while the other is copied), kDev record
+// buffers on the device: a staging buffer is free again when its copy has completed, a device buffer when its kernel has -- so up
+// to kDev launches run at the same time (a launch of ~1200 jobs is about one wave per SIMD, each waiting most of the time: they
+// interleave).  Pool threads call in: every entry sets the device.
+class HipDeviceFill final : public DeviceFill {
+ public:
+  HipDeviceFill(int device, int A, size_t max_tables, size_t batch_recs)
+      : device_(device), A_(A), max_tables_(max_tables), batch_recs_(batch_recs) {}
 
-bool DeviceFill::available() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return false;
+  bool init(const double* guard_lo, const double* guard_hi) {
+    WALKER_TRY(hipSetDevice(device_));
+    const size_t bands = (size_t)A_ + 2, tb = max_tables_ * 2 * (size_t)A_;
+    WALKER_TRY(buf_.device(d_lo_, bands));
+    WALKER_TRY(buf_.device(d_hi_, bands));
+    WALKER_TRY(buf_.device(d_tables_, tb));
+    WALKER_TRY(buf_.device(d_flags_, max_tables_));
+    WALKER_TRY(hipMemcpy(d_lo_, guard_lo, bands * sizeof(double), hipMemcpyHostToDevice));
+    WALKER_TRY(hipMemcpy(d_hi_, guard_hi, bands * sizeof(double), hipMemcpyHostToDevice));
+    WALKER_TRY(hipMemset(d_tables_, 0, tb * sizeof(double)));
+    WALKER_TRY(hipMemset(d_flags_, 0, max_tables_ * sizeof(int)));
+    for (int b = 0; b < 2; b++) {
+      WALKER_TRY(buf_.pinned(h_jobs_[b], kMaxJobs));
+      WALKER_TRY(hipEventCreateWithFlags(&ev_h2d_[b], hipEventDisableTiming));
+    }
+    for (int b = 0; b < kDev; b++) {
+      WALKER_TRY(buf_.device(d_jobs_[b], kMaxJobs));
+      WALKER_TRY(hipStreamCreateWithFlags(&stream_[b], hipStreamNonBlocking));
+      for (int k = 0; k < 2; k++) WALKER_TRY(hipEventCreate(&ev_[b][k]));
+    }
+    WALKER_TRY(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
+    WALKER_TRY(hipEventCreateWithFlags(&upload_ev_, hipEventDisableTiming));
+    return true;
   }
-  return true;
-}
 
-DeviceFill* DeviceFill::create(int device, int A, const double* guard_lo, const double* guard_hi, size_t max_tables, size_t batch_recs,
-                               std::string& why) {
+  ~HipDeviceFill() override {
+    (void)hipSetDevice(device_);
+    // every stream first (errors ignored): after a failed submit copies out of the pinned uniform ring may still be in flight
+    if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
+    for (hipStream_t s : stream_)
+      if (s) (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+    for (void* p : registered_) (void)hipHostUnregister(p);
+    for (hipEvent_t e : {ev_h2d_[0], ev_h2d_[1], upload_ev_})
+      if (e) (void)hipEventDestroy(e);
+    for (int b = 0; b < kDev; b++) {
+      for (hipEvent_t e : ev_[b])
+        if (e) (void)hipEventDestroy(e);
+      if (stream_[b]) (void)hipStreamDestroy(stream_[b]);
+    }
+    if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
+  }  // (buf_ frees the device and the page-locked memory behind this)
+
+  bool alloc_staging() override {
+    WALKER_TRY(hipSetDevice(device_));
+    for (int b = 0; b < kDev; b++) WALKER_TRY(buf_.device(d_recs_[b], batch_recs_));
+    for (int b = 0; b < 2; b++) WALKER_TRY(buf_.pinned(stage_[b], batch_recs_));
+    return true;
+  }
+
+  bool alloc_uniforms(uint64_t max_uniforms) override {
+    WALKER_TRY(hipSetDevice(device_));
+    WALKER_TRY(buf_.device(d_u_, max_uniforms + kDraws));
+    max_uniforms_ = max_uniforms;
+    return true;
+  }
+
+  FillRec* staging() override { return stage_[cur_]; }
+  size_t staging_capacity() const override { return batch_recs_; }
+
+  void pin(void* p, size_t bytes) override {
+    if (hipSetDevice(device_) != hipSuccess) return;
+    if (hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess) registered_.push_back(p);
+    else (void)hipGetLastError();
+  }
+
+  bool upload_uniforms(uint64_t off, const double* src, size_t n) override {
+    if (off + n > max_uniforms_ + kDraws) return fail("uniform stream longer than the device buffer", COLATE_EINVAL);
+    WALKER_TRY(hipSetDevice(device_));
+    WALKER_TRY(hipMemcpyAsync(d_u_ + off, src, n * sizeof(double), hipMemcpyHostToDevice, copy_stream_));
+    uploads_pending_ = true;
+    return true;
+  }
+
+  bool sync_uploads() override {
+    if (!uploads_pending_) return true;
+    WALKER_TRY(hipSetDevice(device_));
+    WALKER_TRY(hipStreamSynchronize(copy_stream_));
+    uploads_pending_ = false;
+    return true;
+  }
+
+  bool submit(const std::vector<FillJob>& jobs, size_t nrecs) override {
+    if (jobs.empty()) return true;
+    if (jobs.size() > kMaxJobs || nrecs > batch_recs_) return fail("batch larger than its buffers", COLATE_EINVAL);
+    WALKER_TRY(hipSetDevice(device_));
+    const int h = cur_, d = dcur_;
+    const hipStream_t s = stream_[d];
+    if (launched_[d]) {  // the device buffer's previous kernel (kDev launches ago)
+      WALKER_TRY(hipEventSynchronize(ev_[d][1]));
+      book_kernel(d);
+    }
+    if (uploads_pending_) {  // the launch reads uniforms whose copies may still be in flight on the copy stream
+      WALKER_TRY(hipEventRecord(upload_ev_, copy_stream_));
+      WALKER_TRY(hipStreamWaitEvent(s, upload_ev_, 0));
+    }
+    std::memcpy(h_jobs_[h], jobs.data(), jobs.size() * sizeof(FillJob));
+    WALKER_TRY(hipMemcpyAsync(d_recs_[d], stage_[h], nrecs * sizeof(FillRec), hipMemcpyHostToDevice, s));
+    WALKER_TRY(hipMemcpyAsync(d_jobs_[d], h_jobs_[h], jobs.size() * sizeof(FillJob), hipMemcpyHostToDevice, s));
+    WALKER_TRY(hipEventRecord(ev_h2d_[h], s));
+    copied_[h] = true;
+    WALKER_TRY(hipEventRecord(ev_[d][0], s));
+    WALKER_TRY(fill_sample_launch(d_jobs_[d], (int)jobs.size(), d_recs_[d], d_u_, d_lo_, d_hi_, A_, d_tables_, d_flags_, s));
+    WALKER_TRY(hipEventRecord(ev_[d][1], s));
+    launched_[d] = true;
+    // one (pair, block) table is touched by one job only: launches need no order among themselves.  The other staging buffer is what
+    // the host fills next: the copy out of it (two submits ago) must have completed
+    dcur_ = (dcur_ + 1) % kDev;
+    cur_ ^= 1;
+    if (copied_[cur_]) {
+      WALKER_TRY(hipEventSynchronize(ev_h2d_[cur_]));
+      copied_[cur_] = false;
+    }
+    return true;
+  }
+
+  bool finish(std::vector<double>& tables, std::vector<int>& flags) override {
+    WALKER_TRY(hipSetDevice(device_));
+    if (!sync_uploads()) return false;
+    for (int b = 0; b < kDev; b++) {
+      WALKER_TRY(hipStreamSynchronize(stream_[b]));
+      if (launched_[b]) book_kernel(b);
+    }
+    tables.resize(max_tables_ * 2 * (size_t)A_);
+    flags.resize(max_tables_);
+    WALKER_TRY(hipMemcpy(tables.data(), d_tables_, tables.size() * sizeof(double), hipMemcpyDeviceToHost));
+    WALKER_TRY(hipMemcpy(flags.data(), d_flags_, flags.size() * sizeof(int), hipMemcpyDeviceToHost));
+    return true;
+  }
+
+ private:
+  static constexpr int kDev = 4;
+  static constexpr size_t kMaxJobs = 1u << 16;  // per submit
+
+  // the time of device buffer b's latest kernel, which has completed
+  void book_kernel(int b) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev_[b][0], ev_[b][1]) == hipSuccess) gpu_s_ += ms * 1e-3;
+    launched_[b] = false;
+  }
+
+  const int device_, A_;
+  const size_t max_tables_, batch_recs_;
+  uint64_t max_uniforms_ = 0;
+  int cur_ = 0, dcur_ = 0;  // the staging buffer the host fills, the device buffer the next submit takes
+  colate::DeviceBuffers buf_;
+  double *d_u_ = nullptr, *d_lo_ = nullptr, *d_hi_ = nullptr, *d_tables_ = nullptr;
+  int* d_flags_ = nullptr;
+  FillRec* stage_[2] = {};
+  FillJob* h_jobs_[2] = {};
+  hipEvent_t ev_h2d_[2] = {};
+  bool copied_[2] = {};
+  FillRec* d_recs_[kDev] = {};
+  FillJob* d_jobs_[kDev] = {};
+  hipStream_t stream_[kDev] = {};
+  hipEvent_t ev_[kDev][2] = {};  // per device buffer: start / end of its latest kernel
+  bool launched_[kDev] = {};
+  hipStream_t copy_stream_ = nullptr;
+  hipEvent_t upload_ev_ = nullptr;
+  bool uploads_pending_ = false;
+  std::vector<void*> registered_;  // (pin)
+};
+
+int device_count() {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
     (void)hipGetLastError();
+    return 0;
+  }
+  return n;
+}
+
+}  // namespace
+
+bool fill_device_available() { return device_count() > 0; }
+
+std::unique_ptr<DeviceFill> make_device_fill(int device, int A, const double* guard_lo, const double* guard_hi, size_t max_tables,
+                                             size_t batch_recs, std::string& why) {
+  const int n = device_count();
+  if (n < 1) {
     why = "no HIP device";
     return nullptr;
   }
@@ -189,177 +356,12 @@ DeviceFill* DeviceFill::create(int device, int A, const double* guard_lo, const 
     why = "age bins outside 1 .. 256";
     return nullptr;
   }
-  DeviceFill* d = new DeviceFill;
-  d->device_ = device % n, d->A_ = A, d->max_uniforms_ = 0, d->max_tables_ = max_tables, d->batch_recs_ = batch_recs;
-  d->max_jobs_ = 1u << 16;
-  auto init = [&]() -> bool {
-    DeviceFill& o = *d;
-    if (hipSetDevice(o.device_) != hipSuccess) return o.fail("hipSetDevice", (int)hipGetLastError());
-    const size_t tb = max_tables * 2 * (size_t)A * sizeof(double);
-    if (hipMalloc(&o.d_lo_, (A + 2) * sizeof(double)) != hipSuccess || hipMalloc(&o.d_hi_, (A + 2) * sizeof(double)) != hipSuccess ||
-        hipMalloc(&o.d_tables_, tb) != hipSuccess || hipMalloc(&o.d_flags_, max_tables * sizeof(int)) != hipSuccess)
-      return o.fail("hipMalloc (tables)", (int)hipGetLastError());
-    if (hipMemcpy(o.d_lo_, guard_lo, (A + 2) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(o.d_hi_, guard_hi, (A + 2) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(o.d_tables_, 0, tb) != hipSuccess || hipMemset(o.d_flags_, 0, max_tables * sizeof(int)) != hipSuccess)
-      return o.fail("hipMemcpy (thresholds)", (int)hipGetLastError());
-    for (int b = 0; b < 2; b++) {
-      if (hipHostMalloc(reinterpret_cast<void**>(&o.h_jobs_[b]), o.max_jobs_ * sizeof(FillJob), hipHostMallocDefault) != hipSuccess)
-        return o.fail("hipHostMalloc (jobs)", (int)hipGetLastError());
-      hipEvent_t e;
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return o.fail("hipEventCreate", (int)hipGetLastError());
-      o.ev_h2d_[b] = e;
-    }
-    for (int b = 0; b < kDev; b++) {
-      if (hipMalloc(&o.d_jobs_[b], o.max_jobs_ * sizeof(FillJob)) != hipSuccess) return o.fail("hipMalloc (jobs)", (int)hipGetLastError());
-      hipStream_t s;
-      if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return o.fail("hipStreamCreate", (int)hipGetLastError());
-      o.stream_[b] = s;
-      for (int k = 0; k < 2; k++) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return o.fail("hipEventCreate", (int)hipGetLastError());
-        o.ev_[b][k] = e;
-      }
-    }
-    hipStream_t cs;
-    if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) return o.fail("hipStreamCreate", (int)hipGetLastError());
-    o.copy_stream_ = cs;
-    hipEvent_t ue;
-    if (hipEventCreateWithFlags(&ue, hipEventDisableTiming) != hipSuccess) return o.fail("hipEventCreate", (int)hipGetLastError());
-    o.upload_ev_ = ue;
-    return true;
-  };
-  if (!init()) {
-    why = d->err_;
-    delete d;
+  std::unique_ptr<HipDeviceFill> d(new HipDeviceFill(device % n, A, max_tables, batch_recs));
+  if (!d->init(guard_lo, guard_hi)) {
+    why = d->error();
     return nullptr;
   }
   return d;
-}
-
-DeviceFill::~DeviceFill() {
-  (void)hipSetDevice(device_);
-  // every stream first (errors ignored): after a failed submit copies out of the pinned uniform ring may still be in flight
-  if (copy_stream_) (void)hipStreamSynchronize((hipStream_t)copy_stream_);
-  for (int b = 0; b < kDev; b++)
-    if (stream_[b]) (void)hipStreamSynchronize((hipStream_t)stream_[b]);
-  (void)hipGetLastError();
-  for (void* p : pinned_) (void)hipHostUnregister(p);
-  for (int b = 0; b < 2; b++) {
-    if (stage_[b]) (void)hipHostFree(stage_[b]);
-    if (h_jobs_[b]) (void)hipHostFree(h_jobs_[b]);
-    if (ev_h2d_[b]) (void)hipEventDestroy((hipEvent_t)ev_h2d_[b]);
-  }
-  for (int b = 0; b < kDev; b++) {
-    if (d_recs_[b]) (void)hipFree(d_recs_[b]);
-    if (d_jobs_[b]) (void)hipFree(d_jobs_[b]);
-    for (int k = 0; k < 2; k++)
-      if (ev_[b][k]) (void)hipEventDestroy((hipEvent_t)ev_[b][k]);
-    if (stream_[b]) (void)hipStreamDestroy((hipStream_t)stream_[b]);
-  }
-  if (upload_ev_) (void)hipEventDestroy((hipEvent_t)upload_ev_);
-  if (copy_stream_) (void)hipStreamDestroy((hipStream_t)copy_stream_);
-  for (void* p : {(void*)d_u_, (void*)d_lo_, (void*)d_hi_, (void*)d_tables_, (void*)d_flags_})
-    if (p) (void)hipFree(p);
-}
-
-bool DeviceFill::alloc_staging() {
-  FILL_TRY(hipSetDevice(device_));
-  for (int b = 0; b < kDev; b++) FILL_TRY(hipMalloc(&d_recs_[b], batch_recs_ * sizeof(FillRec)));
-  for (int b = 0; b < 2; b++) FILL_TRY(hipHostMalloc(reinterpret_cast<void**>(&stage_[b]), batch_recs_ * sizeof(FillRec), hipHostMallocDefault));
-  return true;
-}
-
-bool DeviceFill::alloc_uniforms(uint64_t max_uniforms) {
-  FILL_TRY(hipSetDevice(device_));
-  FILL_TRY(hipMalloc(&d_u_, (max_uniforms + kDraws) * sizeof(double)));
-  max_uniforms_ = max_uniforms;
-  return true;
-}
-
-void DeviceFill::pin(void* p, size_t bytes) {
-  if (hipSetDevice(device_) != hipSuccess) return;
-  if (hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess) pinned_.push_back(p);
-  else (void)hipGetLastError();
-}
-
-bool DeviceFill::upload_uniforms(uint64_t off, const double* src, size_t n) {
-  if (off + n > max_uniforms_ + kDraws) {
-    err_ = "uniform stream longer than the device buffer";
-    return false;
-  }
-  FILL_TRY(hipSetDevice(device_));
-  FILL_TRY(hipMemcpyAsync(d_u_ + off, src, n * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)copy_stream_));
-  uploads_pending_ = true;
-  return true;
-}
-
-bool DeviceFill::sync_uploads() {
-  if (!uploads_pending_) return true;
-  FILL_TRY(hipSetDevice(device_));
-  FILL_TRY(hipStreamSynchronize((hipStream_t)copy_stream_));
-  uploads_pending_ = false;
-  return true;
-}
-
-bool DeviceFill::submit(const std::vector<FillJob>& jobs, size_t nrecs) {
-  if (jobs.empty()) return true;
-  if (jobs.size() > max_jobs_ || nrecs > batch_recs_) {
-    err_ = "batch larger than its buffers";
-    return false;
-  }
-  FILL_TRY(hipSetDevice(device_));
-  const int h = cur_, d = dcur_;
-  hipStream_t s = (hipStream_t)stream_[d];
-  if (launched_[d]) {  // the device buffer's previous kernel (kDev launches ago)
-    FILL_TRY(hipEventSynchronize((hipEvent_t)ev_[d][1]));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, (hipEvent_t)ev_[d][0], (hipEvent_t)ev_[d][1]) == hipSuccess) gpu_s_ += ms * 1e-3;
-    launched_[d] = false;
-  }
-  if (uploads_pending_) {  // the launch reads uniforms whose copies may still be in flight on the copy stream
-    FILL_TRY(hipEventRecord((hipEvent_t)upload_ev_, (hipStream_t)copy_stream_));
-    FILL_TRY(hipStreamWaitEvent(s, (hipEvent_t)upload_ev_, 0));
-  }
-  std::memcpy(h_jobs_[h], jobs.data(), jobs.size() * sizeof(FillJob));
-  FILL_TRY(hipMemcpyAsync(d_recs_[d], stage_[h], nrecs * sizeof(FillRec), hipMemcpyHostToDevice, s));
-  FILL_TRY(hipMemcpyAsync(d_jobs_[d], h_jobs_[h], jobs.size() * sizeof(FillJob), hipMemcpyHostToDevice, s));
-  FILL_TRY(hipEventRecord((hipEvent_t)ev_h2d_[h], s));
-  copied_[h] = true;
-  FILL_TRY(hipEventRecord((hipEvent_t)ev_[d][0], s));
-  const int nj = (int)jobs.size();
-  hipLaunchKernelGGL(fill_sample_kernel, dim3((nj + kJobsPerBlock - 1) / kJobsPerBlock), dim3(kJobsPerBlock * kWave), 0, s, d_jobs_[d], nj, d_recs_[d],
-                     d_u_, d_lo_, d_hi_, A_, d_tables_, d_flags_);
-  FILL_TRY(hipGetLastError());
-  FILL_TRY(hipEventRecord((hipEvent_t)ev_[d][1], s));
-  launched_[d] = true;
-  // one (pair, block) table is touched by one job only: launches need no order among themselves.  The other staging buffer is what
-  // the host fills next: the copy out of it (two submits ago) must have completed
-  dcur_ = (dcur_ + 1) % kDev;
-  cur_ ^= 1;
-  if (copied_[cur_]) {
-    FILL_TRY(hipEventSynchronize((hipEvent_t)ev_h2d_[cur_]));
-    copied_[cur_] = false;
-  }
-  return true;
-}
-
-bool DeviceFill::finish(std::vector<double>& tables, std::vector<int>& flags) {
-  FILL_TRY(hipSetDevice(device_));
-  if (!sync_uploads()) return false;
-  for (int b = 0; b < kDev; b++) {
-    FILL_TRY(hipStreamSynchronize((hipStream_t)stream_[b]));
-    if (launched_[b]) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, (hipEvent_t)ev_[b][0], (hipEvent_t)ev_[b][1]) == hipSuccess) gpu_s_ += ms * 1e-3;
-      launched_[b] = false;
-    }
-  }
-  tables.resize(max_tables_ * 2 * (size_t)A_);
-  flags.resize(max_tables_);
-  FILL_TRY(hipMemcpy(tables.data(), d_tables_, tables.size() * sizeof(double), hipMemcpyDeviceToHost));
-  FILL_TRY(hipMemcpy(flags.data(), d_flags_, flags.size() * sizeof(int), hipMemcpyDeviceToHost));
-  return true;
 }
 
 }  // namespace colate_drv

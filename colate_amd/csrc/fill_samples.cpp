@@ -1,17 +1,23 @@
 // colate_amd/csrc/fill_samples.cpp -- the host side of colate_fill_samples (fill_samples.h: the contract): the checks of both
 // forms, the host twin -- a plain loop per pair with a std::mt19937 of its own, the logarithm of age_bin_index and the redraw
-// loop of coal.cpp:2279-2295, so it is right for every input --, the chunk plan of the device form, and the C entry points.
+// loop of coal.cpp:2279-2295, so it is right for every input --, the chunk plan of the device form, the C entry points, and
+// fill_sample_pairs, the fill of `Colate --mode mut --samples` around the device form (mut_feeder.h).
 #include <algorithm>
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
+#include <iostream>
 #include <random>
+#include <string>
 #include <vector>
 
+#include "age_bins.hpp"
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "fill_samples.h"
 #include "interval_walk.h"
 #include "mut_feeder.h"
+#include "uniform_stream.hpp"
 
 using colate::fail;
 using colate_drv::FillRec;
@@ -40,7 +46,7 @@ int size_result(const View& v, int A, const int* cnt, const int* last, std::vect
 
 namespace {
 // inside the guard band of a located step: lo[k] <= x < hi[k] for some k in 1 .. A (the bands do not overlap and ascend)
-bool in_band(const colate_drv::AgeBins* bands, int A, double x) {
+bool in_band(const colate_drv::FastBin* bands, int A, double x) {
   if (!bands) return false;
   const double* lo = bands->guard_lo();
   const double* hi = bands->guard_hi();
@@ -49,7 +55,7 @@ bool in_band(const colate_drv::AgeBins* bands, int A, double x) {
 }
 }  // namespace
 
-void twin_pair(const View& v, int p, int A, unsigned seed, const int* blk0, const colate_drv::AgeBins* bands, Result& out) {
+void twin_pair(const View& v, int p, int A, unsigned seed, const int* blk0, const colate_drv::FastBin* bands, Result& out) {
   const double C = 10.0, age = 0.0;
   const size_t n = (size_t)out.used[(size_t)p];
   std::vector<FillRec> recs(n);
@@ -114,7 +120,7 @@ int fill_view_host(const View& v, int A, unsigned seed, Result& out) {
   std::vector<int> cnt(PC), last(PC), blk0;
   for (int p = 0; p < v.P; p++) host_count(v, p, cnt.data() + (size_t)p * v.C, last.data() + (size_t)p * v.C);
   if (int rc = size_result(v, A, cnt.data(), last.data(), blk0, out)) return rc;
-  const colate_drv::AgeBins bands(A);
+  const colate_drv::FastBin bands(A, 10.0);
   for (int p = 0; p < v.P; p++) twin_pair(v, p, A, seed, blk0.data() + (size_t)p * v.C, bands.ok() ? &bands : nullptr, out);
   out.chunks = 0, out.kernel_s = 0.0;
   return COLATE_OK;
@@ -180,6 +186,63 @@ int fill_call(bool device, const FlatView& f, int A, unsigned seed, long long ca
 }  // namespace
 
 }  // namespace colate_fs
+
+namespace colate_drv {
+
+// (mut_feeder.h)
+bool fill_sample_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                       const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& out) {
+  const auto through_engine = [&](const char* why) {
+    std::cerr << "pairs walked and filled through the engine of --pairs (" << why << ")" << std::endl;
+    return fill_pairs(opt, names, mut_files, pairs, todo, seed, A, out);
+  };
+  for (const char* name : {"COLATE_DEVICE_FILL", "COLATE_DEVICE_FILL_WALK"})
+    if (const char* e = std::getenv(name))
+      if (std::atoi(e) == 0) return through_engine((std::string(name) + "=0").c_str());
+  if (colate_device_count() < 1) return through_engine("no device");
+  if (opt.has("device"))
+    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc) == 0;
+  const double t0 = StageTimes::now();
+  std::vector<PairSpec> mine;
+  for (size_t p : todo) mine.push_back(pairs[p]);
+  WalkInputs in;
+  if (!load_walk_inputs(names, mut_files, mine, in)) return false;
+  if (!in.indexed) return through_engine("a sample has no walk index");
+  View v;
+  v.C = (int)names.size(), v.row_off = in.row_off.data(), v.rows = in.row_ptrs.data(), v.S = in.S, v.idx = in.idx_ptrs.data(), v.M = in.M;
+  v.masks = in.mask_ptrs.data(), v.P = (int)mine.size(), v.pairs = in.pairs.data(), v.nbpb = kIntervalBasesPerBlock;
+  const double t1 = StageTimes::now();
+  colate_fs::Result res;
+  if (int rc = colate_fs::fill_view_device(v, A, (unsigned)seed, res)) return api_error(rc) == 0;
+  // the pairs' generators after their fills: one sweep through the seed's stream, in the order of the words taken
+  out.assign(pairs.size(), PairTables());
+  std::vector<size_t> order(mine.size());
+  for (size_t j = 0; j < order.size(); j++) order[j] = j;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return res.words[a] < res.words[b]; });
+  std::mt19937 g0((unsigned)seed);
+  BulkMt19937 bulk;
+  if (!bulk.load(g0)) return false;
+  unsigned long long at = 0;
+  int handed_back = 0;
+  for (size_t j : order) {
+    PairTables& pt = out[todo[j]];
+    bulk.skip(res.words[j] - at), at = res.words[j];
+    if (!bulk.store(pt.rng)) return false;
+    const double* const src = res.tables.data() + res.table_off[j];
+    pt.set_blocks(res.nb[j], A, [src, A](int b) { return src + (size_t)b * 4 * A; });
+    handed_back += res.handed_back[j];
+  }
+  std::cerr << in.S << " samples and " << in.M << " masks staged, " << mine.size() << " pairs walked and filled on the device ("
+            << handed_back << " handed back to the host)" << std::endl;
+  g_times.parse_mut = t1 - t0, g_times.table_fill = StageTimes::now() - t1;
+  if (g_times.on)
+    std::cerr << "Timing: samples fill: inputs " << t1 - t0 << " s, walks and fills " << g_times.table_fill << " s (device kernels "
+              << res.kernel_s << " s, " << res.chunks << " chunk(s)); " << in.row_off.back() << " rows, " << in.S << " index arrays and "
+              << in.M << " masks staged, " << 100 * *std::max_element(res.used.begin(), res.used.end()) << " uniforms uploaded" << std::endl;
+  return true;
+}
+
+}  // namespace colate_drv
 
 extern "C" {
 

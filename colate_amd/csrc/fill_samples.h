@@ -1,6 +1,6 @@
 // colate_amd/csrc/fill_samples.h -- the table fill of `Colate --mode mut` for every pair of a sample list, over per-sample walk
-// indices (internal to libcolate_amd.so): what the host twin (fill_samples.cpp), the device form (fill_samples_kernel.hip) and the
-// command line (mut_driver.cpp: --samples) share.
+// indices (internal to libcolate_amd.so): what the host side (fill_samples.cpp: the host twin, and fill_sample_pairs, which the
+// command line of --samples fills its pairs through) and the device form (fill_samples_kernel.hip) share.
 //
 // THE CONTRACT is coal.cpp:2221-2297 as Engine::use_snp and Engine::sample restate it (mut_pairs.cpp), with age = ref_age = 0
 // inside the fill (coal.cpp:2074-2075).  Per pair: the walk of interval_walk.h picks the used rows and their genome blocks; a
@@ -10,34 +10,20 @@
 //     then 100 draws, x = u * (end - begin) + begin by a separate multiply and add, clamped at 0, each adding w_ns to the
 //     not-shared table at bin(x) (nothing for a bin >= A);
 //   * else 100 accepted draws, each adding w_sh and w_ns at bin(x); a draw with x < 0 or bin(x) >= A is drawn again.
-// bin = age_bin_index(x, 10) (mut_feeder.h).  Tables per block in the order of Block::t: shared, not shared, shared row 0,
+// bin = age_bin_index(x, 10) (age_bins.hpp).  Tables per block in the order of Block::t: shared, not shared, shared row 0,
 // not-shared row 0, [A] each, every sum from 0.0 in the order of the draws, every addition rounded.
 // A used row that is never redrawn takes exactly 100 uniforms, so record number k of a pair reads the seed's stream at 100 k:
 // that is what the device form relies on, and a pair in which it does not hold is handed back to the twin.
 #pragma once
 #include <cstdint>
-#include <memory>
 #include <utility>
 #include <vector>
 
 #include "interval_walk.h"
 
 namespace colate_drv {
-// mut_pairs.cpp: what this fill takes from the engine of `--pairs` -- the located steps of the age bins with their guard bands
-// (FastBin), and the bulk generator's check against this machine's std::mt19937.
-class AgeBins {
- public:
-  explicit AgeBins(int A);
-  ~AgeBins();
-  bool ok() const;                 // the table passed its self-check
-  const double* guard_lo() const;  // [A + 2], as FastBin::guard_lo
-  const double* guard_hi() const;
- private:
-  struct Impl;
-  std::unique_ptr<Impl> impl_;
-};
-bool fill_bulk_stream_ok(unsigned seed);
-}  // namespace colate_drv
+class FastBin;  // age_bins.hpp
+}
 
 namespace colate_fs {
 
@@ -61,7 +47,7 @@ int check_fill(const colate_iw::View& v, int A);
 int size_result(const colate_iw::View& v, int A, const int* cnt, const int* last, std::vector<int>& blk0, Result& out);
 // The twin's fill of pair p (blk0: the pair's [C]): tables (zeroed here), words and near_band of `out` at p.  bands: the guard
 // bands near_band is measured against (null: only the redraw conditions count).
-void twin_pair(const colate_iw::View& v, int p, int A, unsigned seed, const int* blk0, const colate_drv::AgeBins* bands, Result& out);
+void twin_pair(const colate_iw::View& v, int p, int A, unsigned seed, const int* blk0, const colate_drv::FastBin* bands, Result& out);
 // runs of consecutive pairs whose records fit `budget_recs`; a larger pair goes alone
 std::vector<std::pair<int, int>> plan_chunks(int P, const long long* rec_off, long long budget_recs);
 

@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "age_bins.hpp"
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "em_job.hpp"
@@ -32,7 +33,7 @@
 #include "fill_samples.h"
 #include "interval_cells.h"
 #include "interval_groups.h"
-#include "mut_feeder.h"
+#include "uniform_stream.hpp"
 #include "walk_resident.hpp"
 
 using namespace colate;
@@ -110,34 +111,16 @@ namespace colate_fs {
 
 namespace {
 
-// generate_canonical<double, 53> on two outputs of mt19937 (libstdc++ bits/random.tcc), as mut_pairs.cpp forms it; checked against
-// the library on the first draws of the seed before it is trusted (upload_uniforms)
-inline double uniform_from_words(uint32_t r1, uint32_t r2) {
-  double ret = ((double)r1 + (double)r2 * 4294967296.0) * 0x1p-64;
-  if (ret >= 1.0) ret = std::nextafter(1.0, 0.0);
-  return ret;
-}
-
 // The seed's uniforms [0, n) into d_U through two page-locked buffers that take turns: the words of a buffer come from the bulk
 // generator, one after the other (0.6 ns a word); turning two words into a double costs more than that and has no order, so a
-// few threads share it; the copy out of one buffer runs while the other is filled.  *ok = false (nothing uploaded) where the
-// conversion does not reproduce the library's distribution on this machine.
-int upload_uniforms(unsigned seed, size_t n, double* d_U, DeviceBuffers& buf, hipStream_t stream, bool* ok) {
+// few threads share it; the copy out of one buffer runs while the other is filled.  (The caller has checked the generator and the
+// conversion against this machine's library: bulk_stream_ok.)
+int upload_uniforms(unsigned seed, size_t n, double* d_U, DeviceBuffers& buf, hipStream_t stream) {
   constexpr size_t kRing = 8u << 20;  // doubles per buffer (64 MB)
-  *ok = true;
   if (n == 0) return COLATE_OK;
   std::mt19937 g(seed);
   colate_drv::BulkMt19937 bulk;
   if (!bulk.load(g)) return fail(COLATE_EINVAL, "the generator's state could not be read");
-  {
-    std::mt19937 lib(seed);
-    std::uniform_real_distribution<double> d(0, 1);
-    colate_drv::BulkMt19937 probe = bulk;
-    uint32_t w[128];
-    probe.generate(w, 128);
-    for (int i = 0; i < 64; i++) *ok = *ok && d(lib) == uniform_from_words(w[2 * i], w[2 * i + 1]);
-    if (!*ok) return COLATE_OK;
-  }
   double* h[2] = {nullptr, nullptr};
   hipEvent_t ev[2];
   const size_t room = std::min(n, kRing);
@@ -160,7 +143,7 @@ int upload_uniforms(unsigned seed, size_t n, double* d_U, DeviceBuffers& buf, hi
     double* const dst = h[k];
     const uint32_t* const src = w.data();
     const auto convert = [dst, src](size_t i0, size_t i1) {
-      for (size_t i = i0; i < i1; i++) dst[i] = uniform_from_words(src[2 * i], src[2 * i + 1]);
+      for (size_t i = i0; i < i1; i++) dst[i] = colate_drv::canonical_from_words(src[2 * i], src[2 * i + 1]);
     };
     const size_t share = (m + threads - 1) / threads;
     std::vector<std::thread> helpers;
@@ -186,8 +169,8 @@ int fill_view_device(const View& v, int A, unsigned seed, Result& out) {
   ProfRange range("colate_fill_samples: H2D + walk count pass + uniform stream; per chunk walk write pass + F rows + jobs + age sampling + D2H");
   float T[kBins];
   if (int rc = colate_ic::build_thresholds(T)) return rc;
-  const colate_drv::AgeBins bands(A);
-  const bool device_ok = bands.ok() && colate_drv::fill_bulk_stream_ok(seed);
+  const colate_drv::FastBin bands(A, 10.0);
+  const bool device_ok = bands.ok() && colate_drv::bulk_stream_ok(seed);
   if (int rc = thread_workspace().reserve(256, 256)) return rc;  // (the workspace's stream: no second one)
   hipStream_t stream = thread_workspace().stream;
   KernelTimer timer(stream);
@@ -204,11 +187,10 @@ int fill_view_device(const View& v, int A, unsigned seed, Result& out) {
   const size_t PC = (size_t)P * C;
   if (int rc = size_result(v, A, res.cnt.data(), res.last.data(), blk0, out)) return rc;
   out.chunks = 0, out.kernel_s = 0.0;
-  const auto all_through_the_twin = [&] {  // no located steps, or a stream the bulk form does not reproduce on this machine
+  if (!device_ok) {  // no located steps, or a stream the bulk form does not reproduce on this machine: all through the twin
     for (int p = 0; p < P; p++) twin_pair(v, p, A, seed, blk0.data() + (size_t)p * C, nullptr, out), out.handed_back[(size_t)p] = 1;
     return COLATE_OK;
-  };
-  if (!device_ok) return all_through_the_twin();
+  }
   long long max_used = 0;
   for (int p = 0; p < P; p++) max_used = std::max(max_used, out.used[(size_t)p]), out.words[(size_t)p] = 2ull * kDraws * (unsigned long long)out.used[(size_t)p];
 
@@ -223,9 +205,7 @@ int fill_view_device(const View& v, int A, unsigned seed, Result& out) {
   HIP_TRY(h2d(stream, d_lo, bands.guard_lo(), sizeof(double) * ((size_t)A + 2)));
   HIP_TRY(h2d(stream, d_hi, bands.guard_hi(), sizeof(double) * ((size_t)A + 2)));
   HIP_TRY(h2d(stream, d_blk0, res.blk0.data(), sizeof(int) * PC));
-  bool stream_ok = true;
-  if (int rc = upload_uniforms(seed, n_uniforms, d_U, buf, stream, &stream_ok)) return rc;
-  if (!stream_ok) return all_through_the_twin();
+  if (int rc = upload_uniforms(seed, n_uniforms, d_U, buf, stream)) return rc;
 
   // ---- the chunks: runs of consecutive pairs within the record budget; scratch once, for the largest
   const long long budget = std::max<long long>(

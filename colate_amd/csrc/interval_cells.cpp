@@ -11,7 +11,7 @@
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "interval_cells.h"
-#include "mut_feeder.h"
+#include "age_bins.hpp"
 
 using colate::fail;
 

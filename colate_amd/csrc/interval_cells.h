@@ -4,7 +4,7 @@
 // between the mutation's lower and upper age.  The interval fit (colate_bootstrap_em_interval_batch) treats that uniform
 // distribution exactly, so here a used SNP is ONE observation of each kind and nothing is drawn:
 //   * its ages are snapped to the 185-point age grid: bb = bin(age_begin), be = bin(age_end), bin = age_bin_index(x, 10)
-//     (mut_feeder.h) on the float ages as the walk holds them; the cell (kind, bb, be), bb <= be, is the row
+//     (age_bins.hpp) on the float ages as the walk holds them; the cell (kind, bb, be), bb <= be, is the row
 //     [age_bin[bb], age_bin[be]] of that kind; be >= 185 drops the SNP (counted);
 //   * bin() is a step function of a float: T[n], n = 1 .. 185, is the smallest float whose age_bin_index is >= n (located
 //     once on the host by bisection over float bit patterns on the library expression itself, checked at both neighbours),

@@ -37,20 +37,30 @@ constexpr int kWaves = kTile / 64;
 
 COLATE_IC_HD inline int block_of_pos(int pos, int nbpb) { return pos > 0 ? (pos - 1) / nbpb : 0; }
 
-// a used row as one interval-dated observation (use_snp: the float product, the conversion and the double division are
-// three separate roundings; -ffp-contract=off on the host and on the device)
-COLATE_IC_HD inline colate_ic::IntervalRec make_rec(const Row& m, const Idx& t, const Idx& r) {
-  const int tgt_DAF = t.DAF, tgt_AAF = t.AAF, DAF_ref = r.DAF, N_ref = (int)r.DAF + (int)r.AAF;
+// What both records of a used row start from (use_snp): the target genotype rounded to a haploid call in single precision, and
+// its two float products with the reference's derived count.
+struct GenotypeProducts {
+  float p_sh, p_ns;  // (derived, ancestral) of the target times DAF_ref
+};
+COLATE_IC_HD inline GenotypeProducts genotype_products(const Idx& t, const Idx& r) {
+  const int tgt_DAF = t.DAF, tgt_AAF = t.AAF, DAF_ref = r.DAF;
   const int N_target = tgt_DAF + tgt_AAF;
-  double age_begin = m.age_begin;
-  if (age_begin < 0.0) age_begin = 0.0;
   float f_DAF_target = (float)tgt_DAF, f_AAF_target = (float)tgt_AAF;
   f_DAF_target = (float)((double)f_DAF_target / (N_target / 2.0));
   f_AAF_target = (float)((double)f_AAF_target / (N_target / 2.0));
   f_DAF_target = roundf(f_DAF_target);
   f_AAF_target = roundf(f_AAF_target);
-  const float p_sh = f_DAF_target * (float)DAF_ref, p_ns = f_AAF_target * (float)DAF_ref;
-  return colate_ic::IntervalRec{(float)age_begin, m.age_end, (double)p_sh / (double)N_ref, (double)p_ns / (double)N_ref};
+  return GenotypeProducts{f_DAF_target * (float)DAF_ref, f_AAF_target * (float)DAF_ref};
+}
+
+// a used row as one interval-dated observation (use_snp: the float product, the conversion and the double division are
+// three separate roundings; -ffp-contract=off on the host and on the device)
+COLATE_IC_HD inline colate_ic::IntervalRec make_rec(const Row& m, const Idx& t, const Idx& r) {
+  const int N_ref = (int)r.DAF + (int)r.AAF;
+  double age_begin = m.age_begin;
+  if (age_begin < 0.0) age_begin = 0.0;
+  const GenotypeProducts g = genotype_products(t, r);
+  return colate_ic::IntervalRec{(float)age_begin, m.age_end, (double)g.p_sh / (double)N_ref, (double)g.p_ns / (double)N_ref};
 }
 
 // The same used row as `--mode mut` samples it (Engine::use_snp, the table branch; coal.cpp:2221-2297 with age = ref_age = 0):
@@ -62,20 +72,14 @@ struct FillSide {
 };
 static_assert(sizeof(FillSide) == 16, "FillSide");
 COLATE_IC_HD inline colate_drv::FillRec make_fill_rec(const Row& m, const Idx& t, const Idx& r, FillSide& side) {
-  const int tgt_DAF = t.DAF, tgt_AAF = t.AAF, DAF_ref = r.DAF, N_ref = (int)r.DAF + (int)r.AAF;
-  const int N_target = tgt_DAF + tgt_AAF;
+  const int N_ref = (int)r.DAF + (int)r.AAF;
   double age_begin = m.age_begin;
   if (age_begin < 0.0) age_begin = 0.0;
-  float f_DAF_target = (float)tgt_DAF, f_AAF_target = (float)tgt_AAF;
-  f_DAF_target = (float)((double)f_DAF_target / (N_target / 2.0));
-  f_AAF_target = (float)((double)f_AAF_target / (N_target / 2.0));
-  f_DAF_target = roundf(f_DAF_target);
-  f_AAF_target = roundf(f_AAF_target);
-  const float p_sh = f_DAF_target * (float)DAF_ref, p_ns = f_AAF_target * (float)DAF_ref;
-  side.e_sh = (double)p_sh / (double)N_ref, side.e_ns = (double)p_ns / (double)N_ref;
+  const GenotypeProducts g = genotype_products(t, r);
+  side.e_sh = (double)g.p_sh / (double)N_ref, side.e_ns = (double)g.p_ns / (double)N_ref;
   const double hundredth = (double)N_ref * 100.0;
-  const double w_sh = age_begin <= 0.0 ? 0.0 : (double)p_sh / hundredth;
-  return colate_drv::FillRec{(float)age_begin, m.age_end, w_sh, (double)p_ns / hundredth};
+  const double w_sh = age_begin <= 0.0 ? 0.0 : (double)g.p_sh / hundredth;
+  return colate_drv::FillRec{(float)age_begin, m.age_end, w_sh, (double)g.p_ns / hundredth};
 }
 
 // The inputs as both stages read them: chromosome c's rows are rows[c][0 .. row_off[c + 1] - row_off[c]); sample s's index

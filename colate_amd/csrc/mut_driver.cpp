@@ -7,7 +7,7 @@
 // around the GPU EM (colate_em_batch), for one pair (run_mut), for a `--pairs` list
 // (run_mut_pairs; the tables of both come from the engine of mut_pairs.cpp) and for the
 // pairs of a `--samples` list (run_mut_samples; the tables come from the walk and fill on
-// the device, fill_samples.h).  The two lists share run_pair_list, everything behind the fill.
+// the device, fill_samples.cpp).  The two lists share run_pair_list, everything behind the fill.
 //
 // Everything here runs once per invocation on the host; the per-replicate EM,
 // which is where the reference spends its time, is the HIP kernel.
@@ -40,10 +40,9 @@
 #include <thread>
 #include <vector>
 
+#include "age_bins.hpp"
 #include "colate_amd.h"
 #include "colate_internal.h"
-#include "fill_samples.h"
-#include "interval_walk.h"
 #include "mut_feeder.h"
 #include "mut_interval.h"
 
@@ -613,13 +612,13 @@ std::vector<std::string> mask_files(const Options& opt, const std::vector<std::s
 }
 
 // ------------------------------------------------------------------ what the single-pair and the --pairs drivers share
-namespace {
-
-// a failed C-ABI call: "Error: <the library's message> (<rc>)"; returns the exit code
+// (mut_feeder.h)
 int api_error(int rc) {
   std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
   return 1;
 }
+
+namespace {
 
 // The settings every pair of a run shares: --years_per_gen, the age grid of the A bins, then (read_replicates) the seed of
 // the run's generator and the number of bootstrap replicates B.  Two steps: the single-pair driver prints its sample age
@@ -1281,9 +1280,8 @@ int run_pair_list(const Options& opt, const std::vector<PairSpec>& pairs, const 
 }
 
 // `Colate --mode mut --samples LIST`: every (target line, reference line) of the list, each pair's files byte for byte what
-// `--pairs` writes for the expanded list.  Where there is a device and every sample has a walk index, no pair is walked on the
-// host: N index arrays and the rows go to the device once, and colate_fill_samples' device form walks, forms the records and
-// fills the tables there (fill_samples.h).  Otherwise one line on stderr says why, and the expanded list goes through fill_pairs.
+// `--pairs` writes for the expanded list.  The tables come from fill_sample_pairs (fill_samples.cpp): walked and filled on the
+// device where there is one, else through fill_pairs.
 int run_mut_samples(const Options& opt) {
   for (const char* o : {"pairs", "target_tmp", "reference_tmp", "target_mask", "reference_mask", "target_age", "reference_age", "ranks"})
     if (opt.has(o)) {
@@ -1314,62 +1312,9 @@ int run_mut_samples(const Options& opt) {
     std::cerr << "Error: " << opt.get("samples") << ": no pair of a target and a reference on different lines." << std::endl;
     return 1;
   }
-  const auto fill = [&](const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& tabs) -> bool {
-    const auto through_engine = [&](const char* why) {
-      std::cerr << "pairs walked and filled through the engine of --pairs (" << why << ")" << std::endl;
-      return fill_pairs(opt, chr_names, mut_files, pairs, todo, seed, A, tabs);
-    };
-    for (const char* name : {"COLATE_DEVICE_FILL", "COLATE_DEVICE_FILL_WALK"})
-      if (const char* e = std::getenv(name))
-        if (std::atoi(e) == 0) return through_engine((std::string(name) + "=0").c_str());
-    if (colate_device_count() < 1) return through_engine("no device");
-    if (opt.has("device"))
-      if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc) == 0;
-    const double t0 = StageTimes::now();
-    std::vector<PairSpec> mine;
-    for (size_t p : todo) mine.push_back(pairs[p]);
-    WalkInputs in;
-    if (!load_walk_inputs(chr_names, mut_files, mine, in)) return false;
-    if (!in.indexed) return through_engine("a sample has no walk index");
-    colate_iw::View v;
-    v.C = (int)chr_names.size(), v.row_off = in.row_off.data(), v.rows = in.row_ptrs.data(), v.S = in.S, v.idx = in.idx_ptrs.data(), v.M = in.M;
-    v.masks = in.mask_ptrs.data(), v.P = (int)mine.size(), v.pairs = in.pairs.data(), v.nbpb = kIntervalBasesPerBlock;
-    const double t1 = StageTimes::now();
-    colate_fs::Result res;
-    if (int rc = colate_fs::fill_view_device(v, A, (unsigned)seed, res)) return api_error(rc) == 0;
-    // the pairs' generators after their fills: one sweep through the seed's stream, in the order of the words taken
-    tabs.assign(pairs.size(), PairTables());
-    std::vector<size_t> order(mine.size());
-    for (size_t j = 0; j < order.size(); j++) order[j] = j;
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return res.words[a] < res.words[b]; });
-    std::mt19937 g0((unsigned)seed);
-    BulkMt19937 bulk;
-    if (!bulk.load(g0)) return false;
-    unsigned long long at = 0;
-    int handed_back = 0;
-    for (size_t j : order) {
-      PairTables& pt = tabs[todo[j]];
-      bulk.skip(res.words[j] - at), at = res.words[j];
-      if (!bulk.store(pt.rng)) return false;
-      pt.nb = res.nb[j];
-      std::vector<double>* const tab[4] = {&pt.sh, &pt.ns, &pt.she, &pt.nse};  // (the order of Block::t)
-      const double* src = res.tables.data() + res.table_off[j];
-      for (int k = 0; k < 4; k++) {
-        tab[k]->resize((size_t)pt.nb * A);
-        for (int b = 0; b < pt.nb; b++) std::copy_n(src + ((size_t)b * 4 + k) * A, A, tab[k]->begin() + (size_t)b * A);
-      }
-      handed_back += res.handed_back[j];
-    }
-    std::cerr << in.S << " samples and " << in.M << " masks staged, " << mine.size() << " pairs walked and filled on the device ("
-              << handed_back << " handed back to the host)" << std::endl;
-    g_times.parse_mut = t1 - t0, g_times.table_fill = StageTimes::now() - t1;
-    if (g_times.on)
-      std::cerr << "Timing: samples fill: inputs " << t1 - t0 << " s, walks and fills " << g_times.table_fill << " s (device kernels "
-                << res.kernel_s << " s, " << res.chunks << " chunk(s)); " << in.row_off.back() << " rows, " << in.S << " index arrays and "
-                << in.M << " masks staged, " << 100 * *std::max_element(res.used.begin(), res.used.end()) << " uniforms uploaded" << std::endl;
-    return true;
-  };
-  return run_pair_list(opt, pairs, fill);
+  return run_pair_list(opt, pairs, [&](const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& tabs) {
+    return fill_sample_pairs(opt, chr_names, mut_files, pairs, todo, seed, A, tabs);
+  });
 }
 
 void write_counts_file(const std::string& path, int B, int A, const std::vector<double>& grid,

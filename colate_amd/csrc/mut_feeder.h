@@ -1,11 +1,13 @@
-// colate_amd/csrc/mut_feeder.h -- what the two host-side translation units of the `Colate --mode mut` driver share:
-// mut_driver.cpp (command line, readers, the sequential feeder of include/coal/coal.cpp:2071-2321, the single-pair and the
-// --pairs drivers around mut(), --ranks launcher) and mut_pairs.cpp (the table-fill engine of the batched front end, SURVEY.md
-// section 8 f2 / BASELINE configs[4], which fills every table of a `--pairs` run and of a single pair, and hands a pair it cannot
-// fill exactly to the sequential feeder).
+// colate_amd/csrc/mut_feeder.h -- what the host-side translation units of the `Colate --mode mut` driver share: mut_driver.cpp
+// (command line, readers, the sequential feeder of include/coal/coal.cpp:2071-2321, the single-pair, --pairs and --samples
+// drivers around mut(), --ranks launcher), mut_pairs.cpp (the table-fill engine of the batched front end, SURVEY.md section 8
+// f2 / BASELINE configs[4], which fills every table of a `--pairs` run and of a single pair, and hands a pair it cannot fill
+// exactly to the sequential feeder) and fill_samples.cpp (the fill of a `--samples` run on the device, which falls back to that
+// engine).  The age bins and the uniform stream of the fills are in age_bins.hpp and uniform_stream.hpp.
 #pragma once
 #include <zlib.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -94,84 +96,16 @@ struct PairTables {  // flat [nb][A] tables of one pair, as the bootstrap takes 
   int nb = 0;
   std::vector<double> sh, ns, she, nse;
   std::mt19937 rng;  // the run's generator after the table fill
-};
-
-inline int age_bin_index(double x, double C) {  // coal.cpp:2265, 2284
-  const double v = std::round(std::log(10 * x) * C);
-  if (!(v > -2e9)) return 0;  // log(0) = -inf: the reference's (int) cast yields INT_MIN -> max(0, .) = 0
-  return std::max(0, (int)v + 1);
-}
-
-// std::mt19937's recurrence with the state regenerated 624 words at a time in loops the compiler vectorises (the library's
-// operator() does the same work word by word: 7.5 ns per word on the build container, against ~2 here).  Same sequence by
-// construction; bulk_stream_ok (mut_pairs.cpp) checks it against the library's generator before it is trusted.  State goes in and out of a
-// std::mt19937 through its textual form (the 624 words and the position, [rand.eng.mers]).
-class BulkMt19937 {
- public:
-  bool load(const std::mt19937& g) {
-    std::ostringstream os;
-    os << g;
-    std::istringstream is(os.str());
-    for (int i = 0; i < 624; i++)
-      if (!(is >> x_[i])) return false;
-    if (!(is >> p_) || p_ > 624) return false;
-    return true;
-  }
-  bool store(std::mt19937& g) const {
-    std::ostringstream os;
-    for (int i = 0; i < 624; i++) os << x_[i] << ' ';
-    os << p_;
-    std::istringstream is(os.str());
-    return static_cast<bool>(is >> g);
-  }
-  // the next n 32-bit outputs
-  void generate(uint32_t* out, size_t n) {
-    while (n) {
-      if (p_ >= 624) twist();
-      const size_t k = std::min(n, (size_t)(624 - p_));
-      const uint32_t* x = x_ + p_;
-      for (size_t i = 0; i < k; i++) {  // tempering
-        uint32_t y = x[i];
-        y ^= y >> 11;
-        y ^= (y << 7) & 0x9d2c5680u;
-        y ^= (y << 15) & 0xefc60000u;
-        y ^= y >> 18;
-        out[i] = y;
-      }
-      out += k, n -= k, p_ += (uint32_t)k;
+  // the four tables from `blocks` blocks of [4][A] in the order of the fill (sh | ns | she | nse); block(j): block j's
+  template <class BlockAt>
+  void set_blocks(int blocks, int A, BlockAt block) {
+    nb = blocks;
+    std::vector<double>* const tab[4] = {&sh, &ns, &she, &nse};
+    for (int k = 0; k < 4; k++) {
+      tab[k]->resize((size_t)nb * A);
+      for (int j = 0; j < nb; j++) std::copy_n(block(j) + (size_t)k * A, A, tab[k]->begin() + (size_t)j * A);
     }
   }
-  // the same position as discard(n), without forming the outputs on the way (tempering is no part of the state)
-  void skip(unsigned long long n) {
-    while (n) {
-      if (p_ >= 624) twist();
-      const unsigned long long k = std::min<unsigned long long>(n, 624 - p_);
-      p_ += (uint32_t)k, n -= k;
-    }
-  }
-  void discard(unsigned long long n) {
-    uint32_t tmp[624];
-    while (n) {
-      const size_t k = (size_t)std::min<unsigned long long>(n, 624);
-      generate(tmp, k);
-      n -= k;
-    }
-  }
-
- private:
-  static uint32_t mix(uint32_t a, uint32_t b) {
-    const uint32_t y = (a & 0x80000000u) | (b & 0x7fffffffu);
-    return (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-  }
-  void twist() {
-    for (int i = 0; i < 227; i++) x_[i] = x_[i + 397] ^ mix(x_[i], x_[i + 1]);          // (old words only)
-    for (int i = 227; i < 454; i++) x_[i] = x_[i - 227] ^ mix(x_[i], x_[i + 1]);        // (new words of the first loop)
-    for (int i = 454; i < 623; i++) x_[i] = x_[i - 227] ^ mix(x_[i], x_[i + 1]);        // (new words of the second)
-    x_[623] = x_[396] ^ mix(x_[623], x_[0]);
-    p_ = 0;
-  }
-  uint32_t x_[624];
-  uint32_t p_ = 624;
 };
 
 // `--ranks N`: this process is rank `rank` of `nranks` (run_ranked forks them); the 128-byte RCCL id travels from
@@ -220,7 +154,14 @@ int run_condcoal(const Options& opt);  // "CPU Time spent: ...; Max Memory usage
 // error message.
 bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
                 const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& out);
-
+// fill_samples.cpp: the same for the pairs of a `--samples` list.  Where there is a device and every sample has a walk index,
+// no pair is walked on the host: the index arrays and the rows go to the device once, and colate_fill_samples' device form
+// walks, forms the records and fills the tables there (fill_samples.h).  Otherwise one line on stderr says why, and the pairs
+// go through fill_pairs.
+bool fill_sample_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                       const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& out);
+// mut_driver.cpp: a failed C-ABI call: "Error: <the library's message> (<rc>)"; returns the exit code
+int api_error(int rc);
 
 // mut_pairs.cpp: the engine's walk for `--mode mut_interval`.  The SNPs the pair uses -- use filter, block advance, masks and
 // the float rounding of the target genotype are those of fill_pairs, coal.cpp:2148-2244 -- as interval-dated observations

@@ -133,11 +133,6 @@ bool read_interval_rows(const std::string& path, double epoch0, IntervalRows& ou
   return true;
 }
 
-static int api_error(int rc) {
-  std::cerr << "Error: " << colate_last_error() << " (" << rc << ")" << std::endl;
-  return 1;
-}
-
 // The used SNPs of --mut / --target_tmp / --reference_tmp as rows and per-block tables (interval_cells.h): the engine's walk
 // (mut_pairs.cpp) gives the records, colate_interval_cells -- or its host twin after a line on stderr -- the cells.
 static bool rows_from_mut(const Options& opt, bool on_host, const std::string& host_why, IntervalRows& out) {

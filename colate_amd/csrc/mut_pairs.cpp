@@ -45,12 +45,13 @@
 #include <set>
 #include <thread>
 
+#include "age_bins.hpp"
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "fill_device.h"
-#include "fill_samples.h"
 #include "interval_cells.h"
 #include "mut_feeder.h"
+#include "uniform_stream.hpp"
 
 namespace colate_drv {
 namespace {
@@ -475,28 +476,8 @@ void build_walk_index(TmpFile& f, const WalkRows& w) {
 }
 
 // ------------------------------------------------------------------ the uniform stream of the seed, generated once
-// std::uniform_real_distribution<double>(0, 1) on std::mt19937 = generate_canonical<double, 53>: two 32-bit draws per value
-// (libstdc++ bits/random.tcc).  One producer thread fills a ring of chunks; readers address the stream by offset.
-inline double canonical_from_words(uint32_t r1, uint32_t r2) {
-  double ret = ((double)r1 + (double)r2 * 4294967296.0) * 0x1p-64;
-  if (ret >= 1.0) ret = std::nextafter(1.0, 0.0);
-  return ret;
-}
-
-// does the bulk generator reproduce this machine's library on this seed?  (the sequence is part of the result)
-bool bulk_stream_ok(unsigned seed) {
-  std::mt19937 lib(seed);
-  BulkMt19937 b;
-  if (!b.load(lib)) return false;
-  std::uniform_real_distribution<double> d(0, 1);
-  uint32_t w[2 * 1300];
-  b.generate(w, 2 * 1300);  // (across two regenerations of the state)
-  for (int i = 0; i < 1300; i++)
-    if (d(lib) != canonical_from_words(w[2 * i], w[2 * i + 1])) return false;
-  std::mt19937 back;
-  return b.store(back) && back == lib;
-}
-
+// (uniform_stream.hpp: the generator and the conversion.)  One producer thread fills a ring of chunks; readers address the
+// stream by offset.
 class SharedUniforms {
  public:
   static constexpr uint64_t kChunk = 1u << 18;  // doubles per chunk (2 MB)
@@ -647,95 +628,6 @@ class SharedUniforms {
   std::thread converter_;
   std::atomic<double> waited_{0.0};
   std::atomic<double> gen_s_{0.0}, conv_s_{0.0};  // (written by the producer / the converter only)
-};
-
-// ------------------------------------------------------------------ the age bin of a sampled age, without the logarithm
-// bin(x) = max(0, (int)round(log(10 x) * C) + 1) (coal.cpp:2265, 2284) is a step function of x with one step per age bin.
-// The steps are located once by bisection over the doubles ON THE LIBRARY EXPRESSION ITSELF (age_bin_index); a sample is
-// then classified by a table on its leading bits and one or two comparisons.  The library expression may disagree with the
-// exact mathematical step by the last bits of log(): any x within 64 ulps of a located step goes through the library
-// expression instead (log's error, under one ulp of a value below 24, moves the step by fewer than 16 ulps of x), so the
-// result equals age_bin_index(x) for every x, by construction and by the self-check in the constructor.
-class FastBin {
- public:
-  FastBin(int A, double C) : A_(A), C_(C), thr_(A + 2), lo_(A + 2), hi_(A + 2) {
-    const double inf = std::numeric_limits<double>::infinity();
-    thr_[0] = lo_[0] = hi_[0] = -inf;
-    thr_[A + 1] = lo_[A + 1] = hi_[A + 1] = inf;
-    for (int k = 1; k <= A; k++) {
-      uint64_t a = bits(1e-300), b = bits(1e300);  // f(a) < k <= f(b)
-      while (b - a > 1) {
-        const uint64_t mid = a + (b - a) / 2;
-        if (f(from_bits(mid)) >= k) b = mid; else a = mid;
-      }
-      thr_[k] = from_bits(b);
-      lo_[k] = from_bits(b - 64);
-      hi_[k] = from_bits(b + 64);
-    }
-    base_ = bits(thr_[1]) >> kShift;
-    const uint64_t top = bits(thr_[A]) >> kShift;
-    cell_.resize(top - base_ + 2);
-    for (size_t c = 0; c < cell_.size(); c++) {
-      const double edge = std::max(from_bits((base_ + c) << kShift), thr_[1]);
-      cell_[c] = (uint16_t)std::min(f(edge), A);
-    }
-    // self-check on the steps, their neighbourhoods and random samples; a failure switches the table off
-    ok_ = true;
-    std::mt19937_64 g(99);
-    for (int k = 1; k <= A && ok_; k++)
-      for (int d = -200; d <= 200 && ok_; d++) ok_ = agrees(from_bits(bits(thr_[k]) + d));
-    for (int i = 0; i < 200000 && ok_; i++)
-      ok_ = agrees(std::exp(std::uniform_real_distribution<double>(std::log(0.01), std::log(2e7))(g)));
-    ok_ = ok_ && agrees(0.0) && agrees(1e-310) && agrees(0.05) && agrees(1e9);
-  }
-  bool ok() const { return ok_; }
-  int bins() const { return A_; }
-  // lower / upper edge of the guard band around step k (k = 1 .. A; [0] = -inf, [A + 1] = +inf): bin(x) = #{k : hi(k) <= x} for
-  // every x outside all bands
-  const double* guard_lo() const { return lo_.data(); }
-  const double* guard_hi() const { return hi_.data(); }
-  // age_bin_index(x, C), with every value >= A returned as A
-  int operator()(double x) const {
-    if (!ok_) return std::min(f(x), A_);
-    if (x < lo_[1]) return 0;
-    if (x >= hi_[A_]) return A_;
-    if (x < hi_[1]) return x < thr_[1] ? std::min(f(x), A_) : slow_or(x, 1);
-    const size_t c = (size_t)((bits(x) >> kShift) - base_);
-    const int k = cell_[c];
-    if (x < hi_[k]) return std::min(f(x), A_);
-    if (x < lo_[k + 1]) return k;
-    if (x >= hi_[k + 1]) return std::min(k + 1, A_);
-    return std::min(f(x), A_);
-  }
-
- private:
-  static constexpr int kShift = 46;  // 11 exponent bits + 6 leading mantissa bits: a cell spans a factor <= 1 + 1/64, a bin e^0.1
-  static uint64_t bits(double x) {
-    uint64_t u;
-    std::memcpy(&u, &x, 8);
-    return u;
-  }
-  static double from_bits(uint64_t u) {
-    double x;
-    std::memcpy(&x, &u, 8);
-    return x;
-  }
-  int f(double x) const { return age_bin_index(x, C_); }
-  int slow_or(double x, int k) const { return x >= hi_[k] ? k : std::min(f(x), A_); }
-  bool agrees(double x) const {
-    FastBin* self = const_cast<FastBin*>(this);
-    const bool keep = self->ok_;
-    self->ok_ = true;
-    const int fast = (*this)(x);
-    self->ok_ = keep;
-    return fast == std::min(f(x), A_);
-  }
-  int A_;
-  double C_;
-  std::vector<double> thr_, lo_, hi_;
-  std::vector<uint16_t> cell_;
-  uint64_t base_ = 0;
-  bool ok_ = false;
 };
 
 // ------------------------------------------------------------------ the 100 sampled ages of one SNP, eight (four) at a time
@@ -890,7 +782,7 @@ class DeviceSampler {
       return;
     }
     colate::mark_device_touched();  // (the HIP runtime comes up here: no --ranks fork from this process afterwards)
-    if (!DeviceFill::available()) {
+    if (!fill_device_available()) {
       note_ = "no HIP device";
       return;
     }
@@ -921,8 +813,8 @@ class DeviceSampler {
     const double t0 = now_s();
     A_ = A, W_ = W;
     const uint64_t max_uniforms = (n_kept * 100 / SharedUniforms::kChunk + W + 3) * SharedUniforms::kChunk;
-    dev_.reset(DeviceFill::create(device_, A, fastbin_.guard_lo(), fastbin_.guard_hi(), npairs * kMaxBlocks,
-                                  std::min<uint64_t>(batch_, std::max<uint64_t>(1024, n_kept * npairs)), note_));
+    dev_ = make_device_fill(device_, A, fastbin_.guard_lo(), fastbin_.guard_hi(), npairs * kMaxBlocks,
+                            std::min<uint64_t>(batch_, std::max<uint64_t>(1024, n_kept * npairs)), note_);
     if (!dev_ || !dev_->alloc_uniforms(max_uniforms)) {
       std::cerr << "Note: age sampling on the GPU could not be set up (" << (dev_ ? dev_->error() : note_) << "); sampling on the host." << std::endl;
       if (dev_) note_ = dev_->error();
@@ -1493,28 +1385,12 @@ Fills open_pairs(const Inputs& in, const std::vector<PairSpec>& pairs, const std
 // the pair's tables as the drivers take them (false: the pair has to be filled again, sequentially)
 bool collect(const PairFill& pf, int A, PairTables& pt) {
   if (pf.redo.load()) return false;
-  pt.nb = pf.num_blocks;
-  std::vector<double>* const tab[4] = {&pt.sh, &pt.ns, &pt.she, &pt.nse};  // (the order of Block::t)
-  for (int k = 0; k < 4; k++) {
-    tab[k]->resize((size_t)pt.nb * A);
-    for (int j = 0; j < pt.nb; j++) std::copy_n(pf.blocks[(size_t)j]->t.data() + k * A, A, tab[k]->begin() + (size_t)j * A);
-  }
+  pt.set_blocks(pf.num_blocks, A, [&pf](int j) { return pf.blocks[(size_t)j]->t.data(); });
   pt.rng = pf.rng_end;
   return true;
 }
 
 }  // namespace
-
-// (fill_samples.h)
-struct AgeBins::Impl {
-  FastBin fb;
-};
-AgeBins::AgeBins(int A) : impl_(new Impl{FastBin(A, 10.0)}) {}
-AgeBins::~AgeBins() = default;
-bool AgeBins::ok() const { return impl_->fb.ok(); }
-const double* AgeBins::guard_lo() const { return impl_->fb.guard_lo(); }
-const double* AgeBins::guard_hi() const { return impl_->fb.guard_hi(); }
-bool fill_bulk_stream_ok(unsigned seed) { return bulk_stream_ok(seed); }
 
 // (mut_feeder.h)
 bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,

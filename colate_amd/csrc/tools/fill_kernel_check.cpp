@@ -68,7 +68,7 @@ int main(int argc, char** argv) {
   // (declared before the DeviceFill: its destructor unregisters the page-locked upload sources, which must still be there)
   std::vector<std::unique_ptr<std::vector<double>>> sources;
   std::string why;
-  std::unique_ptr<DeviceFill> dev(DeviceFill::create(0, A, lo.data(), hi.data(), max_tables, batch_recs, why));
+  const std::unique_ptr<DeviceFill> dev = colate_drv::make_device_fill(0, A, lo.data(), hi.data(), max_tables, batch_recs, why);
   if (!dev) return api_error("create", why);
   if (!dev->alloc_staging()) return api_error("alloc_staging", dev->error());
   if (!dev->alloc_uniforms(max_uniforms)) return api_error("alloc_uniforms", dev->error());

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "colate_amd.h"
-#include "mut_feeder.h"
+#include "age_bins.hpp"
 
 static int bin_libm(float x) { return colate_drv::age_bin_index((double)x, 10.0); }
 static int bin_table(const float* T, float x) {

@@ -107,20 +107,11 @@ int fill_view_device(const colate_iw::View&, int, unsigned, Result&) { return no
 // the age sampling on the device (fill_device.h): there is none in this build, the host code samples
 #include "fill_device.h"
 namespace colate_drv {
-DeviceFill* DeviceFill::create(int, int, const double*, const double*, size_t, size_t, std::string& why) {
+bool fill_device_available() { return false; }
+std::unique_ptr<DeviceFill> make_device_fill(int, int, const double*, const double*, size_t, size_t, std::string& why) {
   why = "built without a device";
   return nullptr;
 }
-bool DeviceFill::available() { return false; }
-DeviceFill::~DeviceFill() {}
-bool DeviceFill::alloc_staging() { return false; }
-bool DeviceFill::alloc_uniforms(uint64_t) { return false; }
-void DeviceFill::pin(void*, size_t) {}
-bool DeviceFill::upload_uniforms(uint64_t, const double*, size_t) { return false; }
-bool DeviceFill::sync_uploads() { return false; }
-bool DeviceFill::submit(const std::vector<FillJob>&, size_t) { return false; }
-bool DeviceFill::finish(std::vector<double>&, std::vector<int>&) { return false; }
-bool DeviceFill::fail(const char*, int) { return false; }
 }  // namespace colate_drv
 
 // the CondCoalRates walks on the device (condcoal.h): none in this build, the host twin walks

@@ -19,7 +19,7 @@ CELLS = BINS * (BINS + 1) // 2
 
 
 def bin_restated(x):
-    """age_bin_index(x, 10) of csrc/mut_feeder.h (coal.cpp:2265) for a float32 widened to double: max(0, (int)round(log(10 x) * 10)
+    """age_bin_index(x, 10) of csrc/age_bins.hpp (coal.cpp:2265) for a float32 widened to double: max(0, (int)round(log(10 x) * 10)
     + 1), round = half away from zero, log(0) -> bin 0"""
     x = float(x)
     if x <= 0.0:

@@ -1,6 +1,6 @@
 """The age-sampling kernel of the table fill (colate_amd/csrc/fill_kernel.hip, fill_device.h) against a float64 reference written
 here, kernel by kernel rather than through the CLI: colate_amd/bin/fill_kernel_check links the product's fill_kernel.o and drives
-DeviceFill (create, alloc_staging, alloc_uniforms, upload_uniforms, sync_uploads, submit, finish) over a scripted case.
+DeviceFill (make_device_fill, alloc_staging, alloc_uniforms, upload_uniforms, sync_uploads, submit, finish) over a scripted case.
 
 The contract (fill_device.h, mut_pairs.cpp Engine::sample): for each used SNP, 100 ages x = u * span + begin (a multiply and an add,
 each rounded), bin(x) = max(0, round_half_away(log(10 x) * 10) + 1) (coal.cpp:2265, 2284); the SNP's weight is added to the bin once
@@ -40,7 +40,7 @@ def _round_half_away(v):
 
 
 def age_bin(x):
-    """The library expression (mut_feeder.h age_bin_index, C = 10), with the scalar libm logarithm."""
+    """The library expression (age_bins.hpp age_bin_index, C = 10), with the scalar libm logarithm."""
     if not x > 0.0:
         return 0  # log(0) = -inf (and log(x < 0) = nan): the reference's cast ends at max(0, .) = 0
     return max(0, _round_half_away(math.log(10 * x) * 10.0) + 1)
