@@ -616,6 +616,42 @@ def fill_samples(row_off, rows, idx, masks, pairs, num_bases_per_block, seed, A=
                 near_band=None if device else near)
 
 
+def compare_samples(row_off, rows, idx, pairs, first_pos, last_pos, window, device=True, cap=None):
+    """colate_compare_samples[_host]: the windowed pair mismatch of `--mode compare_tmp` for every pair of `pairs` over
+    per-sample walk indices.  row_off, rows, idx, pairs: the inputs of interval_walk (no masks: a pair's mask ids are -1), every
+    row a searched row; first_pos / last_pos [C]: the positions of each chromosome's first and last raw rows; window: the window
+    in bases (the command line: 10 000 000).  Returns (win_off [C + 1], mismatch [P][win_off[C]], snps [P][win_off[C]]).  cap:
+    the room given per output (default: what the call needs).  device=False: the host twin, the same ints."""
+    args, keep = _walk_inputs(row_off, rows, idx, None, pairs)
+    C, P = keep[0].size - 1, keep[4].size
+    first_pos = np.ascontiguousarray(first_pos, dtype=np.int32).ravel()
+    last_pos = np.ascontiguousarray(last_pos, dtype=np.int32).ravel()
+    if first_pos.size != C or last_pos.size != C:
+        raise ValueError("first_pos and last_pos hold one position per chromosome")
+    window = int(window)
+    if cap is None:  # (the library checks everything again and names what is wrong)
+        f, l = first_pos.astype(np.int64), last_pos.astype(np.int64)
+        cap = P * int((np.where(l > f, (l - f - 1) // max(window, 1), 0) + 1).sum())
+    cap = int(cap)
+    win_off = np.zeros(C + 1, dtype=np.int64)
+    mismatch, snps = np.zeros(max(cap, 0), dtype=np.int32), np.zeros(max(cap, 0), dtype=np.int32)
+    fn = lib.colate_compare_samples if device else lib.colate_compare_samples_host
+    check(fn(args[0], args[1], args[2], args[3], args[4], args[7], args[8], _p(first_pos), _p(last_pos), window, cap, _p(win_off),
+             _p(mismatch), _p(snps)))
+    n = int(win_off[-1])
+    return win_off, mismatch[:P * n].reshape(P, n).copy(), snps[:P * n].reshape(P, n).copy()
+
+
+def compare_samples_chunks():
+    """Chunks of pairs in this thread's last compare_samples(device=True) (diagnostic)."""
+    return lib.colate_compare_samples_chunks()
+
+
+def compare_samples_kernel_seconds():
+    """Seconds the kernels of this thread's last compare_samples(device=True) took on the device."""
+    return lib.colate_compare_samples_kernel_seconds()
+
+
 def fill_samples_chunks():
     """Chunks of the write pass in this thread's last fill_samples(device=True) (diagnostic)."""
     return lib.colate_fill_samples_chunks()

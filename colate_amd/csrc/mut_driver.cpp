@@ -117,7 +117,7 @@ bool parse_options(int argc, char** argv, Options& o, std::string& err) {
 void print_help() {
   std::cout << "Usage:\n  Colate [OPTION...]\n\n"
             << "      --help                 Print help.\n"
-            << "      --mode arg             Choose which part of the algorithm to run (colate_amd: mut, mut_interval, make_tmp, CondCoalRates).\n"
+            << "      --mode arg             Choose which part of the algorithm to run (colate_amd: mut, mut_interval, compare_tmp, make_tmp, CondCoalRates).\n"
             << "      --mut arg              Filename of file containing mut.\n"
             << "      --target_tmp arg       Filename of target tmp file\n"
             << "      --reference_tmp arg    Filename of reference tmp file\n"
@@ -148,6 +148,8 @@ void print_help() {
             << "                             each the file `--pairs` writes for that pair.\n"
             << "                             (--mode mut) the same list, a line may add age=YEARS; the pairs are walked and their tables\n"
             << "                             filled on the GPU; PREFIX_<target>_<reference>.coal (and .counts) as `--mode mut --pairs` writes them.\n"
+            << "                             (--mode compare_tmp) the same list without mask= and age=; with --mut and -o PREFIX every pair's\n"
+            << "                             windowed mismatch counts, compared on the GPU: PREFIX_<target>_<reference>.txt and PREFIX.pairs.txt.\n"
             << "      --counts_out arg       Optional (colate_amd): write the bootstrap count tables (.colate_mat layout).\n"
             << "      --counts_only          Optional (colate_amd): stop after --counts_out (no GPU needed).\n"
             << "      --write_colate_mat     Optional (colate_amd): write <output>.colate_mat as the reference does for BCF/BAM inputs.\n"
@@ -1691,6 +1693,14 @@ extern "C" int colate_mut_main(int argc, char** argv) {
       return 1;
     }
   }
+  if (mode == "compare_tmp") {
+    try {
+      return run_compare_tmp(opt);
+    } catch (const std::exception& e) {
+      std::cerr << "Error: " << e.what() << std::endl;
+      return 1;
+    }
+  }
   if (mode == "make_tmp") {
     try {
       return run_make_tmp(opt);
@@ -1708,7 +1718,7 @@ extern "C" int colate_mut_main(int argc, char** argv) {
     }
   }
   std::cout << "####### error #######" << std::endl;
-  std::cout << "colate_amd implements --mode mut, --mode mut_interval, --mode make_tmp --target_table and --mode CondCoalRates (preprocess_mut, "
+  std::cout << "colate_amd implements --mode mut, --mode mut_interval, --mode compare_tmp, --mode make_tmp --target_table and --mode CondCoalRates (preprocess_mut, "
                "make_tmp from BCF/BAM, calc_depth, print_tmp stay with the reference build)."
             << std::endl;
   return 1;

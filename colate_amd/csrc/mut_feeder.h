@@ -146,6 +146,7 @@ std::vector<std::string> mask_files(const Options& opt, const std::vector<std::s
 void write_counts_file(const std::string& path, int B, int A, const std::vector<double>& grid, const double* csh,
                        const double* cns);
 void print_usage_footer();
+void print_help();  // mut_driver.cpp: the option list
 // condcoal.cpp: `--mode CondCoalRates`
 int run_condcoal(const Options& opt);  // "CPU Time spent: ...; Max Memory usage: ..." (coal.cpp:3852-3861)
 
@@ -188,6 +189,14 @@ bool collect_interval_records_pairs(const std::vector<std::string>& names, const
 // per (sample, chromosome) the file's index where it lies, per (mask, chromosome) the mask's bits; samples are the distinct
 // .colate.in paths, masks the distinct lists of mask files, both in the order of their names.  The object owns what it points to.
 constexpr int kIntervalBasesPerBlock = (int)30e6;  // the genome block of `--mode mut_interval` (coal.cpp: num_bases_per_block)
+// `--mode compare_tmp`: what the raw rows of a chromosome's .mut file decide (csrc/compare_tmp.h: the windows)
+struct CompareChromosome {
+  int first_pos = 0, last_pos = 0;  // the file's first and last raw rows
+  size_t raw_rows = 0;
+  bool ascend = true;           // no raw row lies below the one in front
+  int windows = 1;              // lines the chromosome prints
+  std::vector<int> row_window;  // per searched row: the lines printed in front of it
+};
 struct WalkInputs {
   struct Loaded;
   std::unique_ptr<Loaded> loaded;
@@ -199,11 +208,21 @@ struct WalkInputs {
   std::vector<const unsigned long long*> mask_ptrs;        // [M][C]
   std::vector<colate_walk_pair> pairs;
   int S = 0, M = 0;
+  std::vector<CompareChromosome> compare;  // [C], with compare = true only
+  bool files_ok = false;                   // every .colate.in file could be opened
   WalkInputs();
   ~WalkInputs();
 };
 bool load_walk_inputs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const std::vector<PairSpec>& pairs,
-                      WalkInputs& out);
+                      WalkInputs& out, bool compare = false);
+// compare = true (`--mode compare_tmp`): the rows kept are those of that mode's filter (compact rows without age_end >= 0), `compare`
+// is filled, and `indexed` also says that no chromosome's raw rows descend.
+// mut_pairs.cpp: the cursor walk of `--mode compare_tmp` (compare_tmp.h: cursor_walk_chromosome) for every pair of a list over inputs
+// loaded with compare = true: mismatch / snps [P][sum of compare[c].windows].  Right for every input; false without loaded inputs.
+bool compare_cursor_pairs(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& pairs,
+                          std::vector<int>& mismatch, std::vector<int>& snps);
+// compare_driver.cpp: `Colate --mode compare_tmp`
+int run_compare_tmp(const Options& opt);
 // collect_interval_records_pairs on inputs loaded before (the path `--samples` takes where a file has no walk index)
 bool collect_interval_records_loaded(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& pairs,
                                      std::vector<PairRecords>& out);

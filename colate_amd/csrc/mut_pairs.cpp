@@ -48,6 +48,7 @@
 #include "age_bins.hpp"
 #include "colate_amd.h"
 #include "colate_internal.h"
+#include "compare_tmp.h"
 #include "fill_device.h"
 #include "interval_cells.h"
 #include "mut_feeder.h"
@@ -186,8 +187,9 @@ struct CompactRow {
   char anc, der;
 };
 
-bool compact_row(const MutRow& m, CompactRow& c) {
-  if (!(m.flipped == 0 && m.num_branches == 1 && m.age_begin < m.age_end && m.age_end >= 0.0)) return false;
+// (need_age_end: false for `--mode compare_tmp`, whose loop has no such condition, coal.cpp:4412)
+bool compact_row(const MutRow& m, CompactRow& c, bool need_age_end = true) {
+  if (!(m.flipped == 0 && m.num_branches == 1 && m.age_begin < m.age_end && (!need_age_end || m.age_end >= 0.0))) return false;
   const std::string& mt = m.mutation_type;  // "anc/der" (mutations.cpp:236-246 splits at the first '/')
   const size_t slash = mt.find('/');
   if (slash != 1 || mt.size() != 3) return false;  // both sides exactly one character (empty sides: `continue`; longer: use = false)
@@ -1264,14 +1266,16 @@ struct Inputs {
   std::map<std::vector<std::string>, std::unique_ptr<MaskBits>> masks;  // (key: the mask's file per chromosome)
   size_t mask_reads = 0;
   size_t n_indexed = 0;  // files with a walk index
+  std::vector<CompareChromosome> compare;  // [chromosome], `--mode compare_tmp` only: the windows, which the raw rows decide
 };
 
 // The .mut files (all chromosomes in parallel), every .colate.in file of the pairs, every distinct mask -- one task per (mask,
 // chromosome) with one FASTA string alive in it (coal.cpp:2169-2174) -- and, unless use_index is false, every file's walk index.
 Inputs load_inputs(Pool& pool, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
-                   const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, bool use_index) {
+                   const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, bool use_index, bool compare = false) {
   Inputs in;
   in.rows.resize(mut_files.size());
+  if (compare) in.compare.resize(mut_files.size());
   std::vector<size_t> rows_total(mut_files.size(), 0);
   for (size_t c = 0; c < mut_files.size(); c++)
     pool.submit([&, c] {
@@ -1279,10 +1283,24 @@ Inputs load_inputs(Pool& pool, const std::vector<std::string>& names, const std:
       HugeVector<CompactRow>& r = in.rows[c];
       size_t n = 0;
       CompactRow cr;
+      // compare_tmp: the rows of its own filter, and in front of EVERY row of the file the window loop of coal.cpp:4405-4410
+      CompareChromosome* const cc = compare ? &in.compare[c] : nullptr;
+      long long current_bp = 0;
+      int lines = 0;
       for_each_mut_row(mut_files[c], [&](const MutRow& m) {
+        if (cc) {
+          if (n == 0) cc->first_pos = m.pos, current_bp = m.pos;
+          else if (m.pos < cc->last_pos) cc->ascend = false;
+          while (m.pos > current_bp + colate_cmp::kBinSize) lines++, current_bp += colate_cmp::kBinSize;
+          cc->last_pos = m.pos, cc->raw_rows++;
+        }
         n++;
-        if (compact_row(m, cr)) r.push_back(cr);
+        if (compact_row(m, cr, !compare)) {
+          r.push_back(cr);
+          if (cc) cc->row_window.push_back(lines);
+        }
       });
+      if (cc) cc->windows = lines + 1;
       rows_total[c] = n;
       WorkSeconds::add(g_work.parse_mut, now_s() - t0);
     });
@@ -1504,11 +1522,12 @@ void walk_pairs_for_records(Pool& pool, const Inputs& in, const std::vector<std:
   }
 }
 
-Inputs load_all(Pool& pool, const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const std::vector<PairSpec>& pairs) {
+Inputs load_all(Pool& pool, const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const std::vector<PairSpec>& pairs,
+                bool compare = false) {
   std::vector<size_t> todo(pairs.size());
   for (size_t p = 0; p < todo.size(); p++) todo[p] = p;
   const char* e_idx = std::getenv("COLATE_INDEXED_WALK");
-  return load_inputs(pool, names, mut_files, pairs, todo, !(e_idx && std::atoi(e_idx) == 0));
+  return load_inputs(pool, names, mut_files, pairs, todo, !(e_idx && std::atoi(e_idx) == 0), compare);
 }
 
 }  // namespace
@@ -1541,16 +1560,20 @@ static_assert(sizeof(TmpFile::RowIdx) == sizeof(colate_walk_idx) && offsetof(Tmp
 static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "mask words");
 
 bool load_walk_inputs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const std::vector<PairSpec>& pairs,
-                      WalkInputs& out) {
+                      WalkInputs& out, bool compare) {
   const double t0 = now_s();
   out.loaded.reset(new WalkInputs::Loaded);
   Pool pool(pairs_threads());
-  out.loaded->in = load_all(pool, names, mut_files, pairs);
+  out.loaded->in = load_all(pool, names, mut_files, pairs, compare);
   const Inputs& in = out.loaded->in;
+  out.compare = in.compare;
+  out.files_ok = true;
+  for (const auto& kv : in.tmp_files) out.files_ok = out.files_ok && kv.second->ok;
   g_times.parse_mut = now_s() - t0;
   const size_t C = in.rows.size();
   out.indexed = true;
   for (const auto& kv : in.tmp_files) out.indexed = out.indexed && kv.second->indexed;
+  for (const CompareChromosome& cc : in.compare) out.indexed = out.indexed && cc.ascend;  // (window_of needs raw rows that do not descend)
   if (!out.indexed) return true;
   // the rows as the walk reads them, the samples and masks in the order of their names, the pairs by their ids
   out.row_off.assign(1, 0);
@@ -1589,6 +1612,28 @@ bool collect_interval_records_loaded(const WalkInputs& loaded, const std::vector
   Pool pool(pairs_threads());
   walk_pairs_for_records(pool, loaded.loaded->in, names, pairs, out);
   g_times.table_fill = now_s() - t1;
+  return true;
+}
+
+// (mut_feeder.h)
+bool compare_cursor_pairs(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& pairs,
+                          std::vector<int>& mismatch, std::vector<int>& snps) {
+  if (!loaded.loaded || loaded.compare.size() != names.size()) return false;
+  const Inputs& in = loaded.loaded->in;
+  std::vector<size_t> win_off(1, 0);
+  for (const CompareChromosome& cc : in.compare) win_off.push_back(win_off.back() + (size_t)cc.windows);
+  const size_t Wt = win_off.back();
+  mismatch.assign(pairs.size() * Wt, 0), snps.assign(pairs.size() * Wt, 0);
+  Pool pool(pairs_threads());
+  for (size_t p = 0; p < pairs.size(); p++)
+    pool.submit([&, p] {  // one pair per task: its two cursors go through the chromosomes in the list's order
+      Cursor tgt, ref;
+      tgt.open(*in.tmp_files.at(pairs[p].target)), ref.open(*in.tmp_files.at(pairs[p].reference));
+      for (size_t c = 0; c < names.size(); c++)
+        colate_cmp::cursor_walk_chromosome(tgt, ref, names[c].c_str(), c == 0, in.rows[c].data(), in.rows[c].size(), in.compare[c].row_window.data(),
+                                           mismatch.data() + p * Wt + win_off[c], snps.data() + p * Wt + win_off[c]);
+    });
+  pool.wait_idle();
   return true;
 }
 

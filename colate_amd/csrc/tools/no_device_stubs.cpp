@@ -104,6 +104,16 @@ namespace colate_fs {
 int fill_view_device(const colate_iw::View&, int, unsigned, Result&) { return nodev(); }
 }  // namespace colate_fs
 
+// the pair stage of `--mode compare_tmp` on the device (compare_tmp.h; colate_compare_samples ends here): none in this build
+#include "compare_tmp.h"
+namespace colate_cmp {
+int compare_view_device(const View&, long long, long long*, int*, int*) { return nodev(); }
+}  // namespace colate_cmp
+extern "C" {
+int colate_compare_samples_chunks(void) { return 0; }
+double colate_compare_samples_kernel_seconds(void) { return 0.0; }
+}
+
 // the age sampling on the device (fill_device.h): there is none in this build, the host code samples
 #include "fill_device.h"
 namespace colate_drv {

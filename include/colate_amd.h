@@ -479,6 +479,36 @@ int colate_fill_samples_host(int C, const long long* row_off, const colate_walk_
 int colate_fill_samples_chunks(void);
 double colate_fill_samples_kernel_seconds(void);
 
+/* ---- `Colate --mode compare_tmp` for many pairs over the same walk indices (csrc/compare_tmp.h: the contract;
+ * include/coal/coal.cpp:4297-4521) ----
+ * For every pair and every window of every chromosome two counts: the searched rows both samples hit (snps) and, of those,
+ * the rows on which the two disagree (mismatch).  The inputs are those of colate_interval_walk without masks: every row
+ * given is a searched row (flipped == 0, one branch, age_begin < age_end, single-base alleles), its positions not
+ * descending; a pair's mask ids must both be -1.  Sample s hits row i iff (idx.DAF | idx.AAF) != 0 and idx.prev_bp >= the
+ * position of the row in front of i (-1 at a chromosome's first row); its allele there is fixed = (idx.AAF == 0) -- the
+ * reference's draw `uniform < DAF / (AAF + DAF)` in integer division decides nothing else.  snps counts the rows both
+ * samples hit, mismatch those of them with different `fixed`.  first_pos[C] / last_pos[C]: the positions of the first and
+ * last raw rows of each chromosome's .mut file (first_pos not above the first row given, last_pos not below the last);
+ * chromosome c has W_c = w(last_pos) + 1 windows with w(pos) = pos > first_pos ? (pos - first_pos - 1) / window : 0, and a
+ * row belongs to window w(its position).  `window` >= 1 (the command line: 10 000 000).
+ * Out: win_off[C + 1] (win_off[c + 1] - win_off[c] = W_c) and mismatch / snps as int[P][win_off[C]], each with room for
+ * `cap` ints (P x win_off[C] above it is COLATE_ELIMIT with the needed number in colate_last_error(); nothing is written
+ * then, nor after any other refusal).
+ * _host: the host twin -- two bit planes per sample (hit, fixed & hit; every chromosome starts on a 64-bit word), two
+ * popcounts per pair and window.  colate_compare_samples: the same on the calling thread's device (COLATE_ENODEVICE
+ * without one), all on one stream with one host wait: a plane kernel (one lane per sample and row, ballots), then per chunk
+ * of pairs -- the two output arrays of a chunk within 256 MB -- one workgroup per (pair, chromosome), a wave per window in
+ * turn.  Integers only, no atomics: both forms give the same ints whatever the chunking.
+ * colate_compare_samples_chunks / _kernel_seconds: diagnostics of the calling thread's last device call. */
+int colate_compare_samples(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx, int P,
+                           const colate_walk_pair* pairs, const int* first_pos, const int* last_pos, int window, long long cap,
+                           long long* win_off, int* mismatch, int* snps);
+int colate_compare_samples_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx, int P,
+                                const colate_walk_pair* pairs, const int* first_pos, const int* last_pos, int window, long long cap,
+                                long long* win_off, int* mismatch, int* snps);
+int colate_compare_samples_chunks(void);
+double colate_compare_samples_kernel_seconds(void);
+
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
 int colate_age_grid(double* age_grid, int cap);
