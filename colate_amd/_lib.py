@@ -100,6 +100,13 @@ SIGNATURES = {
                                             ctypes.c_longlong] + [c_void_p] * 3),
     "colate_compare_samples_chunks": (c_int, []),
     "colate_compare_samples_kernel_seconds": (c_double, []),
+    "colate_topo_samples": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
+                                    ctypes.c_longlong] + [c_void_p] * 4),
+    "colate_topo_samples_host": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
+                                         ctypes.c_longlong] + [c_void_p] * 4),
+    "colate_topo_samples_tile": (c_int, []),
+    "colate_topo_samples_chunks": (c_int, []),
+    "colate_topo_samples_kernel_seconds": (c_double, []),
     "colate_age_grid": (c_int, [c_void_p, c_int]),
     "colate_epochs_from_bins": (c_int, [c_char_p, c_double, c_double, c_void_p, c_int, ip]),
     "colate_epochs_from_coal": (c_int, [c_char_p, c_double, c_void_p, c_void_p, c_int]),

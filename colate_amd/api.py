@@ -652,6 +652,50 @@ def compare_samples_kernel_seconds():
     return lib.colate_compare_samples_kernel_seconds()
 
 
+TOPO_TRIPLE = np.dtype([("cond", np.int32), ("target", np.int32), ("reference", np.int32)])
+
+
+def topo_samples(row_off, rows, idx, cond_idx, triples, uniforms, device=True, cap=None):
+    """colate_topo_samples[_host]: the signed topology counts of `--mode count_topo` for every (cond, target, reference) of
+    `triples` (TOPO_TRIPLE: sample ids) over per-sample walk indices.  row_off, rows, idx: the inputs of interval_walk, every row
+    a searched row of this mode; cond_idx [S][rows] (WALK_IDX): per sample and row the counts of the record its cursor stands on,
+    matched or not; uniforms: the stream every triple reads from its start, two per qualifying row.  Returns (word_off [C + 1],
+    plus [P][words] uint64, minus [P][words], draws [P]): bit i & 63 of word word_off[c] + (i >> 6) is row i of chromosome c.
+    cap: the room given per plane in words (default: what the call needs).  device=False: the host twin, the same bits."""
+    args, keep = _walk_inputs(row_off, rows, idx, None, np.zeros(0, dtype=WALK_PAIR))
+    row_off_ = keep[0]
+    cond_idx = np.ascontiguousarray(cond_idx, dtype=WALK_IDX)
+    if cond_idx.shape != keep[2].shape:
+        raise ValueError("cond_idx must be [S][rows], as idx")
+    triples = np.ascontiguousarray(triples, dtype=TOPO_TRIPLE).ravel()
+    uniforms = _f64(uniforms).ravel()
+    P = triples.size
+    words = int(((np.diff(row_off_) + 63) // 64).sum()) if row_off_.size >= 2 and (np.diff(row_off_) >= 0).all() else 0
+    cap = P * words if cap is None else int(cap)  # (the library checks everything again and names what is wrong)
+    word_off, draws = np.zeros(row_off_.size, dtype=np.int64), np.zeros(P, dtype=np.int64)
+    plus, minus = np.zeros(max(cap, 0), dtype=np.uint64), np.zeros(max(cap, 0), dtype=np.uint64)
+    fn = lib.colate_topo_samples if device else lib.colate_topo_samples_host
+    check(fn(args[0], args[1], args[2], args[3], args[4], _p(cond_idx), P, _p(triples), uniforms.size, _p(uniforms), cap, _p(word_off),
+             _p(plus), _p(minus), _p(draws)))
+    n = int(word_off[-1])
+    return word_off, plus[:P * n].reshape(P, n).copy(), minus[:P * n].reshape(P, n).copy(), draws
+
+
+def topo_samples_tile():
+    """Rows of a tile of the draw kernel of topo_samples: 64 words of 64 rows (no device needed)."""
+    return lib.colate_topo_samples_tile()
+
+
+def topo_samples_chunks():
+    """Chunks of triples in this thread's last topo_samples(device=True) (diagnostic)."""
+    return lib.colate_topo_samples_chunks()
+
+
+def topo_samples_kernel_seconds():
+    """Seconds the kernels of this thread's last topo_samples(device=True) took on the device."""
+    return lib.colate_topo_samples_kernel_seconds()
+
+
 def fill_samples_chunks():
     """Chunks of the write pass in this thread's last fill_samples(device=True) (diagnostic)."""
     return lib.colate_fill_samples_chunks()

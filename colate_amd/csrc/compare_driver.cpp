@@ -61,7 +61,7 @@ bool count_pairs(const Options& opt, const std::vector<std::string>& names, cons
       }
       std::fclose(fp);
     }
-  if (!load_walk_inputs(names, mut_files, pairs, in, true)) return false;
+  if (!load_walk_inputs(names, mut_files, pairs, in, RowSet::compare_tmp)) return false;
   if (!in.files_ok) {
     std::cerr << "Error: a .colate.in file could not be read." << std::endl;
     return false;

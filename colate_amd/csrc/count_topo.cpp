@@ -1,0 +1,186 @@
+// colate_amd/csrc/count_topo.cpp -- the host side of colate_topo_samples (count_topo.h: the contract): the checks both forms run
+// before anything is written, the host twin of the three device kernels -- bit planes per sample, a popcount per triple, the
+// ranked draws --, and the C entry points, which view the caller's back-to-back arrays chromosome by chromosome.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "colate_amd.h"
+#include "colate_internal.h"
+#include "count_topo.h"
+
+using colate::fail;
+
+namespace colate_topo {
+
+int check_view(const View& v) {
+  if (v.C < 1 || v.S < 1 || v.P < 1)
+    return fail(COLATE_EINVAL, "bad sizes C=%d S=%d P=%d (at least one chromosome, one sample and one triple)", v.C, v.S, v.P);
+  if (!v.row_off) return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (v.n_uniforms < 0) return fail(COLATE_EINVAL, "n_uniforms = %lld is negative", v.n_uniforms);
+  if (v.n_uniforms > 0 && !v.uniforms) return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (v.row_off[0] != 0) return fail(COLATE_EINVAL, "row_off[0] = %lld must be 0", v.row_off[0]);
+  for (int c = 0; c < v.C; c++) {
+    if (v.row_off[c + 1] < v.row_off[c])
+      return fail(COLATE_EINVAL, "row_off decreases at chromosome %d (%lld after %lld)", c, v.row_off[c + 1], v.row_off[c]);
+    if (v.row_off[c + 1] - v.row_off[c] > 0x7fffffffLL) return fail(COLATE_ELIMIT, "chromosome %d has 2^31 rows or more", c);
+  }
+  if (!v.rows || !v.idx || !v.cidx || !v.triples) return fail(COLATE_EINVAL, "NULL pointer argument");
+  for (int c = 0; c < v.C; c++)
+    if (v.row_off[c + 1] > v.row_off[c] && !v.rows[c]) return fail(COLATE_EINVAL, "NULL pointer argument");
+  for (size_t k = 0; k < (size_t)v.S * v.C; k++)
+    if (v.row_off[k % v.C + 1] > v.row_off[k % v.C] && (!v.idx[k] || !v.cidx[k])) return fail(COLATE_EINVAL, "NULL pointer argument");
+  for (int p = 0; p < v.P; p++) {
+    const Triple& t = v.triples[p];
+    if (t.cond < 0 || t.cond >= v.S || t.target < 0 || t.target >= v.S || t.reference < 0 || t.reference >= v.S)
+      return fail(COLATE_EINVAL, "triple %d: sample id out of range (cond %d, target %d, reference %d, %d samples)", p, t.cond, t.target,
+                  t.reference, v.S);
+  }
+  for (int c = 0; c < v.C; c++) {
+    const long long nc = v.row_off[c + 1] - v.row_off[c];
+    for (long long i = 0; i < nc; i++) {
+      const int pos = v.rows[c][i].pos;
+      if (pos < 0 || (i > 0 && pos < v.rows[c][i - 1].pos))
+        return fail(COLATE_EINVAL, "chromosome %d, row %lld: position %d is negative or below the row in front (the walk index is one of ascending rows)", c, i, pos);
+    }
+  }
+  return COLATE_OK;
+}
+
+int check_outputs(long long cap, const long long* word_off, const unsigned long long* plus, const unsigned long long* minus, const long long* draws) {
+  if (!word_off || !draws) return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (cap < 0) return fail(COLATE_EINVAL, "cap = %lld is negative", cap);
+  if (cap > 0 && (!plus || !minus)) return fail(COLATE_EINVAL, "NULL pointer argument");
+  return COLATE_OK;
+}
+
+int check_capacity(long long P, long long words, long long cap) {
+  if (P * words > cap)
+    return fail(COLATE_ELIMIT, "%lld triples of %lld words, room for %lld words per plane (needed: %lld)", P, words, cap, P * words);
+  return COLATE_OK;
+}
+
+int check_stream(const View& v, const long long* draws) {
+  long long most = 0;
+  int at = 0;
+  for (int p = 0; p < v.P; p++)
+    if (draws[p] > most) most = draws[p], at = p;
+  if (2 * most > v.n_uniforms)
+    return fail(COLATE_ELIMIT, "triple %d has %lld qualifying rows, the stream holds %lld uniforms (needed: %lld)", at, most, v.n_uniforms, 2 * most);
+  return COLATE_OK;
+}
+
+void host_planes(const View& v, int s, const long long* word_off, long long words, unsigned long long* planes) {
+  std::memset(planes, 0, sizeof(unsigned long long) * 2 * (size_t)words);
+  for (int c = 0; c < v.C; c++) {
+    const long long nc = v.row_off[c + 1] - v.row_off[c];
+    const Idx* const X = v.idx[(size_t)s * v.C + c];
+    const Idx* const Y = v.cidx[(size_t)s * v.C + c];
+    for (long long i = 0; i < nc; i++) {
+      const unsigned long long bit = 1ull << (i & 63);
+      if (hits(X[i])) planes[word_off[c] + (i >> 6)] |= bit;
+      if (qualifies(Y[i])) planes[words + word_off[c] + (i >> 6)] |= bit;
+    }
+  }
+}
+
+int topo_view_host(const View& v, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws) {
+  if (int rc = check_outputs(cap, word_off, plus, minus, draws)) return rc;
+  if (int rc = check_view(v)) return rc;
+  std::vector<long long> woff((size_t)v.C + 1);
+  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
+  if (int rc = check_capacity(v.P, words, cap)) return rc;
+  std::vector<unsigned long long> planes((size_t)v.S * 2 * (size_t)words);
+  for (int s = 0; s < v.S; s++) host_planes(v, s, woff.data(), words, planes.data() + (size_t)s * 2 * (size_t)words);
+  auto plane = [&](int s, int which) { return planes.data() + ((size_t)s * 2 + (size_t)which) * (size_t)words; };
+  // the count pass: the stream is checked before anything is written
+  std::vector<long long> n((size_t)v.P, 0);
+  for (int p = 0; p < v.P; p++) {
+    const unsigned long long *T = plane(v.triples[p].target, 0), *R = plane(v.triples[p].reference, 0), *Cq = plane(v.triples[p].cond, 1);
+    for (long long k = 0; k < words; k++) n[(size_t)p] += __builtin_popcountll(T[k] & R[k] & Cq[k]);
+  }
+  if (int rc = check_stream(v, n.data())) return rc;
+  // the draw pass: a running popcount is the rank
+  for (int p = 0; p < v.P; p++) {
+    const Triple& t = v.triples[p];
+    const unsigned long long *T = plane(t.target, 0), *R = plane(t.reference, 0), *Cq = plane(t.cond, 1);
+    unsigned long long* const pl = plus + (size_t)p * (size_t)words;
+    unsigned long long* const mi = minus + (size_t)p * (size_t)words;
+    long long rank = 0;
+    for (int c = 0; c < v.C; c++) {
+      const Idx* const TI = v.idx[(size_t)t.target * v.C + c];
+      const Idx* const RI = v.idx[(size_t)t.reference * v.C + c];
+      for (long long k = woff[(size_t)c]; k < woff[(size_t)c + 1]; k++) {
+        unsigned long long a = 0, b = 0;
+        for (unsigned long long q = T[k] & R[k] & Cq[k]; q; q &= q - 1, rank++) {
+          const int bit = __builtin_ctzll(q);
+          const long long i = (k - woff[(size_t)c]) * 64 + bit;
+          const int sign = draw_sign(TI[i], RI[i], v.uniforms[2 * rank], v.uniforms[2 * rank + 1]);
+          if (sign > 0) a |= 1ull << bit;
+          if (sign < 0) b |= 1ull << bit;
+        }
+        pl[k] = a, mi[k] = b;
+      }
+    }
+    draws[p] = rank;
+  }
+  std::memcpy(word_off, woff.data(), sizeof(long long) * woff.size());
+  return COLATE_OK;
+}
+
+namespace {
+
+// the caller's back-to-back arrays, chromosome by chromosome
+struct FlatView {
+  View v;
+  std::vector<const Row*> rows;
+  std::vector<const Idx*> idx, cidx;
+  FlatView(int C, const long long* row_off, const Row* r, int S, const Idx* x, const Idx* y, int P, const Triple* triples, long long n_uniforms,
+           const double* uniforms) {
+    v.C = C, v.row_off = row_off, v.S = S, v.P = P, v.triples = triples, v.n_uniforms = n_uniforms, v.uniforms = uniforms;
+    bool ok = C >= 1 && S >= 1 && row_off && row_off[0] == 0;
+    for (int c = 0; ok && c < C; c++) ok = row_off[c + 1] >= row_off[c];
+    if (!ok) {  // (check_view names what is wrong with the sizes or offsets: nothing below is dereferenced before it)
+      static const Row* const no_rows = nullptr;
+      static const Idx* const no_idx = nullptr;
+      v.rows = r ? &no_rows : nullptr, v.idx = x ? &no_idx : nullptr, v.cidx = y ? &no_idx : nullptr;
+      return;
+    }
+    const long long n = row_off[C];
+    rows.resize((size_t)C), idx.resize((size_t)S * C), cidx.resize((size_t)S * C);
+    for (int c = 0; c < C; c++) rows[(size_t)c] = r ? r + row_off[c] : nullptr;
+    for (int s = 0; s < S; s++)
+      for (int c = 0; c < C; c++) {
+        idx[(size_t)s * C + c] = x ? x + (size_t)s * n + row_off[c] : nullptr;
+        cidx[(size_t)s * C + c] = y ? y + (size_t)s * n + row_off[c] : nullptr;
+      }
+    v.rows = r ? rows.data() : nullptr, v.idx = x ? idx.data() : nullptr, v.cidx = y ? cidx.data() : nullptr;
+  }
+};
+
+}  // namespace
+
+}  // namespace colate_topo
+
+using namespace colate_topo;
+
+extern "C" {
+
+int colate_topo_samples_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                             const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms,
+                             const double* uniforms, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus,
+                             long long* draws) {
+  const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, n_uniforms, uniforms);
+  return topo_view_host(f.v, cap, word_off, plus, minus, draws);
+}
+
+int colate_topo_samples(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                        const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms, const double* uniforms,
+                        long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws) {
+  const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, n_uniforms, uniforms);
+  return topo_view_device(f.v, cap, word_off, plus, minus, draws);
+}
+
+int colate_topo_samples_tile(void) { return kTileRows; }
+
+}  // extern "C"

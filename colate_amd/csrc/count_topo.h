@@ -1,0 +1,142 @@
+// colate_amd/csrc/count_topo.h -- `Colate --mode count_topo` (internal to libcolate_amd.so): what the cursor walk, the host twin
+// of the indexed form (count_topo.cpp) and the device stage (count_topo_kernel.hip) share.
+//
+// THE CONTRACT (include/coal/coal.cpp:4523-4781, restated).  For a conditioning sample C (--input), a target T and a reference R
+// the mode walks the .mut rows; at every SNP where C carries the derived allele and T and R both have data it samples one allele
+// from T and one from R and prints the SNP with +1 where T is derived and R ancestral, with -1 for the converse.
+// Rows.  Per chromosome the rows of <mut>_chr<name>.mut[.gz] (without --chr: <mut> itself, the empty name).  A row is SEARCHED
+//   when flipped == 0, it has one branch, the float age_begin <= age_end (`<=`: rows with equal ages are searched here and not in
+//   `--mode compare_tmp` or `--mode mut`), and both alleles are one of A C G T (or 0 / 1).
+// Cursors.  At every searched row each of the three cursors advances while it is in the chromosome and bp < pos; none depends on
+//   another.  The counts are NOT reset in front of a search (compare_tmp resets them), so whether the cursor moved does not matter:
+//   T (and likewise R) HITS a row iff its cursor stands on a record of the row's chromosome, position and alleles with AAF + DAF > 0.
+//   Over a file's walk index (mut_pairs.cpp: build_walk_index) that is (idx.DAF | idx.AAF) != 0 and nothing else.
+//   C is never checked against the row: the reference uses DAF_cond and AAF_cond of whatever record C's cursor stands on -- the
+//   first record of the chromosome at or behind the row; behind the chromosome's last record the record that follows the
+//   chromosome's run in the file, or the file's last record where the reads have run out.  C QUALIFIES a row iff that record has
+//   DAF > 0 and DAF + AAF > 0.  The COND INDEX of a file holds those counts row by row (mut_pairs.cpp: build_row_index).
+// Draws.  A row QUALIFIES for the triple iff T hits, R hits and C qualifies.  At every qualifying row, and only there, two uniforms
+//   are drawn from the run's std::mt19937 (seeded once per run) through uniform_real_distribution<double>(0, 1), each ROUNDED TO
+//   FLOAT: qualifying row number k of the run, counted across chromosomes, uses uniforms 2k and 2k + 1 of the seed's stream.  With
+//   pT = (double)DAF_T / N_T and pR likewise, the floats promoted back to double: +1 when d1 <= pT && d2 > pR, -1 when d1 > pT &&
+//   d2 <= pR, else nothing is printed.  (A uniform just below 1 rounds up to 1.0f, and 1.0f <= 1.0 holds.)
+// Output.  One line per printed row, `name pos age_begin age_end sign value` with value = sign * (double)DAF_C / N_C; the ages are
+//   floats in the stream's default format.  No windows, no totals.
+// The run's first chromosome.  The three name buffers are uninitialised in the reference (coal.cpp:4585).  In its compiled form
+//   (oracle/_ref/Colate_ref) they do not hold the listed name, so each skip loop reads one record before it compares -- what
+//   compare_tmp.h records as "a fresh cursor matches no name" -- and the cursor walk below does the same.  In this mode it changes
+//   no output: nothing is reset, every cursor then advances to the row's lower bound whichever record it started from, and with the
+//   empty name of a run without --chr a file whose first record carries another name leaves T and R without a hit either way.  The
+//   `nochr` fixture is the reference's file for such a run.
+//
+// THE INDEXED FORM.  Per sample two bit planes over the searched rows, `hit` from its walk index and `qualifies` from its cond
+// index, each chromosome starting on a 64-bit word (mask_words, interval_walk.h).  Per triple Q = hitT & hitR & qualC; the rank of
+// a set bit of Q among the triple's set bits, chromosomes in order, is the row's position in the stream; two bit planes come out,
+// `plus` and `minus`, and the number of qualifying rows.  Integers decide everything but the two double quotients and the two
+// float roundings of draw_sign, which depend on one row alone: no result depends on an order of operations, and there are no
+// atomics of any kind.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "colate_amd.h"
+#include "interval_walk.h"
+
+namespace colate_topo {
+
+using colate_iw::Idx;
+using colate_iw::Row;
+using Triple = colate_topo_triple;
+static_assert(sizeof(Triple) == 12, "topo triple");
+
+constexpr int kPlaneTile = 256;             // threads of a plane workgroup: four words of one array
+constexpr int kDrawWaves = 4;               // waves of a draw workgroup: each takes every fourth tile of its chromosome
+constexpr int kTileWords = 64;              // words a wave scans at once, one per lane
+constexpr int kTileRows = kTileWords * 64;  // colate_topo_samples_tile()
+
+COLATE_IC_HD inline bool hits(const Idx& x) { return (x.DAF | x.AAF) != 0; }
+COLATE_IC_HD inline bool qualifies(const Idx& c) { return c.DAF > 0; }
+// +1, -1 or 0 at a qualifying row from the two uniforms of its rank (coal.cpp:4742-4749)
+COLATE_IC_HD inline int draw_sign(const Idx& t, const Idx& r, double u1, double u2) {
+  const float d1 = (float)u1, d2 = (float)u2;
+  const int N_target = (int)t.DAF + (int)t.AAF, N_ref = (int)r.DAF + (int)r.AAF;
+  const double pT = (double)t.DAF / N_target, pR = (double)r.DAF / N_ref;
+  if ((double)d1 <= pT && (double)d2 > pR) return 1;
+  if ((double)d1 > pT && (double)d2 <= pR) return -1;
+  return 0;
+}
+
+// The inputs of both stages: every row given is a searched row; idx[s * C + c] is sample s's walk index of chromosome c,
+// cidx[s * C + c] its cond index.
+struct View {
+  int C = 0;
+  const long long* row_off = nullptr;
+  const Row* const* rows = nullptr;
+  int S = 0;
+  const Idx* const* idx = nullptr;
+  const Idx* const* cidx = nullptr;
+  int P = 0;
+  const Triple* triples = nullptr;
+  long long n_uniforms = 0;
+  const double* uniforms = nullptr;
+};
+// What both calls refuse before anything is written (COLATE_EINVAL / COLATE_ELIMIT; colate_last_error() names it): NULLs, bad
+// sizes, decreasing offsets, ids out of range, rows that descend, a negative stream length.
+int check_view(const View& v);
+int check_outputs(long long cap, const long long* word_off, const unsigned long long* plus, const unsigned long long* minus, const long long* draws);
+int check_capacity(long long P, long long words, long long cap);
+// the stream the triples need: 2 x the most qualifying rows of any (COLATE_ELIMIT with the needed length where it is longer than given)
+int check_stream(const View& v, const long long* draws);
+// sample s's planes[2][words]: hit, qualifies
+void host_planes(const View& v, int s, const long long* word_off, long long words, unsigned long long* planes);
+// The host twin / the device stage: word_off[C + 1], plus / minus [P][word_off[C]] with room for cap words each, draws[P].
+int topo_view_host(const View& v, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws);
+int topo_view_device(const View& v, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws);
+
+// THE CURSOR WALK of one chromosome: the reference's loop over three record cursors, correct for every input.  Cur: a cursor
+// with match, bp, anc, der, AAF, DAF, set_name() and next() (mut_pairs.cpp: Cursor); RowT: pos, anc, der.  draw(): the next
+// uniform of the run's stream; emit(i, sign, DAF_cond, N_cond): row i prints.  fresh: the run's first chromosome (above).
+template <class Cur, class RowT, class Draw, class Emit>
+void cursor_walk_chromosome(Cur& cnd, Cur& tgt, Cur& ref, const char* name, bool fresh, const RowT* rows, size_t n, Draw&& draw, Emit&& emit) {
+  Cur* const cur[3] = {&cnd, &tgt, &ref};
+  for (Cur* c : cur) {  // skip to this chromosome, coal.cpp:4621-4652
+    c->set_name(name);
+    for (bool first = fresh; first || !c->match; first = false)
+      if (!c->next()) break;
+  }
+  for (size_t i = 0; i < n; i++) {
+    const RowT& m = rows[i];
+    for (Cur* c : cur)
+      while (c->match && c->bp < m.pos)
+        if (!c->next()) break;
+    const int N_cond = (int)((unsigned)cnd.DAF + (unsigned)cnd.AAF), N_target = (int)((unsigned)tgt.DAF + (unsigned)tgt.AAF),
+              N_ref = (int)((unsigned)ref.DAF + (unsigned)ref.AAF);
+    if (!tgt.match || tgt.bp != m.pos || tgt.anc != m.anc || tgt.der != m.der) continue;
+    if (!ref.match || ref.bp != m.pos || ref.anc != m.anc || ref.der != m.der) continue;
+    if (!(N_cond > 0 && N_ref > 0 && N_target > 0)) continue;
+    if (!(cnd.DAF > 0)) continue;
+    const float d1 = (float)draw(), d2 = (float)draw();
+    const double pT = (double)tgt.DAF / N_target, pR = (double)ref.DAF / N_ref;
+    if ((double)d1 <= pT && (double)d2 > pR) emit(i, 1, cnd.DAF, N_cond);
+    else if ((double)d1 > pT && (double)d2 <= pR) emit(i, -1, cnd.DAF, N_cond);
+  }
+}
+
+}  // namespace colate_topo
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+namespace colate_topo {
+// planes[2 S][words] of the resident inputs, whose arrays 0 .. S - 1 are the walk indices and S .. 2 S - 1 the cond indices:
+// `hit` of the former, `qualifies` of the latter.  One lane per (array, searched row).
+hipError_t planes_launch(const colate_iw::DeviceInputs& in, int S, unsigned long long* planes, hipStream_t stream);
+// cnt[p * C + c] = popc(Q) over chromosome c for triples [0, P): one workgroup per (triple, chromosome)
+hipError_t count_launch(const colate_iw::DeviceInputs& in, int S, int P, const Triple* triples, const unsigned long long* planes, int* cnt,
+                        hipStream_t stream);
+// plus / minus [(p - p0)][words] for triples [p0, p1): one workgroup per (triple, chromosome); base[p * C + c]: the rank of the
+// chromosome's first qualifying row; u: the uniforms, at least 2 x the most qualifying rows of any triple
+hipError_t draw_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
+                       const long long* base, const double* u, unsigned long long* plus, unsigned long long* minus, hipStream_t stream);
+}  // namespace colate_topo
+#endif

@@ -1,0 +1,249 @@
+// colate_amd/csrc/count_topo_kernel.hip -- `Colate --mode count_topo --samples` on the GPU (count_topo.h: the contract;
+// count_topo.cpp: the host twin): the three kernels of the triple stage and the host code that drives them over the resident
+// inputs of the pair walks (walk_resident.hpp), whose index arrays here are the S walk indices followed by the S cond indices.
+//
+//   * topo_planes_kernel: one lane per (array, searched row).  A wave holds the 64 rows of one plane word of one array: each
+//     lane reads its 8-byte entry, forms `hit` (arrays 0 .. S - 1) or `qualifies` (arrays S .. 2 S - 1), and a ballot -- 64
+//     bits on wave64 -- is the word, which lane 0 writes to planes[2 S][words] in HBM.  Every chromosome starts on a word;
+//     lanes beyond the chromosome's end hold "no".
+//   * topo_count_kernel: one workgroup (one wave) per (triple, chromosome): the lanes stride over the chromosome's words,
+//     popc(hitT & hitR & qualC) is summed over the wave by shuffles and lane 0 writes cnt[p][c].
+//   * topo_draw_kernel: one workgroup of four waves per (triple, chromosome).  Every wave goes through the chromosome tile by
+//     tile, a tile being 64 words with one word per lane: popcount, an inclusive scan over the lanes by shuffles, and the
+//     tile's total carried on -- so each wave knows every word's base rank without a barrier or LDS.  Wave w draws the tiles
+//     w, w + 4, ...: word by word, lane = row, rank = base + popc(Q & lanes below); a lane whose bit is set reads u[2 rank],
+//     u[2 rank + 1] and the target's and the reference's index entries (consecutive rows: coalesced), compares, and two ballots
+//     are the `plus` and `minus` words, which the lane of that word keeps and the wave stores, one word per lane, at the end of
+//     the tile.  Every output has one owner; a workgroup reads nothing another workgroup of the same launch writes.
+// No atomics, no LDS, no barrier, no floating-point reduction, no compaction.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "colate_amd.h"
+#include "colate_internal.h"
+#include "count_topo.h"
+#include "em_job.hpp"
+#include "walk_resident.hpp"
+
+using namespace colate;
+using namespace colate_topo;
+using colate_iw::DeviceInputs;
+
+namespace {
+
+__global__ __launch_bounds__(kPlaneTile) void topo_planes_kernel(DeviceInputs in, int S, unsigned long long* __restrict__ planes) {
+  const int lane = threadIdx.x & 63;
+  const long long gw = (long long)blockIdx.x * (kPlaneTile / 64) + (threadIdx.x >> 6);  // the word: alike in the whole wave
+  if (gw >= in.words) return;
+  const int a = blockIdx.y;  // the array: a walk index below S, a cond index from S on
+  int c = 0;
+  while (c + 1 < in.C && in.word_off[c + 1] <= gw) c++;  // (the chromosome of the word; empty chromosomes own no word)
+  const long long r0 = in.row_off[c];
+  const long long i = (gw - in.word_off[c]) * 64 + lane, n = in.row_off[c + 1] - r0;
+  bool yes = false;
+  if (i < n) {
+    const Idx x = in.idx[(size_t)a * in.n + r0 + i];
+    yes = a < S ? hits(x) : qualifies(x);
+  }
+  const unsigned long long w = __ballot(yes);
+  if (lane == 0) planes[(size_t)a * in.words + gw] = w;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(64) void topo_count_kernel(DeviceInputs in, int S, const Triple* __restrict__ triples,
+                                                        const unsigned long long* __restrict__ planes, int* __restrict__ cnt) {
+  const int c = blockIdx.x % in.C, p = blockIdx.x / in.C;
+  const int lane = threadIdx.x;
+  const Triple t = triples[p];
+  const long long w0 = in.word_off[c], W = in.word_off[c + 1] - w0;
+  const unsigned long long* const hT = planes + (size_t)t.target * in.words + w0;
+  const unsigned long long* const hR = planes + (size_t)t.reference * in.words + w0;
+  const unsigned long long* const qC = planes + (size_t)(S + t.cond) * in.words + w0;
+  int n = 0;
+  for (long long k = lane; k < W; k += 64) n += __popcll(hT[k] & hR[k] & qC[k]);
+  n = wave_sum(n);  // (a chromosome has fewer than 2^31 rows)
+  if (lane == 0) cnt[(size_t)p * in.C + c] = n;
+}
+
+__device__ __forceinline__ unsigned long long wave_uniform(unsigned long long v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+__global__ __launch_bounds__(kDrawWaves * 64) void topo_draw_kernel(DeviceInputs in, int S, int p0, const Triple* __restrict__ triples,
+                                                                    const unsigned long long* __restrict__ planes,
+                                                                    const long long* __restrict__ base, const double* __restrict__ u,
+                                                                    unsigned long long* __restrict__ plus, unsigned long long* __restrict__ minus) {
+  const int c = blockIdx.x % in.C, j = blockIdx.x / in.C;  // (triple p0 + j, chromosome c)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const Triple t = triples[p0 + j];
+  const long long w0 = in.word_off[c], W = in.word_off[c + 1] - w0, r0 = in.row_off[c];
+  const unsigned long long* const hT = planes + (size_t)t.target * in.words + w0;
+  const unsigned long long* const hR = planes + (size_t)t.reference * in.words + w0;
+  const unsigned long long* const qC = planes + (size_t)(S + t.cond) * in.words + w0;
+  const Idx* const TI = in.idx + (size_t)t.target * in.n + r0;
+  const Idx* const RI = in.idx + (size_t)t.reference * in.n + r0;
+  unsigned long long* const pl = plus + (size_t)j * in.words + w0;
+  unsigned long long* const mi = minus + (size_t)j * in.words + w0;
+  long long carry = base[(size_t)(p0 + j) * in.C + c];  // the rank of the chromosome's first qualifying row
+  for (long long tile0 = 0, tile = 0; tile0 < W; tile0 += kTileWords, tile++) {
+    const long long k = tile0 + lane;
+    const unsigned long long q = k < W ? hT[k] & hR[k] & qC[k] : 0ull;
+    const int n = __popcll(q);
+    int incl = n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += up;
+    }
+    const int total = __shfl(incl, 63, 64);
+    if (tile % kDrawWaves == wave) {
+      const int nw = (int)(W - tile0 < kTileWords ? W - tile0 : kTileWords);
+      unsigned long long my_plus = 0, my_minus = 0;
+      for (int w = 0; w < nw; w++) {
+        const unsigned long long qw = wave_uniform(__shfl(q, w, 64));
+        if (qw == 0) continue;  // (alike in the whole wave; the lane of this word keeps its zeros)
+        const long long bw = carry + __shfl(incl - n, w, 64);
+        int sign = 0;
+        if ((qw >> lane) & 1) {
+          const long long rank = bw + __popcll(qw & ((1ull << lane) - 1));
+          const long long i = (tile0 + w) * 64 + lane;  // (a set bit of Q is a row of the chromosome)
+          sign = draw_sign(TI[i], RI[i], u[2 * rank], u[2 * rank + 1]);
+        }
+        const unsigned long long a = __ballot(sign > 0), b = __ballot(sign < 0);
+        if (lane == w) my_plus = a, my_minus = b;
+      }
+      if (k < W) pl[k] = my_plus, mi[k] = my_minus;
+    }
+    carry += total;
+  }
+}
+
+thread_local int g_chunks = 0;
+thread_local double g_kernel_s = 0.0;
+
+// bytes of the two output planes a chunk of triples may take on the device (COLATE_TOPO_BUDGET: bytes, for the tests)
+long long output_budget() {
+  if (const char* e = std::getenv("COLATE_TOPO_BUDGET")) return std::max(1LL, std::atoll(e));
+  return 256LL << 20;
+}
+
+}  // namespace
+
+namespace colate_topo {
+
+hipError_t planes_launch(const DeviceInputs& in, int S, unsigned long long* planes, hipStream_t stream) {
+  if (in.words < 1 || in.S < 1) return hipSuccess;
+  const long long blocks = (in.words + kPlaneTile / 64 - 1) / (kPlaneTile / 64);
+  if (blocks > 0x7fffffffLL || in.S > 65535 || in.S != 2 * S) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topo_planes_kernel, dim3((unsigned)blocks, (unsigned)in.S), dim3(kPlaneTile), 0, stream, in, S, planes);
+  return hipGetLastError();
+}
+
+hipError_t count_launch(const DeviceInputs& in, int S, int P, const Triple* triples, const unsigned long long* planes, int* cnt,
+                        hipStream_t stream) {
+  if (P < 1 || in.C < 1) return hipSuccess;
+  const long long grid = (long long)P * in.C;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topo_count_kernel, dim3((unsigned)grid), dim3(64), 0, stream, in, S, triples, planes, cnt);
+  return hipGetLastError();
+}
+
+hipError_t draw_launch(const DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
+                       const long long* base, const double* u, unsigned long long* plus, unsigned long long* minus, hipStream_t stream) {
+  if (p1 <= p0 || in.C < 1) return hipSuccess;
+  const long long grid = (long long)(p1 - p0) * in.C;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topo_draw_kernel, dim3((unsigned)grid), dim3(kDrawWaves * 64), 0, stream, in, S, p0, triples, planes, base, u, plus, minus);
+  return hipGetLastError();
+}
+
+int topo_view_device(const View& v, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws) {
+  if (int rc = check_outputs(cap, word_off, plus, minus, draws)) return rc;
+  if (int rc = check_view(v)) return rc;
+  if (2LL * v.S > 65535) return fail(COLATE_ELIMIT, "S=%d above the grid of the plane kernel (32767)", v.S);
+  if ((long long)v.P * v.C > 0x7fffffffLL) return fail(COLATE_ELIMIT, "P x C = %lld above the grid of the count kernel", (long long)v.P * v.C);
+  std::vector<long long> woff((size_t)v.C + 1);
+  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
+  if (int rc = check_capacity(v.P, words, cap)) return rc;
+  if (int rc = ensure_device()) return rc;
+  ProfRange range("colate_topo_samples: H2D + planes + counts; the uniforms; per chunk of triples the draws + D2H");
+  g_chunks = 0, g_kernel_s = 0.0;
+  if (int rc = thread_workspace().reserve(256, 256)) return rc;  // (the workspace's stream: no second one)
+  hipStream_t stream = thread_workspace().stream;
+  colate_iw::KernelTimer timer(stream);
+  colate_iw::Resident res;
+  DeviceBuffers buf;
+  const size_t PC = (size_t)v.P * v.C;
+  std::vector<int> cnt(PC);
+  std::vector<long long> base(PC), n((size_t)v.P, 0);
+  std::vector<const Idx*> both((size_t)2 * v.S * v.C);  // the walk indices, then the cond indices
+  std::copy_n(v.idx, (size_t)v.S * v.C, both.begin());
+  std::copy_n(v.cidx, (size_t)v.S * v.C, both.begin() + (size_t)v.S * v.C);
+  const colate_iw::StreamSync sync_at_exit{stream};
+  colate_iw::View iv;
+  iv.C = v.C, iv.row_off = v.row_off, iv.rows = v.rows, iv.S = 2 * v.S, iv.idx = both.data(), iv.M = 0, iv.P = 0, iv.pairs = nullptr, iv.nbpb = 1;
+  if (int rc = res.upload(iv, stream)) return rc;
+  // triples per chunk: the two output planes of a chunk within the budget, and the grid within 2^31 workgroups
+  const long long per_triple = std::max(1LL, 2 * words * (long long)sizeof(unsigned long long));
+  const long long chunk = std::max(1LL, std::min<long long>({(long long)v.P, output_budget() / per_triple, 0x7fffffffLL / v.C}));
+  unsigned long long *d_planes = nullptr, *d_plus = nullptr, *d_minus = nullptr;
+  Triple* d_triples = nullptr;
+  int* d_cnt = nullptr;
+  long long* d_base = nullptr;
+  double* d_u = nullptr;
+  HIP_TRY(buf.device(d_planes, (size_t)2 * v.S * (size_t)words)); HIP_TRY(buf.device(d_triples, (size_t)v.P));
+  HIP_TRY(buf.device(d_cnt, PC)); HIP_TRY(buf.device(d_base, PC));
+  HIP_TRY(buf.device(d_plus, (size_t)(chunk * words))); HIP_TRY(buf.device(d_minus, (size_t)(chunk * words)));
+  HIP_TRY(colate_iw::h2d(stream, d_triples, v.triples, sizeof(Triple) * (size_t)v.P));
+  HIP_TRY(timer.mark());
+  if (hipError_t e = planes_launch(res.in, v.S, d_planes, stream)) return hip_fail(e, "topo planes kernel launch");
+  if (hipError_t e = count_launch(res.in, v.S, v.P, d_triples, d_planes, d_cnt, stream)) return hip_fail(e, "topo count kernel launch");
+  HIP_TRY(timer.mark());
+  HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * PC, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));  // the one wait for the counts
+  long long most = 0;
+  for (int p = 0; p < v.P; p++) {
+    for (int c = 0; c < v.C; c++) base[(size_t)p * v.C + c] = n[(size_t)p], n[(size_t)p] += cnt[(size_t)p * v.C + c];
+    most = std::max(most, n[(size_t)p]);
+  }
+  if (int rc = check_stream(v, n.data())) return rc;
+  // every triple starts from the run's seed: one stream for all, as long as the longest needs
+  HIP_TRY(buf.device(d_u, (size_t)(2 * most)));
+  HIP_TRY(colate_iw::h2d(stream, d_u, v.uniforms, sizeof(double) * (size_t)(2 * most)));
+  HIP_TRY(colate_iw::h2d(stream, d_base, base.data(), sizeof(long long) * PC));
+  for (long long p0 = 0; p0 < v.P; p0 += chunk) {  // (a chunk's planes are copied out before the next launch overwrites them: one stream)
+    const long long p1 = std::min<long long>(v.P, p0 + chunk);
+    HIP_TRY(timer.mark());
+    if (hipError_t e = draw_launch(res.in, v.S, (int)p0, (int)p1, d_triples, d_planes, d_base, d_u, d_plus, d_minus, stream))
+      return hip_fail(e, "topo draw kernel launch");
+    HIP_TRY(timer.mark());
+    const size_t bytes = sizeof(unsigned long long) * (size_t)((p1 - p0) * words);
+    if (bytes) {
+      HIP_TRY(hipMemcpyAsync(plus + p0 * words, d_plus, bytes, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(minus + p0 * words, d_minus, bytes, hipMemcpyDeviceToHost, stream));
+    }
+    g_chunks++;
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  g_kernel_s = timer.seconds();
+  std::memcpy(draws, n.data(), sizeof(long long) * (size_t)v.P);
+  std::memcpy(word_off, woff.data(), sizeof(long long) * woff.size());
+  return COLATE_OK;
+}
+
+}  // namespace colate_topo
+
+extern "C" {
+int colate_topo_samples_chunks(void) { return g_chunks; }
+double colate_topo_samples_kernel_seconds(void) { return g_kernel_s; }
+}

@@ -117,7 +117,7 @@ bool parse_options(int argc, char** argv, Options& o, std::string& err) {
 void print_help() {
   std::cout << "Usage:\n  Colate [OPTION...]\n\n"
             << "      --help                 Print help.\n"
-            << "      --mode arg             Choose which part of the algorithm to run (colate_amd: mut, mut_interval, compare_tmp, make_tmp, CondCoalRates).\n"
+            << "      --mode arg             Choose which part of the algorithm to run (colate_amd: mut, mut_interval, compare_tmp, count_topo, make_tmp, CondCoalRates).\n"
             << "      --mut arg              Filename of file containing mut.\n"
             << "      --target_tmp arg       Filename of target tmp file\n"
             << "      --reference_tmp arg    Filename of reference tmp file\n"
@@ -150,6 +150,9 @@ void print_help() {
             << "                             filled on the GPU; PREFIX_<target>_<reference>.coal (and .counts) as `--mode mut --pairs` writes them.\n"
             << "                             (--mode compare_tmp) the same list without mask= and age=; with --mut and -o PREFIX every pair's\n"
             << "                             windowed mismatch counts, compared on the GPU: PREFIX_<target>_<reference>.txt and PREFIX.pairs.txt.\n"
+            << "                             (--mode count_topo) that list with role= a comma-separated subset of cond,target,reference (default: all\n"
+            << "                             three); every (cond, target, reference) of three lines, drawn on the GPU: PREFIX_<cond>_<target>_<reference>.txt\n"
+            << "                             and PREFIX.triples.txt.\n"
             << "      --counts_out arg       Optional (colate_amd): write the bootstrap count tables (.colate_mat layout).\n"
             << "      --counts_only          Optional (colate_amd): stop after --counts_out (no GPU needed).\n"
             << "      --write_colate_mat     Optional (colate_amd): write <output>.colate_mat as the reference does for BCF/BAM inputs.\n"
@@ -815,7 +818,7 @@ bool read_pair_list(const std::string& path, const Options& opt, const std::vect
 
 // (mut_feeder.h)
 bool read_sample_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names, bool with_ages,
-                      std::vector<SampleLine>& samples) {
+                      std::vector<SampleLine>& samples, bool with_cond) {
   std::ifstream is(path);
   if (!is) {
     std::cerr << "Error while opening file " << path << std::endl;
@@ -829,7 +832,7 @@ bool read_sample_list(const std::string& path, const Options& opt, const std::ve
     };
     std::istringstream ss(line);
     SampleLine sl;
-    sl.line = line_no;
+    sl.line = line_no, sl.cond = with_cond;
     if (!(ss >> sl.name)) continue;  // a blank line
     if (sl.name.find('=') != std::string::npos) return fail("the line starts with '" + sl.name + "': the sample's NAME is missing or empty");
     if (sl.name.find('/') != std::string::npos) return fail("the NAME '" + sl.name + "' contains '/'");
@@ -862,14 +865,27 @@ bool read_sample_list(const std::string& path, const Options& opt, const std::ve
         if (used == 0 || used != value.size() || !(v == v)) return fail("the age '" + value + "' is not a number");
         if (v < 0) return fail("the age '" + value + "' is negative");
         sl.age = v;
+      } else if (with_cond) {  // (`--mode count_topo`: a comma-separated subset of the three roles)
+        sl.cond = sl.target = sl.reference = false;
+        std::istringstream roles(value);
+        for (std::string r; std::getline(roles, r, ',');) {
+          bool* const on = r == "cond" ? &sl.cond : r == "target" ? &sl.target : r == "reference" ? &sl.reference : nullptr;
+          if (!on) return fail("unknown role '" + r + "' (known: cond, target, reference)");
+          if (*on) return fail("the role '" + r + "' is given twice");
+          *on = true;
+        }
       } else if (value == "target") sl.reference = false;
       else if (value == "reference") sl.target = false;
       else return fail("unknown role '" + value + "' (known: target, reference)");
     }
     samples.push_back(sl);
   }
-  bool any_t = false, any_r = false;
-  for (const SampleLine& sl : samples) any_t = any_t || sl.target, any_r = any_r || sl.reference;
+  bool any_t = false, any_r = false, any_c = !with_cond;
+  for (const SampleLine& sl : samples) any_t = any_t || sl.target, any_r = any_r || sl.reference, any_c = any_c || sl.cond;
+  if (!any_c) {
+    std::cerr << "Error: " << path << ": the list names no cond sample." << std::endl;
+    return false;
+  }
   if (!any_t || !any_r) {
     std::cerr << "Error: " << path << ": the list names no " << (!any_t ? "target" : "reference") << " sample." << std::endl;
     return false;
@@ -1701,6 +1717,14 @@ extern "C" int colate_mut_main(int argc, char** argv) {
       return 1;
     }
   }
+  if (mode == "count_topo") {
+    try {
+      return run_count_topo(opt);
+    } catch (const std::exception& e) {
+      std::cerr << "Error: " << e.what() << std::endl;
+      return 1;
+    }
+  }
   if (mode == "make_tmp") {
     try {
       return run_make_tmp(opt);
@@ -1718,8 +1742,8 @@ extern "C" int colate_mut_main(int argc, char** argv) {
     }
   }
   std::cout << "####### error #######" << std::endl;
-  std::cout << "colate_amd implements --mode mut, --mode mut_interval, --mode compare_tmp, --mode make_tmp --target_table and --mode CondCoalRates (preprocess_mut, "
-               "make_tmp from BCF/BAM, calc_depth, print_tmp stay with the reference build)."
+  std::cout << "colate_amd implements --mode mut, --mode mut_interval, --mode compare_tmp, --mode count_topo, --mode make_tmp --target_table and --mode "
+               "CondCoalRates (preprocess_mut, make_tmp from BCF/BAM, calc_depth, print_tmp stay with the reference build)."
             << std::endl;
   return 1;
 }

@@ -125,6 +125,7 @@ struct PairSpec {
   double target_age = 0, ref_age = 0;
   std::vector<std::string> target_masks, ref_masks;  // one fasta per chromosome, or none
   std::string coal;                                   // --pairs `coal=FILE`: the pair's epochs and starting rates ("": --bins)
+  std::string cond;                                   // `--mode count_topo`: the conditioning sample's file ("": every other mode)
   size_t line = 0;                                    // --pairs: the line of the list (1-based), and how many ages it carried
   int ages_given = 0;
 };
@@ -207,18 +208,35 @@ struct WalkInputs {
   std::vector<const colate_walk_idx*> idx_ptrs;            // [S][C]
   std::vector<const unsigned long long*> mask_ptrs;        // [M][C]
   std::vector<colate_walk_pair> pairs;
+  std::vector<const colate_walk_idx*> cidx_ptrs;           // [S][C]: the cond indices, with RowSet::count_topo only
+  std::vector<int> cond_ids;                               // [P]: the sample id of every pair's `cond` file
   int S = 0, M = 0;
-  std::vector<CompareChromosome> compare;  // [C], with compare = true only
+  std::vector<CompareChromosome> compare;  // [C], with RowSet::compare_tmp only
   bool files_ok = false;                   // every .colate.in file could be opened
   WalkInputs();
   ~WalkInputs();
 };
+enum class RowSet { mut, compare_tmp, count_topo };  // whose row filter the loader applies
 bool load_walk_inputs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const std::vector<PairSpec>& pairs,
-                      WalkInputs& out, bool compare = false);
-// compare = true (`--mode compare_tmp`): the rows kept are those of that mode's filter (compact rows without age_end >= 0), `compare`
-// is filled, and `indexed` also says that no chromosome's raw rows descend.
+                      WalkInputs& out, RowSet set = RowSet::mut);
+// RowSet::compare_tmp: the rows kept are those of that mode's filter (compact rows without age_end >= 0), `compare` is filled, and
+// `indexed` also says that no chromosome's raw rows descend.
+// RowSet::count_topo: the rows of that mode's filter (age_begin <= age_end, no age_end >= 0); every pair's `cond` file is loaded
+// with the other two, every file gets a cond index next to its walk index, and cidx_ptrs / cond_ids are filled.
+// mut_pairs.cpp: the cursor walk of `--mode count_topo` (count_topo.h: cursor_walk_chromosome) for every triple of a list over
+// inputs loaded with RowSet::count_topo, each triple drawing from its own std::mt19937 on `seed`: the lines a triple prints, in
+// order, and its qualifying rows.  Right for every input; false without loaded inputs.
+struct TopoLine {
+  int chr, pos;
+  float age_begin, age_end;
+  int sign, DAF, N;  // the conditioning record's counts
+};
+bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, unsigned seed,
+                         std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws);
+// topo_driver.cpp: `Colate --mode count_topo`
+int run_count_topo(const Options& opt);
 // mut_pairs.cpp: the cursor walk of `--mode compare_tmp` (compare_tmp.h: cursor_walk_chromosome) for every pair of a list over inputs
-// loaded with compare = true: mismatch / snps [P][sum of compare[c].windows].  Right for every input; false without loaded inputs.
+// loaded with RowSet::compare_tmp: mismatch / snps [P][sum of compare[c].windows].  Right for every input; false without loaded inputs.
 bool compare_cursor_pairs(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& pairs,
                           std::vector<int>& mismatch, std::vector<int>& snps);
 // compare_driver.cpp: `Colate --mode compare_tmp`
@@ -243,11 +261,14 @@ struct SampleLine {
   std::string name, file;
   std::vector<std::string> masks;
   bool target = true, reference = true;
+  bool cond = false;  // with_cond only (default there: all three roles)
   double age = 0;
   size_t line = 0;
 };
+// with_cond (`--mode count_topo` only): role= takes a comma-separated subset of cond,target,reference (default: all three), and a
+// list without a cond sample is an error; every other mode refuses role=cond as an unknown role.
 bool read_sample_list(const std::string& path, const Options& opt, const std::vector<std::string>& chr_names, bool with_ages,
-                      std::vector<SampleLine>& samples);
+                      std::vector<SampleLine>& samples, bool with_cond = false);
 // mut_driver.cpp: `Colate --mode mut --samples LIST`
 int run_mut_samples(const Options& opt);
 

@@ -49,6 +49,7 @@
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "compare_tmp.h"
+#include "count_topo.h"
 #include "fill_device.h"
 #include "interval_cells.h"
 #include "mut_feeder.h"
@@ -187,9 +188,11 @@ struct CompactRow {
   char anc, der;
 };
 
-// (need_age_end: false for `--mode compare_tmp`, whose loop has no such condition, coal.cpp:4412)
-bool compact_row(const MutRow& m, CompactRow& c, bool need_age_end = true) {
-  if (!(m.flipped == 0 && m.num_branches == 1 && m.age_begin < m.age_end && (!need_age_end || m.age_end >= 0.0))) return false;
+// (`--mode compare_tmp` has no age_end >= 0 in its loop, coal.cpp:4412; `--mode count_topo` neither, and age_begin <= age_end,
+// coal.cpp:4662)
+bool compact_row(const MutRow& m, CompactRow& c, RowSet set = RowSet::mut) {
+  const bool ages = set == RowSet::count_topo ? m.age_begin <= m.age_end : m.age_begin < m.age_end;
+  if (!(m.flipped == 0 && m.num_branches == 1 && ages && (set != RowSet::mut || m.age_end >= 0.0))) return false;
   const std::string& mt = m.mutation_type;  // "anc/der" (mutations.cpp:236-246 splits at the first '/')
   const size_t slash = mt.find('/');
   if (slash != 1 || mt.size() != 3) return false;  // both sides exactly one character (empty sides: `continue`; longer: use = false)
@@ -231,6 +234,10 @@ struct TmpFile {
     uint16_t DAF, AAF;  // the lower bound's counts where position and alleles match (coal.cpp:2181-2219), else 0, 0
   };
   std::vector<HugeVector<RowIdx>> idx;  // [chromosome][row]
+  // `--mode count_topo`, the file as the conditioning sample (count_topo.h): per row the counts of the record a cursor stands on
+  // there, whether or not position and alleles are the row's -- the lower bound; behind the chromosome's last record the record
+  // that follows the chromosome's run, or the file's last record (prev_bp: 0, never read)
+  std::vector<HugeVector<RowIdx>> cidx;
   bool indexed = false;                 // the index was built
   TmpFile() = default;
   TmpFile(const TmpFile&) = delete;
@@ -406,6 +413,7 @@ struct WalkRows {
   const std::vector<std::string>* names;
   const std::vector<HugeVector<CompactRow>>* rows;
   bool rows_ascend = false;
+  bool cond = false;  // build the cond index as well
 };
 
 bool find_runs(const TmpFile& f, const std::vector<std::string>& names, std::vector<std::pair<size_t, size_t>>& runs) {
@@ -447,11 +455,13 @@ bool build_row_index(TmpFile& f, const WalkRows& w, const std::vector<std::pair<
   const size_t C = w.names->size();
   const DecRec* const R = f.recs.data();
   f.idx.assign(C, HugeVector<TmpFile::RowIdx>());
+  f.cidx.assign(w.cond ? C : 0, HugeVector<TmpFile::RowIdx>());
   for (size_t c = 0; c < C; c++) {
     const HugeVector<CompactRow>& rr = (*w.rows)[c];
     const size_t b = runs[c].first, e = runs[c].second;
     HugeVector<TmpFile::RowIdx>& out = f.idx[c];
     out.resize(rr.size());
+    if (w.cond) f.cidx[c].resize(rr.size());
     size_t k = b;
     for (size_t i = 0; i < rr.size(); i++) {
       while (k < e && R[k].bp < rr[i].pos) k++;
@@ -465,6 +475,11 @@ bool build_row_index(TmpFile& f, const WalkRows& w, const std::vector<std::pair<
         x.DAF = (uint16_t)R[k].DAF, x.AAF = (uint16_t)R[k].AAF;
       }
       out[i] = x;
+      if (w.cond) {  // (runs[c] is not empty, so the file has a record)
+        const DecRec& at = k < e ? R[k] : e < f.recs.size() ? R[e] : R[f.recs.size() - 1];
+        if (at.DAF < 0 || at.DAF > 65535 || at.AAF < 0 || at.AAF > 65535) return false;
+        f.cidx[c][i] = TmpFile::RowIdx{0, (uint16_t)at.DAF, (uint16_t)at.AAF};
+      }
     }
   }
   return true;
@@ -474,7 +489,7 @@ bool build_row_index(TmpFile& f, const WalkRows& w, const std::vector<std::pair<
 void build_walk_index(TmpFile& f, const WalkRows& w) {
   std::vector<std::pair<size_t, size_t>> runs;
   f.indexed = w.rows_ascend && find_runs(f, *w.names, runs) && build_row_index(f, w, runs);
-  if (!f.indexed) f.idx.clear();
+  if (!f.indexed) f.idx.clear(), f.cidx.clear();
 }
 
 // ------------------------------------------------------------------ the uniform stream of the seed, generated once
@@ -1272,7 +1287,8 @@ struct Inputs {
 // The .mut files (all chromosomes in parallel), every .colate.in file of the pairs, every distinct mask -- one task per (mask,
 // chromosome) with one FASTA string alive in it (coal.cpp:2169-2174) -- and, unless use_index is false, every file's walk index.
 Inputs load_inputs(Pool& pool, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
-                   const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, bool use_index, bool compare = false) {
+                   const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, bool use_index, RowSet set = RowSet::mut) {
+  const bool compare = set == RowSet::compare_tmp;
   Inputs in;
   in.rows.resize(mut_files.size());
   if (compare) in.compare.resize(mut_files.size());
@@ -1295,7 +1311,7 @@ Inputs load_inputs(Pool& pool, const std::vector<std::string>& names, const std:
           cc->last_pos = m.pos, cc->raw_rows++;
         }
         n++;
-        if (compact_row(m, cr, !compare)) {
+        if (compact_row(m, cr, set)) {
           r.push_back(cr);
           if (cc) cc->row_window.push_back(lines);
         }
@@ -1305,8 +1321,8 @@ Inputs load_inputs(Pool& pool, const std::vector<std::string>& names, const std:
       WorkSeconds::add(g_work.parse_mut, now_s() - t0);
     });
   for (size_t p : todo)
-    for (const std::string* path : {&pairs[p].target, &pairs[p].reference})
-      if (!in.tmp_files.count(*path)) {
+    for (const std::string* path : {&pairs[p].cond, &pairs[p].target, &pairs[p].reference})
+      if (!path->empty() && !in.tmp_files.count(*path)) {
         TmpFile* f = new TmpFile;
         f->path = *path;
         in.tmp_files[*path].reset(f);
@@ -1365,7 +1381,7 @@ Inputs load_inputs(Pool& pool, const std::vector<std::string>& names, const std:
       }
     }
   if (use_index) {
-    WalkRows wr{&names, &in.rows, true};
+    WalkRows wr{&names, &in.rows, true, set == RowSet::count_topo};
     for (const HugeVector<CompactRow>& r : in.rows)
       for (size_t i = 1; i < r.size() && wr.rows_ascend; i++) wr.rows_ascend = r[i].pos >= r[i - 1].pos && r[i - 1].pos >= 0;
     for (auto& kv : in.tmp_files) {
@@ -1523,11 +1539,11 @@ void walk_pairs_for_records(Pool& pool, const Inputs& in, const std::vector<std:
 }
 
 Inputs load_all(Pool& pool, const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const std::vector<PairSpec>& pairs,
-                bool compare = false) {
+                RowSet set = RowSet::mut) {
   std::vector<size_t> todo(pairs.size());
   for (size_t p = 0; p < todo.size(); p++) todo[p] = p;
   const char* e_idx = std::getenv("COLATE_INDEXED_WALK");
-  return load_inputs(pool, names, mut_files, pairs, todo, !(e_idx && std::atoi(e_idx) == 0), compare);
+  return load_inputs(pool, names, mut_files, pairs, todo, !(e_idx && std::atoi(e_idx) == 0), set);
 }
 
 }  // namespace
@@ -1560,11 +1576,11 @@ static_assert(sizeof(TmpFile::RowIdx) == sizeof(colate_walk_idx) && offsetof(Tmp
 static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "mask words");
 
 bool load_walk_inputs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const std::vector<PairSpec>& pairs,
-                      WalkInputs& out, bool compare) {
+                      WalkInputs& out, RowSet set) {
   const double t0 = now_s();
   out.loaded.reset(new WalkInputs::Loaded);
   Pool pool(pairs_threads());
-  out.loaded->in = load_all(pool, names, mut_files, pairs, compare);
+  out.loaded->in = load_all(pool, names, mut_files, pairs, set);
   const Inputs& in = out.loaded->in;
   out.compare = in.compare;
   out.files_ok = true;
@@ -1589,6 +1605,8 @@ bool load_walk_inputs(const std::vector<std::string>& names, const std::vector<s
   for (const auto& kv : in.tmp_files) {
     sample_id[kv.first] = (int)sample_id.size();
     for (size_t c = 0; c < C; c++) out.idx_ptrs.push_back(reinterpret_cast<const colate_walk_idx*>(kv.second->idx[c].data()));
+    if (set == RowSet::count_topo)
+      for (size_t c = 0; c < C; c++) out.cidx_ptrs.push_back(reinterpret_cast<const colate_walk_idx*>(kv.second->cidx[c].data()));
   }
   std::map<std::vector<std::string>, int> mask_id;
   for (const auto& kv : in.masks) {
@@ -1601,6 +1619,8 @@ bool load_walk_inputs(const std::vector<std::string>& names, const std::vector<s
     out.pairs.push_back(colate_walk_pair{sample_id.at(ps.target), sample_id.at(ps.reference),
                                          ps.target_masks.empty() ? -1 : mask_id.at(ps.target_masks),
                                          ps.ref_masks.empty() ? -1 : mask_id.at(ps.ref_masks)});
+  for (const PairSpec& ps : pairs)
+    if (!ps.cond.empty()) out.cond_ids.push_back(sample_id.at(ps.cond));
   return true;
 }
 
@@ -1632,6 +1652,32 @@ bool compare_cursor_pairs(const WalkInputs& loaded, const std::vector<std::strin
       for (size_t c = 0; c < names.size(); c++)
         colate_cmp::cursor_walk_chromosome(tgt, ref, names[c].c_str(), c == 0, in.rows[c].data(), in.rows[c].size(), in.compare[c].row_window.data(),
                                            mismatch.data() + p * Wt + win_off[c], snps.data() + p * Wt + win_off[c]);
+    });
+  pool.wait_idle();
+  return true;
+}
+
+// (mut_feeder.h)
+bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, unsigned seed,
+                         std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws) {
+  if (!loaded.loaded || loaded.loaded->in.rows.size() != names.size()) return false;
+  const Inputs& in = loaded.loaded->in;
+  lines.assign(triples.size(), std::vector<TopoLine>()), draws.assign(triples.size(), 0);
+  Pool pool(pairs_threads());
+  for (size_t p = 0; p < triples.size(); p++)
+    pool.submit([&, p] {  // one triple per task: its three cursors go through the chromosomes in the list's order, its generator from the seed
+      Cursor cnd, tgt, ref;
+      cnd.open(*in.tmp_files.at(triples[p].cond)), tgt.open(*in.tmp_files.at(triples[p].target)), ref.open(*in.tmp_files.at(triples[p].reference));
+      std::mt19937 rng(seed);
+      std::uniform_real_distribution<double> dist_unif(0, 1);
+      long long n = 0;
+      for (size_t c = 0; c < names.size(); c++) {
+        const CompactRow* const rows = in.rows[c].data();
+        colate_topo::cursor_walk_chromosome(
+            cnd, tgt, ref, names[c].c_str(), c == 0, rows, in.rows[c].size(), [&] { return n++, dist_unif(rng); },
+            [&](size_t i, int sign, int DAF, int N) { lines[p].push_back(TopoLine{(int)c, rows[i].pos, rows[i].age_begin, rows[i].age_end, sign, DAF, N}); });
+      }
+      draws[p] = n / 2;
     });
   pool.wait_idle();
   return true;

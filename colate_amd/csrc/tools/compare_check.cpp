@@ -2,7 +2,7 @@
 // (compare_tmp.h) against each other:
 //   * small synthetic inputs written here (two chromosomes some 45 Mb long, four .colate.in files; rows at equal positions,
 //     rows with a negative age_end, which only this mode searches, flipped and two-branch rows, which it does not), read,
-//     decoded and indexed by the loader of the command line (load_walk_inputs with compare = true);
+//     decoded and indexed by the loader of the command line (load_walk_inputs with RowSet::compare_tmp);
 //   * the cursor walk (compare_cursor_pairs) against compare_view_host on the loader's view and against
 //     colate_compare_samples_host on back-to-back copies, every int of every pair, both orders of a pair among them;
 //   * mismatch <= snps, and a pair and its swap alike;
@@ -93,7 +93,7 @@ int main(int argc, char** argv) {
   const int P = (int)pairs.size(), C = (int)names.size();
 
   WalkInputs in;
-  if (!load_walk_inputs(names, mut_files, pairs, in, true) || !in.indexed || !in.files_ok || in.S != 4 || (int)in.compare.size() != C) {
+  if (!load_walk_inputs(names, mut_files, pairs, in, RowSet::compare_tmp) || !in.indexed || !in.files_ok || in.S != 4 || (int)in.compare.size() != C) {
     std::fprintf(stderr, "the inputs were not indexed (%d samples)\n", in.S);
     return 1;
   }

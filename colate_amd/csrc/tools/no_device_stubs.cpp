@@ -109,9 +109,16 @@ int fill_view_device(const colate_iw::View&, int, unsigned, Result&) { return no
 namespace colate_cmp {
 int compare_view_device(const View&, long long, long long*, int*, int*) { return nodev(); }
 }  // namespace colate_cmp
+// the triple stage of `--mode count_topo` on the device (count_topo.h; colate_topo_samples ends here): none in this build
+#include "count_topo.h"
+namespace colate_topo {
+int topo_view_device(const View&, long long, long long*, unsigned long long*, unsigned long long*, long long*) { return nodev(); }
+}  // namespace colate_topo
 extern "C" {
 int colate_compare_samples_chunks(void) { return 0; }
 double colate_compare_samples_kernel_seconds(void) { return 0.0; }
+int colate_topo_samples_chunks(void) { return 0; }
+double colate_topo_samples_kernel_seconds(void) { return 0.0; }
 }
 
 // the age sampling on the device (fill_device.h): there is none in this build, the host code samples

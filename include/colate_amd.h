@@ -509,6 +509,45 @@ int colate_compare_samples_host(int C, const long long* row_off, const colate_wa
 int colate_compare_samples_chunks(void);
 double colate_compare_samples_kernel_seconds(void);
 
+/* ---- `Colate --mode count_topo` for many (cond, target, reference) triples over the same walk indices (csrc/count_topo.h:
+ * the contract; include/coal/coal.cpp:4523-4781) ----
+ * The rows are those of colate_interval_walk, every row a searched row of this mode (flipped == 0, one branch, age_begin <=
+ * age_end, single-base alleles), positions not descending.  idx[S][rows]: the samples' walk indices; cond_idx[S][rows]: their
+ * cond indices -- the counts of the record the sample's cursor stands on at that row, whether or not its position and alleles
+ * are the row's (prev_bp is not read).  Sample s HITS row i iff (idx.DAF | idx.AAF) != 0 and QUALIFIES it iff cond_idx.DAF > 0.
+ * A row qualifies for a triple iff the target hits, the reference hits and the cond sample qualifies; the triple's qualifying
+ * row number k, counted over the chromosomes in order, reads uniforms[2 k] and uniforms[2 k + 1]: with d = (float)u promoted
+ * back to double, pT = (double)DAF_T / (DAF_T + AAF_T) and pR likewise, the row's bit is set in `plus` iff d1 <= pT && d2 > pR
+ * and in `minus` iff d1 > pT && d2 <= pR.  Every triple starts at uniforms[0]: the command line hands over the stream of the
+ * run's std::mt19937 through uniform_real_distribution<double>(0, 1).
+ * Out: word_off[C + 1] (chromosome c owns the words [word_off[c], word_off[c + 1]) of a plane, ceil(rows / 64) of them; bit
+ * i & 63 of word i >> 6 is its row i), plus / minus as [P][word_off[C]] words with room for `cap` words each (COLATE_ELIMIT
+ * with the needed number above it), draws[P]: the triple's qualifying rows.  A stream shorter than 2 x the largest draws[p]
+ * is COLATE_ELIMIT with the needed length in colate_last_error().  Nothing is written after a refusal.
+ * _host: the host twin.  colate_topo_samples: the same on the calling thread's device (COLATE_ENODEVICE without one), on one
+ * stream: a plane kernel (one lane per array and row, ballots); a count kernel, one workgroup per (triple, chromosome); one
+ * host wait for the counts, from which the host forms every triple's base rank per chromosome and uploads the longest stream
+ * any triple needs once for all; then per chunk of triples -- the two output planes of a chunk within 256 MB
+ * (COLATE_TOPO_BUDGET: bytes) -- the draw kernel, one workgroup per (triple, chromosome): a wave scans the popcounts of a tile
+ * of 64 words (colate_topo_samples_tile() rows) for each word's base rank, then word by word, lane = row, reads the two
+ * uniforms of its rank and the two index entries, compares and ballots.  No atomics, no compaction, no floating-point
+ * reduction: both forms give the same bits whatever the chunking.
+ * colate_topo_samples_chunks / _kernel_seconds: diagnostics of the calling thread's last device call. */
+typedef struct colate_topo_triple {
+  int cond, target, reference; /* sample ids */
+} colate_topo_triple;
+int colate_topo_samples(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                        const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms,
+                        const double* uniforms, long long cap, long long* word_off, unsigned long long* plus,
+                        unsigned long long* minus, long long* draws);
+int colate_topo_samples_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                             const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms,
+                             const double* uniforms, long long cap, long long* word_off, unsigned long long* plus,
+                             unsigned long long* minus, long long* draws);
+int colate_topo_samples_tile(void); /* rows of a tile of the draw kernel (no device needed) */
+int colate_topo_samples_chunks(void);
+double colate_topo_samples_kernel_seconds(void);
+
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
 int colate_age_grid(double* age_grid, int cap);
