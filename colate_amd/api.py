@@ -56,6 +56,30 @@ def em_force_variant(name=None):
     check(lib.colate_em_force_variant(-1 if name is None else EM_VARIANTS.index(name)))
 
 
+def em_kernel_build(B, E):
+    """The instantiation of the EM kernel a fit of B replicates x E epochs runs on the current device, under the current
+    forcing: `unit-kind/NCHxEROWS`, e.g. "ilp-capped/1x4" (include/colate_amd.h, colate_em_kernel_build)."""
+    name = ctypes.create_string_buffer(64)
+    check(lib.colate_em_kernel_build(int(B), int(E), name, 64))
+    return name.value.decode()
+
+
+def em_kernel_build_for(B, E, cus, forced=None, mode=0):
+    """The same from given numbers, without a device: `cus` compute units (0 = unknown), `forced` one of EM_VARIANTS or
+    None, mode 0 = EM fit, 1 = one E-step."""
+    name = ctypes.create_string_buffer(64)
+    check(lib.colate_em_kernel_build_for(int(mode), int(B), int(E), int(cus), -1 if forced is None else EM_VARIANTS.index(forced),
+                                         name, 64))
+    return name.value.decode()
+
+
+def em_kernel_builds(mode=0):
+    """Every name the dispatch can return for `mode`, in the table's order."""
+    buf = ctypes.create_string_buffer(2048)
+    check(lib.colate_em_kernel_builds(int(mode), buf, 2048))
+    return buf.value.decode().split("\n")
+
+
 def age_grid():
     """coal.cpp:3126-3137."""
     g = np.zeros(256)

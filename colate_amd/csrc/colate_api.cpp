@@ -18,6 +18,7 @@
 
 #include "colate_amd.h"
 #include "colate_internal.h"
+#include "em_build.hpp"
 #include "em_job.hpp"
 #include "em_kernels.h"
 #include "interval_cells.h"
@@ -439,6 +440,20 @@ int colate_em_force_variant(int variant) {
   colate_em_set_forced_variant(variant);
   return COLATE_OK;
 }
+
+static int build_name_result(int rc) { return rc >= 0 ? rc : fail(COLATE_EINVAL, "%s", kEmBuildErrors[-rc]); }
+
+int colate_em_kernel_build(int B, int E, char* name, int cap) {
+  if (B < 0 || E < 1 || E > COLATE_EM_MAX_E) return fail(COLATE_EINVAL, "bad sizes B=%d E=%d", B, E);
+  if (int rc = ensure_device()) return rc;
+  return build_name_result(em_build_copy_name(colate_em_build(0, B, E), name, cap));
+}
+
+int colate_em_kernel_build_for(int mode, int B, int E, int cus, int forced, char* name, int cap) {
+  return build_name_result(em_build_name_for(mode, B, E, cus, forced, name, cap));
+}
+
+int colate_em_kernel_builds(int mode, char* buf, int cap) { return build_name_result(em_build_names(mode, buf, cap)); }
 
 int colate_em_batch_device(int B, int E, int A, const double* age_grid, const double* cnt_shared,
                            const double* cnt_notshared, const double* epochs, int epochs_per_replicate,

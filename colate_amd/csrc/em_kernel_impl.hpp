@@ -53,6 +53,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "em_build.hpp"
 #include "em_kernels.h"
 #include "em_math.hpp"
 
@@ -2143,8 +2144,7 @@ hipError_t launch_one(const ColateEmArgs& args, hipStream_t stream, size_t lds, 
 
 inline int em_groups(int A) { return (A + 63) / 64; }           // bin groups of 64 per role
 inline int em_threads(int A) { return 2 * 64 * em_groups(A); }  // two roles (latency variant)
-inline int em_chunks(int E) { return E <= 64 ? 1 : (E <= 128 ? 2 : (E <= 256 ? 4 : (E <= 512 ? 8 : 16))); }
-inline int em_rows(int E) { return E <= 16 ? 1 : (E <= 32 ? 2 : 4); }  // BASELINE's `--bins 3,7,0.2` gives E = 23
+// (em_chunks, em_rows: em_build.hpp)
 
 inline size_t em_lds_bytes(int E, int A, bool tput) {
   const size_t EPAD = (size_t)em_chunks(E) * kWave;
@@ -2156,21 +2156,20 @@ inline size_t em_lds_bytes(int E, int A, bool tput) {
   return doubles * sizeof(double) + ints * sizeof(int);
 }
 
-// the latency variant (a wave per role and bin group) for 1 or 2 epochs per lane; each translation unit that
-// includes this header gets its own copy, compiled with that unit's flags
-// `alone`: every workgroup has a CU to itself (B <= #CUs): the register cap that keeps three waves per SIMD is not needed
-inline hipError_t launch_latency(const ColateEmArgs& args, hipStream_t stream, bool alone = false) {
+// the latency layout (a wave per role and bin group) for 1 or 2 epochs per lane, by the build em_build_for() chose; each
+// translation unit that includes this header gets its own copy, compiled with that unit's flags
+inline hipError_t launch_latency(const ColateEmArgs& args, hipStream_t stream, const EmBuild& b) {
   const size_t lds = em_lds_bytes(args.E, args.A, false);
   const int threads = em_threads(args.A);
-  if (em_chunks(args.E) == 2) return launch_one<0, 2, 4, false>(args, stream, lds, threads);
+  if (b.nch == 2) return launch_one<0, 2, 4, false>(args, stream, lds, threads);
 #ifdef COLATE_EM_ILP_BUILD
-  if (alone) switch (em_rows(args.E)) {
+  if (b.wpe == 2) switch (b.erows) {  // the free build: no register cap
     case 1: return launch_one<0, 1, 1, false, 2>(args, stream, lds, threads);
     case 2: return launch_one<0, 1, 2, false, 2>(args, stream, lds, threads);
     default: return launch_one<0, 1, 4, false, 2>(args, stream, lds, threads);
   }
 #endif
-  switch (em_rows(args.E)) {
+  switch (b.erows) {
     case 1: return launch_one<0, 1, 1, false>(args, stream, lds, threads);
     case 2: return launch_one<0, 1, 2, false>(args, stream, lds, threads);
     default: return launch_one<0, 1, 4, false>(args, stream, lds, threads);

@@ -44,6 +44,10 @@ hipError_t colate_em_launch(const ColateEmArgs& args, hipStream_t stream);
 int colate_em_variant(int B, int E);
 // force the build for E <= 128 (0, 1, 2 as above; anything else = automatic again)
 void colate_em_set_forced_variant(int v);
+// the instantiation behind that choice (em_build.hpp: one table, one function; colate_em_launch switches on the same
+// result): for `mode` (0 = EM, 1 = one E-step) on the current device under the current forcing; NULL for sizes outside the table
+struct EmBuild;
+const EmBuild* colate_em_build(int mode, int B, int E);
 
 // block bootstrap on the device (bootstrap_kernel.hip)
 hipError_t colate_bootstrap_launch(int B, int nb, int A, const double* age_grid, double age,

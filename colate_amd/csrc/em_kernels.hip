@@ -1,4 +1,5 @@
-// colate_amd/csrc/em_kernels.hip -- instantiation and dispatch of the EM kernel (template in em_kernel_impl.hpp).
+// colate_amd/csrc/em_kernels.hip -- instantiation and dispatch of the EM kernel (template in em_kernel_impl.hpp).  Which
+// instantiation a launch takes is decided in one place, em_build_for() (em_build.hpp); in short:
 //
 //   shape                                   instantiation                     build
 //   one E-step (colate_em_estep)            <1, NCH, 4, false>                this unit
@@ -12,8 +13,10 @@
 
 #include "em_kernel_impl.hpp"
 
-hipError_t colate_em_launch_latency_ilp(const ColateEmArgs& args, hipStream_t stream, bool alone);  // em_kernels_ilp.hip
-hipError_t colate_em_launch_big(const ColateEmArgs& args, hipStream_t stream);                          // em_kernels_big.hip: 257 .. 1024 epochs
+hipError_t colate_em_launch_latency_ilp(const ColateEmArgs& args, hipStream_t stream, const EmBuild& b);  // em_kernels_ilp.hip
+hipError_t colate_em_launch_big(const ColateEmArgs& args, hipStream_t stream, const EmBuild& b);          // em_kernels_big.hip: 257 .. 1024 epochs
+
+static_assert(kEmBuildMaxEpochs == COLATE_EM_MAX_E, "em_build.hpp and em_kernels.h disagree on the epoch limit");
 
 size_t colate_em_lds_bytes(int E, int A) { return em_lds_bytes(E, A, false); }  // (the larger of the two variants' needs)
 
@@ -47,41 +50,33 @@ static std::atomic<int>& variant_forced() {
 void colate_em_set_forced_variant(int v) { variant_forced().store((v >= 0 && v <= 2) ? v : -1, std::memory_order_relaxed); }
 static int variant_override() { return variant_forced().load(std::memory_order_relaxed); }
 
-// 0 = latency (max-ilp build), 1 = latency (default build), 2 = throughput.
+// the build this launch shape takes on the current device under the current forcing (em_build.hpp)
+const EmBuild* colate_em_build(int mode, int B, int E) { return em_build_for(mode, B, E, device_cus(), variant_override()); }
+
+// 0 = latency (max-ilp unit), 1 = latency (default unit), 2 = throughput.
 int colate_em_variant(int B, int E) {
-  if (em_chunks(E) > 2) return 2;  // 129..256 epochs: only the two-wave layout fits the register file without scratch
-  if (variant_override() >= 0) return variant_override();
-  // Measured (tools/variant_sweep.sh, profiles/r02/variants.txt): since the steady-state loops the max-ilp build fits
-  // 3 waves per SIMD as well (157 VGPRs) and is the faster latency build at every batch size (1.29 against 1.33 ms at
-  // B = 400); two 6-wave workgroups per CU beat the two-wave layout up to 2 x #CUs (B = 512: 1.30 against 2.09 ms),
-  // beyond that the throughput variant wins (B = 640: 2.09 against 2.12 ms; B = 1536: 2.70 against 3.65 ms).  The
-  // default-scheduler latency build stays selectable (COLATE_EM_VARIANT=latency) for A/B runs.
-  const int cus = device_cus();
-  if (cus <= 0 || B <= 2 * cus) return 0;
-  return 2;
+  const EmBuild* b = colate_em_build(0, B, E);
+  return b ? em_build_variant(*b) : 2;
 }
 
+// launches what em_build_for() names: the unit first, then the instantiation inside it
 hipError_t colate_em_launch(const ColateEmArgs& args, hipStream_t stream) {
-  const int nch = em_chunks(args.E);
-  if (nch > 4) return colate_em_launch_big(args, stream);
-  if (args.mode == 1) {
+  const EmBuild* b = colate_em_build(args.mode, args.B, args.E);
+  if (!b) return hipErrorInvalidValue;
+  if (b->unit == kEmUnitBig) return colate_em_launch_big(args, stream, *b);
+  if (b->unit == kEmUnitIlp) return colate_em_launch_latency_ilp(args, stream, *b);
+  if (b->mode == 1) {
     const int threads = em_threads(args.A);
     const size_t lds = em_lds_bytes(args.E, args.A, false);
-    if (nch == 1) return launch_one<1, 1, 4, false>(args, stream, lds, threads);
-    if (nch == 2) return launch_one<1, 2, 4, false>(args, stream, lds, threads);
+    if (b->nch == 1) return launch_one<1, 1, 4, false>(args, stream, lds, threads);
+    if (b->nch == 2) return launch_one<1, 2, 4, false>(args, stream, lds, threads);
     return launch_one<1, 4, 4, false>(args, stream, lds, threads);
   }
-  switch (colate_em_variant(args.B, args.E)) {
-    case 0: {
-      const int cus = device_cus();
-      return colate_em_launch_latency_ilp(args, stream, cus > 0 && args.B <= cus);
-    }
-    case 1: return launch_latency(args, stream);
-  }
+  if (!b->tput) return launch_latency(args, stream, *b);
   const size_t lds = em_lds_bytes(args.E, args.A, true);
-  if (nch == 4) return launch_one<0, 4, 4, true>(args, stream, lds, 2 * kWave);
-  if (nch == 2) return launch_one<0, 2, 4, true>(args, stream, lds, 2 * kWave);
-  switch (em_rows(args.E)) {
+  if (b->nch == 4) return launch_one<0, 4, 4, true>(args, stream, lds, 2 * kWave);
+  if (b->nch == 2) return launch_one<0, 2, 4, true>(args, stream, lds, 2 * kWave);
+  switch (b->erows) {
     case 1: return launch_one<0, 1, 1, true>(args, stream, lds, 2 * kWave);
     case 2: return launch_one<0, 1, 2, true>(args, stream, lds, 2 * kWave);
     default: return launch_one<0, 1, 4, true>(args, stream, lds, 2 * kWave);

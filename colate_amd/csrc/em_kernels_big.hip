@@ -5,15 +5,14 @@
 // of them in scratch memory) and only the general loop is compiled: speed is secondary here.
 #include "em_kernel_impl.hpp"
 
-hipError_t colate_em_launch_big(const ColateEmArgs& args, hipStream_t stream) {
-  const int nch = em_chunks(args.E);
-  if (args.mode == 1) {
+hipError_t colate_em_launch_big(const ColateEmArgs& args, hipStream_t stream, const EmBuild& b) {
+  if (b.mode == 1) {
     const int threads = em_threads(args.A);
     const size_t lds = em_lds_bytes(args.E, args.A, false);
-    if (nch == 8) return launch_one<1, 8, 4, false>(args, stream, lds, threads);
+    if (b.nch == 8) return launch_one<1, 8, 4, false>(args, stream, lds, threads);
     return launch_one<1, 16, 4, false>(args, stream, lds, threads);
   }
   const size_t lds = em_lds_bytes(args.E, args.A, true);
-  if (nch == 8) return launch_one<0, 8, 4, true>(args, stream, lds, 2 * kWave);
+  if (b.nch == 8) return launch_one<0, 8, 4, true>(args, stream, lds, 2 * kWave);
   return launch_one<0, 16, 4, true>(args, stream, lds, 2 * kWave);
 }

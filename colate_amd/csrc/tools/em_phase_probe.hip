@@ -15,8 +15,8 @@
 // the build the product runs there -- no register cap, two barriers per iteration -- and not the three-barrier code)
 #define COLATE_EM_ILP_BUILD 1
 #include "../em_kernels.hip"
-hipError_t colate_em_launch_latency_ilp(const ColateEmArgs& args, hipStream_t stream, bool alone) { return launch_latency(args, stream, alone); }
-hipError_t colate_em_launch_big(const ColateEmArgs&, hipStream_t) { return hipErrorNotSupported; }  // (257+ epochs: not probed)
+hipError_t colate_em_launch_latency_ilp(const ColateEmArgs& args, hipStream_t stream, const EmBuild& b) { return launch_latency(args, stream, b); }
+hipError_t colate_em_launch_big(const ColateEmArgs&, hipStream_t, const EmBuild&) { return hipErrorNotSupported; }  // (257+ epochs: not probed)
 
 #include <cmath>
 #include <cstdio>

@@ -9,6 +9,7 @@
 
 #include "colate_amd.h"
 #include "colate_internal.h"
+#include "em_build.hpp"
 
 namespace colate {
 static thread_local std::string g_err;
@@ -36,6 +37,13 @@ int colate_device_count(void) { return nodev(); }
 int colate_set_device(int) { return nodev(); }
 int colate_warm_up(int) { return nodev(); }
 int colate_em_force_variant(int) { return nodev(); }
+int colate_em_kernel_build(int, int, char*, int) { return nodev(); }
+// (the dispatch table needs no device: em_build.hpp's own answers, as in the library)
+static int build_name_result(int rc) { return rc >= 0 ? rc : colate::fail(COLATE_EINVAL, "%s", kEmBuildErrors[-rc]); }
+int colate_em_kernel_build_for(int mode, int B, int E, int cus, int forced, char* name, int cap) {
+  return build_name_result(em_build_name_for(mode, B, E, cus, forced, name, cap));
+}
+int colate_em_kernel_builds(int mode, char* buf, int cap) { return build_name_result(em_build_names(mode, buf, cap)); }
 int colate_em_batch(int, int, int, const double*, const double*, const double*, const double*, const double*, int, int,
                     double, double, double*, int*, double*, int*) { return nodev(); }
 int colate_em_batch_rows(int, int, int, const double*, const double*, const double*, const double*, const double*, int, int,

@@ -6,7 +6,7 @@
 #define COLATE_EM_TRACE 1
 #include "../em_kernels.hip"
 #include "../em_kernels_ilp.hip"  // (same template again: the probe builds one translation unit)
-hipError_t colate_em_launch_big(const ColateEmArgs&, hipStream_t) { return hipErrorNotSupported; }  // (257+ epochs: not probed)
+hipError_t colate_em_launch_big(const ColateEmArgs&, hipStream_t, const EmBuild&) { return hipErrorNotSupported; }  // (257+ epochs: not probed)
 
 #include <algorithm>
 #include <cmath>

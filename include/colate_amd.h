@@ -96,6 +96,18 @@ int colate_em_kernel_variant(int B, int E);
 /* Diagnostic: force that choice for E <= 128 (0, 1 or 2; any other value = automatic again).  Process-wide.  The
  * environment variable COLATE_EM_VARIANT=latency-ilp|latency|throughput sets the initial value (read once). */
 int colate_em_force_variant(int variant);
+/* Diagnostic: the name of the instantiation behind that choice, `unit-kind/NCHxEROWS`: unit ilp |
+ * default | big = the translation unit and its scheduler; kind free | capped | tput | estep; NCH epochs per lane;
+ * EROWS 16-lane rows of epochs.  E.g. `ilp-capped/1x4`: what a batch of #CUs < B <= 2 #CUs replicates at 33 .. 64 epochs runs.
+ * The launch switches on the same table entry that is named here.  Each call writes a NUL-terminated string into
+ * name[cap] and returns its length, or a negative code.
+ *   colate_em_kernel_build       the EM fit of B replicates x E epochs on the current device, under the current forcing
+ *   colate_em_kernel_build_for   the same from given numbers, no device asked: mode 0 = EM fit, 1 = one E-step; cus = the
+ *                                device's compute units (0 = unknown); forced = -1 or colate_em_force_variant's value
+ *   colate_em_kernel_builds      every name the dispatch can return for `mode`, newline-separated */
+int colate_em_kernel_build(int B, int E, char* name, int cap);
+int colate_em_kernel_build_for(int mode, int B, int E, int cus, int forced, char* name, int cap);
+int colate_em_kernel_builds(int mode, char* buf, int cap);
 
 /* ---- the EM hot path ------------------------------------------------------
  * Replaces coal.cpp:3675-3827 (bootstrap EM driver: coal_EM construction,

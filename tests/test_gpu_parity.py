@@ -240,6 +240,13 @@ def test_more_than_256_epochs(ca, bins, E_expect):
     r1, it1, ll1, fl1 = ca.em_batch(grid, csh, cns, ep)
     assert (it0 == it1).all() and ((fl0 & 3) == 0).all() and (ca.status_flags(fl1) == 0).all()
     assert np.allclose(ll1, ll0, rtol=1e-12, atol=0)
+    # the same two replicates tiled to the first batch beyond twice the CU count (asked from the library, as in
+    # tests/em_builds_lib.py): the same instantiation with several workgroups on a CU, every row byte for byte the small batch's
+    B = next(b for b in range(1, 4096) if ca.em_kernel_variant(b, 64) == "throughput")
+    assert ca.em_kernel_build(2, ep.size) == ca.em_kernel_build(B, ep.size) == ("big-tput/8x4" if ep.size <= 512 else "big-tput/16x4")
+    idx = np.arange(B) % 2
+    for a, b in zip((r1, it1, ll1, fl1), ca.em_batch(grid, csh[idx], cns[idx], ep)):
+        assert b.shape[0] == B and np.ascontiguousarray(a[idx]).tobytes() == b.tobytes()
     noise, scaled = ol.rerun_rates(grid, csh, cns, ep)
     mask = ol.mask_from_reruns(r0, noise + scaled)
     assert mask.mean() > 0.8, mask.mean()
