@@ -110,6 +110,12 @@ SIGNATURES = {
     "colate_topo_samples_tile": (c_int, []),
     "colate_topo_samples_chunks": (c_int, []),
     "colate_topo_samples_kernel_seconds": (c_double, []),
+    "colate_topo_profile": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
+                                    c_int] + [c_void_p] * 3),
+    "colate_topo_profile_host": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p,
+                                         c_int] + [c_void_p] * 3),
+    "colate_topo_profile_chunks": (c_int, []),
+    "colate_topo_profile_kernel_seconds": (c_double, []),
     "colate_age_grid": (c_int, [c_void_p, c_int]),
     "colate_epochs_from_bins": (c_int, [c_char_p, c_double, c_double, c_void_p, c_int, ip]),
     "colate_epochs_from_coal": (c_int, [c_char_p, c_double, c_void_p, c_void_p, c_int]),

@@ -720,6 +720,36 @@ def topo_samples_kernel_seconds():
     return lib.colate_topo_samples_kernel_seconds()
 
 
+def topo_profile(row_off, rows, idx, cond_idx, triples, uniforms, epochs, device=True):
+    """colate_topo_profile[_host]: the draws of topo_samples counted per epoch, without a plane leaving the call.  Inputs as for
+    topo_samples; epochs [E]: finite, strictly ascending, 1 <= E <= 1024.  A row's epoch is the number of e in 1 .. E - 1 with
+    epochs[e] <= 0.5f * (age_begin + age_end), the mid formed in float32.  Returns (counts [P, E, 3] int64 -- plus, minus,
+    qualifying --, draws [P] int64).  device=False: the host twin, the same integers."""
+    args, keep = _walk_inputs(row_off, rows, idx, None, np.zeros(0, dtype=WALK_PAIR))
+    cond_idx = np.ascontiguousarray(cond_idx, dtype=WALK_IDX)
+    if cond_idx.shape != keep[2].shape:
+        raise ValueError("cond_idx must be [S][rows], as idx")
+    triples = np.ascontiguousarray(triples, dtype=TOPO_TRIPLE).ravel()
+    uniforms = _f64(uniforms).ravel()
+    epochs = _f64(epochs).ravel()
+    P, E = triples.size, epochs.size
+    counts, draws = np.zeros((P, E, 3), dtype=np.int64), np.zeros(P, dtype=np.int64)
+    fn = lib.colate_topo_profile if device else lib.colate_topo_profile_host
+    check(fn(args[0], args[1], args[2], args[3], args[4], _p(cond_idx), P, _p(triples), uniforms.size, _p(uniforms), E, _p(epochs),
+             _p(counts), _p(draws)))
+    return counts, draws
+
+
+def topo_profile_chunks():
+    """Chunks of triples in this thread's last topo_profile(device=True) (diagnostic)."""
+    return lib.colate_topo_profile_chunks()
+
+
+def topo_profile_kernel_seconds():
+    """Seconds the kernels of this thread's last topo_profile(device=True) took on the device."""
+    return lib.colate_topo_profile_kernel_seconds()
+
+
 def fill_samples_chunks():
     """Chunks of the write pass in this thread's last fill_samples(device=True) (diagnostic)."""
     return lib.colate_fill_samples_chunks()

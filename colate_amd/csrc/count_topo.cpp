@@ -1,7 +1,9 @@
 // colate_amd/csrc/count_topo.cpp -- the host side of colate_topo_samples (count_topo.h: the contract): the checks both forms run
 // before anything is written, the host twin of the three device kernels -- bit planes per sample, a popcount per triple, the
-// ranked draws --, and the C entry points, which view the caller's back-to-back arrays chromosome by chromosome.
+// ranked draws --, the same draws binned by age for colate_topo_profile, and the C entry points, which view the caller's
+// back-to-back arrays chromosome by chromosome.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -128,6 +130,58 @@ int topo_view_host(const View& v, long long cap, long long* word_off, unsigned l
   return COLATE_OK;
 }
 
+int check_epochs(int E, const double* epochs) {
+  if (E < 1 || E > kMaxProfileEpochs) return fail(COLATE_EINVAL, "E = %d epochs: 1 to %d are possible", E, kMaxProfileEpochs);
+  if (!epochs) return fail(COLATE_EINVAL, "NULL pointer argument");
+  for (int e = 0; e < E; e++) {
+    if (!std::isfinite(epochs[e])) return fail(COLATE_EINVAL, "epochs[%d] is not finite", e);
+    if (e > 0 && !(epochs[e] > epochs[e - 1]))
+      return fail(COLATE_EINVAL, "epochs[%d] = %g does not lie above epochs[%d] = %g (the epochs ascend strictly)", e, epochs[e], e - 1, epochs[e - 1]);
+  }
+  return COLATE_OK;
+}
+
+int topo_profile_host(const View& v, int E, const double* epochs, long long* counts, long long* draws) {
+  if (!counts || !draws) return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (int rc = check_epochs(E, epochs)) return rc;
+  if (int rc = check_view(v)) return rc;
+  std::vector<long long> woff((size_t)v.C + 1);
+  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
+  std::vector<unsigned long long> planes((size_t)v.S * 2 * (size_t)words);
+  for (int s = 0; s < v.S; s++) host_planes(v, s, woff.data(), words, planes.data() + (size_t)s * 2 * (size_t)words);
+  auto plane = [&](int s, int which) { return planes.data() + ((size_t)s * 2 + (size_t)which) * (size_t)words; };
+  std::vector<long long> n((size_t)v.P, 0);
+  for (int p = 0; p < v.P; p++) {
+    const unsigned long long *T = plane(v.triples[p].target, 0), *R = plane(v.triples[p].reference, 0), *Cq = plane(v.triples[p].cond, 1);
+    for (long long k = 0; k < words; k++) n[(size_t)p] += __builtin_popcountll(T[k] & R[k] & Cq[k]);
+  }
+  if (int rc = check_stream(v, n.data())) return rc;
+  // the draw pass: a running popcount is the rank, age_epoch the bin of every set bit of Q
+  std::memset(counts, 0, sizeof(long long) * (size_t)v.P * (size_t)E * 3);
+  for (int p = 0; p < v.P; p++) {
+    const Triple& t = v.triples[p];
+    const unsigned long long *T = plane(t.target, 0), *R = plane(t.reference, 0), *Cq = plane(t.cond, 1);
+    long long* const mine = counts + (size_t)p * (size_t)E * 3;
+    long long rank = 0;
+    for (int c = 0; c < v.C; c++) {
+      const Idx* const TI = v.idx[(size_t)t.target * v.C + c];
+      const Idx* const RI = v.idx[(size_t)t.reference * v.C + c];
+      const Row* const rows = v.rows[c];
+      for (long long k = woff[(size_t)c]; k < woff[(size_t)c + 1]; k++)
+        for (unsigned long long q = T[k] & R[k] & Cq[k]; q; q &= q - 1, rank++) {
+          const long long i = (k - woff[(size_t)c]) * 64 + __builtin_ctzll(q);
+          const int sign = draw_sign(TI[i], RI[i], v.uniforms[2 * rank], v.uniforms[2 * rank + 1]);
+          long long* const at = mine + (size_t)age_epoch(rows[i].age_begin, rows[i].age_end, epochs, E) * 3;
+          at[2]++;
+          if (sign > 0) at[0]++;
+          if (sign < 0) at[1]++;
+        }
+    }
+    draws[p] = rank;
+  }
+  return COLATE_OK;
+}
+
 namespace {
 
 // the caller's back-to-back arrays, chromosome by chromosome
@@ -179,6 +233,20 @@ int colate_topo_samples(int C, const long long* row_off, const colate_walk_row* 
                         long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws) {
   const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, n_uniforms, uniforms);
   return topo_view_device(f.v, cap, word_off, plus, minus, draws);
+}
+
+int colate_topo_profile_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                             const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms,
+                             const double* uniforms, int E, const double* epochs, long long* counts, long long* draws) {
+  const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, n_uniforms, uniforms);
+  return topo_profile_host(f.v, E, epochs, counts, draws);
+}
+
+int colate_topo_profile(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                        const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms, const double* uniforms,
+                        int E, const double* epochs, long long* counts, long long* draws) {
+  const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, n_uniforms, uniforms);
+  return topo_profile_device(f.v, E, epochs, counts, draws);
 }
 
 int colate_topo_samples_tile(void) { return kTileRows; }

@@ -67,6 +67,23 @@ COLATE_IC_HD inline int draw_sign(const Idx& t, const Idx& r, double u1, double 
   return 0;
 }
 
+// THE AGE PROFILE (colate_topo_profile).  The epoch of a searched row, for epochs[E] finite and strictly ascending, 1 <= E <=
+// kMaxProfileEpochs: mid = 0.5f * (age_begin + age_end) in single precision -- one float addition, rounded; the product is exact --
+// and the number of e in 1 .. E - 1 with epochs[e] <= (double)mid.  Total: a NaN or negative mid gives 0, +inf gives E - 1.  Per
+// (triple, epoch) three integers: the rows of the epoch set in the `plus` plane, in the `minus` plane, and in Q.  Integers only:
+// no result depends on an order of operations, and no floating-point sum is formed anywhere.
+constexpr int kMaxProfileEpochs = 1024;
+COLATE_IC_HD inline int age_epoch(float age_begin, float age_end, const double* epochs, int E) {
+  const float mid = 0.5f * (age_begin + age_end);
+  int lo = 0, hi = E - 1;  // the answer lies in [lo, hi]: at most 10 steps
+  while (lo < hi) {
+    const int m = (lo + hi + 1) >> 1;
+    if (epochs[m] <= (double)mid) lo = m;
+    else hi = m - 1;
+  }
+  return lo;
+}
+
 // The inputs of both stages: every row given is a searched row; idx[s * C + c] is sample s's walk index of chromosome c,
 // cidx[s * C + c] its cond index.
 struct View {
@@ -93,12 +110,23 @@ void host_planes(const View& v, int s, const long long* word_off, long long word
 // The host twin / the device stage: word_off[C + 1], plus / minus [P][word_off[C]] with room for cap words each, draws[P].
 int topo_view_host(const View& v, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws);
 int topo_view_device(const View& v, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws);
+// The age profile of the same draws, host twin / device stage: counts[P][E][3] -- plus, minus, qualifying per epoch (age_epoch) --
+// and draws[P].  Refused besides what check_view and check_stream refuse, by name: E outside 1 .. kMaxProfileEpochs, an epoch that
+// is not finite, neighbours that do not ascend, NULL outputs.  No plane leaves either form.
+int check_epochs(int E, const double* epochs);
+int topo_profile_host(const View& v, int E, const double* epochs, long long* counts, long long* draws);
+int topo_profile_device(const View& v, int E, const double* epochs, long long* counts, long long* draws);
 
 // THE CURSOR WALK of one chromosome: the reference's loop over three record cursors, correct for every input.  Cur: a cursor
 // with match, bp, anc, der, AAF, DAF, set_name() and next() (mut_pairs.cpp: Cursor); RowT: pos, anc, der.  draw(): the next
 // uniform of the run's stream; emit(i, sign, DAF_cond, N_cond): row i prints.  fresh: the run's first chromosome (above).
-template <class Cur, class RowT, class Draw, class Emit>
-void cursor_walk_chromosome(Cur& cnd, Cur& tgt, Cur& ref, const char* name, bool fresh, const RowT* rows, size_t n, Draw&& draw, Emit&& emit) {
+// drew(i): row i qualifies, printed or not (the age profile counts those rows; nothing by default).
+struct NoRowSink {
+  void operator()(size_t) const {}
+};
+template <class Cur, class RowT, class Draw, class Emit, class Drew = NoRowSink>
+void cursor_walk_chromosome(Cur& cnd, Cur& tgt, Cur& ref, const char* name, bool fresh, const RowT* rows, size_t n, Draw&& draw, Emit&& emit,
+                            Drew&& drew = Drew()) {
   Cur* const cur[3] = {&cnd, &tgt, &ref};
   for (Cur* c : cur) {  // skip to this chromosome, coal.cpp:4621-4652
     c->set_name(name);
@@ -116,6 +144,7 @@ void cursor_walk_chromosome(Cur& cnd, Cur& tgt, Cur& ref, const char* name, bool
     if (!ref.match || ref.bp != m.pos || ref.anc != m.anc || ref.der != m.der) continue;
     if (!(N_cond > 0 && N_ref > 0 && N_target > 0)) continue;
     if (!(cnd.DAF > 0)) continue;
+    drew(i);
     const float d1 = (float)draw(), d2 = (float)draw();
     const double pT = (double)tgt.DAF / N_target, pR = (double)ref.DAF / N_ref;
     if ((double)d1 <= pT && (double)d2 > pR) emit(i, 1, cnd.DAF, N_cond);
@@ -138,5 +167,11 @@ hipError_t count_launch(const colate_iw::DeviceInputs& in, int S, int P, const T
 // chromosome's first qualifying row; u: the uniforms, at least 2 x the most qualifying rows of any triple
 hipError_t draw_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
                        const long long* base, const double* u, unsigned long long* plus, unsigned long long* minus, hipStream_t stream);
+// bin[n] = age_epoch of every searched row, the rows of all chromosomes back to back: one lane per row, the epochs in LDS
+hipError_t bins_launch(const colate_iw::DeviceInputs& in, int E, const double* epochs, unsigned short* bin, hipStream_t stream);
+// part[((p - p0) * C + c)][3][E] for triples [p0, p1): the draws of draw_launch, every set bit of Q counted in its row's epoch --
+// plus, minus, qualifying -- in an LDS histogram of the (triple, chromosome)'s workgroup
+hipError_t profile_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
+                          const long long* base, const double* u, const unsigned short* bin, int E, unsigned* part, hipStream_t stream);
 }  // namespace colate_topo
 #endif

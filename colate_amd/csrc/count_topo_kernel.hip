@@ -15,7 +15,15 @@
 //     u[2 rank + 1] and the target's and the reference's index entries (consecutive rows: coalesced), compares, and two ballots
 //     are the `plus` and `minus` words, which the lane of that word keeps and the wave stores, one word per lane, at the end of
 //     the tile.  Every output has one owner; a workgroup reads nothing another workgroup of the same launch writes.
-// No atomics, no LDS, no barrier, no floating-point reduction, no compaction.
+// No atomics, no LDS, no barrier, no floating-point reduction, no compaction in these three.
+//
+// The age profile (colate_topo_profile) runs the same staging, planes and counts, and then
+//   * topo_bins_kernel: one lane per searched row, once for all triples: the epochs in LDS, age_epoch as a binary search, the
+//     row's epoch as 16 bits in HBM;
+//   * topo_profile_kernel: the draw kernel's body (draw_tiles, shared by both) with another sink: where the draw kernel keeps a
+//     word's two ballots, every lane with a set bit of Q reads its row's epoch and adds 1 to the workgroup's 3 x E histogram in
+//     LDS -- integer adds, whose sum has no order --, and behind a barrier the workgroup writes its own 3 E words of partials.
+//     No global atomics; the host sums the chromosomes' partials in long long.  No plane leaves the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -79,22 +87,20 @@ __device__ __forceinline__ unsigned long long wave_uniform(unsigned long long v)
   return ((unsigned long long)hi << 32) | lo;
 }
 
-__global__ __launch_bounds__(kDrawWaves * 64) void topo_draw_kernel(DeviceInputs in, int S, int p0, const Triple* __restrict__ triples,
-                                                                    const unsigned long long* __restrict__ planes,
-                                                                    const long long* __restrict__ base, const double* __restrict__ u,
-                                                                    unsigned long long* __restrict__ plus, unsigned long long* __restrict__ minus) {
-  const int c = blockIdx.x % in.C, j = blockIdx.x / in.C;  // (triple p0 + j, chromosome c)
+// The body of the draw kernel for the (triple, chromosome) of one workgroup, over what is done with a word: sink.begin() in front
+// of a tile this wave draws, sink.word(w, kw, qw, plus, minus) at word w of the tile -- word kw of the chromosome, qw its Q,
+// the two ballots of the signs -- where qw != 0, sink.end(k, inside) behind the tile for the lane's own word k.  No barrier and
+// no LDS in here; the trip counts depend on W alone.
+template <class Sink>
+__device__ __forceinline__ void draw_tiles(const DeviceInputs& in, int S, const Triple t, int c, long long carry,
+                                           const unsigned long long* __restrict__ planes, const double* __restrict__ u, Sink& sink) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const Triple t = triples[p0 + j];
   const long long w0 = in.word_off[c], W = in.word_off[c + 1] - w0, r0 = in.row_off[c];
   const unsigned long long* const hT = planes + (size_t)t.target * in.words + w0;
   const unsigned long long* const hR = planes + (size_t)t.reference * in.words + w0;
   const unsigned long long* const qC = planes + (size_t)(S + t.cond) * in.words + w0;
   const Idx* const TI = in.idx + (size_t)t.target * in.n + r0;
   const Idx* const RI = in.idx + (size_t)t.reference * in.n + r0;
-  unsigned long long* const pl = plus + (size_t)j * in.words + w0;
-  unsigned long long* const mi = minus + (size_t)j * in.words + w0;
-  long long carry = base[(size_t)(p0 + j) * in.C + c];  // the rank of the chromosome's first qualifying row
   for (long long tile0 = 0, tile = 0; tile0 < W; tile0 += kTileWords, tile++) {
     const long long k = tile0 + lane;
     const unsigned long long q = k < W ? hT[k] & hR[k] & qC[k] : 0ull;
@@ -108,7 +114,7 @@ __global__ __launch_bounds__(kDrawWaves * 64) void topo_draw_kernel(DeviceInputs
     const int total = __shfl(incl, 63, 64);
     if (tile % kDrawWaves == wave) {
       const int nw = (int)(W - tile0 < kTileWords ? W - tile0 : kTileWords);
-      unsigned long long my_plus = 0, my_minus = 0;
+      sink.begin();
       for (int w = 0; w < nw; w++) {
         const unsigned long long qw = wave_uniform(__shfl(q, w, 64));
         if (qw == 0) continue;  // (alike in the whole wave; the lane of this word keeps its zeros)
@@ -120,21 +126,144 @@ __global__ __launch_bounds__(kDrawWaves * 64) void topo_draw_kernel(DeviceInputs
           sign = draw_sign(TI[i], RI[i], u[2 * rank], u[2 * rank + 1]);
         }
         const unsigned long long a = __ballot(sign > 0), b = __ballot(sign < 0);
-        if (lane == w) my_plus = a, my_minus = b;
+        sink.word(w, tile0 + w, qw, a, b);
       }
-      if (k < W) pl[k] = my_plus, mi[k] = my_minus;
+      sink.end(k, k < W);
     }
     carry += total;
   }
 }
 
-thread_local int g_chunks = 0;
-thread_local double g_kernel_s = 0.0;
+// the draw kernel's sink: the lane of a word keeps its two ballots and the wave stores them, one word per lane, behind the tile
+struct StorePlanes {
+  unsigned long long* pl;
+  unsigned long long* mi;
+  unsigned long long my_plus, my_minus;
+  __device__ __forceinline__ void begin() { my_plus = 0, my_minus = 0; }
+  __device__ __forceinline__ void word(int w, long long, unsigned long long, unsigned long long a, unsigned long long b) {
+    if ((int)(threadIdx.x & 63) == w) my_plus = a, my_minus = b;
+  }
+  __device__ __forceinline__ void end(long long k, bool inside) {
+    if (inside) pl[k] = my_plus, mi[k] = my_minus;
+  }
+};
 
-// bytes of the two output planes a chunk of triples may take on the device (COLATE_TOPO_BUDGET: bytes, for the tests)
+__global__ __launch_bounds__(kDrawWaves * 64) void topo_draw_kernel(DeviceInputs in, int S, int p0, const Triple* __restrict__ triples,
+                                                                    const unsigned long long* __restrict__ planes,
+                                                                    const long long* __restrict__ base, const double* __restrict__ u,
+                                                                    unsigned long long* __restrict__ plus, unsigned long long* __restrict__ minus) {
+  const int c = blockIdx.x % in.C, j = blockIdx.x / in.C;  // (triple p0 + j, chromosome c)
+  const long long w0 = in.word_off[c];
+  StorePlanes sink{plus + (size_t)j * in.words + w0, minus + (size_t)j * in.words + w0, 0, 0};
+  // base: the rank of the chromosome's first qualifying row
+  draw_tiles(in, S, triples[p0 + j], c, base[(size_t)(p0 + j) * in.C + c], planes, u, sink);
+}
+
+// bin[i] = age_epoch of searched row i, the chromosomes back to back: one lane per row.  The workgroup loads the epochs -- 8 KB at
+// most -- into LDS behind one barrier, which every thread reaches; the search takes 10 steps at most.
+__global__ __launch_bounds__(kPlaneTile) void topo_bins_kernel(const Row* __restrict__ rows, long long n, int E, const double* __restrict__ epochs,
+                                                               unsigned short* __restrict__ bin) {
+  __shared__ double ep[kMaxProfileEpochs];
+  for (int e = threadIdx.x; e < E; e += kPlaneTile) ep[e] = epochs[e];
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * kPlaneTile + threadIdx.x;
+  if (i < n) bin[i] = (unsigned short)age_epoch(rows[i].age_begin, rows[i].age_end, ep, E);
+}
+
+// the profile kernel's sink: every lane with a set bit of Q counts its row in the row's epoch -- qualifying, and plus or minus by
+// its sign.  Integer adds in LDS: their sum has no order.
+struct BinRows {
+  const unsigned short* bin;  // of the chromosome's first row
+  unsigned* hist;             // [3][E]: plus, minus, qualifying
+  int E;
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ void word(int, long long kw, unsigned long long qw, unsigned long long a, unsigned long long b) {
+    const int lane = threadIdx.x & 63;
+    if ((qw >> lane) & 1) {
+      const int e = bin[kw * 64 + lane];  // (a set bit of Q is a row of the chromosome; bins_launch wrote 0 .. E - 1)
+      atomicAdd(&hist[2 * E + e], 1u);
+      if ((a >> lane) & 1) atomicAdd(&hist[e], 1u);
+      else if ((b >> lane) & 1) atomicAdd(&hist[E + e], 1u);
+    }
+  }
+  __device__ __forceinline__ void end(long long, bool) {}
+};
+
+// One workgroup of kDrawWaves waves per (triple, chromosome): the histogram zeroed behind a barrier, the draws, a second barrier,
+// and the workgroup's own 3 E words of `part`.  Both barriers are reached by every wave.
+__global__ __launch_bounds__(kDrawWaves * 64) void topo_profile_kernel(DeviceInputs in, int S, int p0, const Triple* __restrict__ triples,
+                                                                       const unsigned long long* __restrict__ planes,
+                                                                       const long long* __restrict__ base, const double* __restrict__ u,
+                                                                       const unsigned short* __restrict__ bin, int E, unsigned* __restrict__ part) {
+  __shared__ unsigned hist[3 * kMaxProfileEpochs];
+  const int c = blockIdx.x % in.C, j = blockIdx.x / in.C;  // (triple p0 + j, chromosome c)
+  for (int i = threadIdx.x; i < 3 * E; i += kDrawWaves * 64) hist[i] = 0;
+  __syncthreads();
+  BinRows sink{bin + in.row_off[c], hist, E};
+  draw_tiles(in, S, triples[p0 + j], c, base[(size_t)(p0 + j) * in.C + c], planes, u, sink);
+  __syncthreads();
+  unsigned* const mine = part + (size_t)blockIdx.x * 3 * (size_t)E;
+  for (int i = threadIdx.x; i < 3 * E; i += kDrawWaves * 64) mine[i] = hist[i];
+}
+
+thread_local int g_chunks = 0, g_profile_chunks = 0;
+thread_local double g_kernel_s = 0.0, g_profile_kernel_s = 0.0;
+
+// bytes of what a chunk of triples leaves on the device -- the two output planes of colate_topo_samples, the partial histograms
+// of colate_topo_profile -- (COLATE_TOPO_BUDGET: bytes, for the tests)
 long long output_budget() {
   if (const char* e = std::getenv("COLATE_TOPO_BUDGET")) return std::max(1LL, std::atoll(e));
   return 256LL << 20;
+}
+
+// What both device calls stage on the workspace's stream in front of their chunks of triples: the inputs resident, the planes,
+// the counts with the one host wait for them, every (triple, chromosome)'s first rank and the uniforms the longest triple needs.
+struct Front {
+  colate_iw::Resident res;
+  DeviceBuffers buf;
+  std::vector<const Idx*> both;  // the walk indices, then the cond indices
+  std::vector<int> cnt;
+  std::vector<long long> base, n;  // [P][C], [P]: the qualifying rows
+  unsigned long long* d_planes = nullptr;
+  Triple* d_triples = nullptr;
+  long long* d_base = nullptr;
+  double* d_u = nullptr;
+  int stage(const View& v, long long words, hipStream_t stream, colate_iw::KernelTimer& timer) {
+    const size_t PC = (size_t)v.P * v.C;
+    cnt.resize(PC), base.resize(PC), n.assign((size_t)v.P, 0), both.resize((size_t)2 * v.S * v.C);
+    std::copy_n(v.idx, (size_t)v.S * v.C, both.begin());
+    std::copy_n(v.cidx, (size_t)v.S * v.C, both.begin() + (size_t)v.S * v.C);
+    colate_iw::View iv;
+    iv.C = v.C, iv.row_off = v.row_off, iv.rows = v.rows, iv.S = 2 * v.S, iv.idx = both.data(), iv.M = 0, iv.P = 0, iv.pairs = nullptr, iv.nbpb = 1;
+    if (int rc = res.upload(iv, stream)) return rc;
+    int* d_cnt = nullptr;
+    HIP_TRY(buf.device(d_planes, (size_t)2 * v.S * (size_t)words)); HIP_TRY(buf.device(d_triples, (size_t)v.P));
+    HIP_TRY(buf.device(d_cnt, PC)); HIP_TRY(buf.device(d_base, PC));
+    HIP_TRY(colate_iw::h2d(stream, d_triples, v.triples, sizeof(Triple) * (size_t)v.P));
+    HIP_TRY(timer.mark());
+    if (hipError_t e = planes_launch(res.in, v.S, d_planes, stream)) return hip_fail(e, "topo planes kernel launch");
+    if (hipError_t e = count_launch(res.in, v.S, v.P, d_triples, d_planes, d_cnt, stream)) return hip_fail(e, "topo count kernel launch");
+    HIP_TRY(timer.mark());
+    HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * PC, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // the one wait for the counts
+    long long most = 0;
+    for (int p = 0; p < v.P; p++) {
+      for (int c = 0; c < v.C; c++) base[(size_t)p * v.C + c] = n[(size_t)p], n[(size_t)p] += cnt[(size_t)p * v.C + c];
+      most = std::max(most, n[(size_t)p]);
+    }
+    if (int rc = check_stream(v, n.data())) return rc;
+    // every triple starts from the run's seed: one stream for all, as long as the longest needs
+    HIP_TRY(buf.device(d_u, (size_t)(2 * most)));
+    HIP_TRY(colate_iw::h2d(stream, d_u, v.uniforms, sizeof(double) * (size_t)(2 * most)));
+    HIP_TRY(colate_iw::h2d(stream, d_base, base.data(), sizeof(long long) * PC));
+    return COLATE_OK;
+  }
+};
+
+int check_grids_of(const View& v) {
+  if (2LL * v.S > 65535) return fail(COLATE_ELIMIT, "S=%d above the grid of the plane kernel (32767)", v.S);
+  if ((long long)v.P * v.C > 0x7fffffffLL) return fail(COLATE_ELIMIT, "P x C = %lld above the grid of the count kernel", (long long)v.P * v.C);
+  return COLATE_OK;
 }
 
 }  // namespace
@@ -167,11 +296,27 @@ hipError_t draw_launch(const DeviceInputs& in, int S, int p0, int p1, const Trip
   return hipGetLastError();
 }
 
+hipError_t bins_launch(const DeviceInputs& in, int E, const double* epochs, unsigned short* bin, hipStream_t stream) {
+  if (in.n < 1) return hipSuccess;
+  const long long blocks = (in.n + kPlaneTile - 1) / kPlaneTile;
+  if (blocks > 0x7fffffffLL || E < 1 || E > kMaxProfileEpochs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topo_bins_kernel, dim3((unsigned)blocks), dim3(kPlaneTile), 0, stream, in.rows, in.n, E, epochs, bin);
+  return hipGetLastError();
+}
+
+hipError_t profile_launch(const DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
+                          const long long* base, const double* u, const unsigned short* bin, int E, unsigned* part, hipStream_t stream) {
+  if (p1 <= p0 || in.C < 1) return hipSuccess;
+  const long long grid = (long long)(p1 - p0) * in.C;
+  if (grid > 0x7fffffffLL || E < 1 || E > kMaxProfileEpochs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topo_profile_kernel, dim3((unsigned)grid), dim3(kDrawWaves * 64), 0, stream, in, S, p0, triples, planes, base, u, bin, E, part);
+  return hipGetLastError();
+}
+
 int topo_view_device(const View& v, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws) {
   if (int rc = check_outputs(cap, word_off, plus, minus, draws)) return rc;
   if (int rc = check_view(v)) return rc;
-  if (2LL * v.S > 65535) return fail(COLATE_ELIMIT, "S=%d above the grid of the plane kernel (32767)", v.S);
-  if ((long long)v.P * v.C > 0x7fffffffLL) return fail(COLATE_ELIMIT, "P x C = %lld above the grid of the count kernel", (long long)v.P * v.C);
+  if (int rc = check_grids_of(v)) return rc;
   std::vector<long long> woff((size_t)v.C + 1);
   const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
   if (int rc = check_capacity(v.P, words, cap)) return rc;
@@ -181,50 +326,18 @@ int topo_view_device(const View& v, long long cap, long long* word_off, unsigned
   if (int rc = thread_workspace().reserve(256, 256)) return rc;  // (the workspace's stream: no second one)
   hipStream_t stream = thread_workspace().stream;
   colate_iw::KernelTimer timer(stream);
-  colate_iw::Resident res;
-  DeviceBuffers buf;
-  const size_t PC = (size_t)v.P * v.C;
-  std::vector<int> cnt(PC);
-  std::vector<long long> base(PC), n((size_t)v.P, 0);
-  std::vector<const Idx*> both((size_t)2 * v.S * v.C);  // the walk indices, then the cond indices
-  std::copy_n(v.idx, (size_t)v.S * v.C, both.begin());
-  std::copy_n(v.cidx, (size_t)v.S * v.C, both.begin() + (size_t)v.S * v.C);
+  Front f;
   const colate_iw::StreamSync sync_at_exit{stream};
-  colate_iw::View iv;
-  iv.C = v.C, iv.row_off = v.row_off, iv.rows = v.rows, iv.S = 2 * v.S, iv.idx = both.data(), iv.M = 0, iv.P = 0, iv.pairs = nullptr, iv.nbpb = 1;
-  if (int rc = res.upload(iv, stream)) return rc;
   // triples per chunk: the two output planes of a chunk within the budget, and the grid within 2^31 workgroups
   const long long per_triple = std::max(1LL, 2 * words * (long long)sizeof(unsigned long long));
   const long long chunk = std::max(1LL, std::min<long long>({(long long)v.P, output_budget() / per_triple, 0x7fffffffLL / v.C}));
-  unsigned long long *d_planes = nullptr, *d_plus = nullptr, *d_minus = nullptr;
-  Triple* d_triples = nullptr;
-  int* d_cnt = nullptr;
-  long long* d_base = nullptr;
-  double* d_u = nullptr;
-  HIP_TRY(buf.device(d_planes, (size_t)2 * v.S * (size_t)words)); HIP_TRY(buf.device(d_triples, (size_t)v.P));
-  HIP_TRY(buf.device(d_cnt, PC)); HIP_TRY(buf.device(d_base, PC));
-  HIP_TRY(buf.device(d_plus, (size_t)(chunk * words))); HIP_TRY(buf.device(d_minus, (size_t)(chunk * words)));
-  HIP_TRY(colate_iw::h2d(stream, d_triples, v.triples, sizeof(Triple) * (size_t)v.P));
-  HIP_TRY(timer.mark());
-  if (hipError_t e = planes_launch(res.in, v.S, d_planes, stream)) return hip_fail(e, "topo planes kernel launch");
-  if (hipError_t e = count_launch(res.in, v.S, v.P, d_triples, d_planes, d_cnt, stream)) return hip_fail(e, "topo count kernel launch");
-  HIP_TRY(timer.mark());
-  HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * PC, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));  // the one wait for the counts
-  long long most = 0;
-  for (int p = 0; p < v.P; p++) {
-    for (int c = 0; c < v.C; c++) base[(size_t)p * v.C + c] = n[(size_t)p], n[(size_t)p] += cnt[(size_t)p * v.C + c];
-    most = std::max(most, n[(size_t)p]);
-  }
-  if (int rc = check_stream(v, n.data())) return rc;
-  // every triple starts from the run's seed: one stream for all, as long as the longest needs
-  HIP_TRY(buf.device(d_u, (size_t)(2 * most)));
-  HIP_TRY(colate_iw::h2d(stream, d_u, v.uniforms, sizeof(double) * (size_t)(2 * most)));
-  HIP_TRY(colate_iw::h2d(stream, d_base, base.data(), sizeof(long long) * PC));
+  unsigned long long *d_plus = nullptr, *d_minus = nullptr;
+  HIP_TRY(f.buf.device(d_plus, (size_t)(chunk * words))); HIP_TRY(f.buf.device(d_minus, (size_t)(chunk * words)));
+  if (int rc = f.stage(v, words, stream, timer)) return rc;
   for (long long p0 = 0; p0 < v.P; p0 += chunk) {  // (a chunk's planes are copied out before the next launch overwrites them: one stream)
     const long long p1 = std::min<long long>(v.P, p0 + chunk);
     HIP_TRY(timer.mark());
-    if (hipError_t e = draw_launch(res.in, v.S, (int)p0, (int)p1, d_triples, d_planes, d_base, d_u, d_plus, d_minus, stream))
+    if (hipError_t e = draw_launch(f.res.in, v.S, (int)p0, (int)p1, f.d_triples, f.d_planes, f.d_base, f.d_u, d_plus, d_minus, stream))
       return hip_fail(e, "topo draw kernel launch");
     HIP_TRY(timer.mark());
     const size_t bytes = sizeof(unsigned long long) * (size_t)((p1 - p0) * words);
@@ -236,8 +349,62 @@ int topo_view_device(const View& v, long long cap, long long* word_off, unsigned
   }
   HIP_TRY(hipStreamSynchronize(stream));
   g_kernel_s = timer.seconds();
-  std::memcpy(draws, n.data(), sizeof(long long) * (size_t)v.P);
+  std::memcpy(draws, f.n.data(), sizeof(long long) * (size_t)v.P);
   std::memcpy(word_off, woff.data(), sizeof(long long) * woff.size());
+  return COLATE_OK;
+}
+
+int topo_profile_device(const View& v, int E, const double* epochs, long long* counts, long long* draws) {
+  if (!counts || !draws) return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (int rc = check_epochs(E, epochs)) return rc;
+  if (int rc = check_view(v)) return rc;
+  if (int rc = check_grids_of(v)) return rc;
+  if ((v.row_off[v.C] + kPlaneTile - 1) / kPlaneTile > 0x7fffffffLL)
+    return fail(COLATE_ELIMIT, "%lld rows above the grid of the bins kernel", v.row_off[v.C]);
+  std::vector<long long> woff((size_t)v.C + 1);
+  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
+  if (int rc = ensure_device()) return rc;
+  ProfRange range("colate_topo_profile: H2D + planes + counts + bins; the uniforms; per chunk of triples the binned draws + D2H");
+  g_profile_chunks = 0, g_profile_kernel_s = 0.0;
+  if (int rc = thread_workspace().reserve(256, 256)) return rc;  // (the workspace's stream: no second one)
+  hipStream_t stream = thread_workspace().stream;
+  colate_iw::KernelTimer timer(stream);
+  Front f;
+  // triples per chunk: the partial histograms of a chunk -- 12 E bytes per (triple, chromosome) -- within the budget, and the grid
+  // within 2^31 workgroups
+  const size_t per_block = 3 * (size_t)E;
+  const long long per_triple = (long long)(per_block * sizeof(unsigned)) * v.C;
+  const long long chunk = std::max(1LL, std::min<long long>({(long long)v.P, output_budget() / per_triple, 0x7fffffffLL / v.C}));
+  std::vector<unsigned> part((size_t)chunk * v.C * per_block);
+  const colate_iw::StreamSync sync_at_exit{stream};
+  unsigned short* d_bin = nullptr;
+  double* d_epochs = nullptr;
+  unsigned* d_part = nullptr;
+  HIP_TRY(f.buf.device(d_bin, (size_t)v.row_off[v.C])); HIP_TRY(f.buf.device(d_epochs, (size_t)E)); HIP_TRY(f.buf.device(d_part, part.size()));
+  if (int rc = f.stage(v, words, stream, timer)) return rc;
+  HIP_TRY(colate_iw::h2d(stream, d_epochs, epochs, sizeof(double) * (size_t)E));
+  HIP_TRY(timer.mark());
+  if (hipError_t e = bins_launch(f.res.in, E, d_epochs, d_bin, stream)) return hip_fail(e, "topo bins kernel launch");  // once, for every triple
+  HIP_TRY(timer.mark());
+  std::memset(counts, 0, sizeof(long long) * (size_t)v.P * per_block);
+  for (long long p0 = 0; p0 < v.P; p0 += chunk) {
+    const long long p1 = std::min<long long>(v.P, p0 + chunk);
+    HIP_TRY(timer.mark());
+    if (hipError_t e = profile_launch(f.res.in, v.S, (int)p0, (int)p1, f.d_triples, f.d_planes, f.d_base, f.d_u, d_bin, E, d_part, stream))
+      return hip_fail(e, "topo profile kernel launch");
+    HIP_TRY(timer.mark());
+    HIP_TRY(hipMemcpyAsync(part.data(), d_part, sizeof(unsigned) * (size_t)(p1 - p0) * v.C * per_block, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // (the one wait at the end where one chunk holds every triple)
+    for (long long p = p0; p < p1; p++)  // the chromosomes' partials, summed in long long
+      for (int c = 0; c < v.C; c++) {
+        const unsigned* const h = part.data() + ((size_t)(p - p0) * v.C + c) * per_block;
+        long long* const out = counts + (size_t)p * per_block;
+        for (int e = 0; e < E; e++) out[3 * e] += h[e], out[3 * e + 1] += h[E + e], out[3 * e + 2] += h[2 * E + e];
+      }
+    g_profile_chunks++;
+  }
+  g_profile_kernel_s = timer.seconds();
+  std::memcpy(draws, f.n.data(), sizeof(long long) * (size_t)v.P);
   return COLATE_OK;
 }
 
@@ -246,4 +413,6 @@ int topo_view_device(const View& v, long long cap, long long* word_off, unsigned
 extern "C" {
 int colate_topo_samples_chunks(void) { return g_chunks; }
 double colate_topo_samples_kernel_seconds(void) { return g_kernel_s; }
+int colate_topo_profile_chunks(void) { return g_profile_chunks; }
+double colate_topo_profile_kernel_seconds(void) { return g_profile_kernel_s; }
 }

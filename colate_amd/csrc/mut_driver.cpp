@@ -64,8 +64,8 @@ const char* const kValueOptions[] = {
     "reference_age", "ref_genome", "anc_genome", "mask", "mask_cutoff", "chr", "bins",
     "lineage_bin", "outgroup_tmrca", "years_per_gen", "coal", "seed", "num_bootstraps", "filters",
     "groups", "poplabels", "map", "input", "output", "device", "devices", "ranks", "counts_out", "pairs",
-    "rows", "max_iter", "min_iter", "write_rows", "samples"};
-const char* const kBoolOptions[] = {"help", "strandfilter", "counts_only", "write_colate_mat"};
+    "rows", "max_iter", "min_iter", "write_rows", "samples", "age_profile"};
+const char* const kBoolOptions[] = {"help", "strandfilter", "counts_only", "write_colate_mat", "profile_only"};
 
 bool parse_options(int argc, char** argv, Options& o, std::string& err) {
   for (int i = 1; i < argc; i++) {
@@ -153,6 +153,11 @@ void print_help() {
             << "                             (--mode count_topo) that list with role= a comma-separated subset of cond,target,reference (default: all\n"
             << "                             three); every (cond, target, reference) of three lines, drawn on the GPU: PREFIX_<cond>_<target>_<reference>.txt\n"
             << "                             and PREFIX.triples.txt.\n"
+            << "      --age_profile arg      (--mode count_topo --samples) x,y,stepsize as for --bins [--years_per_gen, default 28]: also write\n"
+            << "                             PREFIX.profile.txt, `cond target reference epoch plus minus qualifying` per (triple, epoch): the\n"
+            << "                             printed rows of either sign and the rows that drew, binned on the GPU by the mid of their ages.\n"
+            << "      --profile_only         (--mode count_topo --samples --age_profile) write no per-triple file: PREFIX.profile.txt and\n"
+            << "                             PREFIX.triples.txt only.\n"
             << "      --counts_out arg       Optional (colate_amd): write the bootstrap count tables (.colate_mat layout).\n"
             << "      --counts_only          Optional (colate_amd): stop after --counts_out (no GPU needed).\n"
             << "      --write_colate_mat     Optional (colate_amd): write <output>.colate_mat as the reference does for BCF/BAM inputs.\n"
@@ -1678,6 +1683,11 @@ extern "C" int colate_mut_main(int argc, char** argv) {
     return 0;
   }
   const std::string& mode = opt.get("mode");
+  for (const char* o : {"age_profile", "profile_only"})
+    if (opt.has(o) && mode != "count_topo") {
+      std::cerr << "Error: --" << o << " is an option of --mode count_topo --samples." << std::endl;
+      return 1;
+    }
   if (mode == "mut") {
     if (opt.has("help")) {
       print_help();

@@ -231,8 +231,15 @@ struct TopoLine {
   float age_begin, age_end;
   int sign, DAF, N;  // the conditioning record's counts
 };
+// profile (`--age_profile`): epochs[E] in, counts[P][E][3] out -- per triple and epoch (count_topo.h: age_epoch) the rows printed
+// with +1, with -1, and the qualifying rows.
+struct TopoProfile {
+  int E = 0;
+  const double* epochs = nullptr;
+  std::vector<long long> counts;
+};
 bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, unsigned seed,
-                         std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws);
+                         std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws, TopoProfile* profile = nullptr);
 // topo_driver.cpp: `Colate --mode count_topo`
 int run_count_topo(const Options& opt);
 // mut_pairs.cpp: the cursor walk of `--mode compare_tmp` (compare_tmp.h: cursor_walk_chromosome) for every pair of a list over inputs

@@ -1659,10 +1659,11 @@ bool compare_cursor_pairs(const WalkInputs& loaded, const std::vector<std::strin
 
 // (mut_feeder.h)
 bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, unsigned seed,
-                         std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws) {
+                         std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws, TopoProfile* profile) {
   if (!loaded.loaded || loaded.loaded->in.rows.size() != names.size()) return false;
   const Inputs& in = loaded.loaded->in;
   lines.assign(triples.size(), std::vector<TopoLine>()), draws.assign(triples.size(), 0);
+  if (profile) profile->counts.assign(triples.size() * (size_t)profile->E * 3, 0);
   Pool pool(pairs_threads());
   for (size_t p = 0; p < triples.size(); p++)
     pool.submit([&, p] {  // one triple per task: its three cursors go through the chromosomes in the list's order, its generator from the seed
@@ -1673,9 +1674,19 @@ bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string
       long long n = 0;
       for (size_t c = 0; c < names.size(); c++) {
         const CompactRow* const rows = in.rows[c].data();
+        // (the profile: a triple's own [E][3] counts, binned by the rows' own floats)
+        auto count = [&](size_t i, int which) {
+          if (profile)
+            profile->counts[(p * (size_t)profile->E + (size_t)colate_topo::age_epoch(rows[i].age_begin, rows[i].age_end, profile->epochs, profile->E)) * 3 +
+                            (size_t)which]++;
+        };
         colate_topo::cursor_walk_chromosome(
             cnd, tgt, ref, names[c].c_str(), c == 0, rows, in.rows[c].size(), [&] { return n++, dist_unif(rng); },
-            [&](size_t i, int sign, int DAF, int N) { lines[p].push_back(TopoLine{(int)c, rows[i].pos, rows[i].age_begin, rows[i].age_end, sign, DAF, N}); });
+            [&](size_t i, int sign, int DAF, int N) {
+              lines[p].push_back(TopoLine{(int)c, rows[i].pos, rows[i].age_begin, rows[i].age_end, sign, DAF, N});
+              count(i, sign > 0 ? 0 : 1);
+            },
+            [&](size_t i) { count(i, 2); });
       }
       draws[p] = n / 2;
     });

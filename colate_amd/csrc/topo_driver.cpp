@@ -10,6 +10,11 @@
 //     triple.  The rows, one walk index and one cond index per sample are staged once and colate_topo_samples draws every triple
 //     on the device; its host twin without a device or with COLATE_DEVICE_TOPO=0; the cursor walk per triple where a sample
 //     cannot be indexed.  All three give the same bytes.
+//     `--age_profile x,y,s [--years_per_gen Y]`: besides, PREFIX.profile.txt with one line `cond target reference epoch plus minus
+//     qualifying` per (triple, epoch) -- the printed rows of either sign and the rows that drew, binned by the mid of their ages
+//     (count_topo.h: age_epoch) into the epochs of `--mode mut --bins x,y,s` -- through colate_topo_profile, a second pass over the
+//     staged inputs.  `--profile_only`: no per-triple file; PREFIX.triples.txt from the profile's sums, the same bytes; only the
+//     profile call runs, and no plane, bit or line is formed.
 #include <unistd.h>
 
 #include <chrono>
@@ -48,7 +53,8 @@ bool write_lines(const std::string& path, const std::vector<std::string>& names,
 }
 
 enum class Path { cursors, host_twin, device };
-double g_triple_stage_s = 0;  // the seconds of the triple stage alone, whichever form ran (COLATE_TIMING)
+double g_triple_stage_s = 0;  // the seconds of the triple stage alone, whichever forms ran (COLATE_TIMING)
+double g_kernel_s = 0;        // ... and of its kernels on the device
 
 unsigned run_seed(const Options& opt) {  // coal.cpp:4545-4549
   int seed = (int)(std::time(nullptr) + getpid());
@@ -56,11 +62,22 @@ unsigned run_seed(const Options& opt) {  // coal.cpp:4545-4549
   return (unsigned)seed;
 }
 
-// Loads the inputs of `triples` (PairSpec with its cond file) and draws every triple: the lines each prints and its qualifying
-// rows.  False after an error message; nothing has been written then.
-bool draw_triples(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
-                  const std::vector<PairSpec>& triples, Path want, unsigned seed, WalkInputs& in, std::vector<std::vector<TopoLine>>& lines,
-                  std::vector<long long>& draws) {
+// The inputs of `triples` (PairSpec with its cond file) as every form of the triple stage takes them: loaded once, the form
+// decided, and -- for the two indexed forms -- the run's stream and the view.
+struct Staged {
+  WalkInputs in;
+  Path path = Path::cursors;
+  unsigned seed = 0;
+  std::vector<double> u;
+  std::vector<colate_topo::Triple> ids;
+  colate_topo::View v;
+  const char* where() const { return path == Path::device ? "device" : "host"; }
+};
+
+// False after an error message; nothing has been written then.
+bool stage_triples(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
+                   const std::vector<PairSpec>& triples, Path want, unsigned seed, Staged& st) {
+  WalkInputs& in = st.in;
   for (const PairSpec& ps : triples)
     for (const std::string* f : {&ps.cond, &ps.target, &ps.reference}) {  // coal.cpp:4588-4603
       FILE* fp = std::fopen(f->c_str(), "rb");
@@ -82,37 +99,51 @@ bool draw_triples(const Options& opt, const std::vector<std::string>& names, con
               << std::endl;
     want = Path::cursors;
   }
-  const double t_stage = StageTimes::now();
-  if (want == Path::cursors) {
-    const bool ok = topo_cursor_triples(in, names, triples, seed, lines, draws);
-    g_triple_stage_s = StageTimes::now() - t_stage;
-    return ok;
-  }
+  st.path = want, st.seed = seed;
+  if (want == Path::cursors) return true;
   const int C = (int)names.size();
   const long long n_rows = in.row_off.back();
   // the run's stream: a row draws two uniforms at most, and every triple starts from the seed
-  std::vector<double> u((size_t)(2 * n_rows));
+  st.u.resize((size_t)(2 * n_rows));
   {
     std::mt19937 rng(seed);
     std::uniform_real_distribution<double> dist_unif(0, 1);
-    for (double& x : u) x = dist_unif(rng);
+    for (double& x : st.u) x = dist_unif(rng);
   }
-  std::vector<colate_topo::Triple> ids(P);
-  for (size_t p = 0; p < P; p++) ids[p] = colate_topo::Triple{in.cond_ids[p], in.pairs[p].target, in.pairs[p].reference};
-  colate_topo::View v;
+  st.ids.resize(P);
+  for (size_t p = 0; p < P; p++) st.ids[p] = colate_topo::Triple{in.cond_ids[p], in.pairs[p].target, in.pairs[p].reference};
+  colate_topo::View& v = st.v;
   v.C = C, v.row_off = in.row_off.data(), v.rows = in.row_ptrs.data(), v.S = in.S, v.idx = in.idx_ptrs.data(), v.cidx = in.cidx_ptrs.data();
-  v.P = (int)P, v.triples = ids.data(), v.n_uniforms = (long long)u.size(), v.uniforms = u.data();
+  v.P = (int)P, v.triples = st.ids.data(), v.n_uniforms = (long long)st.u.size(), v.uniforms = st.u.data();
+  if (want == Path::device && opt.has("device"))
+    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc), false;
+  return true;
+}
+
+// Draws every staged triple: the lines each prints and its qualifying rows.  profile: on the cursor path the same walk fills it.
+bool draw_triples(const Staged& st, const std::vector<std::string>& names, const std::vector<PairSpec>& triples,
+                  std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws, TopoProfile* profile = nullptr) {
+  const WalkInputs& in = st.in;
+  const size_t P = triples.size();
+  const double t_stage = StageTimes::now();
+  if (st.path == Path::cursors) {
+    const bool ok = topo_cursor_triples(in, names, triples, st.seed, lines, draws, profile);
+    g_triple_stage_s += StageTimes::now() - t_stage;
+    return ok;
+  }
+  const int C = (int)names.size();
+  const colate_topo::View& v = st.v;
+  const std::vector<colate_topo::Triple>& ids = st.ids;
   std::vector<long long> word_off((size_t)C + 1);
   const long long words = colate_iw::mask_words(C, v.row_off, word_off.data());
   std::vector<unsigned long long> plus(P * (size_t)words), minus(P * (size_t)words);
   draws.assign(P, 0);
-  if (want == Path::device && opt.has("device"))
-    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc), false;
   const long long cap = (long long)P * words;
-  if (int rc = want == Path::device ? colate_topo::topo_view_device(v, cap, word_off.data(), plus.data(), minus.data(), draws.data())
-                                    : colate_topo::topo_view_host(v, cap, word_off.data(), plus.data(), minus.data(), draws.data()))
+  if (int rc = st.path == Path::device ? colate_topo::topo_view_device(v, cap, word_off.data(), plus.data(), minus.data(), draws.data())
+                                       : colate_topo::topo_view_host(v, cap, word_off.data(), plus.data(), minus.data(), draws.data()))
     return api_error(rc), false;
-  g_triple_stage_s = StageTimes::now() - t_stage;
+  g_triple_stage_s += StageTimes::now() - t_stage;
+  g_kernel_s += colate_topo_samples_kernel_seconds();
   // set bits into lines; the value is that of the conditioning record, which the cond index holds
   lines.assign(P, std::vector<TopoLine>());
   for (size_t p = 0; p < P; p++)
@@ -129,7 +160,30 @@ bool draw_triples(const Options& opt, const std::vector<std::string>& names, con
         }
       }
     }
-  std::cerr << in.S << " samples staged, " << P << " triples drawn on the " << (want == Path::device ? "device" : "host") << std::endl;
+  std::cerr << in.S << " samples staged, " << P << " triples drawn on the " << st.where() << std::endl;
+  return true;
+}
+
+// The age profile of every staged triple (count_topo.h: age_epoch): profile.counts[P][E][3] and the qualifying rows.  No plane and
+// no line is formed on the indexed forms.
+bool profile_triples(const Staged& st, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, TopoProfile& profile,
+                     std::vector<long long>& draws) {
+  const size_t P = triples.size();
+  const double t_stage = StageTimes::now();
+  if (st.path == Path::cursors) {
+    std::vector<std::vector<TopoLine>> lines;
+    const bool ok = topo_cursor_triples(st.in, names, triples, st.seed, lines, draws, &profile);
+    g_triple_stage_s += StageTimes::now() - t_stage;
+    return ok;
+  }
+  profile.counts.assign(P * (size_t)profile.E * 3, 0);
+  draws.assign(P, 0);
+  if (int rc = st.path == Path::device ? colate_topo::topo_profile_device(st.v, profile.E, profile.epochs, profile.counts.data(), draws.data())
+                                       : colate_topo::topo_profile_host(st.v, profile.E, profile.epochs, profile.counts.data(), draws.data()))
+    return api_error(rc), false;
+  g_triple_stage_s += StageTimes::now() - t_stage;
+  g_kernel_s += colate_topo_profile_kernel_seconds();
+  std::cerr << st.in.S << " samples staged, " << P << " triples profiled on the " << st.where() << std::endl;
   return true;
 }
 
@@ -141,8 +195,31 @@ int run_topo_samples(const Options& opt) {
       return 1;
     }
   if (!opt.has("mut") || !opt.has("output")) {
-    std::cerr << "Error: --samples needs --mut and -o PREFIX (optional: --chr, --seed, --device)." << std::endl;
+    std::cerr << "Error: --samples needs --mut and -o PREFIX (optional: --chr, --seed, --device, --age_profile, --years_per_gen, --profile_only)."
+              << std::endl;
     return 1;
+  }
+  // `--age_profile x,y,s`: the epochs a .coal of `--mode mut --bins x,y,s` prints, in generations
+  const bool profiled = opt.has("age_profile"), profile_only = opt.has("profile_only");
+  if (profile_only && !profiled) {
+    std::cerr << "Error: --profile_only needs --age_profile x,y,stepsize." << std::endl;
+    return 1;
+  }
+  std::vector<double> epochs, boundaries;
+  TopoProfile profile;
+  if (profiled) {
+    const double years_per_gen = opt.has("years_per_gen") ? std::stof(opt.get("years_per_gen")) : 28.0;
+    epochs.resize(colate_topo::kMaxProfileEpochs);
+    const int E = colate_epochs_from_bins(opt.get("age_profile").c_str(), 0.0, years_per_gen, epochs.data(), (int)epochs.size(), nullptr);
+    if (E < 0) return api_error(E);
+    epochs.resize((size_t)E);
+    // With age 0 the reference's epochs start 0, 0: epoch 0 is [0, 0) and holds the rows of a negative mid only.  age_epoch reads
+    // epochs[1 .. E - 1] alone, so every form bins over the same boundaries with epochs[0] moved below epochs[1], which ascend
+    // strictly as the call demands; the file prints the reference's.
+    boundaries = epochs;
+    if (E >= 2 && boundaries[0] >= boundaries[1]) boundaries[0] = boundaries[1] - 1.0;
+    if (int rc = colate_topo::check_epochs(E, boundaries.data())) return api_error(rc);
+    profile.E = E, profile.epochs = boundaries.data();
   }
   std::vector<std::string> names, mut_files;
   chromosome_files(opt, names, mut_files);
@@ -182,16 +259,25 @@ int run_topo_samples(const Options& opt) {
     want = Path::host_twin;
   }
   const double t0 = StageTimes::now();
-  WalkInputs in;
+  Staged st;
   std::vector<std::vector<TopoLine>> lines;
   std::vector<long long> draws;
-  if (!draw_triples(opt, names, mut_files, triples, want, seed, in, lines, draws)) return 1;
+  if (!stage_triples(opt, names, mut_files, triples, want, seed, st)) return 1;
+  const WalkInputs& in = st.in;
+  const bool one_walk = st.path == Path::cursors;  // (the cursor walk fills lines and profile at once)
+  if (!profile_only && !draw_triples(st, names, triples, lines, draws, profiled && one_walk ? &profile : nullptr)) return 1;
+  if (profiled && (profile_only || !one_walk) && !profile_triples(st, names, triples, profile, draws)) return 1;
   const double t1 = StageTimes::now();
   std::ofstream os(opt.get("output") + ".triples.txt");
   for (size_t p = 0; p < triples.size(); p++) {
-    if (!write_lines(triples[p].output, names, lines[p])) return 1;
     long long plus = 0, minus = 0;
-    for (const TopoLine& l : lines[p]) (l.sign > 0 ? plus : minus)++;
+    if (profile_only) {  // the profile's sums: the same totals
+      for (int e = 0; e < profile.E; e++)
+        plus += profile.counts[(p * (size_t)profile.E + (size_t)e) * 3], minus += profile.counts[(p * (size_t)profile.E + (size_t)e) * 3 + 1];
+    } else {
+      if (!write_lines(triples[p].output, names, lines[p])) return 1;
+      for (const TopoLine& l : lines[p]) (l.sign > 0 ? plus : minus)++;
+    }
     os << triple_names[p] << " " << plus << " " << minus << " " << draws[p] << "\n";
   }
   os.close();
@@ -199,9 +285,22 @@ int run_topo_samples(const Options& opt) {
     std::cerr << "Error: cannot write " << opt.get("output") << ".triples.txt" << std::endl;
     return 1;
   }
+  if (profiled) {  // `cond target reference epoch plus minus qualifying`: every epoch of every triple, the epoch as a .coal prints it
+    std::ofstream pr(opt.get("output") + ".profile.txt");
+    for (size_t p = 0; p < triples.size(); p++)
+      for (int e = 0; e < profile.E; e++) {
+        const long long* const x = &profile.counts[(p * (size_t)profile.E + (size_t)e) * 3];
+        pr << triple_names[p] << " " << epochs[(size_t)e] << " " << x[0] << " " << x[1] << " " << x[2] << "\n";
+      }
+    pr.close();
+    if (!pr) {
+      std::cerr << "Error: cannot write " << opt.get("output") << ".profile.txt" << std::endl;
+      return 1;
+    }
+  }
   if (g_times.on)
     std::cerr << "Timing: count_topo samples: inputs " << t1 - t0 - g_triple_stage_s << " s, triple stage " << g_triple_stage_s << " s (device kernels "
-              << colate_topo_samples_kernel_seconds() << " s), files " << StageTimes::now() - t1 << " s; " << (in.row_off.empty() ? 0LL : in.row_off.back())
+              << g_kernel_s << " s), files " << StageTimes::now() - t1 << " s; " << (in.row_off.empty() ? 0LL : in.row_off.back())
               << " rows, " << in.S << " samples, " << triples.size() << " triples" << std::endl;
   print_usage_footer();
   return 0;
@@ -211,6 +310,11 @@ int run_topo_samples(const Options& opt) {
 
 int run_count_topo(const Options& opt) {
   if (opt.has("samples")) return run_topo_samples(opt);
+  for (const char* o : {"age_profile", "profile_only"})
+    if (opt.has(o)) {
+      std::cerr << "Error: --" << o << " needs --mode count_topo --samples: the single run of one triple writes its SNP lines only." << std::endl;
+      return 1;
+    }
   const bool missing = !opt.has("target_tmp") || !opt.has("reference_tmp") || !opt.has("input") || !opt.has("mut") || !opt.has("output");
   if (missing || opt.has("help")) {  // coal.cpp:4528-4538
     if (missing) {
@@ -230,10 +334,11 @@ int run_count_topo(const Options& opt) {
   ps.cond = opt.get("input"), ps.target = opt.get("target_tmp"), ps.reference = opt.get("reference_tmp"), ps.output = opt.get("output");
   const char* e = std::getenv("COLATE_DEVICE_TOPO");
   const Path want = e && std::string(e) == "1" ? Path::device : Path::cursors;
-  WalkInputs in;
+  const std::vector<PairSpec> one(1, ps);
+  Staged st;
   std::vector<std::vector<TopoLine>> lines;
   std::vector<long long> draws;
-  if (!draw_triples(opt, names, mut_files, std::vector<PairSpec>(1, ps), want, seed, in, lines, draws)) return 1;
+  if (!stage_triples(opt, names, mut_files, one, want, seed, st) || !draw_triples(st, names, one, lines, draws)) return 1;
   if (!write_lines(ps.output, names, lines[0])) return 1;
   print_usage_footer();
   return 0;

@@ -560,6 +560,30 @@ int colate_topo_samples_tile(void); /* rows of a tile of the draw kernel (no dev
 int colate_topo_samples_chunks(void);
 double colate_topo_samples_kernel_seconds(void);
 
+/* ---- the age profile of those draws: signed counts per epoch, no plane leaves the call (csrc/count_topo.h: age_epoch) ----
+ * Inputs and draws as for colate_topo_samples.  epochs[E]: finite and strictly ascending, 1 <= E <= 1024 (the command line takes
+ * them from colate_epochs_from_bins(spec, 0, years_per_gen), the epochs of a .coal).  The epoch of a row is the number of e in
+ * 1 .. E - 1 with epochs[e] <= (double)mid, where mid = 0.5f * (age_begin + age_end) is formed in single precision; a NaN or
+ * negative mid gives 0, +inf gives E - 1.  Out: counts[P][E][3] -- per triple and epoch the rows of that epoch set in `plus`, in
+ * `minus`, and the qualifying rows (those that drew) -- and draws[P].  Integers only: no result depends on an order of operations.
+ * Refused, by name and before anything is written: what colate_topo_samples refuses of its inputs and stream, E out of range, an
+ * epoch that is not finite, neighbours that do not ascend, NULL outputs.
+ * _host: the host twin.  colate_topo_profile: on the calling thread's device (COLATE_ENODEVICE without one), the staging, plane
+ * kernel, count kernel and host wait of colate_topo_samples; a bins kernel, one lane per row, once for all triples (2 bytes per
+ * row); then per chunk of triples -- 12 E bytes per (triple, chromosome), a chunk within 256 MB (COLATE_TOPO_BUDGET) -- the profile
+ * kernel: the draw kernel's scan, ranks and draws, with every lane of a qualifying row adding to a 3 x E histogram in the
+ * workgroup's LDS (integer adds), written out as the workgroup's own partials; one copy per chunk, and the host sums the
+ * chromosomes in long long.  The same integers whatever the chunking.
+ * colate_topo_profile_chunks / _kernel_seconds: diagnostics of the calling thread's last device call. */
+int colate_topo_profile(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                        const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms,
+                        const double* uniforms, int E, const double* epochs, long long* counts, long long* draws);
+int colate_topo_profile_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                             const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms,
+                             const double* uniforms, int E, const double* epochs, long long* counts, long long* draws);
+int colate_topo_profile_chunks(void);
+double colate_topo_profile_kernel_seconds(void);
+
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
 int colate_age_grid(double* age_grid, int cap);
