@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "coalrate.h"
-#include "mut_feeder.h"
+#include "mut_inputs.h"
 
 namespace colate_drv {
 

@@ -19,9 +19,11 @@
 #include <string>
 #include <vector>
 
+#include "cli_lists.h"
+#include "cli_modes.h"
 #include "colate_amd.h"
 #include "compare_tmp.h"
-#include "mut_feeder.h"
+#include "walk_inputs.h"
 
 namespace colate_drv {
 
@@ -37,30 +39,18 @@ bool write_windows(const std::string& path, const std::vector<std::string>& name
     for (int w = 0; w < chr[c].windows; w++, at++)
       os << names[c] << " " << (int)((long long)chr[c].first_pos + (long long)w * colate_cmp::kBinSize) << " " << (double)mismatch[at] << " "
          << (double)snps[at] << "\n";
-  os.close();
-  if (!os) {
-    std::cerr << "Error: cannot write " << path << std::endl;
-    return false;
-  }
-  return true;
+  return close_checked(os, path);
 }
 
-enum class Path { cursors, host_twin, device };
 double g_pair_stage_s = 0;  // the seconds of the pair stage alone, whichever form ran (COLATE_TIMING)
 
 // Loads the inputs of `pairs` and counts every pair: mismatch / snps [P][sum of windows].  False after an error message;
 // nothing has been written then.
 bool count_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
                  const std::vector<PairSpec>& pairs, Path want, WalkInputs& in, std::vector<int>& mismatch, std::vector<int>& snps) {
-  for (const PairSpec& ps : pairs)
-    for (const std::string* f : {&ps.target, &ps.reference}) {
-      FILE* fp = std::fopen(f->c_str(), "rb");
-      if (!fp) {
-        std::cerr << "Error: cannot open " << *f << std::endl;
-        return false;
-      }
-      std::fclose(fp);
-    }
+  std::vector<const std::string*> files;
+  for (const PairSpec& ps : pairs) files.insert(files.end(), {&ps.target, &ps.reference});
+  if (!check_readable(files, "cannot open")) return false;
   if (!load_walk_inputs(names, mut_files, pairs, in, RowSet::compare_tmp)) return false;
   if (!in.files_ok) {
     std::cerr << "Error: a .colate.in file could not be read." << std::endl;
@@ -92,8 +82,7 @@ bool count_pairs(const Options& opt, const std::vector<std::string>& names, cons
   v.pairs = in.pairs.data(), v.first_pos = first.data(), v.last_pos = last.data(), v.window = colate_cmp::kBinSize;
   mismatch.assign(P * (size_t)Wt, 0), snps.assign(P * (size_t)Wt, 0);
   std::vector<long long> win_off((size_t)C + 1);
-  if (want == Path::device && opt.has("device"))
-    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc), false;
+  if (want == Path::device && !bind_device(opt)) return false;
   const long long cap = (long long)P * Wt;
   if (int rc = want == Path::device ? colate_cmp::compare_view_device(v, cap, win_off.data(), mismatch.data(), snps.data())
                                     : colate_cmp::compare_view_host(v, cap, win_off.data(), mismatch.data(), snps.data()))
@@ -108,12 +97,10 @@ bool count_pairs(const Options& opt, const std::vector<std::string>& names, cons
 }
 
 int run_compare_samples(const Options& opt) {
-  for (const char* o : {"pairs", "target_tmp", "reference_tmp", "target_mask", "reference_mask", "target_age", "reference_age", "bins", "coal",
-                        "num_bootstraps", "ranks", "devices"})
-    if (opt.has(o)) {
-      std::cerr << "Error: --" << o << " cannot be combined with --mode compare_tmp --samples." << std::endl;
-      return 1;
-    }
+  if (refuse_options(opt, {"pairs", "target_tmp", "reference_tmp", "target_mask", "reference_mask", "target_age", "reference_age", "bins", "coal",
+                           "num_bootstraps", "ranks", "devices"},
+                     "--mode compare_tmp --samples"))
+    return 1;
   if (!opt.has("mut") || !opt.has("output")) {
     std::cerr << "Error: --samples needs --mut and -o PREFIX (optional: --chr, --seed, --device)." << std::endl;
     return 1;
@@ -128,30 +115,13 @@ int run_compare_samples(const Options& opt) {
       return 1;
     }
   std::vector<PairSpec> pairs;
-  std::vector<std::pair<std::string, std::string>> pair_names;
-  for (const SampleLine& t : samples)
-    for (const SampleLine& r : samples) {
-      if (!t.target || !r.reference || &t == &r) continue;
-      PairSpec ps;
-      ps.target = t.file, ps.reference = r.file, ps.output = opt.get("output") + "_" + t.name + "_" + r.name + ".txt", ps.line = t.line;
-      pairs.push_back(ps);
-      pair_names.emplace_back(t.name, r.name);
-    }
-  if (pairs.empty()) {
-    std::cerr << "Error: " << opt.get("samples") << ": no pair of a target and a reference on different lines." << std::endl;
-    return 1;
-  }
+  if (!sample_pairs(samples, opt.get("output"), opt.get("samples"), pairs)) return 1;
+  for (PairSpec& ps : pairs) ps.output += ".txt";
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Comparing Colate tmp input files for " << pairs.size() << " pairs.." << std::endl;
-  Path want = Path::device;
-  const char* e = std::getenv("COLATE_DEVICE_COMPARE");
-  if (e && std::string(e) == "0") {
-    std::cerr << "pairs compared on the host (COLATE_DEVICE_COMPARE=0)" << std::endl;
-    want = Path::host_twin;
-  } else if (colate_device_count() <= 0) {
-    std::cerr << "pairs compared on the host (no device)" << std::endl;
-    want = Path::host_twin;
-  }
+  std::string why;
+  const Path want = choose_path("COLATE_DEVICE_COMPARE", true, why);
+  if (want != Path::device) std::cerr << "pairs compared on the host (" << why << ")" << std::endl;
   const double t0 = StageTimes::now();
   WalkInputs in;
   std::vector<int> mismatch, snps;
@@ -163,13 +133,9 @@ int run_compare_samples(const Options& opt) {
     if (!write_windows(pairs[p].output, names, in.compare, mismatch.data() + p * Wt, snps.data() + p * Wt)) return 1;
     long long mm = 0, n = 0;
     for (size_t w = 0; w < Wt; w++) mm += mismatch[p * Wt + w], n += snps[p * Wt + w];
-    os << pair_names[p].first << " " << pair_names[p].second << " " << mm << " " << n << "\n";
+    os << pairs[p].target_name << " " << pairs[p].ref_name << " " << mm << " " << n << "\n";
   }
-  os.close();
-  if (!os) {
-    std::cerr << "Error: cannot write " << opt.get("output") << ".pairs.txt" << std::endl;
-    return 1;
-  }
+  if (!close_checked(os, opt.get("output") + ".pairs.txt")) return 1;
   if (g_times.on)
     std::cerr << "Timing: compare samples: inputs " << t1 - t0 - g_pair_stage_s << " s, pair stage " << g_pair_stage_s << " s (device kernels "
               << colate_compare_samples_kernel_seconds() << " s), files " << StageTimes::now() - t1 << " s; " << (in.row_off.empty() ? 0LL : in.row_off.back()) << " rows, "
@@ -193,13 +159,13 @@ int run_compare_tmp(const Options& opt) {
   }
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating Colate tmp input file for " << opt.get("target_tmp") << ".." << std::endl;
-  if (opt.has("seed")) (void)std::stoi(opt.get("seed"));  // (read as the reference reads it; the draws decide nothing)
+  if (opt.has("seed")) (void)opt.get_int("seed");  // (read as the reference reads it; the draws decide nothing)
   std::vector<std::string> names, mut_files;
   chromosome_files(opt, names, mut_files);
   PairSpec ps;
   ps.target = opt.get("target_tmp"), ps.reference = opt.get("reference_tmp"), ps.output = opt.get("output");
-  const char* e = std::getenv("COLATE_DEVICE_COMPARE");
-  const Path want = e && std::string(e) == "1" ? Path::device : Path::cursors;
+  std::string why;
+  const Path want = choose_path("COLATE_DEVICE_COMPARE", false, why);
   WalkInputs in;
   std::vector<int> mismatch, snps;
   if (!count_pairs(opt, names, mut_files, std::vector<PairSpec>(1, ps), want, in, mismatch, snps)) return 1;

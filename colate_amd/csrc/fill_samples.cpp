@@ -1,7 +1,7 @@
 // colate_amd/csrc/fill_samples.cpp -- the host side of colate_fill_samples (fill_samples.h: the contract): the checks of both
 // forms, the host twin -- a plain loop per pair with a std::mt19937 of its own, the logarithm of age_bin_index and the redraw
 // loop of coal.cpp:2279-2295, so it is right for every input --, the chunk plan of the device form, the C entry points, and
-// fill_sample_pairs, the fill of `Colate --mode mut --samples` around the device form (mut_feeder.h).
+// fill_sample_pairs, the fill of `Colate --mode mut --samples` around the device form (mut_inputs.h).
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -12,12 +12,13 @@
 #include <vector>
 
 #include "age_bins.hpp"
+#include "cli_lists.h"
 #include "colate_amd.h"
 #include "colate_internal.h"
 #include "fill_samples.h"
 #include "interval_walk.h"
-#include "mut_feeder.h"
 #include "uniform_stream.hpp"
+#include "walk_inputs.h"
 
 using colate::fail;
 using colate_drv::FillRec;
@@ -189,7 +190,7 @@ int fill_call(bool device, const FlatView& f, int A, unsigned seed, long long ca
 
 namespace colate_drv {
 
-// (mut_feeder.h)
+// (mut_inputs.h)
 bool fill_sample_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
                        const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& out) {
   const auto through_engine = [&](const char* why) {
@@ -199,18 +200,16 @@ bool fill_sample_pairs(const Options& opt, const std::vector<std::string>& names
   for (const char* name : {"COLATE_DEVICE_FILL", "COLATE_DEVICE_FILL_WALK"})
     if (const char* e = std::getenv(name))
       if (std::atoi(e) == 0) return through_engine((std::string(name) + "=0").c_str());
-  if (colate_device_count() < 1) return through_engine("no device");
-  if (opt.has("device"))
-    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc) == 0;
+  std::string why;
+  if (choose_path(nullptr, true, why) != Path::device) return through_engine(why.c_str());
+  if (!bind_device(opt)) return false;
   const double t0 = StageTimes::now();
   std::vector<PairSpec> mine;
   for (size_t p : todo) mine.push_back(pairs[p]);
   WalkInputs in;
   if (!load_walk_inputs(names, mut_files, mine, in)) return false;
   if (!in.indexed) return through_engine("a sample has no walk index");
-  View v;
-  v.C = (int)names.size(), v.row_off = in.row_off.data(), v.rows = in.row_ptrs.data(), v.S = in.S, v.idx = in.idx_ptrs.data(), v.M = in.M;
-  v.masks = in.mask_ptrs.data(), v.P = (int)mine.size(), v.pairs = in.pairs.data(), v.nbpb = kIntervalBasesPerBlock;
+  const View v = in.walk_view(kIntervalBasesPerBlock);
   const double t1 = StageTimes::now();
   colate_fs::Result res;
   if (int rc = colate_fs::fill_view_device(v, A, (unsigned)seed, res)) return api_error(rc) == 0;

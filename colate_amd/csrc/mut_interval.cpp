@@ -11,15 +11,11 @@
 // With --pairs LIST the second form runs for every line of the list in one pass (colate_interval_fit_groups); with
 // --samples LIST for every target x reference pair of a sample list, the pairs walked on the device
 // (colate_interval_fit_samples).
-#include <unistd.h>
-
 #include <algorithm>
 #include <cerrno>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <ctime>
 #include <fstream>
 #include <iostream>
 #include <map>
@@ -29,9 +25,12 @@
 #include <tuple>
 #include <vector>
 
+#include "cli_lists.h"
+#include "cli_modes.h"
 #include "colate_amd.h"
 #include "interval_walk.h"
 #include "mut_interval.h"
+#include "walk_inputs.h"
 
 namespace colate_drv {
 
@@ -193,62 +192,24 @@ static bool write_interval_rows(const std::string& path, const IntervalRows& row
   return std::fclose(f) == 0;
 }
 
-// What the runs of `--mode mut_interval` share (one pair, --pairs, --samples): the fit options, the choice between device and
-// host twin, epochs and starting rates, and what is said per bootstrap and written per pair.
-struct FitRun {
-  double years_per_gen = 28.0;
-  int B = 1, max_iter = COLATE_DEFAULT_MAX_ITER, min_iter = COLATE_DEFAULT_MIN_ITER;
-  int seed = 0;
+// What the runs of `--mode mut_interval` share (one pair, --pairs, --samples) besides the run's options: the choice between device
+// and host twin, epochs and starting rates, and what is said and written per pair.
+struct FitRun : RunOptions {
+  using RunOptions::RunOptions;
   std::string host_why;  // not empty: the host twins run
   int status = 0;
 };
-static bool fit_run_options(const Options& opt, FitRun& run) {
-  run.seed = std::time(0) + getpid();  // coal.cpp:3158; one seed for the whole run
-  if (opt.has("years_per_gen")) run.years_per_gen = std::stof(opt.get("years_per_gen"));
-  if (opt.has("seed")) run.seed = std::stoi(opt.get("seed"));
-  if (opt.has("num_bootstraps")) run.B = std::stoi(opt.get("num_bootstraps"));
-  if (opt.has("max_iter")) run.max_iter = std::stoi(opt.get("max_iter"));
-  if (opt.has("min_iter")) run.min_iter = std::stoi(opt.get("min_iter"));
-  if (run.B < 1) {
-    std::cerr << "Error: --num_bootstraps must be at least 1." << std::endl;
-    return false;
-  }
-  return true;
-}
 // device or host twin (false after an error message)
 static bool fit_run_device(const Options& opt, FitRun& run) {
-  if (const char* e = std::getenv("COLATE_DEVICE_INTERVAL"))
-    if (std::string(e) == "0") run.host_why = "COLATE_DEVICE_INTERVAL=0";
-  if (run.host_why.empty() && colate_device_count() <= 0) run.host_why = "no device";
-  if (run.host_why.empty() && opt.has("device"))
-    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc), false;
-  return true;
+  return choose_path("COLATE_DEVICE_INTERVAL", true, run.host_why) != Path::device || bind_device(opt);
 }
 // Epochs and starting rates at age 0, as for `mut` with a modern sample (coal.cpp:3501-3646): those of the .coal file where one
 // is given, else --bins with the default starting rate.  False after `lead` and the library's message on stderr.
 static bool fit_run_epochs(const Options& opt, const FitRun& run, const std::string* coal, const std::string& lead, std::vector<double>& epochs,
                            std::vector<double>& init, int& ep_null) {
-  epochs.assign(COLATE_MAX_EPOCHS, 0.0), init.assign(COLATE_MAX_EPOCHS, COLATE_DEFAULT_INIT_RATE);
-  ep_null = 0;
-  const int E = coal ? colate_epochs_from_coal(coal->c_str(), 0.0, epochs.data(), init.data(), COLATE_MAX_EPOCHS)
-                     : colate_epochs_from_bins(opt.get("bins").c_str(), 0.0, run.years_per_gen, epochs.data(), COLATE_MAX_EPOCHS, &ep_null);
-  if (E <= 0) {
-    std::cerr << lead << colate_last_error() << std::endl;
-    return false;
-  }
-  epochs.resize(E), init.resize(E);
-  return true;
-}
-// the lines of a fit's B bootstraps: `lead` in front of each, `who` in front of "bootstrap" in a warning
-static void say_bootstraps(const std::string& lead, const std::string& who, int B, const int* iters, const int* flags) {
-  for (int i = 0; i < B; i++) {
-    std::cerr << lead << "Bootstrap " << i + 1 << ": Total iterations " << iters[i] << std::endl;
-    if (flags[i] & (COLATE_FLAG_NAN | COLATE_FLAG_NEG))
-      std::cerr << "Warning: " << who << "bootstrap " << i + 1 << " produced NaN or negative sufficient statistics." << std::endl;
-  }
-}
-static void say_blocks(size_t p, size_t P, const PairSpec& ps, int nb) {
-  std::cerr << "Pair " << p + 1 << " / " << P << ": " << ps.target << " x " << ps.reference << ": Number of blocks: " << nb << std::endl;
+  const bool ok = epochs_for(opt, coal, 0.0, run.years_per_gen, epochs, init, ep_null) > 0;
+  if (!ok) std::cerr << lead << colate_last_error() << std::endl;
+  return ok;
 }
 // the lines of pair p after its fit, and its .coal (rates: [B][E] of the pair)
 static void report_pair(FitRun& run, size_t p, const PairSpec& ps, int R, long long dropped, int E, const double* epochs, int ep_null,
@@ -262,11 +223,8 @@ static void report_pair(FitRun& run, size_t p, const PairSpec& ps, int R, long l
     run.status = 1;
     return;
   }
-  say_bootstraps(lead, "pair " + std::to_string(p + 1) + " ", run.B, iters, flags);
-  if (colate_write_coal((ps.output + ".coal").c_str(), run.B, E, epochs, rates, 0, ep_null)) {
-    std::cerr << "Error: " << colate_last_error() << std::endl;
-    run.status = 1;
-  }
+  report_bootstraps((int)p + 1, run.B, E, iters, flags, false);
+  if (!write_coal(ps.output, run.B, E, epochs, rates, false, ep_null)) run.status = 1;
 }
 
 // The pairs of a list (`--pairs`, or the expanded list of `--samples` where its pairs cannot be walked over indices): every
@@ -309,14 +267,7 @@ static int fit_pair_list(const Options& opt, FitRun& run, const std::vector<std:
   }
 
   // ---- classes of pairs with the same number of epochs, in order of first appearance: one grouped call each
-  std::vector<std::vector<size_t>> classes;
-  for (size_t p = 0; p < P; p++) {
-    if (!usable[p]) continue;
-    size_t c = 0;
-    while (c < classes.size() && epochs[classes[c][0]].size() != epochs[p].size()) c++;
-    if (c == classes.size()) classes.emplace_back();
-    classes[c].push_back(p);
-  }
+  const std::vector<std::vector<size_t>> classes = classes_by_epoch_count(epochs, &usable);
   std::cerr << "Maximising likelihood using EM.. " << std::endl;
   if (!run.host_why.empty()) std::cerr << "interval cells and fits on the host (" << run.host_why << ")" << std::endl;
   for (const std::vector<size_t>& cls : classes) {
@@ -373,16 +324,10 @@ static int fit_pair_list(const Options& opt, FitRun& run, const std::vector<std:
 
 // `--mode mut_interval --pairs LIST`: the single run above for every line of the list, in one pass (fit_pair_list).
 static int run_mut_interval_pairs(const Options& opt) {
-  for (const char* o : {"target_tmp", "reference_tmp", "rows", "write_rows", "output", "ranks", "target_age", "reference_age"})
-    if (opt.has(o)) {
-      std::cerr << "Error: --" << o << " cannot be combined with --mode mut_interval --pairs." << std::endl;
-      return 1;
-    }
-  for (const char* o : {"target_mask", "reference_mask", "coal"})
-    if (opt.has(o)) {  // (the wording of `--mode mut --pairs`)
-      std::cerr << "Error: --" << o << " cannot be combined with --pairs (give it per line: " << o << "=...)." << std::endl;
-      return 1;
-    }
+  if (refuse_options(opt, {"target_tmp", "reference_tmp", "rows", "write_rows", "output", "ranks", "target_age", "reference_age"},
+                     "--mode mut_interval --pairs") ||
+      refuse_per_line_options(opt))
+    return 1;
   if (!opt.has("mut")) {
     std::cerr << "Error: --pairs needs --mut (and optionally --chr, --bins, --num_bootstraps, --seed, --years_per_gen, --max_iter, "
                  "--min_iter, --device)."
@@ -399,34 +344,27 @@ static int run_mut_interval_pairs(const Options& opt) {
                 << ": --mode mut_interval takes modern samples only: a line cannot carry sample ages." << std::endl;
       return 1;
     }
-  if (!opt.has("bins"))
-    for (size_t p = 0; p < pairs.size(); p++)
-      if (pairs[p].coal.empty()) {  // (a line with coal= takes its epochs from that file)
-        std::cerr << "Error: --pairs needs --bins for pair " << p + 1 << " (it names no coal= file)." << std::endl;
-        return 1;
-      }
+  if (!pairs_have_epochs(opt, pairs)) return 1;
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating coalescence rates from interval-dated mutations for " << pairs.size() << " pairs.." << std::endl;
-  FitRun run;
-  if (!fit_run_options(opt, run)) return 1;
+  FitRun run(opt);
+  if (!run.read_replicates(opt, true)) return 1;
   if (!fit_run_device(opt, run)) return 1;
   return fit_pair_list(opt, run, names, mut_files, pairs, nullptr);
 }
 
 // ------------------------------------------------------------------ `--mode mut_interval --samples LIST`
-// (the list: read_sample_list, mut_feeder.h; no ages here)
+// (the list: read_sample_list, cli_lists.h; no ages here)
 // Every (target line, reference line) of the list with different lines, targets outermost; each pair's PREFIX_<target>_<reference>.coal
 // is, byte for byte, what `--pairs` writes for it given the expanded list.  Where every file has a walk index the pairs are not
 // walked on the host at all: N index arrays and the rows go to the device once and colate_interval_fit_samples forms every pair's
 // records where the cells kernel reads them (its host twin without a device or with COLATE_DEVICE_INTERVAL=0).  Otherwise, or with
 // COLATE_DEVICE_INTERVAL_WALK=0, the expanded list takes the path of `--pairs` after one line on stderr.
 static int run_mut_interval_samples(const Options& opt) {
-  for (const char* o : {"pairs", "rows", "target_tmp", "reference_tmp", "write_rows", "target_mask", "reference_mask", "ranks", "target_age",
-                        "reference_age"})
-    if (opt.has(o)) {
-      std::cerr << "Error: --" << o << " cannot be combined with --mode mut_interval --samples." << std::endl;
-      return 1;
-    }
+  if (refuse_options(opt, {"pairs", "rows", "target_tmp", "reference_tmp", "write_rows", "target_mask", "reference_mask", "ranks", "target_age",
+                           "reference_age"},
+                     "--mode mut_interval --samples"))
+    return 1;
   if (!opt.has("mut") || !opt.has("output") || (!opt.has("bins") && !opt.has("coal"))) {
     std::cerr << "Error: --samples needs --mut, -o PREFIX and --bins x,y,stepsize or --coal FILE (optional: --chr, --num_bootstraps, --seed, "
                  "--years_per_gen, --max_iter, --min_iter, --device)."
@@ -438,23 +376,12 @@ static int run_mut_interval_samples(const Options& opt) {
   std::vector<SampleLine> samples;
   if (!read_sample_list(opt.get("samples"), opt, names, false, samples)) return 1;
   std::vector<PairSpec> pairs;
-  for (const SampleLine& t : samples)
-    for (const SampleLine& r : samples) {
-      if (!t.target || !r.reference || &t == &r) continue;
-      PairSpec ps;
-      ps.target = t.file, ps.reference = r.file, ps.output = opt.get("output") + "_" + t.name + "_" + r.name;
-      ps.target_masks = t.masks, ps.ref_masks = r.masks, ps.line = t.line;
-      pairs.push_back(ps);
-    }
-  if (pairs.empty()) {
-    std::cerr << "Error: " << opt.get("samples") << ": no pair of a target and a reference on different lines." << std::endl;
-    return 1;
-  }
+  if (!sample_pairs(samples, opt.get("output"), opt.get("samples"), pairs)) return 1;
   const size_t P = pairs.size();
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating coalescence rates from interval-dated mutations for " << P << " pairs.." << std::endl;
-  FitRun run;
-  if (!fit_run_options(opt, run)) return 1;
+  FitRun run(opt);
+  if (!run.read_replicates(opt, true)) return 1;
   if (!fit_run_device(opt, run)) return 1;
   if (const char* e = std::getenv("COLATE_DEVICE_INTERVAL_WALK"))
     if (std::string(e) == "0") {
@@ -480,9 +407,7 @@ static int run_mut_interval_samples(const Options& opt) {
             << std::endl;
   std::cerr << "Maximising likelihood using EM.. " << std::endl;
   if (on_host) std::cerr << "interval cells and fits on the host (" << run.host_why << ")" << std::endl;
-  colate_iw::View v;
-  v.C = (int)names.size(), v.row_off = in.row_off.data(), v.rows = in.row_ptrs.data(), v.S = in.S, v.idx = in.idx_ptrs.data(), v.M = in.M;
-  v.masks = in.mask_ptrs.data(), v.P = (int)P, v.pairs = in.pairs.data(), v.nbpb = kIntervalBasesPerBlock;
+  const colate_iw::View v = in.walk_view(kIntervalBasesPerBlock);
   const size_t PB = P * (size_t)run.B;
   std::vector<int> nb(P), R(P), iters(PB), flags(PB);
   std::vector<long long> used(P), dropped(P);
@@ -512,10 +437,7 @@ int run_mut_interval(const Options& opt) {
   if (opt.has("samples")) return run_mut_interval_samples(opt);
   if (opt.has("pairs")) return run_mut_interval_pairs(opt);
   const bool from_mut = opt.has("mut") || opt.has("target_tmp") || opt.has("reference_tmp");
-  if (from_mut && opt.has("rows")) {
-    std::cerr << "Error: --rows cannot be combined with --mut, --target_tmp or --reference_tmp." << std::endl;
-    return 1;
-  }
+  if (from_mut && refuse_options(opt, {"rows"}, "--mut, --target_tmp or --reference_tmp")) return 1;
   if (from_mut && (opt.has("target_age") || opt.has("reference_age"))) {
     std::cerr << "Error: --mode mut_interval takes modern samples only: --target_age and --reference_age are not supported." << std::endl;
     return 1;
@@ -530,8 +452,8 @@ int run_mut_interval(const Options& opt) {
   }
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating coalescence rates from interval-dated mutations.." << std::endl;
-  FitRun run;
-  if (!fit_run_options(opt, run)) return 1;
+  FitRun run(opt);
+  if (!run.read_replicates(opt, true)) return 1;
   // ---- epochs and starting rates (--coal, else --bins; the library's message without a lead), then device or host twin
   std::vector<double> epochs, init_rates;
   int ep_null = 0;
@@ -579,11 +501,8 @@ int run_mut_interval(const Options& opt) {
                                                                max_iter, min_iter, COLATE_DEFAULT_REL_TOL, COLATE_DEFAULT_RATE_FLOOR,
                                                                rates.data(), iters.data(), ll.data(), flags.data(), 1);
   if (rc) return api_error(rc);
-  say_bootstraps("", "", B, iters.data(), flags.data());
-  if (colate_write_coal((opt.get("output") + ".coal").c_str(), B, E, epochs.data(), rates.data(), 0, ep_null)) {
-    std::cerr << "Error: " << colate_last_error() << std::endl;
-    return 1;
-  }
+  report_bootstraps(0, B, E, iters.data(), flags.data(), false);
+  if (!write_coal(opt.get("output"), B, E, epochs.data(), rates.data(), false, ep_null)) return 1;
   print_usage_footer();
   return 0;
 }

@@ -1,11 +1,9 @@
 // colate_amd/csrc/mut_interval.h -- `Colate --mode mut_interval`: the rows file of interval-dated observations per genome
 // block -- or the SNPs a pair uses, through colate_interval_cells -- and the driver around colate_bootstrap_em_interval_batch
-// (mut_interval.cpp); with --pairs, the driver around colate_interval_fit_groups.
+// (mut_interval.cpp; its entry point: cli_modes.h); with --pairs, the driver around colate_interval_fit_groups.
 #pragma once
 #include <string>
 #include <vector>
-
-#include "mut_feeder.h"
 
 namespace colate_drv {
 
@@ -25,7 +23,5 @@ struct IntervalRows {
 // colate_em_interval_calls accepts for epochs[0] = epoch0), a finite weight >= 0 -- is an error: false, and `err` names
 // the file and the line number.  A file without rows is an error as well.
 bool read_interval_rows(const std::string& path, double epoch0, IntervalRows& out, std::string& err);
-
-int run_mut_interval(const Options& opt);
 
 }  // namespace colate_drv

@@ -52,8 +52,10 @@
 #include "count_topo.h"
 #include "fill_device.h"
 #include "interval_cells.h"
-#include "mut_feeder.h"
+#include "mut_inputs.h"
+#include "rank_ctx.h"
 #include "uniform_stream.hpp"
+#include "walk_inputs.h"
 
 namespace colate_drv {
 namespace {
@@ -1426,7 +1428,7 @@ bool collect(const PairFill& pf, int A, PairTables& pt) {
 
 }  // namespace
 
-// (mut_feeder.h)
+// (mut_inputs.h)
 bool fill_pairs(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
                 const std::vector<PairSpec>& pairs, const std::vector<size_t>& todo, int seed, int A, std::vector<PairTables>& out) {
   const double C = 10;
@@ -1548,7 +1550,7 @@ Inputs load_all(Pool& pool, const std::vector<std::string>& names, const std::ve
 
 }  // namespace
 
-// (mut_feeder.h)
+// (walk_inputs.h)
 bool collect_interval_records_pairs(const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
                                     const std::vector<PairSpec>& pairs, std::vector<PairRecords>& out) {
   const double t0 = now_s();
@@ -1563,7 +1565,7 @@ bool collect_interval_records_pairs(const std::vector<std::string>& names, const
   return true;
 }
 
-// (mut_feeder.h)
+// (walk_inputs.h)
 struct WalkInputs::Loaded {
   Inputs in;
 };
@@ -1635,7 +1637,7 @@ bool collect_interval_records_loaded(const WalkInputs& loaded, const std::vector
   return true;
 }
 
-// (mut_feeder.h)
+// (walk_inputs.h)
 bool compare_cursor_pairs(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& pairs,
                           std::vector<int>& mismatch, std::vector<int>& snps) {
   if (!loaded.loaded || loaded.compare.size() != names.size()) return false;
@@ -1657,7 +1659,7 @@ bool compare_cursor_pairs(const WalkInputs& loaded, const std::vector<std::strin
   return true;
 }
 
-// (mut_feeder.h)
+// (walk_inputs.h)
 bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, unsigned seed,
                          std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws, TopoProfile* profile) {
   if (!loaded.loaded || loaded.loaded->in.rows.size() != names.size()) return false;

@@ -19,7 +19,8 @@
 
 #include "colate_amd.h"
 #include "compare_tmp.h"
-#include "mut_feeder.h"
+#include "cli_lists.h"
+#include "walk_inputs.h"
 
 namespace {
 

@@ -22,7 +22,8 @@
 #include "colate_amd.h"
 #include "fill_samples.h"
 #include "interval_walk.h"
-#include "mut_feeder.h"
+#include "cli_lists.h"
+#include "walk_inputs.h"
 
 namespace {
 

@@ -24,7 +24,8 @@
 
 #include "colate_amd.h"
 #include "interval_groups.h"
-#include "mut_feeder.h"
+#include "cli_lists.h"
+#include "walk_inputs.h"
 
 namespace {
 

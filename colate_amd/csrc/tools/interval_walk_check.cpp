@@ -19,7 +19,8 @@
 
 #include "colate_amd.h"
 #include "interval_walk.h"
-#include "mut_feeder.h"
+#include "cli_lists.h"
+#include "walk_inputs.h"
 
 namespace {
 

@@ -23,7 +23,8 @@
 
 #include "colate_amd.h"
 #include "count_topo.h"
-#include "mut_feeder.h"
+#include "cli_lists.h"
+#include "walk_inputs.h"
 
 namespace {
 

@@ -15,21 +15,19 @@
 //     (count_topo.h: age_epoch) into the epochs of `--mode mut --bins x,y,s` -- through colate_topo_profile, a second pass over the
 //     staged inputs.  `--profile_only`: no per-triple file; PREFIX.triples.txt from the profile's sums, the same bytes; only the
 //     profile call runs, and no plane, bit or line is formed.
-#include <unistd.h>
-
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
-#include <ctime>
 #include <fstream>
 #include <iostream>
 #include <random>
 #include <string>
 #include <vector>
 
+#include "cli_lists.h"
+#include "cli_modes.h"
 #include "colate_amd.h"
 #include "count_topo.h"
-#include "mut_feeder.h"
+#include "walk_inputs.h"
 
 namespace colate_drv {
 
@@ -44,23 +42,11 @@ bool write_lines(const std::string& path, const std::vector<std::string>& names,
     if (l.sign > 0) os << 1 << " " << ((double)l.DAF) / l.N << "\n";
     else os << -1 << " " << -((double)l.DAF) / l.N << "\n";
   }
-  os.close();
-  if (!os) {
-    std::cerr << "Error: cannot write " << path << std::endl;
-    return false;
-  }
-  return true;
+  return close_checked(os, path);
 }
 
-enum class Path { cursors, host_twin, device };
 double g_triple_stage_s = 0;  // the seconds of the triple stage alone, whichever forms ran (COLATE_TIMING)
 double g_kernel_s = 0;        // ... and of its kernels on the device
-
-unsigned run_seed(const Options& opt) {  // coal.cpp:4545-4549
-  int seed = (int)(std::time(nullptr) + getpid());
-  if (opt.has("seed")) seed = std::stoi(opt.get("seed"));
-  return (unsigned)seed;
-}
 
 // The inputs of `triples` (PairSpec with its cond file) as every form of the triple stage takes them: loaded once, the form
 // decided, and -- for the two indexed forms -- the run's stream and the view.
@@ -78,15 +64,9 @@ struct Staged {
 bool stage_triples(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
                    const std::vector<PairSpec>& triples, Path want, unsigned seed, Staged& st) {
   WalkInputs& in = st.in;
-  for (const PairSpec& ps : triples)
-    for (const std::string* f : {&ps.cond, &ps.target, &ps.reference}) {  // coal.cpp:4588-4603
-      FILE* fp = std::fopen(f->c_str(), "rb");
-      if (!fp) {
-        std::cerr << "Error: Failed to open " << *f << std::endl;
-        return false;
-      }
-      std::fclose(fp);
-    }
+  std::vector<const std::string*> files;
+  for (const PairSpec& ps : triples) files.insert(files.end(), {&ps.cond, &ps.target, &ps.reference});  // coal.cpp:4588-4603
+  if (!check_readable(files, "Failed to open")) return false;
   if (!load_walk_inputs(names, mut_files, triples, in, RowSet::count_topo)) return false;
   if (!in.files_ok) {
     std::cerr << "Error: a .colate.in file could not be read." << std::endl;
@@ -115,9 +95,7 @@ bool stage_triples(const Options& opt, const std::vector<std::string>& names, co
   colate_topo::View& v = st.v;
   v.C = C, v.row_off = in.row_off.data(), v.rows = in.row_ptrs.data(), v.S = in.S, v.idx = in.idx_ptrs.data(), v.cidx = in.cidx_ptrs.data();
   v.P = (int)P, v.triples = st.ids.data(), v.n_uniforms = (long long)st.u.size(), v.uniforms = st.u.data();
-  if (want == Path::device && opt.has("device"))
-    if (int rc = colate_set_device(std::stoi(opt.get("device")))) return api_error(rc), false;
-  return true;
+  return want != Path::device || bind_device(opt);
 }
 
 // Draws every staged triple: the lines each prints and its qualifying rows.  profile: on the cursor path the same walk fills it.
@@ -188,12 +166,10 @@ bool profile_triples(const Staged& st, const std::vector<std::string>& names, co
 }
 
 int run_topo_samples(const Options& opt) {
-  for (const char* o : {"input", "pairs", "target_tmp", "reference_tmp", "target_mask", "reference_mask", "target_age", "reference_age", "bins", "coal",
-                        "num_bootstraps", "ranks", "devices"})
-    if (opt.has(o)) {
-      std::cerr << "Error: --" << o << " cannot be combined with --mode count_topo --samples." << std::endl;
-      return 1;
-    }
+  if (refuse_options(opt, {"input", "pairs", "target_tmp", "reference_tmp", "target_mask", "reference_mask", "target_age", "reference_age", "bins",
+                           "coal", "num_bootstraps", "ranks", "devices"},
+                     "--mode count_topo --samples"))
+    return 1;
   if (!opt.has("mut") || !opt.has("output")) {
     std::cerr << "Error: --samples needs --mut and -o PREFIX (optional: --chr, --seed, --device, --age_profile, --years_per_gen, --profile_only)."
               << std::endl;
@@ -208,7 +184,7 @@ int run_topo_samples(const Options& opt) {
   std::vector<double> epochs, boundaries;
   TopoProfile profile;
   if (profiled) {
-    const double years_per_gen = opt.has("years_per_gen") ? std::stof(opt.get("years_per_gen")) : 28.0;
+    const double years_per_gen = RunOptions(opt).years_per_gen;
     epochs.resize(colate_topo::kMaxProfileEpochs);
     const int E = colate_epochs_from_bins(opt.get("age_profile").c_str(), 0.0, years_per_gen, epochs.data(), (int)epochs.size(), nullptr);
     if (E < 0) return api_error(E);
@@ -246,18 +222,12 @@ int run_topo_samples(const Options& opt) {
     std::cerr << "Error: " << opt.get("samples") << ": no triple of a cond, a target and a reference on three different lines." << std::endl;
     return 1;
   }
-  const unsigned seed = run_seed(opt);
+  const unsigned seed = (unsigned)run_seed(opt);
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Counting topologies for " << triples.size() << " triples.." << std::endl;
-  Path want = Path::device;
-  const char* e = std::getenv("COLATE_DEVICE_TOPO");
-  if (e && std::string(e) == "0") {
-    std::cerr << "triples drawn on the host (COLATE_DEVICE_TOPO=0)" << std::endl;
-    want = Path::host_twin;
-  } else if (colate_device_count() <= 0) {
-    std::cerr << "triples drawn on the host (no device)" << std::endl;
-    want = Path::host_twin;
-  }
+  std::string why;
+  const Path want = choose_path("COLATE_DEVICE_TOPO", true, why);
+  if (want != Path::device) std::cerr << "triples drawn on the host (" << why << ")" << std::endl;
   const double t0 = StageTimes::now();
   Staged st;
   std::vector<std::vector<TopoLine>> lines;
@@ -280,11 +250,7 @@ int run_topo_samples(const Options& opt) {
     }
     os << triple_names[p] << " " << plus << " " << minus << " " << draws[p] << "\n";
   }
-  os.close();
-  if (!os) {
-    std::cerr << "Error: cannot write " << opt.get("output") << ".triples.txt" << std::endl;
-    return 1;
-  }
+  if (!close_checked(os, opt.get("output") + ".triples.txt")) return 1;
   if (profiled) {  // `cond target reference epoch plus minus qualifying`: every epoch of every triple, the epoch as a .coal prints it
     std::ofstream pr(opt.get("output") + ".profile.txt");
     for (size_t p = 0; p < triples.size(); p++)
@@ -292,11 +258,7 @@ int run_topo_samples(const Options& opt) {
         const long long* const x = &profile.counts[(p * (size_t)profile.E + (size_t)e) * 3];
         pr << triple_names[p] << " " << epochs[(size_t)e] << " " << x[0] << " " << x[1] << " " << x[2] << "\n";
       }
-    pr.close();
-    if (!pr) {
-      std::cerr << "Error: cannot write " << opt.get("output") << ".profile.txt" << std::endl;
-      return 1;
-    }
+    if (!close_checked(pr, opt.get("output") + ".profile.txt")) return 1;
   }
   if (g_times.on)
     std::cerr << "Timing: count_topo samples: inputs " << t1 - t0 - g_triple_stage_s << " s, triple stage " << g_triple_stage_s << " s (device kernels "
@@ -327,13 +289,13 @@ int run_count_topo(const Options& opt) {
   }
   std::cerr << "---------------------------------------------------------" << std::endl;
   std::cerr << "Calculating Colate tmp input file for " << opt.get("target_tmp") << ".." << std::endl;
-  const unsigned seed = run_seed(opt);
+  const unsigned seed = (unsigned)run_seed(opt);
   std::vector<std::string> names, mut_files;
   chromosome_files(opt, names, mut_files);
   PairSpec ps;
   ps.cond = opt.get("input"), ps.target = opt.get("target_tmp"), ps.reference = opt.get("reference_tmp"), ps.output = opt.get("output");
-  const char* e = std::getenv("COLATE_DEVICE_TOPO");
-  const Path want = e && std::string(e) == "1" ? Path::device : Path::cursors;
+  std::string why;
+  const Path want = choose_path("COLATE_DEVICE_TOPO", false, why);
   const std::vector<PairSpec> one(1, ps);
   Staged st;
   std::vector<std::vector<TopoLine>> lines;

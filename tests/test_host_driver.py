@@ -588,7 +588,7 @@ def test_ranks_refused_once_the_process_has_used_the_device(ca, tmp_path):
 
 
 def _counts(tmp_path, threads, extra=()):
-    """COLATE_THREADS=1: the pair through the sequential feeder of mut_driver.cpp; more: the engine of the batched front end
+    """COLATE_THREADS=1: the pair through the sequential feeder of mut_readers.cpp; more: the engine of the batched front end
     (mut_pairs.cpp) with a list of one pair."""
     env = dict(os.environ, COLATE_THREADS=str(threads), COLATE_TIMING="1")
     out = f"c{threads}"
