@@ -750,6 +750,62 @@ def topo_profile_kernel_seconds():
     return lib.colate_topo_profile_kernel_seconds()
 
 
+def topo_blocks(row_off, rows, num_bases_per_block):
+    """colate_topo_blocks: blk_off [C + 1] int32 of the searched rows (no device needed).  With k(pos) = (pos - 1) //
+    num_bases_per_block for pos > 0, else 0, a chromosome owns k(pos of its last row) + 1 blocks, or 1 without a row; a row's global
+    block is blk_off[c] + k(pos).  A function of the rows alone: not the blocks of `--mode mut`."""
+    row_off = np.ascontiguousarray(row_off, dtype=np.int64).ravel()
+    rows = np.ascontiguousarray(rows, dtype=WALK_ROW).ravel()
+    if row_off.size >= 2 and row_off[0] == 0 and (np.diff(row_off) >= 0).all() and row_off[-1] != rows.size:
+        raise ValueError("row_off[-1] must be the number of rows")  # (else the library names what is wrong)
+    blk_off = np.zeros(max(row_off.size, 1), dtype=np.int32)
+    check(lib.colate_topo_blocks(row_off.size - 1, _p(row_off), _p(rows), int(num_bases_per_block), _p(blk_off)))
+    return blk_off
+
+
+def topo_profile_blocks(row_off, rows, idx, cond_idx, triples, uniforms, epochs, num_bases_per_block, device=True):
+    """colate_topo_profile_blocks[_host]: topo_profile per genome block of topo_blocks, from the same draws.  Returns (blk_off
+    [C + 1] int32, counts [P, nb, E, 3] int64 -- plus, minus, qualifying --, draws [P] int64); counts.sum(axis=1) is topo_profile's
+    counts for every num_bases_per_block.  device=False: the host twin, the same integers."""
+    blk_off = topo_blocks(row_off, rows, num_bases_per_block)
+    args, keep = _walk_inputs(row_off, rows, idx, None, np.zeros(0, dtype=WALK_PAIR))
+    cond_idx = np.ascontiguousarray(cond_idx, dtype=WALK_IDX)
+    if cond_idx.shape != keep[2].shape:
+        raise ValueError("cond_idx must be [S][rows], as idx")
+    triples = np.ascontiguousarray(triples, dtype=TOPO_TRIPLE).ravel()
+    uniforms = _f64(uniforms).ravel()
+    epochs = _f64(epochs).ravel()
+    P, E, nb = triples.size, epochs.size, int(blk_off[-1])
+    counts, draws = np.zeros((P, nb, E, 3), dtype=np.int64), np.zeros(P, dtype=np.int64)
+    fn = lib.colate_topo_profile_blocks if device else lib.colate_topo_profile_blocks_host
+    check(fn(args[0], args[1], args[2], args[3], args[4], _p(cond_idx), P, _p(triples), uniforms.size, _p(uniforms), E, _p(epochs),
+             int(num_bases_per_block), nb, _p(counts), _p(draws)))
+    return blk_off, counts, draws
+
+
+def topo_profile_blocks_chunks():
+    """Chunks of triples in this thread's last topo_profile_blocks(device=True) (diagnostic)."""
+    return lib.colate_topo_profile_blocks_chunks()
+
+
+def topo_profile_blocks_kernel_seconds():
+    """Seconds the kernels of this thread's last topo_profile_blocks(device=True) took on the device."""
+    return lib.colate_topo_profile_blocks_kernel_seconds()
+
+
+def topo_jackknife(counts):
+    """colate_topo_jackknife: the weighted delete-one block jackknife (Busing, Meijer and van der Leeden) on one triple's counts
+    [nb, E, 3] of topo_profile_blocks.  Returns (stats [E + 1, 4] float64 -- D, D_jack, se, Z per epoch and, last, for the sum over
+    the epochs; NaN: not available --, used [E + 1] int32: the blocks with plus + minus > 0).  Host only."""
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    if counts.ndim != 3 or counts.shape[2] != 3:
+        raise ValueError("counts must be [nb][E][3], one triple's")
+    nb, E = counts.shape[:2]
+    stats, used = np.zeros((E + 1, 4), dtype=np.float64), np.zeros(E + 1, dtype=np.int32)
+    check(lib.colate_topo_jackknife(nb, E, _p(counts), _p(stats), _p(used)))
+    return stats, used
+
+
 def fill_samples_chunks():
     """Chunks of the write pass in this thread's last fill_samples(device=True) (diagnostic)."""
     return lib.colate_fill_samples_chunks()

@@ -1,10 +1,12 @@
 // colate_amd/csrc/count_topo.cpp -- the host side of colate_topo_samples (count_topo.h: the contract): the checks both forms run
 // before anything is written, the host twin of the three device kernels -- bit planes per sample, a popcount per triple, the
-// ranked draws --, the same draws binned by age for colate_topo_profile, and the C entry points, which view the caller's
-// back-to-back arrays chromosome by chromosome.
+// ranked draws --, the same draws binned by age for colate_topo_profile and by genome block and age for
+// colate_topo_profile_blocks, the blocks themselves, the block jackknife on those counts (colate_topo_jackknife: host only), and the
+// C entry points, which view the caller's back-to-back arrays chromosome by chromosome.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "colate_amd.h"
@@ -182,6 +184,151 @@ int topo_profile_host(const View& v, int E, const double* epochs, long long* cou
   return COLATE_OK;
 }
 
+int block_offsets(int C, const int* max_pos, int nbpb, int* blk_off) {
+  if (C < 1) return fail(COLATE_EINVAL, "bad sizes C=%d (at least one chromosome)", C);
+  if (!max_pos || !blk_off) return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (nbpb < 1) return fail(COLATE_EINVAL, "num_bases_per_block = %d: at least 1", nbpb);
+  long long nb = 0;
+  for (int c = 0; c < C; c++) {
+    if ((long long)max_pos[c] >= (1LL << 31) - nbpb)
+      return fail(COLATE_EINVAL, "chromosome %d: position %d at or above 2^31 - num_bases_per_block (%d)", c, max_pos[c], nbpb);
+    nb += block_of_pos(max_pos[c], nbpb) + 1;
+  }
+  if (nb > kMaxTopoBlocks)
+    return fail(COLATE_ELIMIT, "%lld blocks of %d bases, %d are possible (needed: %lld)", nb, nbpb, kMaxTopoBlocks, nb);
+  blk_off[0] = 0;
+  for (int c = 0; c < C; c++) blk_off[c + 1] = blk_off[c] + block_of_pos(max_pos[c], nbpb) + 1;
+  return COLATE_OK;
+}
+
+int topo_blocks(int C, const long long* row_off, const Row* const* rows, int nbpb, int* blk_off) {
+  if (C < 1) return fail(COLATE_EINVAL, "bad sizes C=%d (at least one chromosome)", C);
+  if (!row_off || !blk_off) return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (row_off[0] != 0) return fail(COLATE_EINVAL, "row_off[0] = %lld must be 0", row_off[0]);
+  for (int c = 0; c < C; c++)
+    if (row_off[c + 1] < row_off[c])
+      return fail(COLATE_EINVAL, "row_off decreases at chromosome %d (%lld after %lld)", c, row_off[c + 1], row_off[c]);
+  if (row_off[C] > 0 && !rows) return fail(COLATE_EINVAL, "NULL pointer argument");
+  std::vector<int> max_pos((size_t)C, 0);
+  for (int c = 0; c < C; c++) {
+    const long long nc = row_off[c + 1] - row_off[c];
+    if (nc > 0 && !rows[c]) return fail(COLATE_EINVAL, "NULL pointer argument");
+    for (long long i = 0; i < nc; i++) max_pos[(size_t)c] = std::max(max_pos[(size_t)c], rows[c][i].pos);
+  }
+  return block_offsets(C, max_pos.data(), nbpb, blk_off);
+}
+
+int check_blocks(const View& v, int E, int nbpb, int nb, std::vector<int>& blk_off) {
+  blk_off.assign((size_t)v.C + 1, 0);
+  if (int rc = topo_blocks(v.C, v.row_off, v.rows, nbpb, blk_off.data())) return rc;
+  if (nb != blk_off[(size_t)v.C])
+    return fail(COLATE_EINVAL, "nb = %d is not the %d blocks of these rows at %d bases per block (colate_topo_blocks)", nb, blk_off[(size_t)v.C], nbpb);
+  const long long bytes = 12LL * E * nb;
+  if (bytes > kMaxBlockPartialBytes)
+    return fail(COLATE_ELIMIT, "%d epochs x %d blocks: %lld bytes of partials per triple, %lld are possible", E, nb, bytes, kMaxBlockPartialBytes);
+  return COLATE_OK;
+}
+
+void block_segments(const View& v, int nbpb, const int* blk_off, Segment* seg) {
+  for (int c = 0; c < v.C; c++) {
+    const Row* const r = v.rows[c];
+    const long long nc = v.row_off[c + 1] - v.row_off[c];
+    const int nbc = blk_off[c + 1] - blk_off[c];
+    long long first = 0;  // (positions ascend: the rows of block k are those between two partition points)
+    for (int k = 0; k < nbc; k++) {
+      const long long end =
+          k + 1 == nbc ? nc : std::partition_point(r + first, r + nc, [&](const Row& m) { return block_of_pos(m.pos, nbpb) <= k; }) - r;
+      seg[blk_off[c] + k] = Segment{c, (int)first, (int)end};
+      first = end;
+    }
+  }
+}
+
+int topo_profile_blocks_host(const View& v, int E, const double* epochs, int nbpb, int nb, long long* counts, long long* draws) {
+  if (!counts || !draws) return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (int rc = check_epochs(E, epochs)) return rc;
+  if (int rc = check_view(v)) return rc;
+  std::vector<int> blk_off;
+  if (int rc = check_blocks(v, E, nbpb, nb, blk_off)) return rc;
+  std::vector<long long> woff((size_t)v.C + 1);
+  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
+  std::vector<unsigned long long> planes((size_t)v.S * 2 * (size_t)words);
+  for (int s = 0; s < v.S; s++) host_planes(v, s, woff.data(), words, planes.data() + (size_t)s * 2 * (size_t)words);
+  auto plane = [&](int s, int which) { return planes.data() + ((size_t)s * 2 + (size_t)which) * (size_t)words; };
+  std::vector<long long> n((size_t)v.P, 0);
+  for (int p = 0; p < v.P; p++) {
+    const unsigned long long *T = plane(v.triples[p].target, 0), *R = plane(v.triples[p].reference, 0), *Cq = plane(v.triples[p].cond, 1);
+    for (long long k = 0; k < words; k++) n[(size_t)p] += __builtin_popcountll(T[k] & R[k] & Cq[k]);
+  }
+  if (int rc = check_stream(v, n.data())) return rc;
+  // the draw pass of topo_profile_host: the rank runs on across blocks and chromosomes; the row's position names the block
+  const size_t per_block = (size_t)E * 3;
+  std::memset(counts, 0, sizeof(long long) * (size_t)v.P * (size_t)nb * per_block);
+  for (int p = 0; p < v.P; p++) {
+    const Triple& t = v.triples[p];
+    const unsigned long long *T = plane(t.target, 0), *R = plane(t.reference, 0), *Cq = plane(t.cond, 1);
+    long long* const mine = counts + (size_t)p * (size_t)nb * per_block;
+    long long rank = 0;
+    for (int c = 0; c < v.C; c++) {
+      const Idx* const TI = v.idx[(size_t)t.target * v.C + c];
+      const Idx* const RI = v.idx[(size_t)t.reference * v.C + c];
+      const Row* const rows = v.rows[c];
+      for (long long k = woff[(size_t)c]; k < woff[(size_t)c + 1]; k++)
+        for (unsigned long long q = T[k] & R[k] & Cq[k]; q; q &= q - 1, rank++) {
+          const long long i = (k - woff[(size_t)c]) * 64 + __builtin_ctzll(q);
+          const int sign = draw_sign(TI[i], RI[i], v.uniforms[2 * rank], v.uniforms[2 * rank + 1]);
+          const size_t b = (size_t)(blk_off[(size_t)c] + block_of_pos(rows[i].pos, nbpb));
+          long long* const at = mine + b * per_block + (size_t)age_epoch(rows[i].age_begin, rows[i].age_end, epochs, E) * 3;
+          at[2]++;
+          if (sign > 0) at[0]++;
+          if (sign < 0) at[1]++;
+        }
+    }
+    draws[p] = rank;
+  }
+  return COLATE_OK;
+}
+
+void jackknife(int nb, int E, const long long* counts, double* out, int* used) {
+  const double na = std::numeric_limits<double>::quiet_NaN();
+  std::vector<long long> a((size_t)nb), b((size_t)nb);
+  for (int cell = 0; cell <= E; cell++) {
+    long long A = 0, M = 0;
+    int g = 0;
+    for (int j = 0; j < nb; j++) {
+      long long aj = 0, bj = 0;
+      for (int e = cell < E ? cell : 0; e < (cell < E ? cell + 1 : E); e++)
+        aj += counts[((size_t)j * E + e) * 3], bj += counts[((size_t)j * E + e) * 3 + 1];
+      a[(size_t)j] = aj, b[(size_t)j] = bj, A += aj, M += bj, g += aj + bj > 0;
+    }
+    double* const o = out + (size_t)cell * 4;
+    o[0] = o[1] = o[2] = o[3] = na, used[cell] = g;
+    const long long n = A + M;
+    if (n == 0) continue;
+    const double D = (double)(A - M) / (double)n;
+    o[0] = D;
+    if (g < 2) continue;
+    auto theta = [&](size_t j) { return (double)((A - a[j]) - (M - b[j])) / (double)(n - (a[j] + b[j])); };
+    double s = 0.0;
+    for (size_t j = 0; j < (size_t)nb; j++) {
+      const long long nj = a[j] + b[j];
+      if (nj > 0) s += ((double)(n - nj) / (double)n) * theta(j);
+    }
+    const double D_jack = (double)g * D - s;
+    double var = 0.0;
+    for (size_t j = 0; j < (size_t)nb; j++) {
+      const long long nj = a[j] + b[j];
+      if (nj == 0) continue;
+      const double h = (double)n / (double)nj;
+      const double tau = h * D - (h - 1.0) * theta(j);
+      const double d = tau - D_jack;
+      var += (d * d) / (h - 1.0);
+    }
+    const double se = std::sqrt(var / (double)g);
+    o[1] = D_jack, o[2] = se, o[3] = se > 0 ? D_jack / se : na;
+  }
+}
+
 namespace {
 
 // the caller's back-to-back arrays, chromosome by chromosome
@@ -247,6 +394,40 @@ int colate_topo_profile(int C, const long long* row_off, const colate_walk_row* 
                         int E, const double* epochs, long long* counts, long long* draws) {
   const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, n_uniforms, uniforms);
   return topo_profile_device(f.v, E, epochs, counts, draws);
+}
+
+int colate_topo_blocks(int C, const long long* row_off, const colate_walk_row* rows, int num_bases_per_block, int* blk_off) {
+  std::vector<const Row*> ptrs;
+  bool ok = C >= 1 && row_off && row_off[0] == 0;
+  for (int c = 0; ok && c < C; c++) ok = row_off[c + 1] >= row_off[c];
+  if (ok && rows)  // (topo_blocks names what is wrong with the sizes or offsets: nothing is dereferenced before it)
+    for (int c = 0; c < C; c++) ptrs.push_back(rows + row_off[c]);
+  return topo_blocks(C, row_off, ptrs.empty() ? nullptr : ptrs.data(), num_bases_per_block, blk_off);
+}
+
+int colate_topo_profile_blocks_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                                    const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms,
+                                    const double* uniforms, int E, const double* epochs, int num_bases_per_block, int nb, long long* counts,
+                                    long long* draws) {
+  const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, n_uniforms, uniforms);
+  return topo_profile_blocks_host(f.v, E, epochs, num_bases_per_block, nb, counts, draws);
+}
+
+int colate_topo_profile_blocks(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                               const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms,
+                               const double* uniforms, int E, const double* epochs, int num_bases_per_block, int nb, long long* counts,
+                               long long* draws) {
+  const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, n_uniforms, uniforms);
+  return topo_profile_blocks_device(f.v, E, epochs, num_bases_per_block, nb, counts, draws);
+}
+
+int colate_topo_jackknife(int nb, int E, const long long* counts, double* out, int* used) {
+  if (nb < 1 || E < 1) return fail(COLATE_EINVAL, "bad sizes nb=%d E=%d (at least one block and one epoch)", nb, E);
+  if (!counts || !out || !used) return fail(COLATE_EINVAL, "NULL pointer argument");
+  for (size_t k = 0; k < (size_t)nb * (size_t)E * 3; k++)
+    if (counts[k] < 0) return fail(COLATE_EINVAL, "counts[%zu] = %lld is negative", k, counts[k]);
+  jackknife(nb, E, counts, out, used);
+  return COLATE_OK;
 }
 
 int colate_topo_samples_tile(void) { return kTileRows; }

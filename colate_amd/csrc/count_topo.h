@@ -45,6 +45,7 @@
 
 namespace colate_topo {
 
+using colate_iw::block_of_pos;
 using colate_iw::Idx;
 using colate_iw::Row;
 using Triple = colate_topo_triple;
@@ -84,6 +85,32 @@ COLATE_IC_HD inline int age_epoch(float age_begin, float age_end, const double* 
   return lo;
 }
 
+// THE BLOCKS OF THIS MODE (colate_topo_blocks, colate_topo_profile_blocks, `--jackknife`).  A function of the searched rows alone,
+// not of the triple: with nbpb bases per block the block of a searched row within its chromosome is k(pos) = block_of_pos(pos,
+// nbpb) (interval_walk.h: pos in (k nbpb, (k + 1) nbpb], everything up to nbpb in block 0).  A chromosome owns k(pos of its last
+// searched row) + 1 blocks -- the largest k of its rows; positions ascend in every indexed form -- or 1 block without a searched
+// row; a row's global block is the sum of the earlier chromosomes' block counts plus k(pos); nb is the sum over the chromosomes.  A
+// block that holds no searched row exists and is all zeros (a gap in the positions leaves one).  These are NOT the blocks of
+// `--mode mut`, which start at a pair's first used row and so depend on the pair.
+// Per (triple, block, epoch) the three integers of the age profile, from the same draws: a triple's qualifying row number k,
+// counted across the whole genome in order, reads uniforms 2k and 2k + 1 whatever the blocks, so the sum over a triple's blocks is
+// colate_topo_profile's counts in every integer, for every nbpb.
+constexpr int kMaxTopoBlocks = 65535;
+constexpr long long kMaxBlockPartialBytes = 1LL << 30;  // one triple's partials, 12 E nb bytes
+// blk_off[C + 1] from max_pos[C], the largest position of each chromosome's searched rows (0 without one).  Refused: nbpb < 1, a
+// position at or above 2^31 - nbpb, more than kMaxTopoBlocks blocks (COLATE_ELIMIT with the needed number).
+int block_offsets(int C, const int* max_pos, int nbpb, int* blk_off);
+
+// THE BLOCK JACKKNIFE (colate_topo_jackknife): the one copy of the arithmetic, host only.  counts[nb][E][3] of one triple; cell e <
+// E is epoch e, cell E the sum over the epochs.  Per cell, with a_j = plus, b_j = minus, n_j = a_j + b_j of block j, the used blocks
+// those with n_j > 0 in ascending order, g of them, and the integers A = sum a_j, M = sum b_j, n = A + M: D = (A - M) / n; for g >=
+// 2 the weighted delete-one jackknife of Busing, Meijer and van der Leeden (1999) -- theta_j = ((A - a_j) - (M - b_j)) / (n - n_j),
+// h_j = n / n_j, D_jack = g D - sum_j ((n - n_j) / n) theta_j, pseudo-values tau_j = h_j D - (h_j - 1) theta_j, se^2 = (1 / g) sum_j
+// (tau_j - D_jack)^2 / (h_j - 1), Z = D_jack / se -- every operation an IEEE double, rounded, in the order written in
+// count_topo.cpp, no contraction.  out[E + 1][4]: D, D_jack, se, Z, NaN for "not available" (all four at n == 0; all but D at
+// g < 2; Z where se is not > 0); used[E + 1]: g.
+void jackknife(int nb, int E, const long long* counts, double* out, int* used);
+
 // The inputs of both stages: every row given is a searched row; idx[s * C + c] is sample s's walk index of chromosome c,
 // cidx[s * C + c] its cond index.
 struct View {
@@ -116,6 +143,20 @@ int topo_view_device(const View& v, long long cap, long long* word_off, unsigned
 int check_epochs(int E, const double* epochs);
 int topo_profile_host(const View& v, int E, const double* epochs, long long* counts, long long* draws);
 int topo_profile_device(const View& v, int E, const double* epochs, long long* counts, long long* draws);
+// The blocks of the view's rows (above): blk_off[C + 1].  No device.
+int topo_blocks(int C, const long long* row_off, const Row* const* rows, int nbpb, int* blk_off);
+// The age profile per block, host twin / device stage: counts[P][nb][E][3] and draws[P].  Refused besides what the profile refuses,
+// by name and before anything is written: what topo_blocks refuses, an nb that is not blk_off[C], one triple's partials above
+// kMaxBlockPartialBytes (COLATE_ELIMIT).
+int check_blocks(const View& v, int E, int nbpb, int nb, std::vector<int>& blk_off);
+int topo_profile_blocks_host(const View& v, int E, const double* epochs, int nbpb, int nb, long long* counts, long long* draws);
+int topo_profile_blocks_device(const View& v, int E, const double* epochs, int nbpb, int nb, long long* counts, long long* draws);
+// A block as the device stage takes it: the rows [first, end) of chromosome c (first == end: no row)
+struct Segment {
+  int c, first, end;
+};
+// seg[nb] of the view's blocks: every searched row lies in exactly one
+void block_segments(const View& v, int nbpb, const int* blk_off, Segment* seg);
 
 // THE CURSOR WALK of one chromosome: the reference's loop over three record cursors, correct for every input.  Cur: a cursor
 // with match, bp, anc, der, AAF, DAF, set_name() and next() (mut_pairs.cpp: Cursor); RowT: pos, anc, der.  draw(): the next
@@ -173,5 +214,15 @@ hipError_t bins_launch(const colate_iw::DeviceInputs& in, int E, const double* e
 // plus, minus, qualifying -- in an LDS histogram of the (triple, chromosome)'s workgroup
 hipError_t profile_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
                           const long long* base, const double* u, const unsigned short* bin, int E, unsigned* part, hipStream_t stream);
+// cnt[(p - p0) * nb + b] = popc(Q) over the rows of block b for triples [p0, p1): one wave per (triple, block), the segment's first
+// and last word masked
+hipError_t block_count_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
+                              int nb, const Segment* seg, int* cnt, hipStream_t stream);
+// part[((p - p0) * nb + b)][3][E] for triples [p0, p1): profile_launch per (triple, block) -- the same scan, ranks and draws over
+// the segment's words, a word cut by a block boundary read by both neighbours, each keeping its own rows; base[p * nb + b]: the rank
+// of the block's first qualifying row; an empty segment writes zeros
+hipError_t block_profile_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
+                                int nb, const Segment* seg, const long long* base, const double* u, const unsigned short* bin, int E, unsigned* part,
+                                hipStream_t stream);
 }  // namespace colate_topo
 #endif

@@ -24,6 +24,15 @@
 //     word's two ballots, every lane with a set bit of Q reads its row's epoch and adds 1 to the workgroup's 3 x E histogram in
 //     LDS -- integer adds, whose sum has no order --, and behind a barrier the workgroup writes its own 3 E words of partials.
 //     No global atomics; the host sums the chromosomes' partials in long long.  No plane leaves the device.
+//
+// The profile per genome block (colate_topo_profile_blocks; count_topo.h: the blocks of this mode) runs the staging, planes and bins,
+// with every block as a segment (chromosome, first row, end row) of the searched rows, and
+//   * topo_block_count_kernel in place of the count kernel: one wave per (triple, block), the popcount of Q over the segment's
+//     words, the first and the last one masked; from these the host forms every block's base rank behind the one wait;
+//   * topo_block_profile_kernel: topo_profile_kernel per (triple, block).  draw_tiles takes a span -- the words gone through and
+//     the rows kept of each: the whole chromosome for the two kernels above, whose code is what it was, or a segment's words with
+//     the same masks --; a word cut by a block boundary is read by both neighbours and each keeps its own rows.  The same 3 x E
+//     histogram and bins; the workgroup writes its own 3 E partials, zeros for a segment without a row.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -87,23 +96,48 @@ __device__ __forceinline__ unsigned long long wave_uniform(unsigned long long v)
   return ((unsigned long long)hi << 32) | lo;
 }
 
+// The words of a chromosome a workgroup goes through, and the rows it keeps of each.  All W words and every row:
+struct WholeChromosome {
+  __device__ __forceinline__ long long first() const { return 0; }
+  __device__ __forceinline__ long long end(long long W) const { return W; }
+  __device__ __forceinline__ unsigned long long keep(long long) const { return ~0ull; }
+};
+// ... or the rows [first, end) of a block (count_topo.h: Segment): the words they touch, the first and the last one masked.  A word
+// cut by a block boundary belongs to both neighbours' ranges, and each keeps its own rows of it.  No row: no word.
+struct SegmentWords {
+  long long w_first, w_end;
+  unsigned long long m_first, m_last;
+  __device__ __forceinline__ explicit SegmentWords(const Segment& sg) {
+    const bool any = sg.end > sg.first;
+    w_first = any ? sg.first >> 6 : 0, w_end = any ? ((long long)sg.end + 63) >> 6 : 0;
+    m_first = ~0ull << (sg.first & 63), m_last = (sg.end & 63) ? ~0ull >> (64 - (sg.end & 63)) : ~0ull;
+  }
+  __device__ __forceinline__ long long first() const { return w_first; }
+  __device__ __forceinline__ long long end(long long) const { return w_end; }
+  __device__ __forceinline__ unsigned long long keep(long long k) const {
+    return (k == w_first ? m_first : ~0ull) & (k == w_end - 1 ? m_last : ~0ull);
+  }
+};
+
 // The body of the draw kernel for the (triple, chromosome) of one workgroup, over what is done with a word: sink.begin() in front
 // of a tile this wave draws, sink.word(w, kw, qw, plus, minus) at word w of the tile -- word kw of the chromosome, qw its Q,
 // the two ballots of the signs -- where qw != 0, sink.end(k, inside) behind the tile for the lane's own word k.  No barrier and
-// no LDS in here; the trip counts depend on W alone.
-template <class Sink>
+// no LDS in here; the trip counts depend on the span's words alone.  span: the words gone through and the rows kept (above); carry:
+// the rank of the span's first qualifying row.
+template <class Sink, class Span = WholeChromosome>
 __device__ __forceinline__ void draw_tiles(const DeviceInputs& in, int S, const Triple t, int c, long long carry,
-                                           const unsigned long long* __restrict__ planes, const double* __restrict__ u, Sink& sink) {
+                                           const unsigned long long* __restrict__ planes, const double* __restrict__ u, Sink& sink,
+                                           const Span span = Span()) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long long w0 = in.word_off[c], W = in.word_off[c + 1] - w0, r0 = in.row_off[c];
+  const long long w0 = in.word_off[c], W = span.end(in.word_off[c + 1] - w0), r0 = in.row_off[c];
   const unsigned long long* const hT = planes + (size_t)t.target * in.words + w0;
   const unsigned long long* const hR = planes + (size_t)t.reference * in.words + w0;
   const unsigned long long* const qC = planes + (size_t)(S + t.cond) * in.words + w0;
   const Idx* const TI = in.idx + (size_t)t.target * in.n + r0;
   const Idx* const RI = in.idx + (size_t)t.reference * in.n + r0;
-  for (long long tile0 = 0, tile = 0; tile0 < W; tile0 += kTileWords, tile++) {
+  for (long long tile0 = span.first(), tile = 0; tile0 < W; tile0 += kTileWords, tile++) {
     const long long k = tile0 + lane;
-    const unsigned long long q = k < W ? hT[k] & hR[k] & qC[k] : 0ull;
+    const unsigned long long q = k < W ? hT[k] & hR[k] & qC[k] & span.keep(k) : 0ull;
     const int n = __popcll(q);
     int incl = n;
 #pragma unroll
@@ -206,8 +240,47 @@ __global__ __launch_bounds__(kDrawWaves * 64) void topo_profile_kernel(DeviceInp
   for (int i = threadIdx.x; i < 3 * E; i += kDrawWaves * 64) mine[i] = hist[i];
 }
 
-thread_local int g_chunks = 0, g_profile_chunks = 0;
-thread_local double g_kernel_s = 0.0, g_profile_kernel_s = 0.0;
+// One wave per (triple, block): popc(Q) over the segment's words, the first and the last one masked; lane 0 writes cnt[p][b].
+__global__ __launch_bounds__(64) void topo_block_count_kernel(DeviceInputs in, int S, int p0, const Triple* __restrict__ triples,
+                                                              const unsigned long long* __restrict__ planes, int nb,
+                                                              const Segment* __restrict__ seg, int* __restrict__ cnt) {
+  const int b = blockIdx.x % nb, j = blockIdx.x / nb;  // (triple p0 + j, block b)
+  const int lane = threadIdx.x;
+  const Triple t = triples[p0 + j];
+  const Segment sg = seg[b];
+  const SegmentWords span(sg);
+  const long long w0 = in.word_off[sg.c];
+  const unsigned long long* const hT = planes + (size_t)t.target * in.words + w0;
+  const unsigned long long* const hR = planes + (size_t)t.reference * in.words + w0;
+  const unsigned long long* const qC = planes + (size_t)(S + t.cond) * in.words + w0;
+  int n = 0;
+  for (long long k = span.w_first + lane; k < span.w_end; k += 64) n += __popcll(hT[k] & hR[k] & qC[k] & span.keep(k));
+  n = wave_sum(n);  // (a chromosome has fewer than 2^31 rows)
+  if (lane == 0) cnt[(size_t)(p0 + j) * nb + b] = n;
+}
+
+// One workgroup of kDrawWaves waves per (triple, block): topo_profile_kernel over the words of the block's segment.  base: the rank
+// of the block's first qualifying row; an empty segment goes through no word and writes zeros.  Both barriers are reached by every
+// wave.
+__global__ __launch_bounds__(kDrawWaves * 64) void topo_block_profile_kernel(DeviceInputs in, int S, int p0, const Triple* __restrict__ triples,
+                                                                             const unsigned long long* __restrict__ planes, int nb,
+                                                                             const Segment* __restrict__ seg, const long long* __restrict__ base,
+                                                                             const double* __restrict__ u, const unsigned short* __restrict__ bin,
+                                                                             int E, unsigned* __restrict__ part) {
+  __shared__ unsigned hist[3 * kMaxProfileEpochs];
+  const int b = blockIdx.x % nb, j = blockIdx.x / nb;  // (triple p0 + j, block b)
+  const Segment sg = seg[b];
+  for (int i = threadIdx.x; i < 3 * E; i += kDrawWaves * 64) hist[i] = 0;
+  __syncthreads();
+  BinRows sink{bin + in.row_off[sg.c], hist, E};
+  draw_tiles(in, S, triples[p0 + j], sg.c, base[(size_t)(p0 + j) * nb + b], planes, u, sink, SegmentWords(sg));
+  __syncthreads();
+  unsigned* const mine = part + (size_t)blockIdx.x * 3 * (size_t)E;
+  for (int i = threadIdx.x; i < 3 * E; i += kDrawWaves * 64) mine[i] = hist[i];
+}
+
+thread_local int g_chunks = 0, g_profile_chunks = 0, g_blocks_chunks = 0;
+thread_local double g_kernel_s = 0.0, g_profile_kernel_s = 0.0, g_blocks_kernel_s = 0.0;
 
 // bytes of what a chunk of triples leaves on the device -- the two output planes of colate_topo_samples, the partial histograms
 // of colate_topo_profile -- (COLATE_TOPO_BUDGET: bytes, for the tests)
@@ -216,20 +289,29 @@ long long output_budget() {
   return 256LL << 20;
 }
 
-// What both device calls stage on the workspace's stream in front of their chunks of triples: the inputs resident, the planes,
+// What the device calls stage on the workspace's stream in front of their chunks of triples: the inputs resident, the planes,
 // the counts with the one host wait for them, every (triple, chromosome)'s first rank and the uniforms the longest triple needs.
+// With G and count given, the groups of a triple are not its C chromosomes: count(d_cnt) launches what fills cnt[P][G], the
+// groups in the genome's order (colate_topo_profile_blocks: the blocks).
 struct Front {
   colate_iw::Resident res;
   DeviceBuffers buf;
   std::vector<const Idx*> both;  // the walk indices, then the cond indices
   std::vector<int> cnt;
-  std::vector<long long> base, n;  // [P][C], [P]: the qualifying rows
+  std::vector<long long> base, n;  // [P][G], [P]: the qualifying rows
   unsigned long long* d_planes = nullptr;
   Triple* d_triples = nullptr;
   long long* d_base = nullptr;
   double* d_u = nullptr;
   int stage(const View& v, long long words, hipStream_t stream, colate_iw::KernelTimer& timer) {
-    const size_t PC = (size_t)v.P * v.C;
+    return stage(v, words, stream, timer, v.C, [&](int* d_cnt) {
+      if (hipError_t e = count_launch(res.in, v.S, v.P, d_triples, d_planes, d_cnt, stream)) return hip_fail(e, "topo count kernel launch");
+      return (int)COLATE_OK;
+    });
+  }
+  template <class Count>
+  int stage(const View& v, long long words, hipStream_t stream, colate_iw::KernelTimer& timer, int G, Count&& count) {
+    const size_t PC = (size_t)v.P * (size_t)G;
     cnt.resize(PC), base.resize(PC), n.assign((size_t)v.P, 0), both.resize((size_t)2 * v.S * v.C);
     std::copy_n(v.idx, (size_t)v.S * v.C, both.begin());
     std::copy_n(v.cidx, (size_t)v.S * v.C, both.begin() + (size_t)v.S * v.C);
@@ -242,13 +324,13 @@ struct Front {
     HIP_TRY(colate_iw::h2d(stream, d_triples, v.triples, sizeof(Triple) * (size_t)v.P));
     HIP_TRY(timer.mark());
     if (hipError_t e = planes_launch(res.in, v.S, d_planes, stream)) return hip_fail(e, "topo planes kernel launch");
-    if (hipError_t e = count_launch(res.in, v.S, v.P, d_triples, d_planes, d_cnt, stream)) return hip_fail(e, "topo count kernel launch");
+    if (int rc = count(d_cnt)) return rc;
     HIP_TRY(timer.mark());
     HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * PC, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));  // the one wait for the counts
     long long most = 0;
     for (int p = 0; p < v.P; p++) {
-      for (int c = 0; c < v.C; c++) base[(size_t)p * v.C + c] = n[(size_t)p], n[(size_t)p] += cnt[(size_t)p * v.C + c];
+      for (int c = 0; c < G; c++) base[(size_t)p * G + c] = n[(size_t)p], n[(size_t)p] += cnt[(size_t)p * G + c];
       most = std::max(most, n[(size_t)p]);
     }
     if (int rc = check_stream(v, n.data())) return rc;
@@ -310,6 +392,26 @@ hipError_t profile_launch(const DeviceInputs& in, int S, int p0, int p1, const T
   const long long grid = (long long)(p1 - p0) * in.C;
   if (grid > 0x7fffffffLL || E < 1 || E > kMaxProfileEpochs) return hipErrorInvalidValue;
   hipLaunchKernelGGL(topo_profile_kernel, dim3((unsigned)grid), dim3(kDrawWaves * 64), 0, stream, in, S, p0, triples, planes, base, u, bin, E, part);
+  return hipGetLastError();
+}
+
+hipError_t block_count_launch(const DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes, int nb,
+                              const Segment* seg, int* cnt, hipStream_t stream) {
+  if (p1 <= p0 || nb < 1) return hipSuccess;
+  const long long grid = (long long)(p1 - p0) * nb;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topo_block_count_kernel, dim3((unsigned)grid), dim3(64), 0, stream, in, S, p0, triples, planes, nb, seg, cnt);
+  return hipGetLastError();
+}
+
+hipError_t block_profile_launch(const DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes, int nb,
+                                const Segment* seg, const long long* base, const double* u, const unsigned short* bin, int E, unsigned* part,
+                                hipStream_t stream) {
+  if (p1 <= p0 || nb < 1) return hipSuccess;
+  const long long grid = (long long)(p1 - p0) * nb;
+  if (grid > 0x7fffffffLL || E < 1 || E > kMaxProfileEpochs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topo_block_profile_kernel, dim3((unsigned)grid), dim3(kDrawWaves * 64), 0, stream, in, S, p0, triples, planes, nb, seg, base, u,
+                     bin, E, part);
   return hipGetLastError();
 }
 
@@ -408,9 +510,80 @@ int topo_profile_device(const View& v, int E, const double* epochs, long long* c
   return COLATE_OK;
 }
 
+int topo_profile_blocks_device(const View& v, int E, const double* epochs, int nbpb, int nb, long long* counts, long long* draws) {
+  if (!counts || !draws) return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (int rc = check_epochs(E, epochs)) return rc;
+  if (int rc = check_view(v)) return rc;
+  std::vector<int> blk_off;
+  if (int rc = check_blocks(v, E, nbpb, nb, blk_off)) return rc;
+  if (int rc = check_grids_of(v)) return rc;
+  if ((v.row_off[v.C] + kPlaneTile - 1) / kPlaneTile > 0x7fffffffLL)
+    return fail(COLATE_ELIMIT, "%lld rows above the grid of the bins kernel", v.row_off[v.C]);
+  std::vector<long long> woff((size_t)v.C + 1);
+  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
+  std::vector<Segment> seg((size_t)nb);
+  block_segments(v, nbpb, blk_off.data(), seg.data());
+  if (int rc = ensure_device()) return rc;
+  ProfRange range("colate_topo_profile_blocks: H2D + planes + block counts + bins; the uniforms; per chunk of triples the binned draws of every block + D2H");
+  g_blocks_chunks = 0, g_blocks_kernel_s = 0.0;
+  if (int rc = thread_workspace().reserve(256, 256)) return rc;  // (the workspace's stream: no second one)
+  hipStream_t stream = thread_workspace().stream;
+  colate_iw::KernelTimer timer(stream);
+  Front f;
+  // triples per chunk: the partial histograms of a chunk -- 12 E bytes per (triple, block) -- within the budget, and the grid within
+  // 2^31 workgroups; one triple where its partials alone are above the budget
+  const size_t per_block = 3 * (size_t)E;
+  const long long per_triple = (long long)(per_block * sizeof(unsigned)) * nb;
+  const long long grid_most = 0x7fffffffLL / nb;
+  const long long chunk = std::max(1LL, std::min<long long>({(long long)v.P, output_budget() / per_triple, grid_most}));
+  std::vector<unsigned> part((size_t)chunk * (size_t)nb * per_block);
+  const colate_iw::StreamSync sync_at_exit{stream};
+  unsigned short* d_bin = nullptr;
+  double* d_epochs = nullptr;
+  unsigned* d_part = nullptr;
+  Segment* d_seg = nullptr;
+  HIP_TRY(f.buf.device(d_bin, (size_t)v.row_off[v.C])); HIP_TRY(f.buf.device(d_epochs, (size_t)E)); HIP_TRY(f.buf.device(d_part, part.size()));
+  HIP_TRY(f.buf.device(d_seg, (size_t)nb));
+  HIP_TRY(colate_iw::h2d(stream, d_seg, seg.data(), sizeof(Segment) * (size_t)nb));
+  // the counts per (triple, block) take the place of those per (triple, chromosome): a block's base is the sum of the blocks in front
+  const int staged = f.stage(v, words, stream, timer, nb, [&](int* d_cnt) {
+    for (long long p0 = 0; p0 < v.P; p0 += grid_most)
+      if (hipError_t e = block_count_launch(f.res.in, v.S, (int)p0, (int)std::min<long long>(v.P, p0 + grid_most), f.d_triples, f.d_planes, nb, d_seg,
+                                            d_cnt, stream))
+        return hip_fail(e, "topo block count kernel launch");
+    return (int)COLATE_OK;
+  });
+  if (staged) return staged;
+  HIP_TRY(colate_iw::h2d(stream, d_epochs, epochs, sizeof(double) * (size_t)E));
+  HIP_TRY(timer.mark());
+  if (hipError_t e = bins_launch(f.res.in, E, d_epochs, d_bin, stream)) return hip_fail(e, "topo bins kernel launch");  // once, for every triple
+  HIP_TRY(timer.mark());
+  for (long long p0 = 0; p0 < v.P; p0 += chunk) {
+    const long long p1 = std::min<long long>(v.P, p0 + chunk);
+    HIP_TRY(timer.mark());
+    if (hipError_t e = block_profile_launch(f.res.in, v.S, (int)p0, (int)p1, f.d_triples, f.d_planes, nb, d_seg, f.d_base, f.d_u, d_bin, E, d_part,
+                                            stream))
+      return hip_fail(e, "topo block profile kernel launch");
+    HIP_TRY(timer.mark());
+    HIP_TRY(hipMemcpyAsync(part.data(), d_part, sizeof(unsigned) * (size_t)(p1 - p0) * (size_t)nb * per_block, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // (the one wait at the end where one chunk holds every triple)
+    for (size_t k = 0; k < (size_t)(p1 - p0) * (size_t)nb; k++) {  // every (triple, block) owns its partials: [3][E] into [E][3]
+      const unsigned* const h = part.data() + k * per_block;
+      long long* const out = counts + ((size_t)p0 * (size_t)nb + k) * per_block;
+      for (int e = 0; e < E; e++) out[3 * e] = h[e], out[3 * e + 1] = h[E + e], out[3 * e + 2] = h[2 * E + e];
+    }
+    g_blocks_chunks++;
+  }
+  g_blocks_kernel_s = timer.seconds();
+  std::memcpy(draws, f.n.data(), sizeof(long long) * (size_t)v.P);
+  return COLATE_OK;
+}
+
 }  // namespace colate_topo
 
 extern "C" {
+int colate_topo_profile_blocks_chunks(void) { return g_blocks_chunks; }
+double colate_topo_profile_blocks_kernel_seconds(void) { return g_blocks_kernel_s; }
 int colate_topo_samples_chunks(void) { return g_chunks; }
 double colate_topo_samples_kernel_seconds(void) { return g_kernel_s; }
 int colate_topo_profile_chunks(void) { return g_profile_chunks; }

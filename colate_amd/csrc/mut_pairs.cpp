@@ -1666,6 +1666,9 @@ bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string
   const Inputs& in = loaded.loaded->in;
   lines.assign(triples.size(), std::vector<TopoLine>()), draws.assign(triples.size(), 0);
   if (profile) profile->counts.assign(triples.size() * (size_t)profile->E * 3, 0);
+  const bool blocked = profile && profile->nbpb > 0 && profile->blk_off;
+  const size_t nb = blocked ? (size_t)profile->blk_off[names.size()] : 0;
+  if (blocked) profile->blocks.assign(triples.size() * nb * (size_t)profile->E * 3, 0);
   Pool pool(pairs_threads());
   for (size_t p = 0; p < triples.size(); p++)
     pool.submit([&, p] {  // one triple per task: its three cursors go through the chromosomes in the list's order, its generator from the seed
@@ -1678,8 +1681,11 @@ bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string
         const CompactRow* const rows = in.rows[c].data();
         // (the profile: a triple's own [E][3] counts, binned by the rows' own floats)
         auto count = [&](size_t i, int which) {
-          if (profile)
-            profile->counts[(p * (size_t)profile->E + (size_t)colate_topo::age_epoch(rows[i].age_begin, rows[i].age_end, profile->epochs, profile->E)) * 3 +
+          if (!profile) return;
+          const size_t e = (size_t)colate_topo::age_epoch(rows[i].age_begin, rows[i].age_end, profile->epochs, profile->E);
+          profile->counts[(p * (size_t)profile->E + e) * 3 + (size_t)which]++;
+          if (blocked)  // (the block the row's own position names: the sinks bin by block as well)
+            profile->blocks[((p * nb + (size_t)(profile->blk_off[c] + colate_iw::block_of_pos(rows[i].pos, profile->nbpb))) * (size_t)profile->E + e) * 3 +
                             (size_t)which]++;
         };
         colate_topo::cursor_walk_chromosome(
@@ -1694,6 +1700,17 @@ bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string
     });
   pool.wait_idle();
   return true;
+}
+
+// (walk_inputs.h)
+int topo_cursor_blocks(const WalkInputs& loaded, int nbpb, std::vector<int>& blk_off) {
+  if (!loaded.loaded) return COLATE_EINVAL;
+  const Inputs& in = loaded.loaded->in;
+  std::vector<int> max_pos(in.rows.size(), 0);
+  for (size_t c = 0; c < in.rows.size(); c++)
+    for (size_t i = 0; i < in.rows[c].size(); i++) max_pos[c] = std::max(max_pos[c], in.rows[c].data()[i].pos);
+  blk_off.assign(in.rows.size() + 1, 0);
+  return colate_topo::block_offsets((int)in.rows.size(), max_pos.data(), nbpb, blk_off.data());
 }
 
 bool collect_interval_records(const std::vector<std::string>& names, const std::vector<std::string>& mut_files, const PairSpec& pair,

@@ -122,6 +122,7 @@ int compare_view_device(const View&, long long, long long*, int*, int*) { return
 namespace colate_topo {
 int topo_view_device(const View&, long long, long long*, unsigned long long*, unsigned long long*, long long*) { return nodev(); }
 int topo_profile_device(const View&, int, const double*, long long*, long long*) { return nodev(); }
+int topo_profile_blocks_device(const View&, int, const double*, int, int, long long*, long long*) { return nodev(); }
 }  // namespace colate_topo
 extern "C" {
 int colate_compare_samples_chunks(void) { return 0; }
@@ -130,6 +131,8 @@ int colate_topo_samples_chunks(void) { return 0; }
 double colate_topo_samples_kernel_seconds(void) { return 0.0; }
 int colate_topo_profile_chunks(void) { return 0; }
 double colate_topo_profile_kernel_seconds(void) { return 0.0; }
+int colate_topo_profile_blocks_chunks(void) { return 0; }
+double colate_topo_profile_blocks_kernel_seconds(void) { return 0.0; }
 }
 
 // the age sampling on the device (fill_device.h): there is none in this build, the host code samples

@@ -15,6 +15,14 @@
 //     (count_topo.h: age_epoch) into the epochs of `--mode mut --bins x,y,s` -- through colate_topo_profile, a second pass over the
 //     staged inputs.  `--profile_only`: no per-triple file; PREFIX.triples.txt from the profile's sums, the same bytes; only the
 //     profile call runs, and no plane, bit or line is formed.
+//     `--jackknife [--block_bases N]` (with --age_profile; N >= 1, default 30000000): besides, PREFIX.jackknife.txt with one line
+//     `cond target reference epoch plus minus blocks D D_jack se Z` per (triple, epoch) and, last of a triple, for epoch `all` --
+//     the delete-one block jackknife of count_topo.h over the genome blocks of this mode, which are a function of the searched rows
+//     alone.  The counts per (triple, block, epoch) come from colate_topo_profile_blocks in place of the profile call (its host twin;
+//     on the cursor path the walk's sinks bin by block); PREFIX.profile.txt and PREFIX.triples.txt are formed from their sums over
+//     the blocks, the same bytes as without the option.
+#include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -143,7 +151,8 @@ bool draw_triples(const Staged& st, const std::vector<std::string>& names, const
 }
 
 // The age profile of every staged triple (count_topo.h: age_epoch): profile.counts[P][E][3] and the qualifying rows.  No plane and
-// no line is formed on the indexed forms.
+// no line is formed on the indexed forms.  With profile.nbpb > 0 (`--jackknife`) profile.blocks[P][nb][E][3] is formed, per genome
+// block, and profile.counts from its sums over the blocks.
 bool profile_triples(const Staged& st, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, TopoProfile& profile,
                      std::vector<long long>& draws) {
   const size_t P = triples.size();
@@ -156,6 +165,22 @@ bool profile_triples(const Staged& st, const std::vector<std::string>& names, co
   }
   profile.counts.assign(P * (size_t)profile.E * 3, 0);
   draws.assign(P, 0);
+  if (profile.nbpb > 0) {
+    const int nb = profile.blk_off[st.v.C];
+    const size_t per_block = (size_t)profile.E * 3;
+    profile.blocks.assign(P * (size_t)nb * per_block, 0);
+    if (int rc = st.path == Path::device
+                     ? colate_topo::topo_profile_blocks_device(st.v, profile.E, profile.epochs, profile.nbpb, nb, profile.blocks.data(), draws.data())
+                     : colate_topo::topo_profile_blocks_host(st.v, profile.E, profile.epochs, profile.nbpb, nb, profile.blocks.data(), draws.data()))
+      return api_error(rc), false;
+    for (size_t p = 0; p < P; p++)
+      for (size_t b = 0; b < (size_t)nb; b++)
+        for (size_t k = 0; k < per_block; k++) profile.counts[p * per_block + k] += profile.blocks[(p * (size_t)nb + b) * per_block + k];
+    g_triple_stage_s += StageTimes::now() - t_stage;
+    g_kernel_s += colate_topo_profile_blocks_kernel_seconds();
+    std::cerr << st.in.S << " samples staged, " << P << " triples profiled in " << nb << " blocks on the " << st.where() << std::endl;
+    return true;
+  }
   if (int rc = st.path == Path::device ? colate_topo::topo_profile_device(st.v, profile.E, profile.epochs, profile.counts.data(), draws.data())
                                        : colate_topo::topo_profile_host(st.v, profile.E, profile.epochs, profile.counts.data(), draws.data()))
     return api_error(rc), false;
@@ -180,6 +205,27 @@ int run_topo_samples(const Options& opt) {
   if (profile_only && !profiled) {
     std::cerr << "Error: --profile_only needs --age_profile x,y,stepsize." << std::endl;
     return 1;
+  }
+  // `--jackknife [--block_bases N]`: the genome blocks of count_topo.h, N bases each
+  const bool jackknifed = opt.has("jackknife");
+  if (jackknifed && !profiled) {
+    std::cerr << "Error: --jackknife needs --age_profile x,y,stepsize." << std::endl;
+    return 1;
+  }
+  if (opt.has("block_bases") && !jackknifed) {
+    std::cerr << "Error: --block_bases needs --jackknife." << std::endl;
+    return 1;
+  }
+  int block_bases = kIntervalBasesPerBlock;
+  if (opt.has("block_bases")) {
+    const std::string& text = opt.get("block_bases");
+    char* end = nullptr;
+    const long long n = std::strtoll(text.c_str(), &end, 10);
+    if (text.empty() || *end != '\0' || n < 1 || n > INT_MAX) {
+      std::cerr << "Error: --block_bases takes an integer of at least 1 (given: " << text << ")." << std::endl;
+      return 1;
+    }
+    block_bases = (int)n;
   }
   std::vector<double> epochs, boundaries;
   TopoProfile profile;
@@ -235,6 +281,14 @@ int run_topo_samples(const Options& opt) {
   if (!stage_triples(opt, names, mut_files, triples, want, seed, st)) return 1;
   const WalkInputs& in = st.in;
   const bool one_walk = st.path == Path::cursors;  // (the cursor walk fills lines and profile at once)
+  std::vector<int> blk_off;
+  if (jackknifed) {  // the blocks are those of the searched rows, whichever form walks them
+    blk_off.resize(names.size() + 1);
+    if (int rc = one_walk ? topo_cursor_blocks(in, block_bases, blk_off)
+                          : colate_topo::topo_blocks(st.v.C, st.v.row_off, st.v.rows, block_bases, blk_off.data()))
+      return api_error(rc);
+    profile.nbpb = block_bases, profile.blk_off = blk_off.data();
+  }
   if (!profile_only && !draw_triples(st, names, triples, lines, draws, profiled && one_walk ? &profile : nullptr)) return 1;
   if (profiled && (profile_only || !one_walk) && !profile_triples(st, names, triples, profile, draws)) return 1;
   const double t1 = StageTimes::now();
@@ -260,6 +314,34 @@ int run_topo_samples(const Options& opt) {
       }
     if (!close_checked(pr, opt.get("output") + ".profile.txt")) return 1;
   }
+  if (jackknifed) {  // `cond target reference epoch plus minus blocks D D_jack se Z`: every epoch of every triple, then `all`
+    const int E = profile.E, nb = blk_off.back();
+    std::ofstream jk(opt.get("output") + ".jackknife.txt");
+    std::vector<double> stats(((size_t)E + 1) * 4);
+    std::vector<int> used((size_t)E + 1);
+    auto number = [](double x) {  // %.6g, NA for "not available"
+      char text[40];
+      std::snprintf(text, sizeof(text), "%.6g", x);
+      return std::isnan(x) ? std::string("NA") : std::string(text);
+    };
+    for (size_t p = 0; p < triples.size(); p++) {
+      colate_topo::jackknife(nb, E, &profile.blocks[p * (size_t)nb * (size_t)E * 3], stats.data(), used.data());
+      long long plus = 0, minus = 0;
+      for (int e = 0; e <= E; e++) {
+        jk << triple_names[p] << " ";
+        if (e < E) {
+          const long long* const x = &profile.counts[(p * (size_t)E + (size_t)e) * 3];
+          plus += x[0], minus += x[1];
+          jk << epochs[(size_t)e] << " " << x[0] << " " << x[1];
+        } else {
+          jk << "all " << plus << " " << minus;
+        }
+        const double* const o = &stats[(size_t)e * 4];
+        jk << " " << used[(size_t)e] << " " << number(o[0]) << " " << number(o[1]) << " " << number(o[2]) << " " << number(o[3]) << "\n";
+      }
+    }
+    if (!close_checked(jk, opt.get("output") + ".jackknife.txt")) return 1;
+  }
   if (g_times.on)
     std::cerr << "Timing: count_topo samples: inputs " << t1 - t0 - g_triple_stage_s << " s, triple stage " << g_triple_stage_s << " s (device kernels "
               << g_kernel_s << " s), files " << StageTimes::now() - t1 << " s; " << (in.row_off.empty() ? 0LL : in.row_off.back())
@@ -272,7 +354,7 @@ int run_topo_samples(const Options& opt) {
 
 int run_count_topo(const Options& opt) {
   if (opt.has("samples")) return run_topo_samples(opt);
-  for (const char* o : {"age_profile", "profile_only"})
+  for (const char* o : {"age_profile", "profile_only", "jackknife", "block_bases"})
     if (opt.has(o)) {
       std::cerr << "Error: --" << o << " needs --mode count_topo --samples: the single run of one triple writes its SNP lines only." << std::endl;
       return 1;

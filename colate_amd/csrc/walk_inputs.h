@@ -91,7 +91,15 @@ struct TopoProfile {
   int E = 0;
   const double* epochs = nullptr;
   std::vector<long long> counts;
+  // `--jackknife`: nbpb > 0 and blk_off[C + 1] in (count_topo.h: the blocks of this mode), blocks[P][nb][E][3] out -- the same
+  // three integers per genome block, whose sum over the blocks is `counts`
+  int nbpb = 0;
+  const int* blk_off = nullptr;
+  std::vector<long long> blocks;
 };
+// blk_off[C + 1] of the loaded searched rows for the cursor walk, which takes rows in any order: a chromosome owns the largest k of
+// its rows + 1 blocks.  The library's code (colate_last_error() names a refusal); COLATE_EINVAL without loaded inputs.
+int topo_cursor_blocks(const WalkInputs& loaded, int nbpb, std::vector<int>& blk_off);
 bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, unsigned seed,
                          std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws, TopoProfile* profile = nullptr);
 // mut_pairs.cpp: the cursor walk of `--mode compare_tmp` (compare_tmp.h: cursor_walk_chromosome) for every pair of a list over inputs

@@ -584,6 +584,46 @@ int colate_topo_profile_host(int C, const long long* row_off, const colate_walk_
 int colate_topo_profile_chunks(void);
 double colate_topo_profile_kernel_seconds(void);
 
+/* ---- the age profile per genome block, and the block jackknife on it (csrc/count_topo.h: the blocks of this mode) ----
+ * colate_topo_blocks: blk_off[C + 1] of the searched rows, no device.  With k(pos) = pos > 0 ? (pos - 1) / num_bases_per_block : 0
+ * a chromosome owns k(pos of its last row) + 1 blocks (the largest k of its rows), or 1 without a row; a row's global block is
+ * blk_off[c] + k(pos); blk_off[C] = nb.  A block without a row exists and is all zeros.  These blocks are a function of the rows
+ * alone; they are not those of `--mode mut`, which depend on a pair's used rows.  Refused: num_bases_per_block < 1, a position at
+ * or above 2^31 - num_bases_per_block, nb > 65535 (COLATE_ELIMIT with the needed number).
+ * colate_topo_profile_blocks: inputs, epochs and draws as for colate_topo_profile -- a triple's qualifying row number k, counted
+ * across the whole genome in order, reads uniforms[2 k] and uniforms[2 k + 1] whatever the blocks -- and counts[P][nb][E][3]: plus,
+ * minus and qualifying per (triple, block, epoch).  The sum over a triple's blocks is colate_topo_profile's counts in every integer,
+ * for every num_bases_per_block.  Refused, by name and before anything is written: what colate_topo_profile and colate_topo_blocks
+ * refuse, an nb that is not blk_off[C], one triple's partials (12 E nb bytes) above 1 GB (COLATE_ELIMIT; no E <= 1024 with nb <=
+ * 65535 reaches it).  _host: the host twin.  On the device (COLATE_ENODEVICE without one), one stream: the staging, plane kernel and
+ * bins kernel of colate_topo_profile; every block as a segment (chromosome, first row, end row); a count kernel, one wave per
+ * (triple, block), the segment's first and last word masked; one host wait, after which the host forms every block's base rank;
+ * then per chunk of triples -- 12 E bytes per (triple, block), a chunk within 256 MB (COLATE_TOPO_BUDGET), one triple where its
+ * partials alone are larger -- the profile kernel, one workgroup per (triple, block), over the segment's words with the same masks.
+ * Integers only, no global atomics: the same integers whatever the chunking.
+ * colate_topo_profile_blocks_chunks / _kernel_seconds: diagnostics of the calling thread's last device call.
+ * colate_topo_jackknife: host only, the one copy of the statistic.  counts[nb][E][3] of one triple (none negative); out[E + 1][4]:
+ * D, D_jack, se, Z per epoch and, in cell E, for the sum over the epochs; used[E + 1]: the blocks with plus + minus > 0.  Per cell,
+ * over the used blocks j in ascending order, g of them, with a_j = plus, b_j = minus, n_j = a_j + b_j, A = sum a_j, M = sum b_j,
+ * n = A + M as integers and every operation a rounded IEEE double in this order, nothing contracted: D = (double)(A - M) /
+ * (double)n; theta_j = (double)((A - a_j) - (M - b_j)) / (double)(n - n_j); h_j = (double)n / (double)n_j; s = sum of
+ * ((double)(n - n_j) / (double)n) * theta_j; D_jack = (double)g * D - s; v = sum of (d * d) / (h_j - 1.0) with d = (h_j * D -
+ * (h_j - 1.0) * theta_j) - D_jack; se = sqrt(v / (double)g); Z = D_jack / se -- the weighted delete-one jackknife of Busing,
+ * Meijer and van der Leeden (1999).  NaN stands for "not available": all four at n == 0, all but D at g < 2, Z where se is not
+ * > 0. */
+int colate_topo_blocks(int C, const long long* row_off, const colate_walk_row* rows, int num_bases_per_block, int* blk_off);
+int colate_topo_profile_blocks(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                               const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms,
+                               const double* uniforms, int E, const double* epochs, int num_bases_per_block, int nb,
+                               long long* counts, long long* draws);
+int colate_topo_profile_blocks_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                                    const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, long long n_uniforms,
+                                    const double* uniforms, int E, const double* epochs, int num_bases_per_block, int nb,
+                                    long long* counts, long long* draws);
+int colate_topo_profile_blocks_chunks(void);
+double colate_topo_profile_blocks_kernel_seconds(void);
+int colate_topo_jackknife(int nb, int E, const long long* counts, double* out, int* used);
+
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
 int colate_age_grid(double* age_grid, int cap);
