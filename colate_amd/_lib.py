@@ -124,6 +124,12 @@ SIGNATURES = {
     "colate_topo_profile_blocks_chunks": (c_int, []),
     "colate_topo_profile_blocks_kernel_seconds": (c_double, []),
     "colate_topo_jackknife": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "colate_topo_expected_blocks": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                            c_void_p]),
+    "colate_topo_expected_blocks_host": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                                 c_int, c_void_p]),
+    "colate_topo_expected_blocks_chunks": (c_int, []),
+    "colate_topo_expected_blocks_kernel_seconds": (c_double, []),
     "colate_age_grid": (c_int, [c_void_p, c_int]),
     "colate_epochs_from_bins": (c_int, [c_char_p, c_double, c_double, c_void_p, c_int, ip]),
     "colate_epochs_from_coal": (c_int, [c_char_p, c_double, c_void_p, c_void_p, c_int]),

@@ -806,6 +806,36 @@ def topo_jackknife(counts):
     return stats, used
 
 
+def topo_expected_blocks(row_off, rows, idx, cond_idx, triples, epochs, num_bases_per_block, device=True):
+    """colate_topo_expected_blocks[_host]: what the draws of topo_profile_blocks estimate, formed without a draw.  At every
+    qualifying row floor(DAF_T * AAF_R * 2^30 / (N_T * N_R)) goes to plus and floor(AAF_T * DAF_R * 2^30 / (N_T * N_R)) to minus:
+    pT (1 - pR) and (1 - pT) pR in units of 2^-30, each short of the exact product by less than 2^-30.  Returns (blk_off [C + 1]
+    int32, counts [P, nb, E, 3] int64 -- sum plus, sum minus, qualifying rows); counts[..., 2] is that of topo_profile_blocks, and
+    topo_jackknife takes counts[p] as it is.  No uniforms, no seed.  device=False: the host twin, the same integers."""
+    blk_off = topo_blocks(row_off, rows, num_bases_per_block)
+    args, keep = _walk_inputs(row_off, rows, idx, None, np.zeros(0, dtype=WALK_PAIR))
+    cond_idx = np.ascontiguousarray(cond_idx, dtype=WALK_IDX)
+    if cond_idx.shape != keep[2].shape:
+        raise ValueError("cond_idx must be [S][rows], as idx")
+    triples = np.ascontiguousarray(triples, dtype=TOPO_TRIPLE).ravel()
+    epochs = _f64(epochs).ravel()
+    P, E, nb = triples.size, epochs.size, int(blk_off[-1])
+    counts = np.zeros((P, nb, E, 3), dtype=np.int64)
+    fn = lib.colate_topo_expected_blocks if device else lib.colate_topo_expected_blocks_host
+    check(fn(args[0], args[1], args[2], args[3], args[4], _p(cond_idx), P, _p(triples), E, _p(epochs), int(num_bases_per_block), nb, _p(counts)))
+    return blk_off, counts
+
+
+def topo_expected_blocks_chunks():
+    """Chunks of triples in this thread's last topo_expected_blocks(device=True) (diagnostic)."""
+    return lib.colate_topo_expected_blocks_chunks()
+
+
+def topo_expected_blocks_kernel_seconds():
+    """Seconds the kernels of this thread's last topo_expected_blocks(device=True) took on the device."""
+    return lib.colate_topo_expected_blocks_kernel_seconds()
+
+
 def fill_samples_chunks():
     """Chunks of the write pass in this thread's last fill_samples(device=True) (diagnostic)."""
     return lib.colate_fill_samples_chunks()

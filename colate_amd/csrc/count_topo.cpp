@@ -1,8 +1,8 @@
 // colate_amd/csrc/count_topo.cpp -- the host side of colate_topo_samples (count_topo.h: the contract): the checks both forms run
 // before anything is written, the host twin of the three device kernels -- bit planes per sample, a popcount per triple, the
 // ranked draws --, the same draws binned by age for colate_topo_profile and by genome block and age for
-// colate_topo_profile_blocks, the blocks themselves, the block jackknife on those counts (colate_topo_jackknife: host only), and the
-// C entry points, which view the caller's back-to-back arrays chromosome by chromosome.
+// colate_topo_profile_blocks, the blocks themselves, the block jackknife on those counts (colate_topo_jackknife: host only), the
+// expected counts per block and age in fixed point without a draw (colate_topo_expected_blocks), and the C entry points, which view the caller's back-to-back arrays chromosome by chromosome.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -289,6 +289,50 @@ int topo_profile_blocks_host(const View& v, int E, const double* epochs, int nbp
   return COLATE_OK;
 }
 
+int check_expected(const View& v, int E, const double* epochs, int nbpb, int nb, const long long* counts, std::vector<int>& blk_off) {
+  if (!counts) return fail(COLATE_EINVAL, "NULL pointer argument");
+  if (int rc = check_epochs(E, epochs)) return rc;
+  View w = v;
+  w.n_uniforms = 0, w.uniforms = nullptr;  // (no stream goes in)
+  if (int rc = check_view(w)) return rc;
+  if (int rc = check_blocks(v, E, nbpb, nb, blk_off)) return rc;
+  if (v.row_off[v.C] > kMaxExpectedRows)
+    return fail(COLATE_ELIMIT, "%lld searched rows, %lld are possible (the sums of the expected counts stay below 2^62)", v.row_off[v.C], kMaxExpectedRows);
+  return COLATE_OK;
+}
+
+int topo_expected_blocks_host(const View& v, int E, const double* epochs, int nbpb, int nb, long long* counts) {
+  std::vector<int> blk_off;
+  if (int rc = check_expected(v, E, epochs, nbpb, nb, counts, blk_off)) return rc;
+  std::vector<long long> woff((size_t)v.C + 1);
+  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
+  std::vector<unsigned long long> planes((size_t)v.S * 2 * (size_t)words);
+  for (int s = 0; s < v.S; s++) host_planes(v, s, woff.data(), words, planes.data() + (size_t)s * 2 * (size_t)words);
+  auto plane = [&](int s, int which) { return planes.data() + ((size_t)s * 2 + (size_t)which) * (size_t)words; };
+  // one pass over the set bits of Q: a row's addends depend on that row alone
+  const size_t per_block = (size_t)E * 3;
+  std::memset(counts, 0, sizeof(long long) * (size_t)v.P * (size_t)nb * per_block);
+  for (int p = 0; p < v.P; p++) {
+    const Triple& t = v.triples[p];
+    const unsigned long long *T = plane(t.target, 0), *R = plane(t.reference, 0), *Cq = plane(t.cond, 1);
+    long long* const mine = counts + (size_t)p * (size_t)nb * per_block;
+    for (int c = 0; c < v.C; c++) {
+      const Idx* const TI = v.idx[(size_t)t.target * v.C + c];
+      const Idx* const RI = v.idx[(size_t)t.reference * v.C + c];
+      const Row* const rows = v.rows[c];
+      for (long long k = woff[(size_t)c]; k < woff[(size_t)c + 1]; k++)
+        for (unsigned long long q = T[k] & R[k] & Cq[k]; q; q &= q - 1) {
+          const long long i = (k - woff[(size_t)c]) * 64 + __builtin_ctzll(q);
+          const Addends x = expected_addends(TI[i], RI[i]);
+          const size_t b = (size_t)(blk_off[(size_t)c] + block_of_pos(rows[i].pos, nbpb));
+          long long* const at = mine + b * per_block + (size_t)age_epoch(rows[i].age_begin, rows[i].age_end, epochs, E) * 3;
+          at[0] += (long long)x.plus, at[1] += (long long)x.minus, at[2]++;
+        }
+    }
+  }
+  return COLATE_OK;
+}
+
 void jackknife(int nb, int E, const long long* counts, double* out, int* used) {
   const double na = std::numeric_limits<double>::quiet_NaN();
   std::vector<long long> a((size_t)nb), b((size_t)nb);
@@ -419,6 +463,20 @@ int colate_topo_profile_blocks(int C, const long long* row_off, const colate_wal
                                long long* draws) {
   const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, n_uniforms, uniforms);
   return topo_profile_blocks_device(f.v, E, epochs, num_bases_per_block, nb, counts, draws);
+}
+
+int colate_topo_expected_blocks_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                                     const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, int E, const double* epochs,
+                                     int num_bases_per_block, int nb, long long* counts) {
+  const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, 0, nullptr);
+  return topo_expected_blocks_host(f.v, E, epochs, num_bases_per_block, nb, counts);
+}
+
+int colate_topo_expected_blocks(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                                const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, int E, const double* epochs,
+                                int num_bases_per_block, int nb, long long* counts) {
+  const FlatView f(C, row_off, rows, S, idx, cond_idx, P, triples, 0, nullptr);
+  return topo_expected_blocks_device(f.v, E, epochs, num_bases_per_block, nb, counts);
 }
 
 int colate_topo_jackknife(int nb, int E, const long long* counts, double* out, int* used) {

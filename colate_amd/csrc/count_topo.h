@@ -111,6 +111,56 @@ int block_offsets(int C, const int* max_pos, int nbpb, int* blk_off);
 // g < 2; Z where se is not > 0); used[E + 1]: g.
 void jackknife(int nb, int E, const long long* counts, double* out, int* used);
 
+// THE EXPECTED COUNTS (colate_topo_expected_blocks, `--expected`): what the sampled counts estimate, formed directly.  Given the
+// read counts a qualifying row prints +1 with probability pT (1 - pR) and -1 with probability (1 - pT) pR; summing those over the
+// rows is the Rao-Blackwellised statistic -- the same expectation, a strictly smaller variance, no seed -- and where T and R are
+// fixed at every row (DAF == 0 or AAF == 0) it IS the sampled count.  A row qualifies as above: hits(T) && hits(R) && qualifies(C).
+// At a qualifying row, with N_T = DAF_T + AAF_T, N_R = DAF_R + AAF_R and every value an unsigned integer,
+//   plus_fx  = floor((DAF_T * AAF_R) * 2^30 / (N_T * N_R)),   minus_fx = floor((AAF_T * DAF_R) * 2^30 / (N_T * N_R)):
+// the two probabilities in units of 2^-30 (kExpectedOne), rounded down.  With the 16-bit counts of an Idx a numerator is below 2^32,
+// a shifted one below 2^62, and every intermediate fits 64 bits.  plus_fx + minus_fx <= 2^30 per row; a row at which T and R are
+// both fixed adds exactly 2^30 to plus iff T is all derived and R all ancestral, exactly 2^30 to minus for the converse, else 0.
+// Per (triple, block, epoch) -- the blocks of this mode, age_epoch -- three integers: sum plus_fx, sum minus_fx, and the qualifying
+// rows, which are column 2 of colate_topo_profile_blocks whatever the uniforms.  Only integers are summed: no result depends on an
+// order of operations, on the chunking or on the block size, and counts at a finer block size, regrouped, are those at a coarser
+// multiple.  Each addend is short of the exact product by less than 2^-30, so a cell of n rows is short by less than n 2^-30.  With
+// fewer than 2^31 searched rows (kMaxExpectedRows; more are refused, COLATE_ELIMIT) every cell, every sum over blocks and the
+// jackknife's n = A + M stay below 2^62.  Every formula of the jackknife is a ratio of counts: it takes these scaled integers as
+// they are.
+constexpr int kExpectedShift = 30;
+constexpr long long kExpectedOne = 1LL << kExpectedShift;
+constexpr long long kMaxExpectedRows = (1LL << 31) - 1;
+// The two addends of a qualifying row from the counts of T and R (N_T, N_R > 0) -- the one copy: the host twin, the kernel and the
+// cursor path.  Counts below 2^16, an Idx's, take 64-bit arithmetic; larger ones, which only the record cursors of the host meet
+// (32-bit counts), a 128-bit intermediate.
+struct Addends {
+  unsigned long long plus, minus;
+};
+// floor(num 2^30 / den) for num <= den < 2^34.  The device has no 64-bit integer division and the compiler's expansion of one is
+// some 250 instructions, so a double quotient makes the first guess -- both operands are exact doubles, the shifted numerator having
+// at most 32 significant bits, and the guess lies within one of the floor -- and the exact integer remainder decides: the result is
+// the floor for every input, whatever the rounding of the division.
+COLATE_IC_HD inline unsigned long long expected_quotient(unsigned long long num, unsigned long long den) {
+  const unsigned long long shifted = num << kExpectedShift;
+  unsigned long long q = (unsigned long long)((double)shifted / (double)den);
+  long long r = (long long)(shifted - q * den);  // (|r| stays below 2^63: shifted < 2^62, and q den is within a few den of it)
+  while (r < 0) q--, r += (long long)den;
+  while (r >= (long long)den) q++, r -= (long long)den;
+  return q;
+}
+COLATE_IC_HD inline Addends expected_addends(unsigned long long DAF_T, unsigned long long AAF_T, unsigned long long DAF_R, unsigned long long AAF_R) {
+#ifndef __HIP_DEVICE_COMPILE__
+  if ((DAF_T | AAF_T | DAF_R | AAF_R) >> 16) {
+    const unsigned __int128 den = (unsigned __int128)(DAF_T + AAF_T) * (DAF_R + AAF_R);
+    return Addends{(unsigned long long)((((unsigned __int128)DAF_T * AAF_R) << kExpectedShift) / den),
+                   (unsigned long long)((((unsigned __int128)AAF_T * DAF_R) << kExpectedShift) / den)};
+  }
+#endif
+  const unsigned long long den = (DAF_T + AAF_T) * (DAF_R + AAF_R);
+  return Addends{expected_quotient(DAF_T * AAF_R, den), expected_quotient(AAF_T * DAF_R, den)};
+}
+COLATE_IC_HD inline Addends expected_addends(const Idx& t, const Idx& r) { return expected_addends(t.DAF, t.AAF, r.DAF, r.AAF); }
+
 // The inputs of both stages: every row given is a searched row; idx[s * C + c] is sample s's walk index of chromosome c,
 // cidx[s * C + c] its cond index.
 struct View {
@@ -157,6 +207,12 @@ struct Segment {
 };
 // seg[nb] of the view's blocks: every searched row lies in exactly one
 void block_segments(const View& v, int nbpb, const int* blk_off, Segment* seg);
+// The expected counts per block, host twin / device stage: counts[P][nb][E][3] -- sum plus_fx, sum minus_fx, qualifying rows.  No
+// stream goes in (v.n_uniforms and v.uniforms are not read) and no draws come out.  Refused, by name and before anything is
+// written: what the profile per block refuses of the same arguments, and kMaxExpectedRows.
+int check_expected(const View& v, int E, const double* epochs, int nbpb, int nb, const long long* counts, std::vector<int>& blk_off);
+int topo_expected_blocks_host(const View& v, int E, const double* epochs, int nbpb, int nb, long long* counts);
+int topo_expected_blocks_device(const View& v, int E, const double* epochs, int nbpb, int nb, long long* counts);
 
 // THE CURSOR WALK of one chromosome: the reference's loop over three record cursors, correct for every input.  Cur: a cursor
 // with match, bp, anc, der, AAF, DAF, set_name() and next() (mut_pairs.cpp: Cursor); RowT: pos, anc, der.  draw(): the next
@@ -224,5 +280,11 @@ hipError_t block_count_launch(const colate_iw::DeviceInputs& in, int S, int p0, 
 hipError_t block_profile_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
                                 int nb, const Segment* seg, const long long* base, const double* u, const unsigned short* bin, int E, unsigned* part,
                                 hipStream_t stream);
+// part[((p - p0) * nb + b)][E][3] for triples [p0, p1), 64-bit: the expected counts of block b -- one workgroup of kDrawWaves waves per
+// (triple, block) over the segment's words, masked as block_profile_launch masks them; lane = row, expected_addends into a [2][E]
+// 64-bit and an [E] 32-bit histogram in LDS; the workgroup writes its own 3 E integers, zeros for an empty segment.  No rank, no
+// uniform, no count pass in front.
+hipError_t block_expected_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
+                                 int nb, const Segment* seg, const unsigned short* bin, int E, long long* part, hipStream_t stream);
 }  // namespace colate_topo
 #endif

@@ -33,6 +33,15 @@
 //     the rows kept of each: the whole chromosome for the two kernels above, whose code is what it was, or a segment's words with
 //     the same masks --; a word cut by a block boundary is read by both neighbours and each keeps its own rows.  The same 3 x E
 //     histogram and bins; the workgroup writes its own 3 E partials, zeros for a segment without a row.
+//
+// The expected counts per genome block (colate_topo_expected_blocks; count_topo.h: the expected counts) run the staging, planes, bins
+// and segments, and nothing of the draws: no count kernel, no host wait, no rank and no stream of uniforms, since a row's addends
+// depend on that row alone.
+//   * topo_block_expected_kernel: one workgroup per (triple, block) over the segment's words; at every set bit of Q the two
+//     fixed-point addends of expected_addends -- two 64-bit integer quotients, each a double first guess put right by its exact
+//     integer remainder -- go into 64-bit LDS histograms, the row into a 32-bit one; the workgroup writes its 3 E integers as [E][3],
+//     which the host copies into `counts` as they lie.  draw_tiles is not used and not touched.  No global atomics, no floating point
+//     in the result.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -279,8 +288,61 @@ __global__ __launch_bounds__(kDrawWaves * 64) void topo_block_profile_kernel(Dev
   for (int i = threadIdx.x; i < 3 * E; i += kDrawWaves * 64) mine[i] = hist[i];
 }
 
-thread_local int g_chunks = 0, g_profile_chunks = 0, g_blocks_chunks = 0;
-thread_local double g_kernel_s = 0.0, g_profile_kernel_s = 0.0, g_blocks_kernel_s = 0.0;
+// One workgroup of kDrawWaves waves per (triple, block): the expected counts of the block (count_topo.h: expected_addends).  Wave w
+// takes the tiles w, w + kDrawWaves, ... of the segment's words, a tile being 64 words with one word per lane, masked as SegmentWords
+// masks them; a ballot names the words of the tile with a set bit of Q, and at each of those, lane = row, a lane whose bit is set reads
+// the target's and the reference's index entries and its row's epoch, forms the two addends and adds them -- and 1 for the row -- to
+// the workgroup's histograms in LDS: [2][E] 64-bit sums, [E] 32-bit rows (a segment has fewer than 2^31 rows), 20 E bytes.  A zero
+// addend is not added: where T and R are fixed one of the two always is.  Integer adds, whose sum has no order; no rank, no uniform,
+// nothing carried from tile to tile.  Both barriers are reached by every wave, whatever its trip count; behind the second the
+// workgroup writes its own 3 E integers as [E][3], the layout of `counts`: zeros where the segment holds no row.
+__global__ __launch_bounds__(kDrawWaves * 64) void topo_block_expected_kernel(DeviceInputs in, int S, int p0, const Triple* __restrict__ triples,
+                                                                              const unsigned long long* __restrict__ planes, int nb,
+                                                                              const Segment* __restrict__ seg, const unsigned short* __restrict__ bin,
+                                                                              int E, long long* __restrict__ part) {
+  __shared__ unsigned long long sums[2 * kMaxProfileEpochs];
+  __shared__ unsigned rows_in[kMaxProfileEpochs];
+  const int b = blockIdx.x % nb, j = blockIdx.x / nb;  // (triple p0 + j, block b)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const Triple t = triples[p0 + j];
+  const Segment sg = seg[b];
+  const SegmentWords span(sg);
+  for (int i = threadIdx.x; i < 2 * E; i += kDrawWaves * 64) sums[i] = 0;
+  for (int i = threadIdx.x; i < E; i += kDrawWaves * 64) rows_in[i] = 0;
+  __syncthreads();
+  const long long w0 = in.word_off[sg.c], r0 = in.row_off[sg.c];
+  const unsigned long long* const hT = planes + (size_t)t.target * in.words + w0;
+  const unsigned long long* const hR = planes + (size_t)t.reference * in.words + w0;
+  const unsigned long long* const qC = planes + (size_t)(S + t.cond) * in.words + w0;
+  const Idx* const TI = in.idx + (size_t)t.target * in.n + r0;
+  const Idx* const RI = in.idx + (size_t)t.reference * in.n + r0;
+  const unsigned short* const epoch_of = bin + r0;
+  for (long long tile0 = span.w_first + (long long)wave * kTileWords; tile0 < span.w_end; tile0 += kDrawWaves * kTileWords) {
+    const long long k = tile0 + lane;
+    const unsigned long long q = k < span.w_end ? hT[k] & hR[k] & qC[k] & span.keep(k) : 0ull;
+    for (unsigned long long left = __ballot(q != 0); left; left &= left - 1) {  // (alike in the whole wave)
+      const int w = __builtin_ctzll(left);
+      const unsigned long long qw = wave_uniform(__shfl(q, w, 64));
+      if ((qw >> lane) & 1) {
+        const long long i = (tile0 + w) * 64 + lane;  // (a set bit of Q is a row of the chromosome, and of the segment by the mask)
+        const Addends x = expected_addends(TI[i], RI[i]);
+        const int e = epoch_of[i];  // (bins_launch wrote 0 .. E - 1)
+        if (x.plus) atomicAdd(&sums[e], x.plus);
+        if (x.minus) atomicAdd(&sums[E + e], x.minus);
+        atomicAdd(&rows_in[e], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  long long* const mine = part + (size_t)blockIdx.x * 3 * (size_t)E;
+  for (int i = threadIdx.x; i < 3 * E; i += kDrawWaves * 64) {
+    const int e = i / 3, which = i - 3 * e;
+    mine[i] = which < 2 ? (long long)sums[which * E + e] : (long long)rows_in[e];
+  }
+}
+
+thread_local int g_chunks = 0, g_profile_chunks = 0, g_blocks_chunks = 0, g_expected_chunks = 0;
+thread_local double g_kernel_s = 0.0, g_profile_kernel_s = 0.0, g_blocks_kernel_s = 0.0, g_expected_kernel_s = 0.0;
 
 // bytes of what a chunk of triples leaves on the device -- the two output planes of colate_topo_samples, the partial histograms
 // of colate_topo_profile -- (COLATE_TOPO_BUDGET: bytes, for the tests)
@@ -412,6 +474,16 @@ hipError_t block_profile_launch(const DeviceInputs& in, int S, int p0, int p1, c
   if (grid > 0x7fffffffLL || E < 1 || E > kMaxProfileEpochs) return hipErrorInvalidValue;
   hipLaunchKernelGGL(topo_block_profile_kernel, dim3((unsigned)grid), dim3(kDrawWaves * 64), 0, stream, in, S, p0, triples, planes, nb, seg, base, u,
                      bin, E, part);
+  return hipGetLastError();
+}
+
+hipError_t block_expected_launch(const DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes, int nb,
+                                 const Segment* seg, const unsigned short* bin, int E, long long* part, hipStream_t stream) {
+  if (p1 <= p0 || nb < 1) return hipSuccess;
+  const long long grid = (long long)(p1 - p0) * nb;
+  if (grid > 0x7fffffffLL || E < 1 || E > kMaxProfileEpochs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topo_block_expected_kernel, dim3((unsigned)grid), dim3(kDrawWaves * 64), 0, stream, in, S, p0, triples, planes, nb, seg, bin, E,
+                     part);
   return hipGetLastError();
 }
 
@@ -579,9 +651,71 @@ int topo_profile_blocks_device(const View& v, int E, const double* epochs, int n
   return COLATE_OK;
 }
 
+int topo_expected_blocks_device(const View& v, int E, const double* epochs, int nbpb, int nb, long long* counts) {
+  std::vector<int> blk_off;
+  if (int rc = check_expected(v, E, epochs, nbpb, nb, counts, blk_off)) return rc;
+  if (int rc = check_grids_of(v)) return rc;
+  std::vector<long long> woff((size_t)v.C + 1);
+  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
+  std::vector<Segment> seg((size_t)nb);
+  block_segments(v, nbpb, blk_off.data(), seg.data());
+  if (int rc = ensure_device()) return rc;
+  ProfRange range("colate_topo_expected_blocks: H2D + planes + bins; per chunk of triples the expected counts of every block + D2H");
+  g_expected_chunks = 0, g_expected_kernel_s = 0.0;
+  if (int rc = thread_workspace().reserve(256, 256)) return rc;  // (the workspace's stream: no second one)
+  hipStream_t stream = thread_workspace().stream;
+  colate_iw::KernelTimer timer(stream);
+  colate_iw::Resident res;
+  DeviceBuffers buf;
+  // triples per chunk: the partials of a chunk -- 24 E bytes per (triple, block) -- within the budget, and the grid within 2^31
+  // workgroups; one triple where its partials alone are above the budget
+  const size_t per_block = 3 * (size_t)E;
+  const long long per_triple = (long long)(per_block * sizeof(long long)) * nb;
+  const long long chunk = std::max(1LL, std::min<long long>({(long long)v.P, output_budget() / per_triple, 0x7fffffffLL / nb}));
+  const colate_iw::StreamSync sync_at_exit{stream};
+  std::vector<const Idx*> both((size_t)2 * v.S * v.C);  // the walk indices, then the cond indices
+  std::copy_n(v.idx, (size_t)v.S * v.C, both.begin());
+  std::copy_n(v.cidx, (size_t)v.S * v.C, both.begin() + (size_t)v.S * v.C);
+  colate_iw::View iv;
+  iv.C = v.C, iv.row_off = v.row_off, iv.rows = v.rows, iv.S = 2 * v.S, iv.idx = both.data(), iv.M = 0, iv.P = 0, iv.pairs = nullptr, iv.nbpb = 1;
+  if (int rc = res.upload(iv, stream)) return rc;
+  unsigned long long* d_planes = nullptr;
+  Triple* d_triples = nullptr;
+  unsigned short* d_bin = nullptr;
+  double* d_epochs = nullptr;
+  long long* d_part = nullptr;
+  Segment* d_seg = nullptr;
+  HIP_TRY(buf.device(d_planes, (size_t)2 * v.S * (size_t)words)); HIP_TRY(buf.device(d_triples, (size_t)v.P));
+  HIP_TRY(buf.device(d_bin, (size_t)v.row_off[v.C])); HIP_TRY(buf.device(d_epochs, (size_t)E));
+  HIP_TRY(buf.device(d_part, (size_t)chunk * (size_t)nb * per_block)); HIP_TRY(buf.device(d_seg, (size_t)nb));
+  HIP_TRY(colate_iw::h2d(stream, d_triples, v.triples, sizeof(Triple) * (size_t)v.P));
+  HIP_TRY(colate_iw::h2d(stream, d_seg, seg.data(), sizeof(Segment) * (size_t)nb));
+  HIP_TRY(colate_iw::h2d(stream, d_epochs, epochs, sizeof(double) * (size_t)E));
+  HIP_TRY(timer.mark());
+  if (hipError_t e = planes_launch(res.in, v.S, d_planes, stream)) return hip_fail(e, "topo planes kernel launch");
+  if (hipError_t e = bins_launch(res.in, E, d_epochs, d_bin, stream)) return hip_fail(e, "topo bins kernel launch");  // once, for every triple
+  HIP_TRY(timer.mark());
+  for (long long p0 = 0; p0 < v.P; p0 += chunk) {  // (a chunk's partials are copied out before the next launch overwrites them: one stream)
+    const long long p1 = std::min<long long>(v.P, p0 + chunk);
+    HIP_TRY(timer.mark());
+    if (hipError_t e = block_expected_launch(res.in, v.S, (int)p0, (int)p1, d_triples, d_planes, nb, d_seg, d_bin, E, d_part, stream))
+      return hip_fail(e, "topo block expected kernel launch");
+    HIP_TRY(timer.mark());
+    // every (triple, block) owns its partials, written as [E][3]: they are `counts` as they lie
+    HIP_TRY(hipMemcpyAsync(counts + (size_t)p0 * (size_t)nb * per_block, d_part, sizeof(long long) * (size_t)(p1 - p0) * (size_t)nb * per_block,
+                           hipMemcpyDeviceToHost, stream));
+    g_expected_chunks++;
+  }
+  HIP_TRY(hipStreamSynchronize(stream));  // the one wait of the call
+  g_expected_kernel_s = timer.seconds();
+  return COLATE_OK;
+}
+
 }  // namespace colate_topo
 
 extern "C" {
+int colate_topo_expected_blocks_chunks(void) { return g_expected_chunks; }
+double colate_topo_expected_blocks_kernel_seconds(void) { return g_expected_kernel_s; }
 int colate_topo_profile_blocks_chunks(void) { return g_blocks_chunks; }
 double colate_topo_profile_blocks_kernel_seconds(void) { return g_blocks_kernel_s; }
 int colate_topo_samples_chunks(void) { return g_chunks; }

@@ -45,7 +45,7 @@ const char* const kValueOptions[] = {
     "lineage_bin", "outgroup_tmrca", "years_per_gen", "coal", "seed", "num_bootstraps", "filters",
     "groups", "poplabels", "map", "input", "output", "device", "devices", "ranks", "counts_out", "pairs",
     "rows", "max_iter", "min_iter", "write_rows", "samples", "age_profile", "block_bases"};
-const char* const kBoolOptions[] = {"help", "strandfilter", "counts_only", "write_colate_mat", "profile_only", "jackknife"};
+const char* const kBoolOptions[] = {"help", "strandfilter", "counts_only", "write_colate_mat", "profile_only", "jackknife", "expected"};
 
 bool parse_options(int argc, char** argv, Options& o, std::string& err) {
   for (int i = 1; i < argc; i++) {
@@ -142,6 +142,9 @@ void print_help() {
             << "                             epoch plus minus blocks D D_jack se Z` per (triple, epoch) and for epoch `all`: the delete-one block\n"
             << "                             jackknife of (plus - minus) / (plus + minus) over genome blocks, counted per block on the GPU.\n"
             << "      --block_bases arg      (--jackknife) bases per genome block, an integer of at least 1 (default 30000000).\n"
+            << "      --expected             (--mode count_topo --samples --age_profile) write PREFIX.expected.txt in place of every sampled file:\n"
+            << "                             per (triple, epoch) the expected plus and minus given the read counts, summed on the GPU in units\n"
+            << "                             of 2^-30; no draws, --seed has no effect.  With --jackknife also PREFIX.expected.jackknife.txt.\n"
             << "      --counts_out arg       Optional (colate_amd): write the bootstrap count tables (.colate_mat layout).\n"
             << "      --counts_only          Optional (colate_amd): stop after --counts_out (no GPU needed).\n"
             << "      --write_colate_mat     Optional (colate_amd): write <output>.colate_mat as the reference does for BCF/BAM inputs.\n"
@@ -706,7 +709,7 @@ extern "C" int colate_mut_main(int argc, char** argv) {
     return 0;
   }
   const std::string& mode = opt.get("mode");
-  for (const char* o : {"age_profile", "profile_only", "jackknife", "block_bases"})
+  for (const char* o : {"age_profile", "profile_only", "jackknife", "block_bases", "expected"})
     if (opt.has(o) && mode != "count_topo") {
       std::cerr << "Error: --" << o << " is an option of --mode count_topo --samples." << std::endl;
       return 1;

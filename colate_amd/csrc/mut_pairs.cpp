@@ -1703,6 +1703,35 @@ bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string
 }
 
 // (walk_inputs.h)
+bool topo_cursor_expected(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples,
+                          TopoProfile& profile) {
+  if (!loaded.loaded || loaded.loaded->in.rows.size() != names.size() || profile.nbpb < 1 || !profile.blk_off) return false;
+  const Inputs& in = loaded.loaded->in;
+  const size_t E = (size_t)profile.E, nb = (size_t)profile.blk_off[names.size()];
+  profile.counts.assign(triples.size() * E * 3, 0), profile.blocks.assign(triples.size() * nb * E * 3, 0);
+  Pool pool(pairs_threads());
+  for (size_t p = 0; p < triples.size(); p++)
+    pool.submit([&, p] {  // one triple per task, as topo_cursor_triples walks it; no generator
+      Cursor cnd, tgt, ref;
+      cnd.open(*in.tmp_files.at(triples[p].cond)), tgt.open(*in.tmp_files.at(triples[p].target)), ref.open(*in.tmp_files.at(triples[p].reference));
+      for (size_t c = 0; c < names.size(); c++) {
+        const CompactRow* const rows = in.rows[c].data();
+        colate_topo::cursor_walk_chromosome(
+            cnd, tgt, ref, names[c].c_str(), c == 0, rows, in.rows[c].size(), [] { return 0.5; }, [](size_t, int, int, int) {},
+            [&](size_t i) {  // row i qualifies: the addends from the counts the cursors stand on, 32 bits each
+              const colate_topo::Addends x = colate_topo::expected_addends((unsigned)tgt.DAF, (unsigned)tgt.AAF, (unsigned)ref.DAF, (unsigned)ref.AAF);
+              const size_t e = (size_t)colate_topo::age_epoch(rows[i].age_begin, rows[i].age_end, profile.epochs, profile.E);
+              const size_t b = (size_t)(profile.blk_off[c] + colate_iw::block_of_pos(rows[i].pos, profile.nbpb));
+              for (long long* at : {&profile.counts[(p * E + e) * 3], &profile.blocks[((p * nb + b) * E + e) * 3]})
+                at[0] += (long long)x.plus, at[1] += (long long)x.minus, at[2]++;
+            });
+      }
+    });
+  pool.wait_idle();
+  return true;
+}
+
+// (walk_inputs.h)
 int topo_cursor_blocks(const WalkInputs& loaded, int nbpb, std::vector<int>& blk_off) {
   if (!loaded.loaded) return COLATE_EINVAL;
   const Inputs& in = loaded.loaded->in;

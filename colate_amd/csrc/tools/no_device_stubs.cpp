@@ -123,6 +123,7 @@ namespace colate_topo {
 int topo_view_device(const View&, long long, long long*, unsigned long long*, unsigned long long*, long long*) { return nodev(); }
 int topo_profile_device(const View&, int, const double*, long long*, long long*) { return nodev(); }
 int topo_profile_blocks_device(const View&, int, const double*, int, int, long long*, long long*) { return nodev(); }
+int topo_expected_blocks_device(const View&, int, const double*, int, int, long long*) { return nodev(); }
 }  // namespace colate_topo
 extern "C" {
 int colate_compare_samples_chunks(void) { return 0; }
@@ -133,6 +134,8 @@ int colate_topo_profile_chunks(void) { return 0; }
 double colate_topo_profile_kernel_seconds(void) { return 0.0; }
 int colate_topo_profile_blocks_chunks(void) { return 0; }
 double colate_topo_profile_blocks_kernel_seconds(void) { return 0.0; }
+int colate_topo_expected_blocks_chunks(void) { return 0; }
+double colate_topo_expected_blocks_kernel_seconds(void) { return 0.0; }
 }
 
 // the age sampling on the device (fill_device.h): there is none in this build, the host code samples

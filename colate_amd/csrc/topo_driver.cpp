@@ -21,6 +21,12 @@
 //     alone.  The counts per (triple, block, epoch) come from colate_topo_profile_blocks in place of the profile call (its host twin;
 //     on the cursor path the walk's sinks bin by block); PREFIX.profile.txt and PREFIX.triples.txt are formed from their sums over
 //     the blocks, the same bytes as without the option.
+//     `--expected [--jackknife [--block_bases N]]` (with --age_profile): nothing sampled is written; PREFIX.expected.txt holds one line
+//     `cond target reference epoch plus minus qualifying` per (triple, epoch) with plus and minus the EXPECTED counts given the read
+//     counts -- the sums of pT (1 - pR) and (1 - pT) pR over the qualifying rows, formed in units of 2^-30 by
+//     colate_topo_expected_blocks (its host twin; the cursor walk's `drew` sink) and printed %.6f --, and with --jackknife
+//     PREFIX.expected.jackknife.txt the columns of PREFIX.jackknife.txt from those integers as they are.  No stream of uniforms is
+//     formed; --seed is accepted and has no effect.
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -57,7 +63,8 @@ double g_triple_stage_s = 0;  // the seconds of the triple stage alone, whicheve
 double g_kernel_s = 0;        // ... and of its kernels on the device
 
 // The inputs of `triples` (PairSpec with its cond file) as every form of the triple stage takes them: loaded once, the form
-// decided, and -- for the two indexed forms -- the run's stream and the view.
+// decided, and -- for the two indexed forms -- the run's stream (stage_triples with stream = false: none, `--expected` draws
+// nothing) and the view.
 struct Staged {
   WalkInputs in;
   Path path = Path::cursors;
@@ -70,7 +77,7 @@ struct Staged {
 
 // False after an error message; nothing has been written then.
 bool stage_triples(const Options& opt, const std::vector<std::string>& names, const std::vector<std::string>& mut_files,
-                   const std::vector<PairSpec>& triples, Path want, unsigned seed, Staged& st) {
+                   const std::vector<PairSpec>& triples, Path want, unsigned seed, Staged& st, bool stream = true) {
   WalkInputs& in = st.in;
   std::vector<const std::string*> files;
   for (const PairSpec& ps : triples) files.insert(files.end(), {&ps.cond, &ps.target, &ps.reference});  // coal.cpp:4588-4603
@@ -92,8 +99,8 @@ bool stage_triples(const Options& opt, const std::vector<std::string>& names, co
   const int C = (int)names.size();
   const long long n_rows = in.row_off.back();
   // the run's stream: a row draws two uniforms at most, and every triple starts from the seed
-  st.u.resize((size_t)(2 * n_rows));
-  {
+  if (stream) {
+    st.u.resize((size_t)(2 * n_rows));
     std::mt19937 rng(seed);
     std::uniform_real_distribution<double> dist_unif(0, 1);
     for (double& x : st.u) x = dist_unif(rng);
@@ -190,6 +197,81 @@ bool profile_triples(const Staged& st, const std::vector<std::string>& names, co
   return true;
 }
 
+// `--expected`: the expected counts of every staged triple per genome block and epoch (count_topo.h: the expected counts), in units
+// of 2^-30: profile.blocks[P][nb][E][3] and profile.counts, their sums over the blocks.  No stream, no draw.
+bool expected_triples(const Staged& st, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, TopoProfile& profile) {
+  const size_t P = triples.size();
+  const double t_stage = StageTimes::now();
+  if (st.path == Path::cursors) {
+    const bool ok = topo_cursor_expected(st.in, names, triples, profile);
+    g_triple_stage_s += StageTimes::now() - t_stage;
+    return ok;
+  }
+  const int nb = profile.blk_off[st.v.C];
+  const size_t per_block = (size_t)profile.E * 3;
+  profile.counts.assign(P * per_block, 0), profile.blocks.assign(P * (size_t)nb * per_block, 0);
+  if (int rc = st.path == Path::device
+                   ? colate_topo::topo_expected_blocks_device(st.v, profile.E, profile.epochs, profile.nbpb, nb, profile.blocks.data())
+                   : colate_topo::topo_expected_blocks_host(st.v, profile.E, profile.epochs, profile.nbpb, nb, profile.blocks.data()))
+    return api_error(rc), false;
+  for (size_t p = 0; p < P; p++)
+    for (size_t b = 0; b < (size_t)nb; b++)
+      for (size_t k = 0; k < per_block; k++) profile.counts[p * per_block + k] += profile.blocks[(p * (size_t)nb + b) * per_block + k];
+  g_triple_stage_s += StageTimes::now() - t_stage;
+  g_kernel_s += colate_topo_expected_blocks_kernel_seconds();
+  std::cerr << st.in.S << " samples staged, " << P << " triples expected in " << nb << " blocks on the " << st.where() << std::endl;
+  return true;
+}
+
+// %.6g, NA for "not available"
+std::string stat_text(double x) {
+  char text[40];
+  std::snprintf(text, sizeof(text), "%.6g", x);
+  return std::isnan(x) ? std::string("NA") : std::string(text);
+}
+
+// a fixed-point sum as the expected files print it: %.6f of (double)sum * 2^-30
+std::string fixed_text(long long sum) {
+  char text[48];
+  std::snprintf(text, sizeof(text), "%.6f", (double)sum * 0x1p-30);
+  return text;
+}
+
+// PREFIX.expected.txt, `cond target reference epoch plus minus qualifying` per (triple, epoch), and with `--jackknife`
+// PREFIX.expected.jackknife.txt, the columns of PREFIX.jackknife.txt, the statistics from the fixed-point integers as they are.
+bool write_expected(const std::string& prefix, const std::vector<std::string>& triple_names, const std::vector<double>& epochs, const TopoProfile& profile,
+                    int nb, bool jackknifed) {
+  const int E = profile.E;
+  std::ofstream ex(prefix + ".expected.txt");
+  for (size_t p = 0; p < triple_names.size(); p++)
+    for (int e = 0; e < E; e++) {
+      const long long* const x = &profile.counts[(p * (size_t)E + (size_t)e) * 3];
+      ex << triple_names[p] << " " << epochs[(size_t)e] << " " << fixed_text(x[0]) << " " << fixed_text(x[1]) << " " << x[2] << "\n";
+    }
+  if (!close_checked(ex, prefix + ".expected.txt")) return false;
+  if (!jackknifed) return true;
+  std::ofstream jk(prefix + ".expected.jackknife.txt");
+  std::vector<double> stats(((size_t)E + 1) * 4);
+  std::vector<int> used((size_t)E + 1);
+  for (size_t p = 0; p < triple_names.size(); p++) {
+    colate_topo::jackknife(nb, E, &profile.blocks[p * (size_t)nb * (size_t)E * 3], stats.data(), used.data());
+    long long plus = 0, minus = 0;
+    for (int e = 0; e <= E; e++) {
+      jk << triple_names[p] << " ";
+      if (e < E) {
+        const long long* const x = &profile.counts[(p * (size_t)E + (size_t)e) * 3];
+        plus += x[0], minus += x[1];
+        jk << epochs[(size_t)e] << " " << fixed_text(x[0]) << " " << fixed_text(x[1]);
+      } else {
+        jk << "all " << fixed_text(plus) << " " << fixed_text(minus);
+      }
+      const double* const o = &stats[(size_t)e * 4];
+      jk << " " << used[(size_t)e] << " " << stat_text(o[0]) << " " << stat_text(o[1]) << " " << stat_text(o[2]) << " " << stat_text(o[3]) << "\n";
+    }
+  }
+  return close_checked(jk, prefix + ".expected.jackknife.txt");
+}
+
 int run_topo_samples(const Options& opt) {
   if (refuse_options(opt, {"input", "pairs", "target_tmp", "reference_tmp", "target_mask", "reference_mask", "target_age", "reference_age", "bins",
                            "coal", "num_bootstraps", "ranks", "devices"},
@@ -204,6 +286,16 @@ int run_topo_samples(const Options& opt) {
   const bool profiled = opt.has("age_profile"), profile_only = opt.has("profile_only");
   if (profile_only && !profiled) {
     std::cerr << "Error: --profile_only needs --age_profile x,y,stepsize." << std::endl;
+    return 1;
+  }
+  // `--expected`: the expected counts in place of everything sampled
+  const bool expected = opt.has("expected");
+  if (expected && profile_only) {
+    std::cerr << "Error: --profile_only does not go with --expected, which writes no sampled file." << std::endl;
+    return 1;
+  }
+  if (expected && !profiled) {
+    std::cerr << "Error: --expected needs --age_profile x,y,stepsize." << std::endl;
     return 1;
   }
   // `--jackknife [--block_bases N]`: the genome blocks of count_topo.h, N bases each
@@ -278,16 +370,27 @@ int run_topo_samples(const Options& opt) {
   Staged st;
   std::vector<std::vector<TopoLine>> lines;
   std::vector<long long> draws;
-  if (!stage_triples(opt, names, mut_files, triples, want, seed, st)) return 1;
+  if (!stage_triples(opt, names, mut_files, triples, want, seed, st, !expected)) return 1;
   const WalkInputs& in = st.in;
   const bool one_walk = st.path == Path::cursors;  // (the cursor walk fills lines and profile at once)
   std::vector<int> blk_off;
-  if (jackknifed) {  // the blocks are those of the searched rows, whichever form walks them
+  if (jackknifed || expected) {  // the blocks are those of the searched rows, whichever form walks them
     blk_off.resize(names.size() + 1);
     if (int rc = one_walk ? topo_cursor_blocks(in, block_bases, blk_off)
                           : colate_topo::topo_blocks(st.v.C, st.v.row_off, st.v.rows, block_bases, blk_off.data()))
       return api_error(rc);
     profile.nbpb = block_bases, profile.blk_off = blk_off.data();
+  }
+  if (expected) {  // (the file does not depend on the blocks: without --jackknife they are the default's)
+    if (!expected_triples(st, names, triples, profile)) return 1;
+    const double t1 = StageTimes::now();
+    if (!write_expected(opt.get("output"), triple_names, epochs, profile, blk_off.back(), jackknifed)) return 1;
+    if (g_times.on)
+      std::cerr << "Timing: count_topo samples: inputs " << t1 - t0 - g_triple_stage_s << " s, triple stage " << g_triple_stage_s << " s (device kernels "
+                << g_kernel_s << " s), files " << StageTimes::now() - t1 << " s; " << (in.row_off.empty() ? 0LL : in.row_off.back())
+                << " rows, " << in.S << " samples, " << triples.size() << " triples" << std::endl;
+    print_usage_footer();
+    return 0;
   }
   if (!profile_only && !draw_triples(st, names, triples, lines, draws, profiled && one_walk ? &profile : nullptr)) return 1;
   if (profiled && (profile_only || !one_walk) && !profile_triples(st, names, triples, profile, draws)) return 1;
@@ -319,11 +422,7 @@ int run_topo_samples(const Options& opt) {
     std::ofstream jk(opt.get("output") + ".jackknife.txt");
     std::vector<double> stats(((size_t)E + 1) * 4);
     std::vector<int> used((size_t)E + 1);
-    auto number = [](double x) {  // %.6g, NA for "not available"
-      char text[40];
-      std::snprintf(text, sizeof(text), "%.6g", x);
-      return std::isnan(x) ? std::string("NA") : std::string(text);
-    };
+    const auto number = stat_text;
     for (size_t p = 0; p < triples.size(); p++) {
       colate_topo::jackknife(nb, E, &profile.blocks[p * (size_t)nb * (size_t)E * 3], stats.data(), used.data());
       long long plus = 0, minus = 0;
@@ -354,7 +453,7 @@ int run_topo_samples(const Options& opt) {
 
 int run_count_topo(const Options& opt) {
   if (opt.has("samples")) return run_topo_samples(opt);
-  for (const char* o : {"age_profile", "profile_only", "jackknife", "block_bases"})
+  for (const char* o : {"age_profile", "profile_only", "jackknife", "block_bases", "expected"})
     if (opt.has(o)) {
       std::cerr << "Error: --" << o << " needs --mode count_topo --samples: the single run of one triple writes its SNP lines only." << std::endl;
       return 1;

@@ -102,6 +102,11 @@ struct TopoProfile {
 int topo_cursor_blocks(const WalkInputs& loaded, int nbpb, std::vector<int>& blk_off);
 bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, unsigned seed,
                          std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws, TopoProfile* profile = nullptr);
+// `--expected` on the cursor path (count_topo.h: the expected counts): the same walk with a `drew` sink that forms the two
+// fixed-point addends of every qualifying row from the counts its cursors stand on -- 32 bits each, a 128-bit intermediate -- and
+// bins them by block and epoch; the walk's draws read a constant and nothing is emitted.  profile.E, epochs, nbpb > 0 and blk_off
+// in; profile.blocks[P][nb][E][3] -- sum plus_fx, sum minus_fx, qualifying rows -- and their sums over the blocks, profile.counts, out.
+bool topo_cursor_expected(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, TopoProfile& profile);
 // mut_pairs.cpp: the cursor walk of `--mode compare_tmp` (compare_tmp.h: cursor_walk_chromosome) for every pair of a list over inputs
 // loaded with RowSet::compare_tmp: mismatch / snps [P][sum of compare[c].windows].  Right for every input; false without loaded inputs.
 bool compare_cursor_pairs(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& pairs,

@@ -624,6 +624,35 @@ int colate_topo_profile_blocks_chunks(void);
 double colate_topo_profile_blocks_kernel_seconds(void);
 int colate_topo_jackknife(int nb, int E, const long long* counts, double* out, int* used);
 
+/* ---- the expected counts per genome block: what the sampled counts estimate, without a draw (csrc/count_topo.h: the expected
+ * counts) ----
+ * Inputs, epochs and blocks as for colate_topo_profile_blocks, without a stream of uniforms and without `draws`.  A row qualifies
+ * as there.  At a qualifying row, with N_T = DAF_T + AAF_T and N_R = DAF_R + AAF_R, all unsigned integers,
+ *   plus_fx = floor((DAF_T * AAF_R) * 2^30 / (N_T * N_R)),  minus_fx = floor((AAF_T * DAF_R) * 2^30 / (N_T * N_R)):
+ * the probabilities pT (1 - pR) of a +1 line and (1 - pT) pR of a -1 line in units of 2^-30, rounded down; every intermediate fits 64
+ * bits.  counts[P][nb][E][3]: sum plus_fx, sum minus_fx and the qualifying rows per (triple, block, epoch).  plus_fx + minus_fx <=
+ * 2^30; where T and R are both fixed at a row it adds exactly 2^30 to plus (T all derived, R all ancestral), to minus (the converse)
+ * or nothing, as the sampled form prints for every uniform in (0, 1); column 2 is column 2 of colate_topo_profile_blocks.  Each
+ * addend is short of the exact product by less than 2^-30: a cell of n rows by less than n 2^-30.  Only integers are summed: the
+ * same integers whatever the order, the chunking or the block size (finer blocks regrouped are the coarser ones).  With fewer than
+ * 2^31 searched rows every sum stays below 2^62, and colate_topo_jackknife -- ratios of counts throughout -- takes one triple's
+ * counts[nb][E][3] as they are.  Refused, by name and before anything is written: what colate_topo_profile_blocks refuses of the
+ * same arguments, and row_off[C] >= 2^31 (COLATE_ELIMIT with the number).  _host: the host twin.  On the device (COLATE_ENODEVICE
+ * without one), one stream and no host wait before the final copy: the staging, plane kernel and bins kernel of
+ * colate_topo_profile; every block as a segment; then per chunk of triples -- 24 E bytes per (triple, block), a chunk within 256 MB
+ * (COLATE_TOPO_BUDGET), one triple where its partials alone are larger -- one kernel, one workgroup per (triple, block) over the
+ * segment's words, the first and last one masked: lane = row, two 64-bit integer quotients (a double quotient as the first guess, the exact integer remainder deciding), 64-bit
+ * histograms in LDS, the workgroup's own 3 E integers out.  No count pass, no rank, no global atomics, no floating point in the result.
+ * colate_topo_expected_blocks_chunks / _kernel_seconds: diagnostics of the calling thread's last device call. */
+int colate_topo_expected_blocks(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                                const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, int E, const double* epochs,
+                                int num_bases_per_block, int nb, long long* counts);
+int colate_topo_expected_blocks_host(int C, const long long* row_off, const colate_walk_row* rows, int S, const colate_walk_idx* idx,
+                                     const colate_walk_idx* cond_idx, int P, const colate_topo_triple* triples, int E,
+                                     const double* epochs, int num_bases_per_block, int nb, long long* counts);
+int colate_topo_expected_blocks_chunks(void);
+double colate_topo_expected_blocks_kernel_seconds(void);
+
 /* ---- host-side pieces of mut() around the hot path (CPU, no device needed) ----
  * coal.cpp:3126-3137: the 185-point age grid.  Returns A or COLATE_EINVAL if cap < A. */
 int colate_age_grid(double* age_grid, int cap);
