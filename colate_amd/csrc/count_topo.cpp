@@ -1,8 +1,10 @@
 // colate_amd/csrc/count_topo.cpp -- the host side of colate_topo_samples (count_topo.h: the contract): the checks both forms run
-// before anything is written, the host twin of the three device kernels -- bit planes per sample, a popcount per triple, the
-// ranked draws --, the same draws binned by age for colate_topo_profile and by genome block and age for
-// colate_topo_profile_blocks, the blocks themselves, the block jackknife on those counts (colate_topo_jackknife: host only), the
-// expected counts per block and age in fixed point without a draw (colate_topo_expected_blocks), and the C entry points, which view the caller's back-to-back arrays chromosome by chromosome.
+// before anything is written; the host twins of the device calls -- HostPlanes builds every sample's bit planes once, and
+// for_each_qualifying is the one walk over a triple's set bits of Q with the running rank; the ranked draws as planes
+// (colate_topo_samples), binned by age (colate_topo_profile), by genome block and age (colate_topo_profile_blocks) and the expected
+// counts in fixed point without a draw (colate_topo_expected_blocks) are a sink of that walk each --; the blocks themselves, the block
+// jackknife on those counts (colate_topo_jackknife: host only), and the C entry points, which view the caller's back-to-back arrays
+// chromosome by chromosome.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -74,61 +76,115 @@ int check_stream(const View& v, const long long* draws) {
   return COLATE_OK;
 }
 
-void host_planes(const View& v, int s, const long long* word_off, long long words, unsigned long long* planes) {
-  std::memset(planes, 0, sizeof(unsigned long long) * 2 * (size_t)words);
+namespace {
+
+// Every sample's two bit planes over the searched rows -- `hit` from its walk index, `qualifies` from its cond index, every
+// chromosome starting on a word -- and from them a triple's Q: the host's form of what the planes kernel writes.
+struct HostPlanes {
+  const View& v;
+  std::vector<long long> woff;
+  long long words;
+  std::vector<unsigned long long> bits;  // [S][2][words]
+  explicit HostPlanes(const View& view) : v(view), woff((size_t)view.C + 1) {
+    words = colate_iw::mask_words(v.C, v.row_off, woff.data());
+    bits.assign((size_t)v.S * 2 * (size_t)words, 0);
+    for (int s = 0; s < v.S; s++)
+      for (int c = 0; c < v.C; c++) {
+        const long long nc = v.row_off[c + 1] - v.row_off[c];
+        const Idx* const X = v.idx[(size_t)s * v.C + c];
+        const Idx* const Y = v.cidx[(size_t)s * v.C + c];
+        unsigned long long* const hit = bits.data() + (size_t)s * 2 * (size_t)words + woff[(size_t)c];
+        unsigned long long* const qual = hit + words;
+        for (long long i = 0; i < nc; i++) {
+          const unsigned long long bit = 1ull << (i & 63);
+          if (hits(X[i])) hit[i >> 6] |= bit;
+          if (qualifies(Y[i])) qual[i >> 6] |= bit;
+        }
+      }
+  }
+  const unsigned long long* plane(int s, int which) const { return bits.data() + ((size_t)s * 2 + (size_t)which) * (size_t)words; }
+  // the three planes of triple p; Q at word k is their conjunction
+  struct OfTriple {
+    const unsigned long long *T, *R, *Cq;
+    unsigned long long operator()(long long k) const { return T[k] & R[k] & Cq[k]; }
+  };
+  OfTriple of(int p) const { return OfTriple{plane(v.triples[p].target, 0), plane(v.triples[p].reference, 0), plane(v.triples[p].cond, 1)}; }
+  long long qualifying(int p) const {
+    const OfTriple q = of(p);
+    long long n = 0;
+    for (long long k = 0; k < words; k++) n += __builtin_popcountll(q(k));
+    return n;
+  }
+  // the count pass of the forms that draw: the stream is checked before anything is written
+  int check_stream() const {
+    std::vector<long long> n((size_t)v.P);
+    for (int p = 0; p < v.P; p++) n[(size_t)p] = qualifying(p);
+    return colate_topo::check_stream(v, n.data());
+  }
+};
+
+// The one walk over the qualifying rows of triple p, in the genome's order: sink(c, i, rank, T, R) at row i of chromosome c, the
+// triple's qualifying row number `rank` -- a running popcount -- with the index entries of its target and its reference there.
+// Returns the number of those rows.
+template <class Sink>
+long long for_each_qualifying(const View& v, const HostPlanes& planes, int p, Sink&& sink) {
+  const Triple& t = v.triples[p];
+  const HostPlanes::OfTriple q = planes.of(p);
+  long long rank = 0;
   for (int c = 0; c < v.C; c++) {
-    const long long nc = v.row_off[c + 1] - v.row_off[c];
-    const Idx* const X = v.idx[(size_t)s * v.C + c];
-    const Idx* const Y = v.cidx[(size_t)s * v.C + c];
-    for (long long i = 0; i < nc; i++) {
-      const unsigned long long bit = 1ull << (i & 63);
-      if (hits(X[i])) planes[word_off[c] + (i >> 6)] |= bit;
-      if (qualifies(Y[i])) planes[words + word_off[c] + (i >> 6)] |= bit;
-    }
+    const Idx* const TI = v.idx[(size_t)t.target * v.C + c];
+    const Idx* const RI = v.idx[(size_t)t.reference * v.C + c];
+    const long long w0 = planes.woff[(size_t)c];
+    for (long long k = w0; k < planes.woff[(size_t)c + 1]; k++)
+      for (unsigned long long w = q(k); w; w &= w - 1, rank++) {
+        const long long i = (k - w0) * 64 + __builtin_ctzll(w);
+        sink(c, i, rank, TI[i], RI[i]);
+      }
+  }
+  return rank;
+}
+
+// The profile twins' sink: the draw of every qualifying row counted in counts[P][nb][E][3] at the row's block -- block_of(c, row) --
+// and epoch: qualifying, and plus or minus by its sign.  The rank runs on across blocks and chromosomes.
+template <class BlockOf>
+void draw_profile(const View& v, const HostPlanes& planes, int E, const double* epochs, size_t nb, BlockOf&& block_of, long long* counts,
+                  long long* draws) {
+  const size_t per_block = (size_t)E * 3;
+  std::memset(counts, 0, sizeof(long long) * (size_t)v.P * nb * per_block);
+  for (int p = 0; p < v.P; p++) {
+    long long* const mine = counts + (size_t)p * nb * per_block;
+    draws[p] = for_each_qualifying(v, planes, p, [&](int c, long long i, long long rank, const Idx& T, const Idx& R) {
+      const Row& m = v.rows[c][i];
+      const int sign = draw_sign(T, R, v.uniforms[2 * rank], v.uniforms[2 * rank + 1]);
+      long long* const at = mine + block_of(c, m) * per_block + (size_t)age_epoch(m.age_begin, m.age_end, epochs, E) * 3;
+      at[2]++;
+      if (sign > 0) at[0]++;
+      if (sign < 0) at[1]++;
+    });
   }
 }
+
+}  // namespace
 
 int topo_view_host(const View& v, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws) {
   if (int rc = check_outputs(cap, word_off, plus, minus, draws)) return rc;
   if (int rc = check_view(v)) return rc;
-  std::vector<long long> woff((size_t)v.C + 1);
-  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
-  if (int rc = check_capacity(v.P, words, cap)) return rc;
-  std::vector<unsigned long long> planes((size_t)v.S * 2 * (size_t)words);
-  for (int s = 0; s < v.S; s++) host_planes(v, s, woff.data(), words, planes.data() + (size_t)s * 2 * (size_t)words);
-  auto plane = [&](int s, int which) { return planes.data() + ((size_t)s * 2 + (size_t)which) * (size_t)words; };
-  // the count pass: the stream is checked before anything is written
-  std::vector<long long> n((size_t)v.P, 0);
+  if (int rc = check_capacity(v.P, colate_iw::mask_words(v.C, v.row_off, nullptr), cap)) return rc;
+  const HostPlanes planes(v);
+  if (int rc = planes.check_stream()) return rc;
+  const size_t words = (size_t)planes.words;
+  std::fill_n(plus, (size_t)v.P * words, 0ull), std::fill_n(minus, (size_t)v.P * words, 0ull);
   for (int p = 0; p < v.P; p++) {
-    const unsigned long long *T = plane(v.triples[p].target, 0), *R = plane(v.triples[p].reference, 0), *Cq = plane(v.triples[p].cond, 1);
-    for (long long k = 0; k < words; k++) n[(size_t)p] += __builtin_popcountll(T[k] & R[k] & Cq[k]);
+    unsigned long long* const pl = plus + (size_t)p * words;
+    unsigned long long* const mi = minus + (size_t)p * words;
+    draws[p] = for_each_qualifying(v, planes, p, [&](int c, long long i, long long rank, const Idx& T, const Idx& R) {
+      const int sign = draw_sign(T, R, v.uniforms[2 * rank], v.uniforms[2 * rank + 1]);
+      const long long k = planes.woff[(size_t)c] + (i >> 6);
+      if (sign > 0) pl[k] |= 1ull << (i & 63);
+      if (sign < 0) mi[k] |= 1ull << (i & 63);
+    });
   }
-  if (int rc = check_stream(v, n.data())) return rc;
-  // the draw pass: a running popcount is the rank
-  for (int p = 0; p < v.P; p++) {
-    const Triple& t = v.triples[p];
-    const unsigned long long *T = plane(t.target, 0), *R = plane(t.reference, 0), *Cq = plane(t.cond, 1);
-    unsigned long long* const pl = plus + (size_t)p * (size_t)words;
-    unsigned long long* const mi = minus + (size_t)p * (size_t)words;
-    long long rank = 0;
-    for (int c = 0; c < v.C; c++) {
-      const Idx* const TI = v.idx[(size_t)t.target * v.C + c];
-      const Idx* const RI = v.idx[(size_t)t.reference * v.C + c];
-      for (long long k = woff[(size_t)c]; k < woff[(size_t)c + 1]; k++) {
-        unsigned long long a = 0, b = 0;
-        for (unsigned long long q = T[k] & R[k] & Cq[k]; q; q &= q - 1, rank++) {
-          const int bit = __builtin_ctzll(q);
-          const long long i = (k - woff[(size_t)c]) * 64 + bit;
-          const int sign = draw_sign(TI[i], RI[i], v.uniforms[2 * rank], v.uniforms[2 * rank + 1]);
-          if (sign > 0) a |= 1ull << bit;
-          if (sign < 0) b |= 1ull << bit;
-        }
-        pl[k] = a, mi[k] = b;
-      }
-    }
-    draws[p] = rank;
-  }
-  std::memcpy(word_off, woff.data(), sizeof(long long) * woff.size());
+  std::memcpy(word_off, planes.woff.data(), sizeof(long long) * planes.woff.size());
   return COLATE_OK;
 }
 
@@ -147,40 +203,9 @@ int topo_profile_host(const View& v, int E, const double* epochs, long long* cou
   if (!counts || !draws) return fail(COLATE_EINVAL, "NULL pointer argument");
   if (int rc = check_epochs(E, epochs)) return rc;
   if (int rc = check_view(v)) return rc;
-  std::vector<long long> woff((size_t)v.C + 1);
-  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
-  std::vector<unsigned long long> planes((size_t)v.S * 2 * (size_t)words);
-  for (int s = 0; s < v.S; s++) host_planes(v, s, woff.data(), words, planes.data() + (size_t)s * 2 * (size_t)words);
-  auto plane = [&](int s, int which) { return planes.data() + ((size_t)s * 2 + (size_t)which) * (size_t)words; };
-  std::vector<long long> n((size_t)v.P, 0);
-  for (int p = 0; p < v.P; p++) {
-    const unsigned long long *T = plane(v.triples[p].target, 0), *R = plane(v.triples[p].reference, 0), *Cq = plane(v.triples[p].cond, 1);
-    for (long long k = 0; k < words; k++) n[(size_t)p] += __builtin_popcountll(T[k] & R[k] & Cq[k]);
-  }
-  if (int rc = check_stream(v, n.data())) return rc;
-  // the draw pass: a running popcount is the rank, age_epoch the bin of every set bit of Q
-  std::memset(counts, 0, sizeof(long long) * (size_t)v.P * (size_t)E * 3);
-  for (int p = 0; p < v.P; p++) {
-    const Triple& t = v.triples[p];
-    const unsigned long long *T = plane(t.target, 0), *R = plane(t.reference, 0), *Cq = plane(t.cond, 1);
-    long long* const mine = counts + (size_t)p * (size_t)E * 3;
-    long long rank = 0;
-    for (int c = 0; c < v.C; c++) {
-      const Idx* const TI = v.idx[(size_t)t.target * v.C + c];
-      const Idx* const RI = v.idx[(size_t)t.reference * v.C + c];
-      const Row* const rows = v.rows[c];
-      for (long long k = woff[(size_t)c]; k < woff[(size_t)c + 1]; k++)
-        for (unsigned long long q = T[k] & R[k] & Cq[k]; q; q &= q - 1, rank++) {
-          const long long i = (k - woff[(size_t)c]) * 64 + __builtin_ctzll(q);
-          const int sign = draw_sign(TI[i], RI[i], v.uniforms[2 * rank], v.uniforms[2 * rank + 1]);
-          long long* const at = mine + (size_t)age_epoch(rows[i].age_begin, rows[i].age_end, epochs, E) * 3;
-          at[2]++;
-          if (sign > 0) at[0]++;
-          if (sign < 0) at[1]++;
-        }
-    }
-    draws[p] = rank;
-  }
+  const HostPlanes planes(v);
+  if (int rc = planes.check_stream()) return rc;
+  draw_profile(v, planes, E, epochs, 1, [](int, const Row&) { return (size_t)0; }, counts, draws);
   return COLATE_OK;
 }
 
@@ -250,42 +275,11 @@ int topo_profile_blocks_host(const View& v, int E, const double* epochs, int nbp
   if (int rc = check_view(v)) return rc;
   std::vector<int> blk_off;
   if (int rc = check_blocks(v, E, nbpb, nb, blk_off)) return rc;
-  std::vector<long long> woff((size_t)v.C + 1);
-  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
-  std::vector<unsigned long long> planes((size_t)v.S * 2 * (size_t)words);
-  for (int s = 0; s < v.S; s++) host_planes(v, s, woff.data(), words, planes.data() + (size_t)s * 2 * (size_t)words);
-  auto plane = [&](int s, int which) { return planes.data() + ((size_t)s * 2 + (size_t)which) * (size_t)words; };
-  std::vector<long long> n((size_t)v.P, 0);
-  for (int p = 0; p < v.P; p++) {
-    const unsigned long long *T = plane(v.triples[p].target, 0), *R = plane(v.triples[p].reference, 0), *Cq = plane(v.triples[p].cond, 1);
-    for (long long k = 0; k < words; k++) n[(size_t)p] += __builtin_popcountll(T[k] & R[k] & Cq[k]);
-  }
-  if (int rc = check_stream(v, n.data())) return rc;
-  // the draw pass of topo_profile_host: the rank runs on across blocks and chromosomes; the row's position names the block
-  const size_t per_block = (size_t)E * 3;
-  std::memset(counts, 0, sizeof(long long) * (size_t)v.P * (size_t)nb * per_block);
-  for (int p = 0; p < v.P; p++) {
-    const Triple& t = v.triples[p];
-    const unsigned long long *T = plane(t.target, 0), *R = plane(t.reference, 0), *Cq = plane(t.cond, 1);
-    long long* const mine = counts + (size_t)p * (size_t)nb * per_block;
-    long long rank = 0;
-    for (int c = 0; c < v.C; c++) {
-      const Idx* const TI = v.idx[(size_t)t.target * v.C + c];
-      const Idx* const RI = v.idx[(size_t)t.reference * v.C + c];
-      const Row* const rows = v.rows[c];
-      for (long long k = woff[(size_t)c]; k < woff[(size_t)c + 1]; k++)
-        for (unsigned long long q = T[k] & R[k] & Cq[k]; q; q &= q - 1, rank++) {
-          const long long i = (k - woff[(size_t)c]) * 64 + __builtin_ctzll(q);
-          const int sign = draw_sign(TI[i], RI[i], v.uniforms[2 * rank], v.uniforms[2 * rank + 1]);
-          const size_t b = (size_t)(blk_off[(size_t)c] + block_of_pos(rows[i].pos, nbpb));
-          long long* const at = mine + b * per_block + (size_t)age_epoch(rows[i].age_begin, rows[i].age_end, epochs, E) * 3;
-          at[2]++;
-          if (sign > 0) at[0]++;
-          if (sign < 0) at[1]++;
-        }
-    }
-    draws[p] = rank;
-  }
+  const HostPlanes planes(v);
+  if (int rc = planes.check_stream()) return rc;
+  // the row's position names the block
+  draw_profile(v, planes, E, epochs, (size_t)nb, [&](int c, const Row& m) { return (size_t)(blk_off[(size_t)c] + block_of_pos(m.pos, nbpb)); },
+               counts, draws);
   return COLATE_OK;
 }
 
@@ -304,31 +298,19 @@ int check_expected(const View& v, int E, const double* epochs, int nbpb, int nb,
 int topo_expected_blocks_host(const View& v, int E, const double* epochs, int nbpb, int nb, long long* counts) {
   std::vector<int> blk_off;
   if (int rc = check_expected(v, E, epochs, nbpb, nb, counts, blk_off)) return rc;
-  std::vector<long long> woff((size_t)v.C + 1);
-  const long long words = colate_iw::mask_words(v.C, v.row_off, woff.data());
-  std::vector<unsigned long long> planes((size_t)v.S * 2 * (size_t)words);
-  for (int s = 0; s < v.S; s++) host_planes(v, s, woff.data(), words, planes.data() + (size_t)s * 2 * (size_t)words);
-  auto plane = [&](int s, int which) { return planes.data() + ((size_t)s * 2 + (size_t)which) * (size_t)words; };
-  // one pass over the set bits of Q: a row's addends depend on that row alone
+  const HostPlanes planes(v);
+  // a row's addends depend on that row alone: no stream, no rank
   const size_t per_block = (size_t)E * 3;
   std::memset(counts, 0, sizeof(long long) * (size_t)v.P * (size_t)nb * per_block);
   for (int p = 0; p < v.P; p++) {
-    const Triple& t = v.triples[p];
-    const unsigned long long *T = plane(t.target, 0), *R = plane(t.reference, 0), *Cq = plane(t.cond, 1);
     long long* const mine = counts + (size_t)p * (size_t)nb * per_block;
-    for (int c = 0; c < v.C; c++) {
-      const Idx* const TI = v.idx[(size_t)t.target * v.C + c];
-      const Idx* const RI = v.idx[(size_t)t.reference * v.C + c];
-      const Row* const rows = v.rows[c];
-      for (long long k = woff[(size_t)c]; k < woff[(size_t)c + 1]; k++)
-        for (unsigned long long q = T[k] & R[k] & Cq[k]; q; q &= q - 1) {
-          const long long i = (k - woff[(size_t)c]) * 64 + __builtin_ctzll(q);
-          const Addends x = expected_addends(TI[i], RI[i]);
-          const size_t b = (size_t)(blk_off[(size_t)c] + block_of_pos(rows[i].pos, nbpb));
-          long long* const at = mine + b * per_block + (size_t)age_epoch(rows[i].age_begin, rows[i].age_end, epochs, E) * 3;
-          at[0] += (long long)x.plus, at[1] += (long long)x.minus, at[2]++;
-        }
-    }
+    for_each_qualifying(v, planes, p, [&](int c, long long i, long long, const Idx& T, const Idx& R) {
+      const Row& m = v.rows[c][i];
+      const Addends x = expected_addends(T, R);
+      const size_t b = (size_t)(blk_off[(size_t)c] + block_of_pos(m.pos, nbpb));
+      long long* const at = mine + b * per_block + (size_t)age_epoch(m.age_begin, m.age_end, epochs, E) * 3;
+      at[0] += (long long)x.plus, at[1] += (long long)x.minus, at[2]++;
+    });
   }
   return COLATE_OK;
 }
@@ -375,6 +357,14 @@ void jackknife(int nb, int E, const long long* counts, double* out, int* used) {
 
 namespace {
 
+// Whether the caller's offsets can be followed at all: where not, the checks name what is wrong with the sizes or offsets, and
+// nothing is dereferenced before them.
+bool offsets_usable(int C, const long long* row_off) {
+  bool ok = C >= 1 && row_off && row_off[0] == 0;
+  for (int c = 0; ok && c < C; c++) ok = row_off[c + 1] >= row_off[c];
+  return ok;
+}
+
 // the caller's back-to-back arrays, chromosome by chromosome
 struct FlatView {
   View v;
@@ -383,9 +373,7 @@ struct FlatView {
   FlatView(int C, const long long* row_off, const Row* r, int S, const Idx* x, const Idx* y, int P, const Triple* triples, long long n_uniforms,
            const double* uniforms) {
     v.C = C, v.row_off = row_off, v.S = S, v.P = P, v.triples = triples, v.n_uniforms = n_uniforms, v.uniforms = uniforms;
-    bool ok = C >= 1 && S >= 1 && row_off && row_off[0] == 0;
-    for (int c = 0; ok && c < C; c++) ok = row_off[c + 1] >= row_off[c];
-    if (!ok) {  // (check_view names what is wrong with the sizes or offsets: nothing below is dereferenced before it)
+    if (S < 1 || !offsets_usable(C, row_off)) {  // (check_view names what is wrong)
       static const Row* const no_rows = nullptr;
       static const Idx* const no_idx = nullptr;
       v.rows = r ? &no_rows : nullptr, v.idx = x ? &no_idx : nullptr, v.cidx = y ? &no_idx : nullptr;
@@ -442,9 +430,7 @@ int colate_topo_profile(int C, const long long* row_off, const colate_walk_row* 
 
 int colate_topo_blocks(int C, const long long* row_off, const colate_walk_row* rows, int num_bases_per_block, int* blk_off) {
   std::vector<const Row*> ptrs;
-  bool ok = C >= 1 && row_off && row_off[0] == 0;
-  for (int c = 0; ok && c < C; c++) ok = row_off[c + 1] >= row_off[c];
-  if (ok && rows)  // (topo_blocks names what is wrong with the sizes or offsets: nothing is dereferenced before it)
+  if (offsets_usable(C, row_off) && rows)  // (topo_blocks names what is wrong)
     for (int c = 0; c < C; c++) ptrs.push_back(rows + row_off[c]);
   return topo_blocks(C, row_off, ptrs.empty() ? nullptr : ptrs.data(), num_bases_per_block, blk_off);
 }

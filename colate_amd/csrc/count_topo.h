@@ -182,8 +182,6 @@ int check_outputs(long long cap, const long long* word_off, const unsigned long 
 int check_capacity(long long P, long long words, long long cap);
 // the stream the triples need: 2 x the most qualifying rows of any (COLATE_ELIMIT with the needed length where it is longer than given)
 int check_stream(const View& v, const long long* draws);
-// sample s's planes[2][words]: hit, qualifies
-void host_planes(const View& v, int s, const long long* word_off, long long words, unsigned long long* planes);
 // The host twin / the device stage: word_off[C + 1], plus / minus [P][word_off[C]] with room for cap words each, draws[P].
 int topo_view_host(const View& v, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws);
 int topo_view_device(const View& v, long long cap, long long* word_off, unsigned long long* plus, unsigned long long* minus, long long* draws);
@@ -250,41 +248,3 @@ void cursor_walk_chromosome(Cur& cnd, Cur& tgt, Cur& ref, const char* name, bool
 }
 
 }  // namespace colate_topo
-
-#ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-namespace colate_topo {
-// planes[2 S][words] of the resident inputs, whose arrays 0 .. S - 1 are the walk indices and S .. 2 S - 1 the cond indices:
-// `hit` of the former, `qualifies` of the latter.  One lane per (array, searched row).
-hipError_t planes_launch(const colate_iw::DeviceInputs& in, int S, unsigned long long* planes, hipStream_t stream);
-// cnt[p * C + c] = popc(Q) over chromosome c for triples [0, P): one workgroup per (triple, chromosome)
-hipError_t count_launch(const colate_iw::DeviceInputs& in, int S, int P, const Triple* triples, const unsigned long long* planes, int* cnt,
-                        hipStream_t stream);
-// plus / minus [(p - p0)][words] for triples [p0, p1): one workgroup per (triple, chromosome); base[p * C + c]: the rank of the
-// chromosome's first qualifying row; u: the uniforms, at least 2 x the most qualifying rows of any triple
-hipError_t draw_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
-                       const long long* base, const double* u, unsigned long long* plus, unsigned long long* minus, hipStream_t stream);
-// bin[n] = age_epoch of every searched row, the rows of all chromosomes back to back: one lane per row, the epochs in LDS
-hipError_t bins_launch(const colate_iw::DeviceInputs& in, int E, const double* epochs, unsigned short* bin, hipStream_t stream);
-// part[((p - p0) * C + c)][3][E] for triples [p0, p1): the draws of draw_launch, every set bit of Q counted in its row's epoch --
-// plus, minus, qualifying -- in an LDS histogram of the (triple, chromosome)'s workgroup
-hipError_t profile_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
-                          const long long* base, const double* u, const unsigned short* bin, int E, unsigned* part, hipStream_t stream);
-// cnt[(p - p0) * nb + b] = popc(Q) over the rows of block b for triples [p0, p1): one wave per (triple, block), the segment's first
-// and last word masked
-hipError_t block_count_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
-                              int nb, const Segment* seg, int* cnt, hipStream_t stream);
-// part[((p - p0) * nb + b)][3][E] for triples [p0, p1): profile_launch per (triple, block) -- the same scan, ranks and draws over
-// the segment's words, a word cut by a block boundary read by both neighbours, each keeping its own rows; base[p * nb + b]: the rank
-// of the block's first qualifying row; an empty segment writes zeros
-hipError_t block_profile_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
-                                int nb, const Segment* seg, const long long* base, const double* u, const unsigned short* bin, int E, unsigned* part,
-                                hipStream_t stream);
-// part[((p - p0) * nb + b)][E][3] for triples [p0, p1), 64-bit: the expected counts of block b -- one workgroup of kDrawWaves waves per
-// (triple, block) over the segment's words, masked as block_profile_launch masks them; lane = row, expected_addends into a [2][E]
-// 64-bit and an [E] 32-bit histogram in LDS; the workgroup writes its own 3 E integers, zeros for an empty segment.  No rank, no
-// uniform, no count pass in front.
-hipError_t block_expected_launch(const colate_iw::DeviceInputs& in, int S, int p0, int p1, const Triple* triples, const unsigned long long* planes,
-                                 int nb, const Segment* seg, const unsigned short* bin, int E, long long* part, hipStream_t stream);
-}  // namespace colate_topo
-#endif

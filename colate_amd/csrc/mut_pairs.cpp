@@ -1659,46 +1659,59 @@ bool compare_cursor_pairs(const WalkInputs& loaded, const std::vector<std::strin
   return true;
 }
 
+// The cursor path of `--mode count_topo`: one triple per task.  Its three cursors are opened and task(p, tgt, ref, walk) runs, which
+// calls walk(draw, emit, drew) once: the cursors go through the chromosomes in the list's order, at each the cursor walk of
+// count_topo.h with draw() the next uniform, emit(c, row, sign, DAF, N) at a row of chromosome c that prints and drew(c, row) at
+// every row that qualifies.  What a triple keeps across its chromosomes -- its generator -- lives in the task.
+template <class Task>
+void topo_cursor_walks(const Inputs& in, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, Task&& task) {
+  Pool pool(pairs_threads());
+  for (size_t p = 0; p < triples.size(); p++)
+    pool.submit([&, p] {
+      Cursor cnd, tgt, ref;
+      cnd.open(*in.tmp_files.at(triples[p].cond)), tgt.open(*in.tmp_files.at(triples[p].target)), ref.open(*in.tmp_files.at(triples[p].reference));
+      task(p, tgt, ref, [&](auto&& draw, auto&& emit, auto&& drew) {
+        for (size_t c = 0; c < names.size(); c++) {
+          const CompactRow* const rows = in.rows[c].data();
+          colate_topo::cursor_walk_chromosome(
+              cnd, tgt, ref, names[c].c_str(), c == 0, rows, in.rows[c].size(), draw,
+              [&](size_t i, int sign, int DAF, int N) { emit(c, rows[i], sign, DAF, N); }, [&](size_t i) { drew(c, rows[i]); });
+        }
+      });
+    });
+  pool.wait_idle();
+}
+
 // (walk_inputs.h)
 bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples, unsigned seed,
                          std::vector<std::vector<TopoLine>>& lines, std::vector<long long>& draws, TopoProfile* profile) {
   if (!loaded.loaded || loaded.loaded->in.rows.size() != names.size()) return false;
-  const Inputs& in = loaded.loaded->in;
   lines.assign(triples.size(), std::vector<TopoLine>()), draws.assign(triples.size(), 0);
   if (profile) profile->counts.assign(triples.size() * (size_t)profile->E * 3, 0);
   const bool blocked = profile && profile->nbpb > 0 && profile->blk_off;
   const size_t nb = blocked ? (size_t)profile->blk_off[names.size()] : 0;
   if (blocked) profile->blocks.assign(triples.size() * nb * (size_t)profile->E * 3, 0);
-  Pool pool(pairs_threads());
-  for (size_t p = 0; p < triples.size(); p++)
-    pool.submit([&, p] {  // one triple per task: its three cursors go through the chromosomes in the list's order, its generator from the seed
-      Cursor cnd, tgt, ref;
-      cnd.open(*in.tmp_files.at(triples[p].cond)), tgt.open(*in.tmp_files.at(triples[p].target)), ref.open(*in.tmp_files.at(triples[p].reference));
-      std::mt19937 rng(seed);
-      std::uniform_real_distribution<double> dist_unif(0, 1);
-      long long n = 0;
-      for (size_t c = 0; c < names.size(); c++) {
-        const CompactRow* const rows = in.rows[c].data();
-        // (the profile: a triple's own [E][3] counts, binned by the rows' own floats)
-        auto count = [&](size_t i, int which) {
-          if (!profile) return;
-          const size_t e = (size_t)colate_topo::age_epoch(rows[i].age_begin, rows[i].age_end, profile->epochs, profile->E);
-          profile->counts[(p * (size_t)profile->E + e) * 3 + (size_t)which]++;
-          if (blocked)  // (the block the row's own position names: the sinks bin by block as well)
-            profile->blocks[((p * nb + (size_t)(profile->blk_off[c] + colate_iw::block_of_pos(rows[i].pos, profile->nbpb))) * (size_t)profile->E + e) * 3 +
-                            (size_t)which]++;
-        };
-        colate_topo::cursor_walk_chromosome(
-            cnd, tgt, ref, names[c].c_str(), c == 0, rows, in.rows[c].size(), [&] { return n++, dist_unif(rng); },
-            [&](size_t i, int sign, int DAF, int N) {
-              lines[p].push_back(TopoLine{(int)c, rows[i].pos, rows[i].age_begin, rows[i].age_end, sign, DAF, N});
-              count(i, sign > 0 ? 0 : 1);
-            },
-            [&](size_t i) { count(i, 2); });
-      }
-      draws[p] = n / 2;
-    });
-  pool.wait_idle();
+  topo_cursor_walks(loaded.loaded->in, names, triples, [&](size_t p, Cursor&, Cursor&, auto&& walk) {
+    std::mt19937 rng(seed);  // the triple's generator from the seed
+    std::uniform_real_distribution<double> dist_unif(0, 1);
+    long long n = 0;
+    // (the profile: a triple's own [E][3] counts, binned by the rows' own floats)
+    auto count = [&](size_t c, const CompactRow& m, int which) {
+      if (!profile) return;
+      const size_t e = (size_t)colate_topo::age_epoch(m.age_begin, m.age_end, profile->epochs, profile->E);
+      profile->counts[(p * (size_t)profile->E + e) * 3 + (size_t)which]++;
+      if (blocked)  // (the block the row's own position names: the sinks bin by block as well)
+        profile->blocks[((p * nb + (size_t)(profile->blk_off[c] + colate_iw::block_of_pos(m.pos, profile->nbpb))) * (size_t)profile->E + e) * 3 +
+                        (size_t)which]++;
+    };
+    walk([&] { return n++, dist_unif(rng); },
+         [&](size_t c, const CompactRow& m, int sign, int DAF, int N) {
+           lines[p].push_back(TopoLine{(int)c, m.pos, m.age_begin, m.age_end, sign, DAF, N});
+           count(c, m, sign > 0 ? 0 : 1);
+         },
+         [&](size_t c, const CompactRow& m) { count(c, m, 2); });
+    draws[p] = n / 2;
+  });
   return true;
 }
 
@@ -1706,28 +1719,19 @@ bool topo_cursor_triples(const WalkInputs& loaded, const std::vector<std::string
 bool topo_cursor_expected(const WalkInputs& loaded, const std::vector<std::string>& names, const std::vector<PairSpec>& triples,
                           TopoProfile& profile) {
   if (!loaded.loaded || loaded.loaded->in.rows.size() != names.size() || profile.nbpb < 1 || !profile.blk_off) return false;
-  const Inputs& in = loaded.loaded->in;
   const size_t E = (size_t)profile.E, nb = (size_t)profile.blk_off[names.size()];
   profile.counts.assign(triples.size() * E * 3, 0), profile.blocks.assign(triples.size() * nb * E * 3, 0);
-  Pool pool(pairs_threads());
-  for (size_t p = 0; p < triples.size(); p++)
-    pool.submit([&, p] {  // one triple per task, as topo_cursor_triples walks it; no generator
-      Cursor cnd, tgt, ref;
-      cnd.open(*in.tmp_files.at(triples[p].cond)), tgt.open(*in.tmp_files.at(triples[p].target)), ref.open(*in.tmp_files.at(triples[p].reference));
-      for (size_t c = 0; c < names.size(); c++) {
-        const CompactRow* const rows = in.rows[c].data();
-        colate_topo::cursor_walk_chromosome(
-            cnd, tgt, ref, names[c].c_str(), c == 0, rows, in.rows[c].size(), [] { return 0.5; }, [](size_t, int, int, int) {},
-            [&](size_t i) {  // row i qualifies: the addends from the counts the cursors stand on, 32 bits each
-              const colate_topo::Addends x = colate_topo::expected_addends((unsigned)tgt.DAF, (unsigned)tgt.AAF, (unsigned)ref.DAF, (unsigned)ref.AAF);
-              const size_t e = (size_t)colate_topo::age_epoch(rows[i].age_begin, rows[i].age_end, profile.epochs, profile.E);
-              const size_t b = (size_t)(profile.blk_off[c] + colate_iw::block_of_pos(rows[i].pos, profile.nbpb));
-              for (long long* at : {&profile.counts[(p * E + e) * 3], &profile.blocks[((p * nb + b) * E + e) * 3]})
-                at[0] += (long long)x.plus, at[1] += (long long)x.minus, at[2]++;
-            });
-      }
-    });
-  pool.wait_idle();
+  topo_cursor_walks(loaded.loaded->in, names, triples, [&](size_t p, Cursor& tgt, Cursor& ref, auto&& walk) {
+    walk([] { return 0.5; },  // no generator: the walk's draws decide nothing here
+         [](size_t, const CompactRow&, int, int, int) {},
+         [&](size_t c, const CompactRow& m) {  // the row qualifies: the addends from the counts the cursors stand on, 32 bits each
+           const colate_topo::Addends x = colate_topo::expected_addends((unsigned)tgt.DAF, (unsigned)tgt.AAF, (unsigned)ref.DAF, (unsigned)ref.AAF);
+           const size_t e = (size_t)colate_topo::age_epoch(m.age_begin, m.age_end, profile.epochs, profile.E);
+           const size_t b = (size_t)(profile.blk_off[c] + colate_iw::block_of_pos(m.pos, profile.nbpb));
+           for (long long* at : {&profile.counts[(p * E + e) * 3], &profile.blocks[((p * nb + b) * E + e) * 3]})
+             at[0] += (long long)x.plus, at[1] += (long long)x.minus, at[2]++;
+         });
+  });
   return true;
 }
 

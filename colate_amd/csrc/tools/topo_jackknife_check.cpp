@@ -1,6 +1,6 @@
 // colate_amd/csrc/tools/topo_jackknife_check.cpp -- stand-alone run of the host forms of `Colate --mode count_topo --jackknife`
 // (count_topo.h: the blocks of this mode, colate_topo_profile_blocks, colate_topo_jackknife) against each other:
-//   * small synthetic inputs written here (three chromosomes, four .colate.in files; rows at equal positions, rows with equal ages
+//   * small synthetic inputs, its own variant of tools/topo_inputs.hpp (three chromosomes, four .colate.in files; rows at equal positions, rows with equal ages
 //     and with negative ages; two samples end before their chromosomes' last rows), read, decoded and indexed by the loader of the
 //     command line (load_walk_inputs with RowSet::count_topo);
 //   * the blocks: topo_cursor_blocks on the loaded rows against colate_topo_blocks on the indexed ones, for several block sizes;
@@ -25,57 +25,14 @@
 #include "colate_amd.h"
 #include "count_topo.h"
 #include "cli_lists.h"
+#include "topo_inputs.hpp"
 #include "walk_inputs.h"
 
 namespace {
 
-unsigned g_s = 97531;
-unsigned next() { return (g_s = g_s * 1664525u + 1013904223u) >> 8; }
-
-void put_rec(FILE* f, const std::string& chrom, int bp, char anc, char der, int aaf, int daf) {
-  const int n = (int)chrom.size();
-  std::fwrite(&n, 4, 1, f), std::fwrite(chrom.data(), 1, chrom.size(), f), std::fwrite(&bp, 4, 1, f);
-  std::fwrite(&anc, 1, 1, f), std::fwrite(&der, 1, 1, f), std::fwrite(&aaf, 4, 1, f), std::fwrite(&daf, 4, 1, f);
-}
-
-bool write_inputs(const std::string& dir, const std::vector<std::string>& chroms, int snps) {
-  const char* const files[4] = {"A", "B", "C", "D"};
-  FILE* f[4];
-  for (int k = 0; k < 4; k++)
-    if (!(f[k] = std::fopen((dir + "/" + files[k] + ".colate.in").c_str(), "wb"))) return false;
-  const char bases[] = "ACGT";
-  for (const std::string& c : chroms) {
-    FILE* m = std::fopen((dir + "/P_chr" + c + ".mut").c_str(), "w");
-    if (!m) return false;
-    std::fprintf(m, "snp;pos_of_snp;dist;rs-id;tree_index;branch_indices;is_not_mapping;is_flipped;age_begin;age_end;"
-                    "ancestral_allele/alternative_allele;upstream_allele;downstream_allele;\n");
-    int bp = 5000;
-    for (int i = 0; i < snps; i++) {
-      int step = (int)(next() % 3000) * (next() % 12 != 0);  // some rows at equal positions
-      if (i == snps / 2) step += 250000;                      // a gap: blocks without a row
-      bp += step;
-      double begin = i % 13 == 0 ? 0.0 : std::exp((next() % 1000) / 100.0) * 2.0;
-      double end = (begin > 30.0 ? begin : 30.0) * (1.0 + (next() % 150) / 100.0);
-      if (i % 17 == 3) begin = -9.0, end = -2.0;
-      if (i % 11 == 5) end = begin;
-      const char a = bases[next() % 4], d = bases[(std::strchr(bases, a) - bases + 1 + next() % 3) % 4];
-      std::fprintf(m, "%d;%d;%d;rs%d;%d;%s;0;%d;%.6g;%.6g;%c/%c;%c;%c;\n", i, bp, 100, i, i / 10, next() % 25 ? "7" : "7 12", next() % 33 == 0,
-                   begin, end, a, d, a, d);
-      for (int k = 0; k < 4; k++) {
-        if ((k == 1 && i >= snps - 15) || (k == 3 && i >= snps - 30)) continue;  // B and D end early
-        if (step >= 2 && next() % 9 == 0) put_rec(f[k], c, bp - 1, 'A', 'G', 1, 1);
-        if (next() % 10) {
-          const int n = (int)(next() % 5), daf = n ? (int)(next() % (unsigned)(n + 1)) : 0;
-          put_rec(f[k], c, bp, next() % 30 ? a : d, d, n - daf, daf);
-        }
-      }
-    }
-    std::fclose(m);
-  }
-  bool ok = true;
-  for (int k = 0; k < 4; k++) ok = std::fclose(f[k]) == 0 && ok;
-  return ok;
-}
+using topo_inputs::TopoInputs;
+using topo_inputs::triples_of;
+using topo_inputs::write_inputs;
 
 bool same(double x, double y) { return (std::isnan(x) && std::isnan(y)) || std::memcmp(&x, &y, sizeof(x)) == 0; }
 
@@ -90,20 +47,13 @@ int main(int argc, char** argv) {
   int bad = 0;
   const std::string dir = argv[1];
   const std::vector<std::string> names = {"1", "2", "3"};
-  if (!write_inputs(dir, names, 300)) {
+  if (!write_inputs(dir, names, 300, TopoInputs{97531, false, true})) {
     std::fprintf(stderr, "cannot write the inputs under %s\n", dir.c_str());
     return 1;
   }
   std::vector<std::string> mut_files;
   for (const std::string& c : names) mut_files.push_back(dir + "/P_chr" + c + ".mut");
-  auto file = [&dir](const char* s) { return dir + "/" + s + ".colate.in"; };
-  const char* const list[][3] = {{"A", "B", "C"}, {"A", "C", "B"}, {"B", "A", "C"}, {"D", "A", "B"}, {"C", "D", "A"}, {"B", "D", "D"}, {"D", "C", "C"}};
-  std::vector<PairSpec> triples;
-  for (const auto& l : list) {
-    PairSpec ps;
-    ps.cond = file(l[0]), ps.target = file(l[1]), ps.reference = file(l[2]);
-    triples.push_back(ps);
-  }
+  const std::vector<PairSpec> triples = triples_of(dir);
   const int P = (int)triples.size(), C = (int)names.size();
   const unsigned seed = 78;
 

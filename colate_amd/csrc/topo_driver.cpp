@@ -157,6 +157,14 @@ bool draw_triples(const Staged& st, const std::vector<std::string>& names, const
   return true;
 }
 
+// profile.counts[P][E][3], zeros before, from the sums of profile.blocks[P][nb][E][3] over the blocks
+void sum_blocks(TopoProfile& profile, size_t P, int nb) {
+  const size_t per_block = (size_t)profile.E * 3;
+  for (size_t p = 0; p < P; p++)
+    for (size_t b = 0; b < (size_t)nb; b++)
+      for (size_t k = 0; k < per_block; k++) profile.counts[p * per_block + k] += profile.blocks[(p * (size_t)nb + b) * per_block + k];
+}
+
 // The age profile of every staged triple (count_topo.h: age_epoch): profile.counts[P][E][3] and the qualifying rows.  No plane and
 // no line is formed on the indexed forms.  With profile.nbpb > 0 (`--jackknife`) profile.blocks[P][nb][E][3] is formed, per genome
 // block, and profile.counts from its sums over the blocks.
@@ -180,9 +188,7 @@ bool profile_triples(const Staged& st, const std::vector<std::string>& names, co
                      ? colate_topo::topo_profile_blocks_device(st.v, profile.E, profile.epochs, profile.nbpb, nb, profile.blocks.data(), draws.data())
                      : colate_topo::topo_profile_blocks_host(st.v, profile.E, profile.epochs, profile.nbpb, nb, profile.blocks.data(), draws.data()))
       return api_error(rc), false;
-    for (size_t p = 0; p < P; p++)
-      for (size_t b = 0; b < (size_t)nb; b++)
-        for (size_t k = 0; k < per_block; k++) profile.counts[p * per_block + k] += profile.blocks[(p * (size_t)nb + b) * per_block + k];
+    sum_blocks(profile, P, nb);
     g_triple_stage_s += StageTimes::now() - t_stage;
     g_kernel_s += colate_topo_profile_blocks_kernel_seconds();
     std::cerr << st.in.S << " samples staged, " << P << " triples profiled in " << nb << " blocks on the " << st.where() << std::endl;
@@ -214,9 +220,7 @@ bool expected_triples(const Staged& st, const std::vector<std::string>& names, c
                    ? colate_topo::topo_expected_blocks_device(st.v, profile.E, profile.epochs, profile.nbpb, nb, profile.blocks.data())
                    : colate_topo::topo_expected_blocks_host(st.v, profile.E, profile.epochs, profile.nbpb, nb, profile.blocks.data()))
     return api_error(rc), false;
-  for (size_t p = 0; p < P; p++)
-    for (size_t b = 0; b < (size_t)nb; b++)
-      for (size_t k = 0; k < per_block; k++) profile.counts[p * per_block + k] += profile.blocks[(p * (size_t)nb + b) * per_block + k];
+  sum_blocks(profile, P, nb);
   g_triple_stage_s += StageTimes::now() - t_stage;
   g_kernel_s += colate_topo_expected_blocks_kernel_seconds();
   std::cerr << st.in.S << " samples staged, " << P << " triples expected in " << nb << " blocks on the " << st.where() << std::endl;
@@ -237,20 +241,29 @@ std::string fixed_text(long long sum) {
   return text;
 }
 
-// PREFIX.expected.txt, `cond target reference epoch plus minus qualifying` per (triple, epoch), and with `--jackknife`
-// PREFIX.expected.jackknife.txt, the columns of PREFIX.jackknife.txt, the statistics from the fixed-point integers as they are.
-bool write_expected(const std::string& prefix, const std::vector<std::string>& triple_names, const std::vector<double>& epochs, const TopoProfile& profile,
-                    int nb, bool jackknifed) {
-  const int E = profile.E;
-  std::ofstream ex(prefix + ".expected.txt");
+// a sampled count as the profile files print it
+std::string integer_text(long long n) { return std::to_string(n); }
+
+// PREFIX.profile.txt and PREFIX.expected.txt: `cond target reference epoch plus minus qualifying` per (triple, epoch), every epoch of
+// every triple, the epoch as a .coal prints it; print_count: plus and minus as the file prints them (integer_text, fixed_text).
+bool write_epoch_table(const std::string& path, const std::vector<std::string>& triple_names, const std::vector<double>& epochs,
+                       const TopoProfile& profile, std::string (*print_count)(long long)) {
+  std::ofstream os(path);
   for (size_t p = 0; p < triple_names.size(); p++)
-    for (int e = 0; e < E; e++) {
-      const long long* const x = &profile.counts[(p * (size_t)E + (size_t)e) * 3];
-      ex << triple_names[p] << " " << epochs[(size_t)e] << " " << fixed_text(x[0]) << " " << fixed_text(x[1]) << " " << x[2] << "\n";
+    for (int e = 0; e < profile.E; e++) {
+      const long long* const x = &profile.counts[(p * (size_t)profile.E + (size_t)e) * 3];
+      os << triple_names[p] << " " << epochs[(size_t)e] << " " << print_count(x[0]) << " " << print_count(x[1]) << " " << x[2] << "\n";
     }
-  if (!close_checked(ex, prefix + ".expected.txt")) return false;
-  if (!jackknifed) return true;
-  std::ofstream jk(prefix + ".expected.jackknife.txt");
+  return close_checked(os, path);
+}
+
+// PREFIX.jackknife.txt and PREFIX.expected.jackknife.txt: `cond target reference epoch plus minus blocks D D_jack se Z` per (triple,
+// epoch) and, last of a triple, for epoch `all`; the statistics from profile.blocks as they are -- sampled counts, or the fixed-point
+// integers of the expected counts.
+bool write_jackknife(const std::string& path, const std::vector<std::string>& triple_names, const std::vector<double>& epochs,
+                     const TopoProfile& profile, int nb, std::string (*print_count)(long long)) {
+  const int E = profile.E;
+  std::ofstream jk(path);
   std::vector<double> stats(((size_t)E + 1) * 4);
   std::vector<int> used((size_t)E + 1);
   for (size_t p = 0; p < triple_names.size(); p++) {
@@ -261,15 +274,23 @@ bool write_expected(const std::string& prefix, const std::vector<std::string>& t
       if (e < E) {
         const long long* const x = &profile.counts[(p * (size_t)E + (size_t)e) * 3];
         plus += x[0], minus += x[1];
-        jk << epochs[(size_t)e] << " " << fixed_text(x[0]) << " " << fixed_text(x[1]);
+        jk << epochs[(size_t)e] << " " << print_count(x[0]) << " " << print_count(x[1]);
       } else {
-        jk << "all " << fixed_text(plus) << " " << fixed_text(minus);
+        jk << "all " << print_count(plus) << " " << print_count(minus);
       }
       const double* const o = &stats[(size_t)e * 4];
       jk << " " << used[(size_t)e] << " " << stat_text(o[0]) << " " << stat_text(o[1]) << " " << stat_text(o[2]) << " " << stat_text(o[3]) << "\n";
     }
   }
-  return close_checked(jk, prefix + ".expected.jackknife.txt");
+  return close_checked(jk, path);
+}
+
+// the line of COLATE_TIMING; t0: the start of the inputs, t1: the start of the files
+void print_timing(double t0, double t1, const WalkInputs& in, size_t triples) {
+  if (!g_times.on) return;
+  std::cerr << "Timing: count_topo samples: inputs " << t1 - t0 - g_triple_stage_s << " s, triple stage " << g_triple_stage_s << " s (device kernels "
+            << g_kernel_s << " s), files " << StageTimes::now() - t1 << " s; " << (in.row_off.empty() ? 0LL : in.row_off.back()) << " rows, " << in.S
+            << " samples, " << triples << " triples" << std::endl;
 }
 
 int run_topo_samples(const Options& opt) {
@@ -384,11 +405,9 @@ int run_topo_samples(const Options& opt) {
   if (expected) {  // (the file does not depend on the blocks: without --jackknife they are the default's)
     if (!expected_triples(st, names, triples, profile)) return 1;
     const double t1 = StageTimes::now();
-    if (!write_expected(opt.get("output"), triple_names, epochs, profile, blk_off.back(), jackknifed)) return 1;
-    if (g_times.on)
-      std::cerr << "Timing: count_topo samples: inputs " << t1 - t0 - g_triple_stage_s << " s, triple stage " << g_triple_stage_s << " s (device kernels "
-                << g_kernel_s << " s), files " << StageTimes::now() - t1 << " s; " << (in.row_off.empty() ? 0LL : in.row_off.back())
-                << " rows, " << in.S << " samples, " << triples.size() << " triples" << std::endl;
+    if (!write_epoch_table(opt.get("output") + ".expected.txt", triple_names, epochs, profile, fixed_text)) return 1;
+    if (jackknifed && !write_jackknife(opt.get("output") + ".expected.jackknife.txt", triple_names, epochs, profile, blk_off.back(), fixed_text)) return 1;
+    print_timing(t0, t1, in, triples.size());
     print_usage_footer();
     return 0;
   }
@@ -408,43 +427,9 @@ int run_topo_samples(const Options& opt) {
     os << triple_names[p] << " " << plus << " " << minus << " " << draws[p] << "\n";
   }
   if (!close_checked(os, opt.get("output") + ".triples.txt")) return 1;
-  if (profiled) {  // `cond target reference epoch plus minus qualifying`: every epoch of every triple, the epoch as a .coal prints it
-    std::ofstream pr(opt.get("output") + ".profile.txt");
-    for (size_t p = 0; p < triples.size(); p++)
-      for (int e = 0; e < profile.E; e++) {
-        const long long* const x = &profile.counts[(p * (size_t)profile.E + (size_t)e) * 3];
-        pr << triple_names[p] << " " << epochs[(size_t)e] << " " << x[0] << " " << x[1] << " " << x[2] << "\n";
-      }
-    if (!close_checked(pr, opt.get("output") + ".profile.txt")) return 1;
-  }
-  if (jackknifed) {  // `cond target reference epoch plus minus blocks D D_jack se Z`: every epoch of every triple, then `all`
-    const int E = profile.E, nb = blk_off.back();
-    std::ofstream jk(opt.get("output") + ".jackknife.txt");
-    std::vector<double> stats(((size_t)E + 1) * 4);
-    std::vector<int> used((size_t)E + 1);
-    const auto number = stat_text;
-    for (size_t p = 0; p < triples.size(); p++) {
-      colate_topo::jackknife(nb, E, &profile.blocks[p * (size_t)nb * (size_t)E * 3], stats.data(), used.data());
-      long long plus = 0, minus = 0;
-      for (int e = 0; e <= E; e++) {
-        jk << triple_names[p] << " ";
-        if (e < E) {
-          const long long* const x = &profile.counts[(p * (size_t)E + (size_t)e) * 3];
-          plus += x[0], minus += x[1];
-          jk << epochs[(size_t)e] << " " << x[0] << " " << x[1];
-        } else {
-          jk << "all " << plus << " " << minus;
-        }
-        const double* const o = &stats[(size_t)e * 4];
-        jk << " " << used[(size_t)e] << " " << number(o[0]) << " " << number(o[1]) << " " << number(o[2]) << " " << number(o[3]) << "\n";
-      }
-    }
-    if (!close_checked(jk, opt.get("output") + ".jackknife.txt")) return 1;
-  }
-  if (g_times.on)
-    std::cerr << "Timing: count_topo samples: inputs " << t1 - t0 - g_triple_stage_s << " s, triple stage " << g_triple_stage_s << " s (device kernels "
-              << g_kernel_s << " s), files " << StageTimes::now() - t1 << " s; " << (in.row_off.empty() ? 0LL : in.row_off.back())
-              << " rows, " << in.S << " samples, " << triples.size() << " triples" << std::endl;
+  if (profiled && !write_epoch_table(opt.get("output") + ".profile.txt", triple_names, epochs, profile, integer_text)) return 1;
+  if (jackknifed && !write_jackknife(opt.get("output") + ".jackknife.txt", triple_names, epochs, profile, blk_off.back(), integer_text)) return 1;
+  print_timing(t0, t1, in, triples.size());
   print_usage_footer();
   return 0;
 }

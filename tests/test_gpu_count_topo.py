@@ -3,10 +3,14 @@ the reference's files.  The cases, their edges and the twin's side are in count_
 (which checks the twin against the numpy model and that the cases are what they say)."""
 import os
 
+import numpy as np
 import pytest
 
 import colate_amd
+import count_topo_expected_lib as xl
+import count_topo_jackknife_lib as jl
 import count_topo_lib as tl
+import count_topo_profile_lib as pl
 
 pytestmark = pytest.mark.gpu
 
@@ -48,6 +52,49 @@ def test_chunking_changes_no_bit():
             os.environ["COLATE_TOPO_BUDGET"] = old
     assert colate_amd.topo_samples_chunks() == 3
     tl.assert_same(got, want)
+
+
+def test_the_four_device_calls_in_one_process_keep_their_own_counters():
+    """The four device entry points on the jackknife's edge case (E = 11, one block per jl.B bases), one after another and then in
+    the reverse order, at the default budget and at one triple per chunk: every result is its host twin's in every integer, and
+    every call's two getters report that call alone -- its chunks and its kernel time -- whatever ran in between.  Last, each call
+    in turn at one triple per chunk with the other three at the default budget, so that the four counts differ."""
+    c, ep = jl.edge_case(), pl.EPOCHS[11]
+    P = len(c["triples"])
+    calls = [(lambda device: tl.topo(c, device=device), colate_amd.topo_samples_chunks, colate_amd.topo_samples_kernel_seconds),
+             (lambda device: pl.profile(c, ep, device), colate_amd.topo_profile_chunks, colate_amd.topo_profile_kernel_seconds),
+             (lambda device: jl.profile_blocks(c, ep, jl.B, device), colate_amd.topo_profile_blocks_chunks,
+              colate_amd.topo_profile_blocks_kernel_seconds),
+             (lambda device: xl.expected(c, ep, jl.B, device), colate_amd.topo_expected_blocks_chunks,
+              colate_amd.topo_expected_blocks_kernel_seconds)]
+    twins = [run(False) for run, _, _ in calls]
+
+    def run_on_device(k, budget):
+        os.environ.pop("COLATE_TOPO_BUDGET", None)
+        if budget is not None:
+            os.environ["COLATE_TOPO_BUDGET"] = budget
+        got = calls[k][0](True)
+        assert len(got) == len(twins[k])
+        for x, y in zip(got, twins[k]):
+            assert x.dtype == y.dtype and np.issubdtype(x.dtype, np.integer) and np.array_equal(x, y), k
+
+    old = os.environ.pop("COLATE_TOPO_BUDGET", None)
+    try:
+        for budget, chunks in ((None, 1), ("1", P)):
+            for order in (range(4), reversed(range(4))):
+                for k in order:
+                    run_on_device(k, budget)
+                    assert calls[k][1]() == chunks and calls[k][2]() > 0, (k, budget)
+                assert [chunks_of() for _, chunks_of, _ in calls] == [chunks] * 4, budget
+                assert all(seconds_of() > 0 for _, _, seconds_of in calls), budget
+        for chunked in range(4):
+            for k in range(4):
+                run_on_device(k, "1" if k == chunked else None)
+            assert [chunks_of() for _, chunks_of, _ in calls] == [P if k == chunked else 1 for k in range(4)], chunked
+    finally:
+        os.environ.pop("COLATE_TOPO_BUDGET", None)
+        if old is not None:
+            os.environ["COLATE_TOPO_BUDGET"] = old
 
 
 def test_samples_cli_on_the_device_writes_the_references_files(tmp_path):
