@@ -176,6 +176,8 @@ SIGNATURES = {
                                                 c_void_p, c_int] + [c_void_p] * 3),
     "colate_coalrate_tree_accumulate": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int] + [c_void_p] * 3),
     "colate_coalrate_tree_accumulate_host": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int] + [c_void_p] * 3),
+    "colate_coalrate_launch_shape": (c_int, [c_void_p]),
+    "colate_coalrate_tree_launch_shape": (c_int, [c_void_p]),
     "colate_coalrate_main": (c_int, [c_int, ctypes.POINTER(c_char_p)]),
 }
 

@@ -1047,3 +1047,21 @@ def coalrate_tree_accumulate(parents, branch_lengths, weights, blocks, num_block
     check(fn(N, T, _p(parents), _p(bl), _p(weights), _p(blocks), int(num_blocks), _p(ages) if ages is not None else None, E,
              _p(epochs), _p(num), _p(denom)))
     return num, denom
+
+
+def _launch_shape(fn):
+    out = np.zeros(5, dtype=np.int32)
+    fn(_p(out))
+    return dict(zip(("launches", "cpw_min", "cpw_max", "lanes_per_call", "lds"), (int(v) for v in out)))
+
+
+def coalrate_launch_shape():
+    """The first-kernel launches of this thread's last coalrate_accumulate(device=True) (diagnostic): their number, the
+    smallest and largest calls per workgroup, the lanes per call, and whether the prefix counts lay in LDS (1 / 0).  All 0
+    where nothing was launched."""
+    return _launch_shape(lib.colate_coalrate_launch_shape)
+
+
+def coalrate_tree_launch_shape():
+    """The same for this thread's last coalrate_tree_accumulate(device=True); lds: whether the sort keys lay in LDS."""
+    return _launch_shape(lib.colate_coalrate_tree_launch_shape)

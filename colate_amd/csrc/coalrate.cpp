@@ -192,6 +192,11 @@ bool make_tables(const CrRun& run, CrTables& tab, std::string& err) {
   return true;
 }
 
+LaunchStats& launch_stats(LaunchMode mode) {
+  static thread_local LaunchStats stats[2];
+  return stats[mode];
+}
+
 size_t device_call_bytes(int N, int G, int E) {
   const size_t GP = (size_t)G * (G + 1) / 2;
   return sizeof(CrNode) * (N - 1) + sizeof(int) * N + (sizeof(int) + sizeof(double)) * E * GP + sizeof(unsigned short) * G * (N + 1) +
@@ -345,6 +350,7 @@ extern "C" int colate_coalrate_accumulate(int N, int T, const int* parents, cons
                                           const int* blocks, int num_blocks, const int* group_vector_ids, int S,
                                           const int* group_vectors, int G, const double* sample_ages, int E, const double* epochs,
                                           double* num, double* denom) {
+  launch_stats(kLaunchLocalAncestry) = LaunchStats();
   return coalrate_accumulate(true, N, T, parents, branch_lengths, weights, blocks, num_blocks, group_vector_ids, S, group_vectors,
                              G, sample_ages, E, epochs, num, denom);
 }
@@ -357,6 +363,8 @@ extern "C" int colate_coalrate_accumulate_host(int N, int T, const int* parents,
   return coalrate_accumulate(false, N, T, parents, branch_lengths, weights, blocks, num_blocks, group_vector_ids, S, group_vectors,
                              G, sample_ages, E, epochs, num, denom);
 }
+
+extern "C" int colate_coalrate_launch_shape(int* out) { return launch_stats(kLaunchLocalAncestry).report(out); }
 
 // ------------------------------------------------------------------ the driver (CoalRate.cpp, coal.cpp:206-590)
 namespace colate_drv {

@@ -171,6 +171,25 @@ std::unique_ptr<CoalRateWalker> make_host_walker(const CrRun& run, const CrTable
 // the calling thread's).
 std::unique_ptr<CoalRateWalker> make_device_walker(int device, const CrRun& run, const CrTables& tab, int max_calls, std::string& why,
                                                    int* code = nullptr);
+// What the first-kernel launches of the calling thread's last device call of a mode looked like (diagnostics:
+// colate_coalrate_launch_shape, colate_coalrate_tree_launch_shape).  The C ABI's device entry resets it, the device walker's
+// launch() notes every launch; all 0 after a call that launched nothing.
+struct LaunchStats {
+  int launches = 0, cpw_min = 0, cpw_max = 0, lpc = 0, lds = 0;
+  void note(int cpw, int lanes_per_call, bool in_lds) {
+    cpw_min = launches ? std::min(cpw_min, cpw) : cpw;
+    cpw_max = launches ? std::max(cpw_max, cpw) : cpw;
+    lpc = lanes_per_call, lds = in_lds ? 1 : 0;
+    launches++;
+  }
+  int report(int* out) const {  // out[5] (or null); returns the launches
+    if (out) out[0] = launches, out[1] = cpw_min, out[2] = cpw_max, out[3] = lpc, out[4] = lds;
+    return launches;
+  }
+};
+enum LaunchMode { kLaunchLocalAncestry = 0, kLaunchTree = 1 };
+LaunchStats& launch_stats(LaunchMode mode);  // the calling thread's
+
 // device bytes per call of a chunk
 size_t device_call_bytes(int N, int G, int E);
 // Calls per chunk: the most that fit 4M node entries and 256 MiB of device memory, or COLATE_COALRATE_CHUNK_TREES where

@@ -202,6 +202,7 @@ class DeviceWalker final : public BlockSumDeviceWalker<CrChunk, CrArrays> {
     if (lds_pre_) hipLaunchKernelGGL(cr_count<true>, dim3(sh.grid), dim3(sh.lanes), lds, stream_, ca);
     else hipLaunchKernelGGL(cr_count<false>, dim3(sh.grid), dim3(sh.lanes), lds, stream_, ca);
     WALKER_TRY(hipGetLastError());
+    launch_stats(kLaunchLocalAncestry).note(sh.cpw, lpc_, lds_pre_);
     FoldArgs fa{T, E_, GP_, OA_, cumB_, R_, s.w.d, s.gv.d, s.block.d, oa_epoch_, pairs_, sub_, width_, num_, den_};
     const int cells = E_ * GP_;
     hipLaunchKernelGGL(cr_fold, dim3((cells + 63) / 64), dim3(64), 0, stream_, fa);

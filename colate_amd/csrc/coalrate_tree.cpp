@@ -175,6 +175,7 @@ int tree_accumulate(bool device, int N, int T, const int* parents, const double*
 extern "C" int colate_coalrate_tree_accumulate(int N, int T, const int* parents, const double* branch_lengths, const double* weights,
                                                const int* blocks, int num_blocks, const double* sample_ages, int E,
                                                const double* epochs, double* num, double* denom) {
+  colate_cr::launch_stats(colate_cr::kLaunchTree) = colate_cr::LaunchStats();
   return tree_accumulate(true, N, T, parents, branch_lengths, weights, blocks, num_blocks, sample_ages, E, epochs, num, denom);
 }
 
@@ -184,3 +185,5 @@ extern "C" int colate_coalrate_tree_accumulate_host(int N, int T, const int* par
                                                     double* denom) {
   return tree_accumulate(false, N, T, parents, branch_lengths, weights, blocks, num_blocks, sample_ages, E, epochs, num, denom);
 }
+
+extern "C" int colate_coalrate_tree_launch_shape(int* out) { return colate_cr::launch_stats(colate_cr::kLaunchTree).report(out); }

@@ -259,6 +259,7 @@ class DeviceWalker final : public colate_cr::BlockSumDeviceWalker<CrtChunk, CrtA
     if (lds_keys_) hipLaunchKernelGGL(crt_sort<true>, dim3(sh.grid), dim3(sh.lanes), lds, stream_, sa);
     else hipLaunchKernelGGL(crt_sort<false>, dim3(sh.grid), dim3(sh.lanes), lds, stream_, sa);
     WALKER_TRY(hipGetLastError());
+    colate_cr::launch_stats(colate_cr::kLaunchTree).note(sh.cpw, lpc_, lds_keys_);
     FoldArgs fa{T, E_, count_, cden_, s.w.d, s.block.d, num_, den_};
     hipLaunchKernelGGL(crt_fold, dim3((E_ + 63) / 64), dim3(64), 0, stream_, fa);
     WALKER_TRY(hipGetLastError());

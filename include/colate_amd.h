@@ -865,6 +865,14 @@ int colate_coalrate_tree_accumulate_host(int N, int T, const int* parents, const
                                          const int* blocks, int num_blocks, const double* sample_ages, int E,
                                          const double* epochs, double* num, double* denom);
 
+/* Diagnostics of the calling thread's last colate_coalrate_accumulate / colate_coalrate_tree_accumulate (the device calls;
+ * each resets its own at its start): out[5] (or NULL) = the launches of the first kernel (cr_count / crt_sort: one per
+ * chunk that holds a call), the smallest and the largest number of calls per workgroup over them, the lanes per call, and 1
+ * where the prefix counts (local_ancestry) or the sort keys (tree) lay in LDS, 0 where in device memory.  All 0 after a call
+ * that launched nothing (refused, failed before its first chunk, or every call of weight 0).  Returns the launches. */
+int colate_coalrate_launch_shape(int* out);
+int colate_coalrate_tree_launch_shape(int* out);
+
 /* The `CoalRate` command line (CoalRate.cpp:6-58) for --mode local_ancestry and --mode tree: same option names, stderr
  * lines and OUTPUT.coal.  Returns the process exit code. */
 int colate_coalrate_main(int argc, char** argv);

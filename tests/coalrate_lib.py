@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 GOLDEN = os.path.join(HERE, "golden")
 CLI = os.path.join(ROOT, "colate_amd", "bin", "CoalRate")
+SHAPE_KEYS = ("launches", "cpw_min", "cpw_max", "lanes_per_call", "lds")   # of colate_amd.coalrate[_tree]_launch_shape()
 CASES = sorted(d[len("coalrate_"):] for d in os.listdir(GOLDEN) if d.startswith("coalrate_")
                and os.path.isdir(os.path.join(GOLDEN, d)))
 
@@ -152,9 +153,10 @@ def sum_reallocations(blocks, cap):
     return reallocations, copying
 
 
-def accumulate_in_child(tmp_path, inp, epochs, device, timeout, chunk_trees=None):
+def accumulate_in_child(tmp_path, inp, epochs, device, timeout, chunk_trees=None, with_shape=False):
     """coalrate_accumulate in a child process under its own time limit; inp = random_input's tuple plus (num_blocks, G).
-    Returns (num, denom); raises on a child that fails (nothing is retried)."""
+    Returns (num, denom), with_shape: and colate_amd.coalrate_launch_shape() after the call; raises on a child that fails
+    (nothing is retried)."""
     import sys
     parents, bl, weights, blocks, gv, groups, ages, num_blocks, G = inp
     src = os.path.join(str(tmp_path), "coalrate_in.npz")
@@ -170,6 +172,8 @@ def accumulate_in_child(tmp_path, inp, epochs, device, timeout, chunk_trees=None
                        env=env, timeout=timeout)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     out = np.load(dst)
+    if with_shape:
+        return out["num"], out["den"], dict(zip(SHAPE_KEYS, out["shape"].tolist()))
     return out["num"], out["den"]
 
 
@@ -180,4 +184,4 @@ if __name__ == "__main__":
     ages = z["ages"] if z["ages"].size else None
     num, den = colate_amd.coalrate_accumulate(z["parents"], z["bl"], z["weights"], z["blocks"], int(z["num_blocks"]), z["gv"],
                                               z["groups"], int(z["G"]), z["epochs"], ages, device=bool(int(sys.argv[3])))
-    np.savez(sys.argv[2], num=num, den=den)
+    np.savez(sys.argv[2], num=num, den=den, shape=[colate_amd.coalrate_launch_shape()[k] for k in SHAPE_KEYS])

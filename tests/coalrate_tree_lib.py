@@ -18,7 +18,6 @@ CASES = sorted(d[len("crtree_"):] for d in os.listdir(GOLDEN) if d.startswith("c
 EXPECTED_CASES = ["ancient", "blocks", "chr", "modern", "settings", "ties"]
 
 LDS_KEYS = 16384          # coalrate_tree.h kLdsKeys: padded keys up to which the device sorts in LDS (N <= 8192)
-WAVE_SLOTS = 256 * 8      # coalrate_tree_kernel.hip: the CUs of an MI355X times kWavesPerCu; a chunk of more one-wave calls is packed
 TIE_EPOCHS = np.array([0.0, 64.0, 128.0, 1024.0, 1e7])   # multiples of the quantum: node times equal boundaries
 
 
@@ -27,14 +26,6 @@ def padded_keys(N):
     while P < 2 * N - 1:
         P *= 2
     return P
-
-
-def calls_per_workgroup(chunk_calls, N):
-    """DeviceWalker::submit's rule: lanes per call = P / 2 in 4 .. 256; one call per workgroup while every call finds a wave
-    slot, beyond that ceil(calls * waves per call / WAVE_SLOTS), at most 256 / lanes."""
-    lpc = min(256, max(4, padded_keys(N) // 2))
-    waves = (lpc + 63) // 64
-    return max(1, min(256 // lpc, -(-chunk_calls * waves // WAVE_SLOTS)))
 
 
 def chunk_straddles_blocks(blocks, cap):
@@ -106,9 +97,10 @@ def random_input(rng, N, T, num_blocks, ancient, epochs, quantum=None, Ne=2000.0
     return parents, bl, weights, blocks, ages
 
 
-def accumulate_in_child(tmp_path, inp, num_blocks, epochs, device, timeout, chunk_trees=None):
+def accumulate_in_child(tmp_path, inp, num_blocks, epochs, device, timeout, chunk_trees=None, with_shape=False):
     """coalrate_tree_accumulate in a child process under its own time limit; inp = random_input's tuple.  Returns
-    (num, denom); raises on a child that fails (nothing is retried)."""
+    (num, denom), with_shape: and colate_amd.coalrate_tree_launch_shape() after the call; raises on a child that fails (nothing
+    is retried)."""
     parents, bl, weights, blocks, ages = inp
     src = os.path.join(str(tmp_path), "crtree_in.npz")
     dst = os.path.join(str(tmp_path), f"crtree_out_{int(device)}.npz")
@@ -124,6 +116,8 @@ def accumulate_in_child(tmp_path, inp, num_blocks, epochs, device, timeout, chun
                        env=env, timeout=timeout)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     out = np.load(dst)
+    if with_shape:
+        return out["num"], out["den"], dict(zip(cl.SHAPE_KEYS, out["shape"].tolist()))
     return out["num"], out["den"]
 
 
@@ -133,4 +127,4 @@ if __name__ == "__main__":
     ages = z["ages"] if z["ages"].size else None
     num, den = colate_amd.coalrate_tree_accumulate(z["parents"], z["bl"], z["weights"], z["blocks"], int(z["num_blocks"]),
                                                    z["epochs"], ages, device=bool(int(sys.argv[3])))
-    np.savez(sys.argv[2], num=num, den=den)
+    np.savez(sys.argv[2], num=num, den=den, shape=[colate_amd.coalrate_tree_launch_shape()[k] for k in cl.SHAPE_KEYS])

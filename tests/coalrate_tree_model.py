@@ -67,3 +67,9 @@ def accumulate(parents, bl, weights, blocks, num_blocks, epochs, ages=None):
         b = int(blocks[k])
         populate(node_times(parents[k], bl[k], ages), weights[k], epochs, num[b], den[b], n_num[b], n_den[b])
     return num, den, n_num, n_den
+
+
+def within_bound(a, b, n):
+    """|a - b| <= 2 n 2^-53 max(a, b): all addends are non-negative and formed by the same expression, so every summation
+    order is within (n - 1) 2^-53 of the exact sum (relative)."""
+    return (np.abs(a - b) <= 2.0 * n * 2.0 ** -53 * np.maximum(a, b)).all()

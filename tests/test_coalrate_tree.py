@@ -32,10 +32,7 @@ def test_cli_host_twin_matches_reference(name, tmp_path):
         assert len(rows) >= 4 and len(set(rows)) > 1
 
 
-def within_bound(a, b, n):
-    """|a - b| <= 2 n 2^-53 max(a, b): all addends are non-negative and formed by the same expression, so every summation
-    order is within (n - 1) 2^-53 of the exact sum (relative)."""
-    return (np.abs(a - b) <= 2.0 * n * 2.0 ** -53 * np.maximum(a, b)).all()
+within_bound = tm.within_bound   # (shared with test_coalrate_edges_cpu.py)
 
 
 # N, T, blocks, ancient, quantum, epochs

@@ -54,7 +54,14 @@ def test_device_equals_host_twin_bit_for_bit(N, G, T, S, nb, ancient, cap, tmp_p
         assert reallocations >= 3 and copying >= 2      # the sums move to larger buffers with earlier blocks in them
     if cap:
         assert T > cap and len(set(inp[3][:cap].tolist())) + len(set(inp[3].tolist())) > 2  # chunks and blocks are crossed
-    dnum, dden = cl.accumulate_in_child(tmp_path, inp, epochs, device=True, timeout=300, chunk_trees=cap)
+    dnum, dden, shape = cl.accumulate_in_child(tmp_path, inp, epochs, device=True, timeout=300, chunk_trees=cap, with_shape=True)
+    # what the device call did (coalrate_launch_shape): chunks launched, lanes per call, shared workgroups, where the prefix counts lay
+    assert shape["launches"] == -(-T // (cap or T)) and shape["lanes_per_call"] == {1: 1, 2: 4, 26: 256}[G], shape
+    assert shape["lds"] == ((N, G) != (4000, 26)), shape
+    if T == 5000:
+        assert shape["cpw_min"] == shape["cpw_max"] >= 2, shape     # several calls share a workgroup
+    else:
+        assert shape["cpw_min"] == shape["cpw_max"] == 1, shape
     hnum, hden = cl.accumulate_in_child(tmp_path, inp, epochs, device=False, timeout=600, chunk_trees=cap)
     assert (hnum != 0).any() and (hden != 0).any()
     assert np.array_equal(dnum.view(np.uint64), hnum.view(np.uint64))

@@ -45,11 +45,6 @@ def test_device_equals_host_twin_bit_for_bit(N, T, nb, ancient, quantum, cap, tm
     P = tl.padded_keys(N)
     if N == 2:
         assert 2 * N - 1 == 3
-    if N == 8 and T == 9000:
-        cpw = tl.calls_per_workgroup(cap, N)
-        assert cap > tl.WAVE_SLOTS and cpw >= 2      # more calls in a chunk than wave slots: workgroups are shared
-        assert cap % cpw != 0 and T > 2 * cap        # the last workgroup of a chunk is partly filled; a last chunk unpacked
-        assert tl.calls_per_workgroup(T - 2 * cap, N) == 1
     if N == 300:
         assert P == 1024 and 2 * N - 1 < P
     if N == 8192:
@@ -66,7 +61,16 @@ def test_device_equals_host_twin_bit_for_bit(N, T, nb, ancient, quantum, cap, tm
         assert reallocations >= 3 and copying >= 2      # the sums move to larger buffers with earlier blocks in them
     if cap:
         assert T > cap and tl.chunk_straddles_blocks(inp[3], cap)   # chunks are crossed, and block boundaries inside them
-    dnum, dden = tl.accumulate_in_child(tmp_path, inp, nb, epochs, device=True, timeout=300, chunk_trees=cap)
+    dnum, dden, shape = tl.accumulate_in_child(tmp_path, inp, nb, epochs, device=True, timeout=300, chunk_trees=cap, with_shape=True)
+    # what the device call did (coalrate_tree_launch_shape), not what a restated rule predicts
+    assert shape["launches"] == -(-T // (cap or T)) and shape["lanes_per_call"] == min(256, max(4, P // 2)), shape
+    assert shape["lds"] == (P <= tl.LDS_KEYS), shape
+    if N == 8 and T == 9000:
+        assert shape["cpw_max"] >= 2, shape                       # more calls in a chunk than wave slots: workgroups are shared
+        assert cap % shape["cpw_max"] != 0 and T > 2 * cap, shape   # the last workgroup of a chunk is partly filled
+        assert shape["cpw_min"] == 1, shape                       # and the last chunk, of two calls, is not packed
+    else:
+        assert shape["cpw_min"] == shape["cpw_max"] == 1, shape
     hnum, hden = tl.accumulate_in_child(tmp_path, inp, nb, epochs, device=False, timeout=600, chunk_trees=cap)
     assert (hnum != 0).any() and (hden != 0).any()
     assert np.array_equal(dnum.view(np.uint64), hnum.view(np.uint64))
